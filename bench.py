@@ -22,8 +22,17 @@ Rank 0 prints ONE JSON line.
 What the line's `value` is (round 6, VERDICT r05's ruling): the library's split-fp32 mode (OFFK_PRECISION_F32SPLIT: every fp32 operand
 as three bf16 planes = the fp32 value exactly, six exact plane products on the bf16 matrix pipe, fp32 accumulation -- the units kernel, the
 batched GEMMs of every conv on a Winograd path, the 1x1 convs on 7x7 maps; measured error against fp64 below the fp32 pipe's on every
-input kind, asserted in tests/test_gpu_split.py) at the full --steps.  The fp32-MFMA-pipe mode of the same library (v_mfma_f32_*) is timed
-beside it as `fp32_pipe_mode`.  `--precision fp32` swaps the two.
+input kind, asserted in tests/test_gpu_split.py) at the full --steps.  With --full the fp32-MFMA-pipe mode of the same library (v_mfma_f32_*)
+is timed beside it as `fp32_pipe_mode`.  `--precision fp32` swaps the two.
+
+A plain run times the headline forward only: set-up, --warmup untimed steps, --steps timed steps, the line.  Everything else it
+can measure or check runs with --full: the profiled second loop (stage times, the standalone K2 launches of the roofline object,
+the per-launch roofline_in_path), the other arithmetic mode, both modes' error tables against fp64, the Flow and two-stream
+configs, units_training, the single-rank RCCL smoke object, the CPU baseline and, with a score exchange on the step, the check
+of the exchanged scores (exchange_ok, --dump-scores).
+
+    python bench.py --full                            # every object above in the line and in bench_detail.json
+    python bench.py --dump-outputs DIR                # + DIR/logits_{7,14,28}.npy: the timed path's outputs of its last step
 
 Output: the ONE stdout line is a compact object (< 8 KB, `compact_line`, pinned by tests/test_bench_line.py); everything else
 (per-launch tables, stage times, both modes' error tables, the CPU baseline's operating points, units_training) goes to
@@ -49,12 +58,12 @@ def parse_args():
     ap.add_argument("--variant", choices=("rgb", "flow"), default="rgb")
     ap.add_argument("--precision", choices=("fp32", "f32split"), default="f32split",
                     help="arithmetic of the headline value (f32split = fp32 operands as three bf16 planes on the bf16 pipe, ruled "
-                         "fp32-equivalent in VERDICT r05; fp32 = the fp32 MFMA pipe); the other mode is always reported beside it at N = 1 "
-                         "with both modes' measured error against fp64")
+                         "fp32-equivalent in VERDICT r05; fp32 = the fp32 MFMA pipe); with --full the other mode is reported beside it at "
+                         "N = 1 with both modes' measured error against fp64")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), metavar="PATH",
                     help="where rank 0 writes the full result object (the stdout line is its compact form)")
     ap.add_argument("--cpu-clips", type=int, default=64, help="clips in the large CPU-baseline sample (0 = skip the CPU baseline)")
-    ap.add_argument("--no-secondary", action="store_true", help="N = 1: skip the f32split / training / CPU-baseline objects")
+    ap.add_argument("--no-secondary", action="store_true", help="--full at N = 1: skip the f32split / training / CPU-baseline objects")
     ap.add_argument("--collective", choices=("allgather", "allreduce"), default="allgather",
                     help="N > 1: the one exchange of per-clip scores (allreduce = zeroed [B,101] buffer + sum, north_star's wording)")
     ap.add_argument("--collective-smoke", action="store_true",
@@ -67,8 +76,18 @@ def parse_args():
     ap.add_argument("--dump-scores", default=None, metavar="PATH",
                     help="with a score exchange on the step (N > 1 or --collective-smoke): rank 0 writes the exchanged scores of the "
                          "verification step, [3 heads (7, 14, 28)][world * clips][classes], to PATH (.npy) -- "
-                         "tests/test_gpu_two_ranks.py compares them with the oracle called per shard")
-    return ap.parse_args()
+                         "tests/test_gpu_two_ranks.py compares them with the oracle called per shard (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline timing: the profiled loop, the roofline objects, the secondary measurements, the CPU "
+                         "baseline and the check of the score exchange (see the module docstring)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed to DIR/logits_{7,14,28}.npy (float32): "
+                         "the three heads' scores [rows][classes], with a score exchange on the step the exchanged scores of every rank "
+                         "[world * clips][classes]")
+    args = ap.parse_args()
+    if args.dump_scores and not args.full:
+        ap.error("--dump-scores is written by the check of the score exchange, which runs with --full")
+    return args
 
 
 def launch_ranks(args):
@@ -206,6 +225,29 @@ def usable_cpus():
     except (OSError, ValueError):
         pass
     return n
+
+
+def make_features(batch, length, config_id, clip_offset):
+    """synth.make_features in chunks on a thread pool: one bench batch is 2 GB of maps, ~14 s on one core, and that is set-up
+    time of every run.  The generator is counter-based (element i of a site is counter i of its stream), so a chunk is
+    synth.feature_values of its own counter range and the maps are bit-identical to synth.make_features'."""
+    from concurrent.futures import ThreadPoolExecutor
+    chunk = 1 << 21
+    feats, jobs = [], []
+    for si, (_name, C, H) in enumerate(spec.SITES):
+        per_clip = length * C * H * H
+        v = np.empty(batch * per_clip, dtype=np.float32)
+        for o in range(0, v.size, chunk):
+            jobs.append((v, synth.feature_seed(config_id, si), clip_offset * per_clip + o, o, min(chunk, v.size - o)))
+        feats.append(v.reshape(batch * length, C, H, H))
+
+    def fill(job):
+        v, seed, start, o, n = job
+        v[o:o + n] = synth.feature_values(seed, start, n)
+
+    with ThreadPoolExecutor(max_workers=min(16, usable_cpus())) as ex:
+        list(ex.map(fill, jobs))
+    return feats
 
 
 def cpu_concurrent(length, variant, seconds=6.0):
@@ -432,6 +474,13 @@ def roofline_in_path(h, arr, out, B, L, precision, steps):
                                      "what": "every fusion-stage launch except the 7x7, 5x5 and 3x3 832->256 convs"},
             "how": "offk_set_profiling(h, 2): HIP events on the forward's stream in front of every launch group, average "
                    "over the loop; frac = algorithmic FLOPs / time / peak (MFMA-bound) or algorithmic bytes / time / 8 TB/s"}
+
+
+def dump_outputs(dirname, heads):
+    """--dump-outputs: the three heads' scores (7, 14, 28) as DIR/logits_{7,14,28}.npy, float32."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in zip(("logits_7", "logits_14", "logits_28"), heads):
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy().astype(np.float32))
 
 
 def timed_loop(fn, steps, fence):
@@ -929,7 +978,7 @@ def main():
     B, L = args.batch, args.length
     consensus = (variant == spec.VARIANT_FLOW) or coll
     weights = synth.make_weights(variant)
-    feats_np = synth.make_features(B, L, config_id=2, clip_offset=rank * B)
+    feats_np = make_features(B, L, config_id=2, clip_offset=rank * B)
     feats = [torch.from_numpy(f).to(dev) for f in feats_np]
     rows = B if consensus else B * (L - 1)
     ncls = spec.NUM_CLASSES
@@ -978,9 +1027,17 @@ def main():
             xchg.all_reduce(i, reduced[i])
             last_exchange[0] = reduced[i]
 
-    def measure(precision, steps, warmup, variant=variant, weights=weights, feats=feats, consensus=consensus, k2=True):
-        """W untimed steps, K timed steps between fences (profiling off), then a second loop of K steps with the
-        library's per-stage HIP events on and a standalone K2 launch (the roofline object) after every forward."""
+    def exchanged():
+        """The scores the last exchange delivered, on the host: [head][rank * rows + row][class]."""
+        got = last_exchange[0]
+        if torch.is_tensor(got) and got.dim() == 4:      # all-gather layout [rank][head][row] -> [head][rank * rows + row]
+            got = got.view(world, 3, rows, ncls).permute(1, 0, 2, 3).reshape(3, world * rows, ncls)
+        return got.cpu()
+
+    def measure(precision, steps, warmup, variant=variant, weights=weights, feats=feats, consensus=consensus, k2=True, dump=None):
+        """W untimed steps, K timed steps between fences (profiling off), the last step's outputs to `dump` (--dump-outputs), then
+        with --full a second loop of K steps with the library's per-stage HIP events on and a standalone K2 launch (the roofline
+        object) after every forward."""
         h = runtime.OffForward(B, L, variant, spec.SLICE_FLAT, consensus, device=dev, precision=precision)
         h.load_state_dict(weights)
         arr = h._feat_array(feats)
@@ -1006,7 +1063,9 @@ def main():
             t = torch.tensor([dt], device="cpu" if over else dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
-        if not k2:
+        if dump and rank == 0:
+            dump_outputs(dump, exchanged() if coll else [o.cpu() for o in out])
+        if not (k2 and args.full):
             return h, dt, None, None
         # second loop: where the time goes, and K2 on its own (HIP events on the stream the kernels run on)
         h.off_units(feats)                      # G / D regions hold real data whichever units path the forward takes
@@ -1027,13 +1086,13 @@ def main():
         k2_us = [a.elapsed_time(b) * 1e3 / K2_PER_PAIR for a, b in k2_ev]
         return h, dt, stages, k2_us
 
-    h, dt, stages, k2_us = measure(args.precision, args.steps, args.warmup)
-    in_path = roofline_in_path(h, h._feat_array(feats), out, B, L, args.precision, min(args.steps, 20)) if world == 1 else None
+    h, dt, stages, k2_us = measure(args.precision, args.steps, args.warmup, dump=args.dump_outputs)
+    in_path = roofline_in_path(h, h._feat_array(feats), out, B, L, args.precision, min(args.steps, 20)) if world == 1 and args.full else None
     # With an exchange on the step: the exchanged scores must hold EVERY rank's shard in clip order.  Checked once, outside the timed
     # region, against an independent reference: one more forward + exchange, this rank's rows cloned BEFORE the collective (in the
     # all-reduce form `local` is a view of the buffer being reduced), the clones of all ranks gathered by a second, plain collective.
     exchange_ok = None
-    if coll:
+    if coll and args.full:
         i_chk = 0
         xchg.finish()
         xchg2.finish()
@@ -1046,10 +1105,7 @@ def main():
         xchg.finish()
         xchg2.finish()
         torch.cuda.synchronize()
-        got = last_exchange[0]
-        if torch.is_tensor(got) and got.dim() == 4:      # all-gather layout [rank][head][row] -> [head][rank * rows + row]
-            got = got.view(world, 3, rows, ncls).permute(1, 0, 2, 3).reshape(3, world * rows, ncls)
-        got = got.cpu()
+        got = exchanged()
         ref_parts = [torch.empty_like(mine.cpu() if over else mine) for _ in range(world)]
         dist.all_gather(ref_parts, mine.cpu() if over else mine)
         ref = torch.cat([r_.cpu() for r_ in ref_parts], 1)
@@ -1068,12 +1124,6 @@ def main():
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         clips_s = world * B * args.steps / dt
-        k2_avg_s = sum(k2_us) / len(k2_us) * 1e-6
-        algo_bytes = spec.algorithmic_bytes_sobel_tdiff(B, L)
-        achieved = algo_bytes / k2_avg_s / 1e9
-        unit_f, fus_f = spec.flops_per_clip(L)
-        stage_ms = dict((k, v[0] / max(v[1], 1)) for k, v in stages.items())
-        gpu_ms = sum(stage_ms.values())
         if not coll:
             coll_txt = ""
         elif smoke:
@@ -1085,11 +1135,7 @@ def main():
                 args.collective, world, ndev)
         else:
             coll_txt = " + SegmentConsensus avg + RCCL %s of per-clip scores" % args.collective
-        peak_tf = MFMA_F32_PEAK_TFLOPS
-        algo_flops = (unit_f + fus_f) * B                  # per rank; ms_step is a rank's time: the fractions below are per GPU
         wino_on = os.environ.get("OFFK_WINOGRAD", "1") != "0"
-        exec_flops = algo_flops - winograd_saved_flops(B * (L - 1), args.precision) if wino_on else algo_flops
-        s_blocks = next((k for k in (in_path or {}).get("kernels", []) if k["launch"].startswith("units:sobel S-blocks")), None)
         res = {
             "metric": "OFF-forward clips/sec (7-seg 224x224)", "value": clips_s, "unit": "clips/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -1109,45 +1155,58 @@ def main():
             "n_ranks_seen": dist.get_world_size() if coll else 1, "collective_backend": backend,
             "exchange": ("async_op=True on two alternating buffer sets: the timed step does not wait for its own collective, only the "
                          "closing fence does (round 5 on; earlier rounds' multi-rank ms_per_step had it inside every step)") if coll else None,
-            "roofline": {"bound": "hbm", "kernel": "sobel_tdiff_kernel (K2: temporal difference + spatial gradient + concat, "
-                                                   "all nine sites, one launch; offk_sobel_tdiff_all)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(B, L, args.variant),
-                         "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": k2_avg_s * 1e6,
-                         "min_launch_us": min(k2_us), "launches": len(k2_us) * K2_PER_PAIR,
-                         "on_default_forward_path": False,
-                         "in_path": None if s_blocks is None else {
-                             "kernel": "sobel_tdiff_kernel<..., ROLES = 3> (the S-blocks: read D, depthwise 3x3 / diagonal Sobel, write S)",
-                             "achieved": s_blocks["achieved_gbs"], "frac": s_blocks["frac"], "avg_launch_us": s_blocks["avg_ms"] * 1e3,
-                             "algorithmic_bytes_per_launch": s_blocks["algorithmic_bytes"]},
-                         "quote_as": "%.2f of 8 TB/s standalone (the whole Sobel + temporal-difference kernel) / %s in path (its S-blocks, "
-                                     "the part the timed forward launches)" % (achieved / HBM_PEAK_GBS,
-                                                                               "n/a" if s_blocks is None else "%.2f" % s_blocks["frac"]),
-                         "path_note": "the north-star object (Sobel + temporal-diff kernel) launched STANDALONE: the default "
-                                      "inference forward fuses the temporal difference into the 1x1 reduce (pw_tdiff, MFMA-bound) "
-                                      "and runs only this kernel's S-blocks; the full kernel serves training and "
-                                      "OFFK_FUSED_UNITS=0.  What bounds the kernels the timed forward launches: roofline_in_path",
-                         "how": "%d standalone launches between one HIP-event pair on the forward's stream, after every "
-                                "forward of a second K-step loop (the wall-clock loop runs without any event); an event "
-                                "pair around a single launch adds ~5 us of command-processor time to this kernel -- "
-                                "rocprofv3's kernel-trace average (profiles/) is the cross-check" % K2_PER_PAIR},
-            "stage_ms": stage_ms,
-            "mfma": {"peak_tflops": peak_tf,
-                     "executed_flops_per_step": exec_flops,
-                     "executed_frac_of_peak": exec_flops / (ms_step * 1e-3) / 1e12 / peak_tf,
-                     "executed_frac_is": "fp32-equivalent FLOPs the matrix pipes execute (direct-conv FLOPs minus what the Winograd forms save) / "
-                                         "wall-clock ms_per_step / the fp32 MFMA peak 157.3 TF, per GPU" +
-                                         ("; in split-fp32 mode the units kernel, the Winograd GEMMs and the 7x7-map 1x1 convs run six bf16 plane "
-                                          "products per fp32 product on the 2.5 PF bf16 pipe, so this is a throughput-equivalent there, "
-                                          "not a utilisation" if args.precision == "f32split" else ""),
-                     "algorithmic_flops_per_step": algo_flops,
-                     "algorithmic_flops_over_peak": algo_flops / (ms_step * 1e-3) / 1e12 / peak_tf,
-                     "algorithmic_tflops_over_summed_stage_time": algo_flops / (gpu_ms * 1e-3) / 1e12 if gpu_ms > 0 else 0.0,
-                     "note": "the Winograd forms: the 3x3 / stride 1 convs on 7x7 maps run 1 / 3.64 of their multiplies, the polyphase 5x5 / "
-                             "stride 2 conv 1 / 3.06, the polyphase 7x7 / stride 2 conv 1 / 4.7, the 3x3 inside a bottleneck chain 1 / 2.25.  "
-                             "algorithmic_flops_over_peak counts DIRECT-convolution FLOPs instead: a throughput-equivalent, NOT a "
-                             "utilisation -- it can exceed 1 under Winograd."},
         }
+        if args.full:
+            k2_avg_s = sum(k2_us) / len(k2_us) * 1e-6
+            algo_bytes = spec.algorithmic_bytes_sobel_tdiff(B, L)
+            achieved = algo_bytes / k2_avg_s / 1e9
+            unit_f, fus_f = spec.flops_per_clip(L)
+            stage_ms = dict((k, v[0] / max(v[1], 1)) for k, v in stages.items())
+            gpu_ms = sum(stage_ms.values())
+            peak_tf = MFMA_F32_PEAK_TFLOPS
+            algo_flops = (unit_f + fus_f) * B                  # per rank; ms_step is a rank's time: the fractions below are per GPU
+            exec_flops = algo_flops - winograd_saved_flops(B * (L - 1), args.precision) if wino_on else algo_flops
+            s_blocks = next((k for k in (in_path or {}).get("kernels", []) if k["launch"].startswith("units:sobel S-blocks")), None)
+            res.update({
+                "roofline": {"bound": "hbm", "kernel": "sobel_tdiff_kernel (K2: temporal difference + spatial gradient + concat, "
+                                                       "all nine sites, one launch; offk_sobel_tdiff_all)",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(B, L, args.variant),
+                             "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": k2_avg_s * 1e6,
+                             "min_launch_us": min(k2_us), "launches": len(k2_us) * K2_PER_PAIR,
+                             "on_default_forward_path": False,
+                             "in_path": None if s_blocks is None else {
+                                 "kernel": "sobel_tdiff_kernel<..., ROLES = 3> (the S-blocks: read D, depthwise 3x3 / diagonal Sobel, write S)",
+                                 "achieved": s_blocks["achieved_gbs"], "frac": s_blocks["frac"], "avg_launch_us": s_blocks["avg_ms"] * 1e3,
+                                 "algorithmic_bytes_per_launch": s_blocks["algorithmic_bytes"]},
+                             "quote_as": "%.2f of 8 TB/s standalone (the whole Sobel + temporal-difference kernel) / %s in path (its S-blocks, "
+                                         "the part the timed forward launches)" % (achieved / HBM_PEAK_GBS,
+                                                                                   "n/a" if s_blocks is None else "%.2f" % s_blocks["frac"]),
+                             "path_note": "the north-star object (Sobel + temporal-diff kernel) launched STANDALONE: the default "
+                                          "inference forward fuses the temporal difference into the 1x1 reduce (pw_tdiff, MFMA-bound) "
+                                          "and runs only this kernel's S-blocks; the full kernel serves training and "
+                                          "OFFK_FUSED_UNITS=0.  What bounds the kernels the timed forward launches: roofline_in_path",
+                             "how": "%d standalone launches between one HIP-event pair on the forward's stream, after every "
+                                    "forward of a second K-step loop (the wall-clock loop runs without any event); an event "
+                                    "pair around a single launch adds ~5 us of command-processor time to this kernel -- "
+                                    "rocprofv3's kernel-trace average (profiles/) is the cross-check" % K2_PER_PAIR},
+                "stage_ms": stage_ms,
+                "mfma": {"peak_tflops": peak_tf,
+                         "executed_flops_per_step": exec_flops,
+                         "executed_frac_of_peak": exec_flops / (ms_step * 1e-3) / 1e12 / peak_tf,
+                         "executed_frac_is": "fp32-equivalent FLOPs the matrix pipes execute (direct-conv FLOPs minus what the Winograd forms save) / "
+                                             "wall-clock ms_per_step / the fp32 MFMA peak 157.3 TF, per GPU" +
+                                             ("; in split-fp32 mode the units kernel, the Winograd GEMMs and the 7x7-map 1x1 convs run six bf16 plane "
+                                              "products per fp32 product on the 2.5 PF bf16 pipe, so this is a throughput-equivalent there, "
+                                              "not a utilisation" if args.precision == "f32split" else ""),
+                         "algorithmic_flops_per_step": algo_flops,
+                         "algorithmic_flops_over_peak": algo_flops / (ms_step * 1e-3) / 1e12 / peak_tf,
+                         "algorithmic_tflops_over_summed_stage_time": algo_flops / (gpu_ms * 1e-3) / 1e12 if gpu_ms > 0 else 0.0,
+                         "note": "the Winograd forms: the 3x3 / stride 1 convs on 7x7 maps run 1 / 3.64 of their multiplies, the polyphase 5x5 / "
+                                 "stride 2 conv 1 / 3.06, the polyphase 7x7 / stride 2 conv 1 / 4.7, the 3x3 inside a bottleneck chain 1 / 2.25.  "
+                                 "algorithmic_flops_over_peak counts DIRECT-convolution FLOPs instead: a throughput-equivalent, NOT a "
+                                 "utilisation -- it can exceed 1 under Winograd."},
+            })
         if in_path is not None:
             dom = max((k for k in in_path["kernels"] if "frac" in k), key=lambda k: k["avg_ms"], default=None)
             if dom is not None:
@@ -1166,7 +1225,7 @@ def main():
                                          "note": "NOT a scaling number: %d ranks time-share %d GPU(s); this run exists to execute "
                                                  "the multi-rank code path (clip_offset sharding, alternating buffers, the score "
                                                  "exchange, max-over-ranks timing) on hardware" % (world, ndev)}
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             other = "f32split" if args.precision == "fp32" else "fp32"
             _h2, dt2, st2, _k2 = measure(other, args.steps, args.warmup)
             sec = {"value": B * args.steps / dt2, "unit": "clips/s", "ms_per_step": dt2 / args.steps * 1e3,

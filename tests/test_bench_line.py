@@ -98,10 +98,11 @@ def test_compact_line_of_a_multi_rank_result_has_no_secondary_objects():
 
 @pytest.mark.gpu
 def test_the_real_line_parses_and_fits(tmp_path):
-    """`python bench.py --steps 2 --warmup 1 --cpu-clips 0` as a child: the last stdout line is THE line, under 8 KB, every key there but
-    the CPU baseline; the full object went to the detail file."""
+    """`python bench.py --full --steps 2 --warmup 1 --cpu-clips 0` as a child: the last stdout line is THE line, under 8 KB, every key
+    there but the CPU baseline; the full object went to the detail file."""
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-clips", "0", "--detail", detail],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-clips", "0",
+                        "--detail", detail],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = r.stdout.strip().splitlines()
@@ -110,3 +111,34 @@ def test_the_real_line_parses_and_fits(tmp_path):
     assert "split-fp32" in line["dtype"] and line["f32split_mode"].get("headline") is True
     full = json.load(open(detail))
     assert full["value"] == pytest.approx(line["value"], rel=1e-4) and "split_launches" in full and "kernels" in full["roofline_in_path"]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A run without --full: the headline keys and none of the --full objects; --dump-outputs holds the three heads' scores of the
+    last timed step, and they are the oracle's on the same synthetic inputs."""
+    import numpy as np
+    import torch
+    import offk_amd  # noqa: F401
+    from offk_amd import spec, synth
+    from oracle import off_oracle as orc
+    B, L = 2, 7
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--length", str(L), "--steps", "3", "--warmup", "1",
+                        "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and "split-fp32" in line["dtype"]
+    assert abs(line["value"] - B * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+    for k in ("roofline", "roofline_in_path", "mfma", "cpu_baseline", "fp32_pipe_mode", "flow_variant", "two_stream", "rccl_single_rank_smoke"):
+        assert k not in line, k
+    w = orc.to_torch_weights(synth.make_weights(spec.VARIANT_RGB))
+    with torch.no_grad():
+        want = orc.off_forward([torch.from_numpy(f) for f in synth.make_features(B, L, config_id=2)], w, B, L, spec.VARIANT_RGB)
+    for name, ref in zip(("logits_7", "logits_14", "logits_28"), want):
+        got = np.load(str(dump / (name + ".npy")))
+        assert got.dtype == np.float32 and got.shape == (B * (L - 1), spec.NUM_CLASSES), (name, got.dtype, got.shape)
+        ref = ref.double().numpy()
+        assert np.abs(got - ref).max() / np.abs(ref).max() < 1e-3, name

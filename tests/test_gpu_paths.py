@@ -310,7 +310,7 @@ def test_single_rank_rccl_smoke():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--collective-smoke", "--batch", "8", "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--collective-smoke", "--full", "--batch", "8", "--steps", "3",
                         "--warmup", "1", "--no-secondary"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -27,8 +27,8 @@ def test_two_oversubscribed_ranks_exchange_the_oracles_scores(tmp_path, collecti
     dump = str(tmp_path / "scores.npy")
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--oversubscribe", "--batch", str(B), "--steps", "3",
-           "--warmup", "1", "--collective", collective, "--dump-scores", dump]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--oversubscribe", "--full", "--batch", str(B),
+           "--steps", "3", "--warmup", "1", "--collective", collective, "--dump-scores", dump]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
