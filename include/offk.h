@@ -23,7 +23,7 @@
  *    two-kernel form (K1 then K2), which offk_off_units / offk_off_units_train always use (the backward needs G).  Both
  *    give the same values (to 2e-6 in fp32: the fused kernel sums k in another grouping).
  *  - a handle is not thread-safe; distinct handles are independent.
- *  - fp32 everywhere.  Boundary tensors are NCHW contiguous exactly as the reference
+ *  - fp32 everywhere (16-bit feature maps: offk_forward_typed).  Boundary tensors are NCHW contiguous exactly as the reference
  *    backbone produces them; INTERNAL activations (workspace, stage entry points) are
  *    channels-last: [rows = image*H*W + y*W + x][channels], see DESIGN.md.
  */
@@ -156,6 +156,32 @@ typedef struct offk_feat_parts {
 int offk_forward_parts(offk_handle* h, void* stream, const offk_feat_parts parts[OFFK_NUM_SITES],
                        float* out7, float* out14, float* out28, void* workspace);
 
+/* 16-bit feature maps (ABI v10, additive).  A backbone run under torch.autocast hands the nine maps over in fp16 (autocast's
+ * default) or bf16; these entries take them as they are, with no fp32 copy.
+ *   feat_dtype OFFK_FEAT_F32: exactly offk_forward / offk_forward_parts / offk_off_units_fused (feats cast to const float*).
+ *   OFFK_FEAT_BF16 / OFFK_FEAT_F16: feats[i] (and offk_feat_parts.data[q], which then holds the address of 16-bit elements cast
+ *   to const float*) point at [B*L, C_i, H_i, H_i] NCHW maps of that type, 4-byte aligned (the units kernel reads the 28x28 and
+ *   14x14 sites as pixel pairs).  Outputs, workspace (offk_workspace_bytes is unchanged) and stream rules are offk_forward's:
+ *   no synchronisation and no allocation on the call, stream-capturable.
+ * Contract: for FINITE maps the three heads and the workspace regions the units fill (the unit channels of fusion_28/14/7,
+ * D_<site>) are EQUAL, element for element (only the sign of a zero may differ), to what the same handle computes from
+ * x.float() -- not a new tolerance.  Why: a bf16 value is exactly its own leading bf16 plane (x_m = x_l = +0), an fp16 value
+ * (11 significant bits, subnormals included: each is a normal number in bf16's exponent range) exactly two (x_l = +0).  The
+ * fp32-map units kernel issues per output tile and 32-k group, into A2: w_l x_h, w_h x_l, w_m x_m, w_m x_h, w_h x_m, then
+ * into A1: w_h x_h; the products of a +0 plane are +-0.  The 16-bit kernel (csrc/pw_tdiff_f16.hip) issues the other MFMAs --
+ * bf16 three, fp16 five -- with the same k in the same operand slots, in the same order, into the same two accumulators,
+ * from the same weight plane image, and ends in the same epilogue; every launch after it is the fp32-map path's, on the
+ * same buffers.  Non-finite maps are outside the equality: every output a non-finite value touches is non-finite, as in
+ * the split mode.
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: an unknown feat_dtype; a 16-bit dtype on an
+ * OFFK_PRECISION_FP32 handle; an NHWC handle; a handle created with OFFK_FUSED_UNITS=0; any gen / down weight bound
+ * through offk_bind_weight; a data pointer that is not 4-byte aligned. */
+enum offk_feat_dtype { OFFK_FEAT_F32 = 0, OFFK_FEAT_BF16 = 1, OFFK_FEAT_F16 = 2 };
+int offk_forward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                       float* out7, float* out14, float* out28, void* workspace);
+int offk_forward_parts_typed(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES],
+                             float* out7, float* out14, float* out28, void* workspace);
+
 /* Named regions of the workspace after offk_forward (for stage-level parity tests):
  * "G_<site>", "D_<site>", "fusion_28", "fusion_14", "fusion_7", "sum_7".  All channels-last. */
 int offk_workspace_region(const offk_handle* h, const char* name, size_t* offset_bytes, size_t* nbytes);
@@ -205,6 +231,9 @@ int offk_off_units(offk_handle* h, void* stream, const float* const feats[OFFK_N
  * temporal difference in one kernel (T and S straight into the fusion_<28|14|7> regions, D_<site> filled, G_<site> NOT) --
  * in the handle's arithmetic (OFFK_PRECISION_F32SPLIT: the split-fp32 kernel).  For stage tests and profiling. */
 int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace);
+/* The same stage for 16-bit maps (offk_forward_typed's dtypes, checks and contract). */
+int offk_off_units_fused_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                               void* workspace);
 
 /* K4. Generic channels-last convolution (the fusion convs, RGB_OFF.py:657-685,762-780,
  * 833-841): y = post( pre(conv(in(x)) + bias) + res ).  x,y,res are channel-sliced views

@@ -12,6 +12,7 @@ STAGE_NAMES = ("pw_reduce", "sobel_tdiff", "fusion_28", "fusion_14", "fusion_7",
 CONV_RELU_IN, CONV_RELU_PRE, CONV_RELU_POST = 1, 2, 4
 PRECISION_FP32, PRECISION_F32SPLIT = 0, 2
 PRECISIONS = {"fp32": 0, "f32split": 2}      # (1 was "bf16x3", retired in ABI v9)
+FEAT_F32, FEAT_BF16, FEAT_F16 = 0, 1, 2      # enum offk_feat_dtype (offk_forward_typed)
 
 
 class OffkError(RuntimeError):
@@ -50,6 +51,8 @@ SIGNATURES = {
     "offk_workspace_bytes": (_c.c_size_t, [_P]),
     "offk_forward": (_I, [_P, _P, _c.POINTER(_F), _F, _F, _F, _P]),
     "offk_forward_parts": (_I, [_P, _P, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
+    "offk_forward_typed": (_I, [_P, _P, _I, _c.POINTER(_P), _F, _F, _F, _P]),
+    "offk_forward_parts_typed": (_I, [_P, _P, _I, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
     "offk_workspace_region": (_I, [_P, _c.c_char_p, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
     "offk_set_profiling": (_I, [_P, _I]),
     "offk_stage_times": (_I, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _I]),
@@ -59,6 +62,7 @@ SIGNATURES = {
     "offk_sobel_tdiff_all": (_I, [_P, _P, _P, _I]),
     "offk_off_units": (_I, [_P, _P, _c.POINTER(_F), _P]),
     "offk_off_units_fused": (_I, [_P, _P, _c.POINTER(_F), _P]),
+    "offk_off_units_fused_typed": (_I, [_P, _P, _I, _c.POINTER(_P), _P]),
     "offk_conv2d": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _F, _I, _I, _I, _F, _I, _I]),
     "offk_conv2d_ex": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _F, _I, _I, _I, _F, _I, _I,
                             _I, _I, _F, _c.c_size_t, _I]),

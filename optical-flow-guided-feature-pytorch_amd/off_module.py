@@ -112,7 +112,8 @@ class OFFSubNetwork(nn.Module):
     def forward(self, feats, want28=True):
         """feats: the nine ``inception_{3a..5b}_output_out`` maps [B*L, C, H, H] fp32 on a HIP
         device -- each either the concatenated tensor or the list of its inception branches in
-        torch.cat order (then the concat never has to exist, offk_forward_parts).  Returns (fc_action_motion_7, fc_action_motion_14, fc_action_motion_28):
+        torch.cat order (then the concat never has to exist, offk_forward_parts).  bf16 / fp16 maps of one dtype (an autocast
+        backbone's) go through as they are on a precision="f32split" module (offk_forward_typed: the values of the maps upcast).  Returns (fc_action_motion_7, fc_action_motion_14, fc_action_motion_28):
         [B*(L-1), classes] each, or [B, classes] with the consensus average."""
         feats = [f.contiguous() if torch.is_tensor(f) else [g.contiguous() for g in f] for f in feats]
         first = feats[0] if torch.is_tensor(feats[0]) else feats[0][0]

@@ -29,6 +29,28 @@ def _check_dev(t, name, device):
         raise ValueError("%s lives on %s, handle on %s" % (name, t.device, device))
 
 
+# 16-bit feature maps (offk_forward_typed): what an autocast backbone hands over
+_FEAT_DTYPES = {torch.bfloat16: _lib.FEAT_BF16, torch.float16: _lib.FEAT_F16}
+
+
+def _check_dev16(t, name, device):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype in _FEAT_DTYPES and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous bf16 or fp16 CUDA/HIP tensor" % name)
+    if t.device != device:
+        raise ValueError("%s lives on %s, handle on %s" % (name, t.device, device))
+
+
+def feat_dtype(feats):
+    """The one dtype of nine feature maps (tensors or lists of channel groups); ValueError when they mix dtypes."""
+    dts = set()
+    for f in feats:
+        for t in ([f] if torch.is_tensor(f) else list(f)):
+            dts.add(t.dtype if torch.is_tensor(t) else type(t))
+    if len(dts) != 1:
+        raise ValueError("feature maps must all have one dtype, got %s" % sorted(str(d) for d in dts))
+    return dts.pop()
+
+
 class OffForward:
     """One liboffk handle for a fixed (batch, length, variant).
 
@@ -134,18 +156,29 @@ class OffForward:
     def out_rows(self):
         return self.batch if self.consensus else self.P
 
-    def _feat_array(self, feats):
+    def _feat16(self, feats):
+        """enum offk_feat_dtype of 16-bit maps, None for fp32 ones (the untyped entries, exactly as before)."""
+        if len(feats) != spec.NUM_SITES:
+            raise ValueError("need nine feature maps")
+        dt = feat_dtype(feats)
+        if dt not in _FEAT_DTYPES:
+            return None
+        if self.precision != _lib.PRECISION_F32SPLIT:
+            raise ValueError("bf16 / fp16 feature maps need a split-fp32 handle (precision=\"f32split\"); this one runs the fp32 pipe")
+        return _FEAT_DTYPES[dt]
+
+    def _feat_array(self, feats, check=_check_dev):
         if len(feats) != spec.NUM_SITES:
             raise ValueError("need nine feature maps")
         shapes = spec.feature_shapes(self.batch, self.length)
         for i, (f, s) in enumerate(zip(feats, shapes)):
-            _check_dev(f, "feats[%d]" % i, self.device)
+            check(f, "feats[%d]" % i, self.device)
             want = s if self.feat_layout == 0 else (s[0], s[2], s[3], s[1])
             if tuple(f.shape) != tuple(want):
                 raise ValueError("feats[%d] has shape %s, expected %s" % (i, tuple(f.shape), tuple(want)))
         return (ctypes.c_void_p * spec.NUM_SITES)(*[f.data_ptr() for f in feats])
 
-    def _parts_array(self, feats):
+    def _parts_array(self, feats, check=_check_dev):
         """feats[i] is a tensor or a sequence of 1..4 tensors (channel groups in concat order)."""
         shapes = spec.feature_shapes(self.batch, self.length)
         arr = (_lib.OffkFeatParts * spec.NUM_SITES)()
@@ -155,7 +188,7 @@ class OffForward:
                 raise ValueError("feats[%d]: 1..4 channel groups" % i)
             arr[i].n_parts = len(parts)
             for q, t in enumerate(parts):
-                _check_dev(t, "feats[%d][%d]" % (i, q), self.device)
+                check(t, "feats[%d][%d]" % (i, q), self.device)
                 c = t.shape[1] if self.feat_layout == 0 else t.shape[3]
                 want = (s[0], c, s[2], s[3]) if self.feat_layout == 0 else (s[0], s[2], s[3], c)
                 if tuple(t.shape) != want:
@@ -165,6 +198,11 @@ class OffForward:
         return arr
 
     def forward(self, feats, want28=True):
+        """feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (split-fp32 handles: offk_forward_typed, the values of
+        the same maps upcast); each map a tensor or a list of its channel groups.  Logits are fp32 either way."""
+        fdt = self._feat16(feats)
+        if fdt is not None:
+            return self._forward16(feats, fdt, want28)
         if any(not torch.is_tensor(f) for f in feats):
             arr = self._parts_array(feats)
             rows = self.out_rows()
@@ -183,6 +221,21 @@ class OffForward:
                                          _ptr(self.workspace)), self._h)
         return out7, out14, out28
 
+    def _forward16(self, feats, fdt, want28):
+        rows = self.out_rows()
+        out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
+        out14 = torch.empty_like(out7)
+        out28 = torch.empty_like(out7) if want28 else None
+        if any(not torch.is_tensor(f) for f in feats):
+            arr = self._parts_array(feats, _check_dev16)
+            _lib.check(self.lib.offk_forward_parts_typed(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14),
+                                                         _ptr(out28), _ptr(self.workspace)), self._h)
+        else:
+            arr = self._feat_array(feats, _check_dev16)
+            _lib.check(self.lib.offk_forward_typed(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
+                                                   _ptr(self.workspace)), self._h)
+        return out7, out14, out28
+
     def forward_into(self, feat_array, out7, out14, out28):
         """Launch-only variant for benchmarking: pre-validated ctypes array + outputs."""
         _lib.check(self.lib.offk_forward(self._h, _stream(self.device), feat_array, _ptr(out7), _ptr(out14), _ptr(out28),
@@ -193,7 +246,13 @@ class OffForward:
         _lib.check(self.lib.offk_off_units(self._h, _stream(self.device), arr, _ptr(self.workspace)), self._h)
 
     def off_units_fused(self, feats):
-        """The units as forward() runs them (fused K1T + S-blocks, the handle's arithmetic); results in the fusion_* / D_* regions."""
+        """The units as forward() runs them (fused K1T + S-blocks, the handle's arithmetic); results in the fusion_* / D_* regions.
+        bf16 / fp16 maps (split-fp32 handles): offk_off_units_fused_typed."""
+        fdt = self._feat16(feats)
+        if fdt is not None:
+            arr = self._feat_array(feats, _check_dev16)
+            _lib.check(self.lib.offk_off_units_fused_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace)), self._h)
+            return
         arr = self._feat_array(feats)
         _lib.check(self.lib.offk_off_units_fused(self._h, _stream(self.device), arr, _ptr(self.workspace)), self._h)
 

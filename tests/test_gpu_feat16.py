@@ -1,0 +1,331 @@
+"""16-bit feature maps on split-fp32 handles (offk_forward_typed, offk_forward_parts_typed, offk_off_units_fused_typed;
+csrc/pw_tdiff_f16.hip).  The contract is equality, not a tolerance: for finite maps everything the 16-bit path computes is
+torch.equal to what the same handle computes from the maps upcast to fp32 (include/offk.h)."""
+import ctypes
+
+import pytest
+import torch
+
+import offk_amd  # noqa: F401
+from offk_amd import _lib, spec, synth
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+
+@pytest.fixture(scope="module")
+def rt():
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from offk_amd import runtime
+    return runtime
+
+
+def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, consensus=None, precision="f32split", **kw):
+    h = rt.OffForward(B, L, variant, slice_mode, consensus, precision=precision, **kw)
+    assert h.load_state_dict(synth.make_weights(variant)) == []
+    return h
+
+
+def relu_maps(B, L, dtype, seed):
+    """ReLU-like synthetic maps, made on the device and rounded to `dtype`."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return [torch.relu(torch.randn(B * L, C, H, H, device="cuda", generator=g)).to(dtype).contiguous() for _, C, H in spec.SITES]
+
+
+def bit_maps(B, L, dtype, seed, full_mantissa=False):
+    """Random finite 16-bit patterns: both signs, every mantissa bit in play (or all set), exponents from the subnormals
+    (exponent field 0) up to 2^10 (fp16) / 2^10 (bf16, from 2^-27)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    out = []
+    for _, C, H in spec.SITES:
+        n = B * L * C * H * H
+        r = torch.randint(0, 1 << 30, (n,), device="cuda", generator=g, dtype=torch.int64)
+        sign = (r & 1) << 15
+        if dtype == torch.float16:
+            mant = torch.full_like(r, 0x3ff) if full_mantissa else (r >> 1) & 0x3ff
+            e = (r >> 11) % 26                                        # 0 (subnormal) .. 25 (2^10)
+            bits = sign | (e << 10) | mant
+        else:
+            mant = torch.full_like(r, 0x7f) if full_mantissa else (r >> 1) & 0x7f
+            e = (r >> 11) % 38
+            e = torch.where(e == 0, e, e + 100)                       # 0 (subnormal) or 101 .. 137
+            bits = sign | (e << 7) | mant
+        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
+        out.append(bits.to(torch.int16).view(dtype).view(B * L, C, H, H).contiguous())
+    return out
+
+
+def heavy_maps(B, L, dtype, seed):
+    """Heavy-tailed maps within fp16's range (expm1 of a scaled normal, up to ~1e4)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return [torch.expm1(1.5 * torch.randn(B * L, C, H, H, device="cuda", generator=g)).clamp(max=3e4).to(dtype).contiguous()
+            for _, C, H in spec.SITES]
+
+
+def unit_regions(h):
+    """Copies of what the units write: the 160 unit channels of every site in its fusion buffer, and D_<site>."""
+    P = h.P
+    out = []
+    for fkey, fd in spec.FUSION.items():
+        width = 160 * len(fd["sites"]) + fd["carry"]
+        buf = h.region("fusion_" + fkey, width).view(P, fd["H"], fd["H"], width)
+        for i, sname in enumerate(fd["sites"]):
+            out.append(buf[..., 160 * i:160 * i + 160].clone())
+            out.append(h.region("D_" + sname, 32).clone())
+    return out
+
+
+def units_equal(h, x16):
+    h.workspace.fill_(0xff)                            # (NaN in every float: what the units leave unwritten shows)
+    h.off_units_fused([x.float() for x in x16])
+    ref = unit_regions(h)
+    h.workspace.fill_(0xff)
+    h.off_units_fused(x16)
+    got = unit_regions(h)
+    torch.cuda.synchronize()
+    for a, b in zip(got, ref):
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b)
+
+
+def split_parts(x, i):
+    """Channel groups of map i in concat order (multiples of 32; 1 .. 4 groups by site)."""
+    C = x.shape[1]
+    cuts = [[C], [C // 2 // 32 * 32, C], [64, 128, C], [32, 96, 224, C]][i % 4]
+    parts, a = [], 0
+    for b in cuts:
+        parts.append(x[:, a:b].contiguous())
+        a = b
+    return parts
+
+
+# ---- 1. the units stage ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("slice_mode", [spec.SLICE_FLAT, spec.SLICE_PER_CLIP])
+@pytest.mark.parametrize("B,L", [(1, 2), (3, 3), (2, 9), (5, 7), (3, 7)])
+def test_units_stage_equals_fp32_maps(rt, name, slice_mode, B, L):
+    """fusion_* unit channels and D_<site> after off_units_fused(x16) == after off_units_fused(x16.float()): short clips, two temporal
+    groups (L = 9), odd batches (pixel pairs and the 7x7 stream across clip boundaries); flat slicing at (3, 7) puts quirk Q1's
+    down rows across clips."""
+    h = make_handle(rt, B, L, slice_mode=slice_mode)
+    units_equal(h, relu_maps(B, L, DTYPES[name], 11 * B + L))
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("kind", ["full_mantissa", "random_bits", "heavy_tail"])
+def test_units_stage_input_kinds(rt, name, kind):
+    """Every mantissa bit set, random bit patterns (negative values, subnormals of the 16-bit type, exponents over 37 octaves), a heavy tail."""
+    B, L = 3, 4
+    dt = DTYPES[name]
+    x = heavy_maps(B, L, dt, 3) if kind == "heavy_tail" else bit_maps(B, L, dt, 4, full_mantissa=kind == "full_mantissa")
+    h = make_handle(rt, B, L)
+    units_equal(h, x)
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_units_stage_subnormal_maps(rt, name):
+    """Maps of subnormals only (bf16: 2^-133 .. 2^-126; fp16: 2^-24 .. 2^-14): the accumulators themselves end up fp32 subnormals,
+    so the MFMAs the 16-bit kernel drops (all products +-0) are shown to leave such an accumulator as it is."""
+    B, L = 2, 3
+    dt = DTYPES[name]
+    g = torch.Generator(device="cuda").manual_seed(9)
+    x = []
+    for _, C, H in spec.SITES:
+        n = B * L * C * H * H
+        r = torch.randint(0, 1 << 20, (n,), device="cuda", generator=g, dtype=torch.int64)
+        bits = ((r & 1) << 15) | ((r >> 1) & (0x3ff if dt == torch.float16 else 0x7f))
+        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
+        x.append(bits.to(torch.int16).view(dt).view(B * L, C, H, H).contiguous())
+    h = make_handle(rt, B, L)
+    units_equal(h, x)
+
+
+# ---- 2. the whole forward ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("B,L,variant,consensus,parts", [(64, 7, spec.VARIANT_RGB, False, False), (64, 7, spec.VARIANT_FLOW, True, True),
+                                                         (10, 25, spec.VARIANT_RGB, True, True), (10, 25, spec.VARIANT_FLOW, False, False)])
+def test_forward_equals_fp32_maps(rt, name, B, L, variant, consensus, parts):
+    h = make_handle(rt, B, L, variant, consensus=consensus)
+    x16 = relu_maps(B, L, DTYPES[name], 7)
+    ref = h.forward([x.float() for x in x16])
+    got = h.forward([split_parts(x, i) for i, x in enumerate(x16)] if parts else x16)
+    torch.cuda.synchronize()
+    for a, b in zip(got, ref):
+        assert a.dtype == torch.float32 and torch.isfinite(a).all()
+        assert torch.equal(a, b)
+
+
+# ---- 4. the oracle anchor ----
+
+def test_forward_f16_against_oracle(rt):
+    from oracle import off_oracle as orc
+    B, L = 2, 3
+    w = synth.make_weights(spec.VARIANT_RGB)
+    x16 = [torch.from_numpy(f).cuda().half().contiguous() for f in synth.make_features(B, L, 9)]
+    h = rt.OffForward(B, L, spec.VARIANT_RGB, precision="f32split")
+    h.load_state_dict(w)
+    out = h.forward(x16)
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        ref = orc.off_forward([x.float().cpu() for x in x16], orc.to_torch_weights(w), B, L, spec.VARIANT_RGB)
+    for o, r in zip(out, ref):
+        err = (o.cpu().double() - r.double()).abs().max().item() / r.double().abs().max().item()
+        assert err < 1e-3, err
+
+
+# ---- 5. capture and determinism ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_forward_typed_capture_and_determinism(rt, name):
+    B, L = 3, 7
+    h = make_handle(rt, B, L)
+    x16 = relu_maps(B, L, DTYPES[name], 21)
+    arr = h._feat_array(x16, rt._check_dev16)
+    fdt = _lib.FEAT_BF16 if name == "bf16" else _lib.FEAT_F16
+    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
+
+    def launch():
+        _lib.check(h.lib.offk_forward_typed(h._h, rt._stream(h.device), fdt, arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
+                                            ctypes.c_void_p(h.workspace.data_ptr())), h._h)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        launch()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    eager = [o.clone() for o in out]
+    again = h.forward(x16)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(eager, again))
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        launch()
+    for o in out:
+        o.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(eager, out))
+
+
+# ---- 6. what is refused, before any launch ----
+
+def _raw_call(h, rt, fdt, x16):
+    """offk_forward_typed straight through ctypes (no Python-side checks); returns (rc, message)."""
+    arr = (ctypes.c_void_p * spec.NUM_SITES)(*[x.data_ptr() for x in x16])
+    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
+    rc = h.lib.offk_forward_typed(h._h, rt._stream(h.device), fdt, arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
+                                  ctypes.c_void_p(h.workspace.data_ptr()))
+    return rc, h.lib.offk_last_error(h._h).decode()
+
+
+def _assert_refused(h, rt, fdt, x16, needle):
+    h.workspace.fill_(0x5a)
+    torch.cuda.synchronize()
+    rc, msg = _raw_call(h, rt, fdt, x16)
+    torch.cuda.synchronize()
+    assert rc == -1 and needle in msg, (rc, msg)
+    assert bool((h.workspace == 0x5a).all())              # nothing was enqueued
+
+
+def test_refusals(rt, monkeypatch):
+    B, L = 2, 3
+    x16 = relu_maps(B, L, torch.bfloat16, 1)
+    # unknown dtype
+    _assert_refused(make_handle(rt, B, L), rt, 7, x16, "unknown feat_dtype")
+    # fp32-pipe handle: in C, and in Python with a message naming precision="f32split"
+    h32 = make_handle(rt, B, L, precision="fp32")
+    _assert_refused(h32, rt, _lib.FEAT_BF16, x16, "OFFK_PRECISION_F32SPLIT")
+    with pytest.raises(ValueError, match="f32split"):
+        h32.forward(x16)
+    # NHWC handle
+    _assert_refused(make_handle(rt, B, L, feat_layout=1), rt, _lib.FEAT_BF16, x16, "NCHW")
+    # OFFK_FUSED_UNITS=0
+    monkeypatch.setenv("OFFK_FUSED_UNITS", "0")
+    hu = make_handle(rt, B, L)
+    monkeypatch.delenv("OFFK_FUSED_UNITS")
+    _assert_refused(hu, rt, _lib.FEAT_F16, [x.half() for x in x16], "OFFK_FUSED_UNITS")
+    # a bound gen weight
+    hb = make_handle(rt, B, L)
+    wg = torch.from_numpy(synth.make_weights(spec.VARIANT_RGB)["motion_conv_gen_3a.weight"]).cuda().contiguous()
+    hb.bind_weight("motion_conv_gen_3a.weight", wg)
+    _assert_refused(hb, rt, _lib.FEAT_BF16, x16, "offk_bind_weight")
+    # a pointer one element off alignment
+    h = make_handle(rt, B, L)
+    bad = list(x16)
+    s = x16[4]
+    buf = torch.empty(s.numel() + 1, dtype=s.dtype, device="cuda")
+    bad[4] = buf[1:].view(s.shape)
+    bad[4].copy_(s)
+    _assert_refused(h, rt, _lib.FEAT_BF16, bad, "4-byte aligned")
+    # mixed dtypes, and the module at its fp32 default
+    with pytest.raises(ValueError, match="one dtype"):
+        h.forward(x16[:8] + [x16[8].half()])
+    from offk_amd.off_module import OFFSubNetwork
+    m = OFFSubNetwork(spec.NUM_CLASSES, B, L, "rgb").cuda()
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(spec.VARIANT_RGB).items()})
+    with pytest.raises(ValueError, match="f32split"):
+        m(x16)
+
+
+# ---- 7. non-finite maps ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_nonfinite_maps(rt, name):
+    """Inf / NaN in a 16-bit map: every D row it touches is non-finite in all 32 channels; every other unit output stays finite."""
+    B, L = 2, 3
+    dt = DTYPES[name]
+    x16 = relu_maps(B, L, dt, 5)
+    x16[0][1, 7, 3, 4] = float("inf")                  # site 3a, frame 1 (clip 0), pixel (3, 4)
+    x16[8][2, 100, 5, 6] = float("nan")                # site 5b, frame 2 (clip 0), pixel (5, 6)
+    h = make_handle(rt, B, L)
+    h.off_units_fused(x16)
+    torch.cuda.synchronize()
+    P = h.P
+    D3a = h.region("D_3a", 32).view(P, 28, 28, 32)
+    D5b = h.region("D_5b", 32).view(P, 7, 7, 32)
+    assert not torch.isfinite(D3a[1, 3, 4]).any() and not torch.isfinite(D5b[2, 5, 6]).any()
+    m3 = torch.ones(P, 28, 28, dtype=torch.bool, device="cuda")
+    m3[1, 3, 4] = False
+    m5 = torch.ones(P, 7, 7, dtype=torch.bool, device="cuda")
+    m5[2, 5, 6] = False
+    assert torch.isfinite(D3a[m3]).all() and torch.isfinite(D5b[m5]).all()
+
+
+# ---- 8. the modules under torch.autocast ----
+
+class ToyBackbone(torch.nn.Module):
+    """Nine maps of the inception shapes out of a 3-channel 28 x 28 input (1x1 convs after average pooling) and a score."""
+
+    def __init__(self):
+        super().__init__()
+        self.convs = torch.nn.ModuleList(torch.nn.Conv2d(3, C, 1) for _, C, _ in spec.SITES)
+        self.fc = torch.nn.Linear(3, spec.NUM_CLASSES)
+
+    def forward(self, x):
+        feats = []
+        for (_, _C, H), conv in zip(spec.SITES, self.convs):
+            feats.append(torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous())
+        return feats, self.fc(x.mean(dim=(2, 3)))
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_bninception_off_under_autocast(rt, name):
+    from offk_amd.off_module import BNInception_OFF
+    B, L = 2, 3
+    torch.manual_seed(0)
+    bb = ToyBackbone().cuda()
+    model = BNInception_OFF(num_classes=spec.NUM_CLASSES, batch=B, length=L, variant="rgb", backbone=bb, precision="f32split").cuda()
+    model.off.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(spec.VARIANT_RGB).items()})
+    x = torch.randn(B * L, 3, 28, 28, device="cuda")
+    with torch.no_grad(), torch.autocast("cuda", dtype=DTYPES[name]):
+        feats, _ = bb(x)
+        assert all(f.dtype == DTYPES[name] for f in feats)
+        fc7, _fgs, fc14 = model(x)
+    with torch.no_grad():
+        r7, r14, _ = model.off([f.float() for f in feats], want28=False)
+    torch.cuda.synchronize()
+    assert fc7.dtype == torch.float32
+    assert torch.equal(fc7, model._squeeze(r7)) and torch.equal(fc14, model._squeeze(r14))

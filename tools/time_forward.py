@@ -1,5 +1,7 @@
 """One process, one library (OFFK_LIB selects an A/B build): wall-clock ms per forward and the per-launch trace.
-    python tools/time_forward.py [batch] [length] [steps] [substring of the launches to list, default: all]"""
+    python tools/time_forward.py [batch] [length] [steps] [substring of the launches to list, default: all]
+OFFK_FEAT_DTYPE=bf16|f16 (with OFFK_PRECISION=f32split): the maps in that dtype through offk_forward_typed (the cast is not timed)."""
+import ctypes
 import os
 import sys
 import time
@@ -9,7 +11,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import offk_amd  # noqa: E402,F401
-from offk_amd import runtime, spec, synth  # noqa: E402
+from offk_amd import _lib, runtime, spec, synth  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 L = int(sys.argv[2]) if len(sys.argv) > 2 else 7
@@ -19,8 +21,19 @@ variant = spec.VARIANT_RGB
 h = runtime.OffForward(B, L, variant, precision=os.environ.get("OFFK_PRECISION", "fp32"))
 h.load_state_dict(synth.make_weights(variant))
 feats = [torch.from_numpy(f).cuda() for f in synth.make_features(B, L, 2)]
-arr = h._feat_array(feats)
 out = [torch.empty(h.out_rows(), 101, device="cuda") for _ in range(3)]
+fdt = {"": None, "f32": None, "bf16": torch.bfloat16, "f16": torch.float16}[os.environ.get("OFFK_FEAT_DTYPE", "")]
+if fdt is None:
+    arr = h._feat_array(feats)
+else:
+    feats = [f.to(fdt) for f in feats]
+    arr = h._feat_array(feats, runtime._check_dev16)
+    code = _lib.FEAT_BF16 if fdt == torch.bfloat16 else _lib.FEAT_F16
+
+    def _typed(arr, o7, o14, o28):
+        _lib.check(h.lib.offk_forward_typed(h._h, runtime._stream(h.device), code, arr, *[ctypes.c_void_p(o.data_ptr()) for o in (o7, o14, o28)],
+                                            ctypes.c_void_p(h.workspace.data_ptr())), h._h)
+    h.forward_into = _typed
 for _ in range(10):
     h.forward_into(arr, *out)
 torch.cuda.synchronize()
@@ -29,8 +42,8 @@ for _ in range(steps):
     h.forward_into(arr, *out)
 torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) / steps * 1e3
-print("lib=%s B=%d L=%d: %.4f ms / forward (%.0f clips/s), checksum %.6f" % (
-    os.path.basename(os.environ.get("OFFK_LIB", "liboffk.so")), B, L, ms, B / ms * 1e3, float(out[0].double().sum())))
+print("lib=%s maps=%s B=%d L=%d: %.4f ms / forward (%.0f clips/s), checksum %.6f" % (
+    os.path.basename(os.environ.get("OFFK_LIB", "liboffk.so")), os.environ.get("OFFK_FEAT_DTYPE", "f32") or "f32", B, L, ms, B / ms * 1e3, float(out[0].double().sum())))
 h.set_profiling(2)
 h.launch_times(reset=True)
 for _ in range(20):
