@@ -406,6 +406,44 @@ int offk_off_units_backward(offk_handle* h, void* stream, const float* const fea
                             const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                             float* grads, int accumulate);
 
+/* ---- 16-bit feature maps on the training side (additive; ABI version unchanged) -----------
+ * The backbone is frozen in training (train_off.py:39-56) and is what runs under autocast, so its nine maps arrive as
+ * bf16 / fp16.  These four entries are offk_pw_reduce, offk_off_units, offk_off_units_train and offk_off_units_backward
+ * on such maps as they are: NCHW [B*L, C_i, H_i, H_i] of `feat_dtype` (enum offk_feat_dtype), no fp32 copy.
+ * OFFK_FEAT_F32 forwards to the untyped entry.  Outputs, gradients and the workspace stay fp32, and
+ * offk_train_workspace_bytes is unchanged.
+ *
+ * Unlike offk_forward_typed they make no condition on the handle: both precisions (a split-fp32 handle runs its training
+ * side on the fp32 kernels anyway), weights bound through offk_bind_weight, any OFFK_FUSED_UNITS setting (they run the
+ * two-kernel form K1 + K2, never the fused kernel).  Only the two kernels that read the maps have 16-bit forms: K1
+ * (the stacked 1x1 reduces) and K1b (the weight-gradient GEMM dW = A^T X); K2, K2b and the reductions are the untyped
+ * entries' own launches.
+ *
+ * Contract: EQUAL VALUES, not a tolerance.  For the same handle, weights, seed and cotangents, everything a typed call
+ * writes -- G_<site>, D_<site>, the unit channels of fusion_28/14/7, the whole flat gradient buffer in both accumulate
+ * modes -- is bit-equal to what the untyped call writes from the maps widened to fp32 (x.float()); not even the sign of a
+ * zero differs.  Why: a 16-bit loader reads the elements, widens each in registers to the exact fp32 value it stands for
+ * (bf16: a 16-bit shift; fp16: the hardware conversion, subnormals included) and stores it into the LDS position the fp32
+ * loader uses.  From the LDS store on the 16-bit forms are the same kernel text as the fp32 ones: the same fp32 operands
+ * in the same LDS slots, the same MFMA sequence in the same order, the same epilogue and slab layout, the same
+ * wgrad reduction.  The launch plan does not depend on feat_dtype either: block count, rows per block, the split-K
+ * chunking of K1b, slab sizes and every summation order are the untyped call's.  Rows past the end of a site read zeros
+ * (K1: through an out-of-range buffer offset; K1b: from the handle's zero page, which serves as 16-bit zeros unchanged).
+ *
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: an unknown feat_dtype; an NHWC handle; a null map; a map
+ * pointer that is not 8-byte aligned (the 14x14 / 28x28 sites fetch four pixels per 8-byte load; every row of those maps
+ * then is 8-byte aligned, the 98-byte rows of the 7x7 sites are read with 2-byte loads); a single map of 2 GiB or more
+ * (the 16-bit loader of K1 exists in the buffer-descriptor form only).  The untyped entries' own checks (dropout
+ * probability, gradient views) apply unchanged. */
+int offk_pw_reduce_typed(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D);
+int offk_off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                         void* workspace);
+int offk_off_units_train_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                               void* workspace, uint64_t drop_seed, double drop_p);
+int offk_off_units_backward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                                  const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed,
+                                  double drop_p, float* grads, int accumulate);
+
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);
 

@@ -16,8 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "liboffk.so")
-SOURCES = ("offk_api.hip", "pw_reduce.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "pw_tdiff.hip",
+SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "pw_tdiff.hip",
            "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip")
+# sources that #include another source: {source: (what it includes, ...)}
+INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",)}
 HEADERS = ("offk_common.h", "offk_internal.h", "winograd_common.h", os.path.join("..", "..", "include", "offk.h"))
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=fast"]
@@ -391,7 +393,7 @@ def build(force=False, verbose=False):
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
-        if force or not _newer(o, [s] + hdrs):
+        if force or not _newer(o, [s] + hdrs + [os.path.join(CSRC, d) for d in INCLUDED_SOURCES.get(src, ())]):
             jobs.append((s, o))
 
     def compile_one(job):

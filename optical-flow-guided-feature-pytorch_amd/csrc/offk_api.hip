@@ -512,8 +512,10 @@ int finalize_pw(offk_handle* h, hipStream_t st) {
   return OFFK_OK;
 }
 
+// feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (the typed training entries; check_feat16_train has passed): K1 runs its 16-bit map form
+// on the same grid; the parts' data pointers then address 16-bit elements.
 int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev,
-                  const DropCfg& drop = DropCfg()) {
+                  const DropCfg& drop = DropCfg(), int feat_dtype = OFFK_FEAT_F32) {
   { int rc = finalize_pw(h, st); if (rc != OFFK_OK) return rc; }
   PwParams pp;
   memset(&pp, 0, sizeof(pp));
@@ -530,8 +532,14 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
   }
   pp.total_blocks = blk;
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
-  { int rc = trace_mark(h, st, "units:pw_reduce (K1)"); if (rc != OFFK_OK) return rc; }
-  HIP_TRY(h, pw_reduce_launch(pp, st));
+  if (feat_dtype != OFFK_FEAT_F32) {
+    if (!pw_reduce_feat16_supported(pp)) return fail(h, OFFK_ERR_INVALID, "16-bit feature maps: a map of 2 GiB or more is not supported");
+    { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, fp16 maps)" : "units:pw_reduce (K1, bf16 maps)"); if (rc != OFFK_OK) return rc; }
+    HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, st));
+  } else {
+    { int rc = trace_mark(h, st, "units:pw_reduce (K1)"); if (rc != OFFK_OK) return rc; }
+    HIP_TRY(h, pw_reduce_launch(pp, st));
+  }
   if (ev) HIP_TRY(h, hipEventRecord(ev[1], st));
 
   { int rc = trace_mark(h, st, "units:sobel_tdiff (K2)"); if (rc != OFFK_OK) return rc; }
@@ -1561,9 +1569,10 @@ int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[
   return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop);
 }
 
-int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
-                            const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
-                            float* grads, int accumulate) {
+// feat_dtype != OFFK_FEAT_F32: feats[] address 16-bit elements and check_feat16_train has passed; only K1b reads them
+static int off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
+                              const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
+                              float* grads, int accumulate, int feat_dtype) {
   if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: null argument");
   if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: NCHW feature maps only");
   DropCfg drop;
@@ -1638,9 +1647,88 @@ int offk_off_units_backward(offk_handle* h, void* stream, const float* const fea
     r.C = w.C; r.cpad = w.ntiles * 128; r.nchunks = w.nchunks; r.nsblocks = nsblocks[s];
   }
   wp.total_blocks = blk;
-  HIP_TRY(h, pw_wgrad_launch(wp, st));
+  if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_wgrad_feat16_launch(wp, feat_dtype, st));
+  else HIP_TRY(h, pw_wgrad_launch(wp, st));
   HIP_TRY(h, wgrad_reduce_launch(rp, st));
   return OFFK_OK;
+}
+
+int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
+                            const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
+                            float* grads, int accumulate) {
+  return off_units_backward(h, stream, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, OFFK_FEAT_F32);
+}
+
+// ---- 16-bit feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_typed and its siblings ----
+// Everything such a call is refused for, checked before anything is enqueued.  Unlike check_feat16 (the inference forward) there is
+// no condition on the handle's precision, on bound weights or on OFFK_FUSED_UNITS: these entries run the fp32 kernels K1 / K1b.
+static int check_feat16_train(offk_handle* h, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
+  const std::string f(fn);
+  if (feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps are NCHW-only (this handle is NHWC)");
+  for (int i = 0; i < count; ++i) {
+    if (!feats[i]) return fail(h, OFFK_ERR_INVALID, f + ": null feature map");
+    if (reinterpret_cast<uintptr_t>(feats[i]) & 7)
+      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature map pointers must be 8-byte aligned (site " + kSites[first + i].name + ")");
+    if ((unsigned long long)h->N * kSites[first + i].H * kSites[first + i].H * kSites[first + i].C * 2ull >= 0x7fffff00ull)
+      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps of 2 GiB or more are not supported (site " + kSites[first + i].name + ")");
+  }
+  return OFFK_OK;
+}
+
+int offk_pw_reduce_typed(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D) {
+  if (feat_dtype == OFFK_FEAT_F32) return offk_pw_reduce(h, stream, site, static_cast<const float*>(feat), G, D);
+  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, "offk_pw_reduce_typed: bad argument");
+  TRY(check_feat16_train(h, feat_dtype, &feat, site, 1, "offk_pw_reduce_typed"));
+  TRY(site_weights_ready(h, site, true, false));
+  DeviceGuard guard(h->cfg.device);
+  PwParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
+  pp.nhwc = 0;
+  pp.zeros = h->zero_page;
+  TRY(finalize_pw(h, static_cast<hipStream_t>(stream)));
+  fill_pw_site(h, site, whole_map(site, static_cast<const float*>(feat)), G, D, &pp.s[0]);
+  pp.total_blocks = pw_blocks_for(pp.s[0].M);
+  HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, static_cast<hipStream_t>(stream)));
+  return OFFK_OK;
+}
+
+static int off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                           const DropCfg& drop, const char* fn) {
+  TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, fn));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  offk_feat_parts parts[kNumSites];
+  for (int s = 0; s < kNumSites; ++s) parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop, feat_dtype);
+}
+
+int offk_off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
+  if (feat_dtype == OFFK_FEAT_F32) return offk_off_units(h, stream, reinterpret_cast<const float* const*>(feats), workspace);
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_typed: null argument");
+  return off_units_typed(h, stream, feat_dtype, feats, workspace, DropCfg(), "offk_off_units_typed");
+}
+
+int offk_off_units_train_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                               uint64_t drop_seed, double drop_p) {
+  if (feat_dtype == OFFK_FEAT_F32)
+    return offk_off_units_train(h, stream, reinterpret_cast<const float* const*>(feats), workspace, drop_seed, drop_p);
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train_typed: null argument");
+  DropCfg drop;
+  TRY(make_drop(h, drop_seed, drop_p, &drop));
+  return off_units_typed(h, stream, feat_dtype, feats, workspace, drop, "offk_off_units_train_typed");
+}
+
+int offk_off_units_backward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                                  const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
+                                  float* grads, int accumulate) {
+  const float* const* f32 = reinterpret_cast<const float* const*>(feats);
+  if (feat_dtype == OFFK_FEAT_F32) return offk_off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate);
+  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward_typed: null argument");
+  TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, "offk_off_units_backward_typed"));
+  return off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype);
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

@@ -157,6 +157,13 @@ struct PwParams {
 };
 int pw_blocks_for(int M);
 hipError_t pw_reduce_launch(const PwParams& p, hipStream_t st);
+// enum offk_feat_dtype for device code (include/offk.h is not seen by the kernels)
+constexpr int kFeatF32 = 0, kFeatBf16 = 1, kFeatF16 = 2;
+// K1 on 16-bit NCHW maps (feat_dtype kFeatBf16 / kFeatF16): xp[] carry pointers to 16-bit elements, 8-byte aligned.  Same grid and
+// the same arithmetic as pw_reduce_launch, so G / D equal the fp32 kernel's on the widened maps.  _supported: NCHW and every part
+// below 2^31 bytes (the 16-bit loaders exist in the buffer-descriptor form only).
+bool pw_reduce_feat16_supported(const PwParams& p);
+hipError_t pw_reduce_feat16_launch(const PwParams& p, int feat_dtype, hipStream_t st);
 
 // ---- K1T: K1 fused with the temporal difference (pw_tdiff.hip) -------------------------
 struct PtSite {
@@ -292,6 +299,8 @@ struct WgParams {
   const float* zeros;   // >= 16 bytes of zeros in device memory: what a masked-out load reads
 };
 hipError_t pw_wgrad_launch(const WgParams& p, hipStream_t st);
+// K1b on 16-bit NCHW maps: as pw_wgrad_launch with xp[] pointing at 16-bit elements (8-byte aligned); same blocks, same slabs
+hipError_t pw_wgrad_feat16_launch(const WgParams& p, int feat_dtype, hipStream_t st);
 
 struct WrSite {
   const float* slab; const float* bpart; const float* dw_part;

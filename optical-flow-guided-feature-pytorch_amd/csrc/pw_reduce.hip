@@ -14,6 +14,10 @@
 // 4 k-rows x 4 pixels per thread with 16-B loads and transposes in registers into the
 // [row][k] LDS image the MFMA core wants.  Outputs are channels-last:
 //   G [N*HW][128] (post-ReLU), D [P*HW][32] (row = output pair index).
+//
+// This file is compiled twice: as it is (the fp32 forms and pw_reduce_launch), and through pw_reduce_f16.hip with
+// OFFK_PW_REDUCE_FEAT16 defined (the bf16 / fp16 map forms and pw_reduce_feat16_launch alone).  Two objects, because the
+// 16-bit instantiations in the same code object changed the register allocation of the fp32 ones.
 #include <cstdlib>
 
 #include "offk_common.h"
@@ -23,7 +27,9 @@ namespace offk {
 
 constexpr int PW_BM = 128, PW_BN = 160, PW_TN = 5;
 
+#ifndef OFFK_PW_REDUCE_FEAT16
 int pw_blocks_for(int M) { return (M + PW_BM - 1) / PW_BM; }
+#endif
 
 // output-pair row of frame f for the spatial branch, or -1 (see spatial_frames in the oracle)
 __device__ __forceinline__ int down_row(int f, int L, int P, int slice_mode) {
@@ -68,10 +74,33 @@ __device__ __forceinline__ void stf(float* q, float v) {
   else *q = v;
 }
 
+// 16-bit feature maps (FEAT = kFeatBf16 / kFeatF16): an element widened to the exact fp32 value it stands for.
+// bf16 is the upper half of an fp32 word; fp16 goes through the hardware conversion, which keeps subnormals.
+template <int FEAT>
+__device__ __forceinline__ float widen16(unsigned h) {   // h: the element in the low 16 bits, upper bits zero
+  if (FEAT == kFeatBf16) return __uint_as_float(h << 16);
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+}
+template <int FEAT>
+__device__ __forceinline__ float4 widen16x4(unsigned lo, unsigned hi) {   // four consecutive elements in two words
+  if (FEAT == kFeatBf16)
+    return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u));
+  return make_float4(widen16<FEAT>(lo & 0xffffu), widen16<FEAT>(lo >> 16), widen16<FEAT>(hi & 0xffffu), widen16<FEAT>(hi >> 16));
+}
+
 // LEAN: buffer-descriptor addressing of the weights and of the NCHW quad loader (mode 0), unconditional prefetch pinned
 // in front of the MFMAs -- as pw_tdiff.hip; needs every feature-map part and the weight tables below 2^31 bytes.
-template <int NT, int LEAN>
+// FEAT: element type of the feature map (enum offk_feat_dtype).  The 16-bit forms (NCHW only, LEAN only) differ from the
+// fp32 kernel in the map loader alone: it fetches half the bytes, keeps them as they are in the prefetch registers and widens
+// them on the way into the SAME LDS positions; everything behind the LDS store is this one text, so their G / D are bit-equal
+// to the fp32 kernel's on the widened maps.  (One template, not a shared body behind three kernels: with the parameter block
+// handed to an inlined function by reference the fp32 forms came out of the compiler changed.)
+template <int V> struct PwMode { static constexpr int value = V; };   // a loader mode known at compile time
+
+template <int NT, int LEAN, int FEAT = kFeatF32>
 __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
+  static_assert(FEAT == kFeatF32 || LEAN, "the 16-bit loaders exist in the buffer-descriptor form only");
+  constexpr int ESZ = FEAT == kFeatF32 ? 4 : 2;   // bytes per feature-map element
   constexpr int LDS_BYTES = (PW_BM + PW_BN) * LDS_K * 4;
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   float* As = reinterpret_cast<float*>(lds);                    // fp32: [128][LDS_K] then [160][LDS_K]
@@ -115,7 +144,7 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   //         8-byte bf16 stores of a group fell into 4 bank positions (60 % of the LDS cycles were conflicts)
   // mode 1: NCHW, any HW      : thread = (pixel i = tid&127, k quads (tid>>7) + 2r)
   // mode 2: channels-last     : thread = (rows (tid>>3)+32r, k quad tid&7)
-  const int mode = p.nhwc ? 2 : ((HW & 3) == 0 ? 0 : 1);
+  const int mode = (FEAT == kFeatF32 && p.nhwc) ? 2 : ((HW & 3) == 0 ? 0 : 1);
   int fr = 0, pix = 0;       // this thread's frame and pixel (modes 0 / 1)
   bool row_ok = true;
   if (mode == 0) {
@@ -154,7 +183,7 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
     wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(S.w), 0, kGenCh * C * 4, 0x00020000);
     wdrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(S.w_down), 0, kDownCh * C * 4, 0x00020000);
     woff = ((tid >> 3) * C + 4 * (tid & 7)) * 4;
-    vA = row_ok ? (koff * HW + pix) * 4 : (int)0x80000000;     // rows past M: an offset past every descriptor -> zeros
+    vA = row_ok ? (koff * HW + pix) * ESZ : (int)0x80000000;   // rows past M: an offset past every descriptor -> zeros
     if (!row_ok) fr = 0;
   }
   auto ld_b = [&](const __amdgpu_buffer_rsrc_t& rs, int voff, int soff) {
@@ -246,8 +275,11 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
   const int nkt = C / BK;
-  load_tile(0);
-  for (int kt = 0; kt < nkt; ++kt) {
+  // (the fp32 loop stays at function scope, switched off by a constant in the 16-bit forms: moved into an `if constexpr` block
+  //  of its own, the fp32 forms came out of the compiler changed)
+  constexpr bool kF32 = FEAT == kFeatF32;
+  if (kF32) load_tile(0);
+  for (int kt = 0; kF32 && kt < nkt; ++kt) {
     store_tile();
     __syncthreads();
     if constexpr (LEAN) {
@@ -265,6 +297,75 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
       else pw_mma<4>(acc, As + wave * 32 * LDS_K, Bs, lane);
     }
     __syncthreads();
+  }
+  if constexpr (!kF32) {
+    // ---- 16-bit maps: a map loader of their own, the weights and everything behind the LDS store as above --------------
+    // rg[0..3] hold the map elements as loaded (bit patterns, never operated on); the store widens them into the fp32
+    // loader's LDS positions.  mode 0: the pixel quad is one 8-byte load through the descriptor (a row past M reads zeros
+    // through its out-of-range offset); mode 1 (98-byte rows): 2-byte loads, zero-extended.  The mode is a compile-time one
+    // (the K loop exists once per mode, a block-uniform choice): with both loaders in one loop the copies that reconciled
+    // their register images behind the loads waited for the prefetch in front of the MFMAs.
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    auto load_tile16 = [&](int k0, auto MT) {
+      const float* xb; int cpart, kl;
+      locate(k0, xb, cpart, kl);
+      if constexpr (decltype(MT)::value == 0) {
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, (M / HW) * cpart * HW * ESZ, 0x00020000);
+        const int voff = fr * (cpart * HW * ESZ) + vA;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(xrs, voff, (kl + j) * HW * ESZ, 0);
+          rg[j].x = __uint_as_float(v.x); rg[j].y = __uint_as_float(v.y);
+        }
+      } else {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const unsigned short* base = reinterpret_cast<const unsigned short*>(xb) + ((size_t)fr * cpart + kl + koff) * HW + pix;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned short* q = base + (size_t)(8 * r) * HW;
+          rg[r] = z;
+          if (row_ok) rg[r] = make_float4(__uint_as_float(q[0]), __uint_as_float(q[HW]), __uint_as_float(q[2 * (size_t)HW]), __uint_as_float(q[3 * (size_t)HW]));
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < PW_TN - 1; ++r) rg[4 + r] = ld_b(wrs, woff, (32 * r * C + k0) * 4);
+      rg[4 + PW_TN - 1] = ld_b(wdrs, woff, k0 * 4);
+    };
+    auto store_tile16 = [&](auto MT) {
+      if constexpr (decltype(MT)::value == 0) {
+        float4 w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = widen16x4<FEAT>(__float_as_uint(rg[j].x), __float_as_uint(rg[j].y));
+        float* dst = As + 4 * (tid >> 3) * LDS_K + 4 * (tid & 7);
+        *reinterpret_cast<float4*>(dst) = make_float4(w[0].x, w[1].x, w[2].x, w[3].x);
+        *reinterpret_cast<float4*>(dst + LDS_K) = make_float4(w[0].y, w[1].y, w[2].y, w[3].y);
+        *reinterpret_cast<float4*>(dst + 2 * LDS_K) = make_float4(w[0].z, w[1].z, w[2].z, w[3].z);
+        *reinterpret_cast<float4*>(dst + 3 * LDS_K) = make_float4(w[0].w, w[1].w, w[2].w, w[3].w);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          *reinterpret_cast<float4*>(As + (tid & 127) * LDS_K + 4 * ((tid >> 7) + 2 * r)) =
+              make_float4(widen16<FEAT>(__float_as_uint(rg[r].x)), widen16<FEAT>(__float_as_uint(rg[r].y)),
+                          widen16<FEAT>(__float_as_uint(rg[r].z)), widen16<FEAT>(__float_as_uint(rg[r].w)));
+      }
+#pragma unroll
+      for (int r = 0; r < PW_TN; ++r)
+        *reinterpret_cast<float4*>(Bs + ((tid >> 3) + 32 * r) * LDS_K + 4 * (tid & 7)) = rg[4 + r];
+    };
+    auto k_loop = [&](auto MT) __attribute__((always_inline)) {
+      load_tile16(0, MT);
+      for (int kt = 0; kt < nkt; ++kt) {
+        store_tile16(MT);
+        __syncthreads();
+        load_tile16(min(kt + 1, nkt - 1) * BK, MT);
+        __builtin_amdgcn_sched_barrier(0);
+        if (down_active) pw_mma<5>(acc, As + wave * 32 * LDS_K, Bs, lane);
+        else pw_mma<4>(acc, As + wave * 32 * LDS_K, Bs, lane);
+        __syncthreads();
+      }
+    };
+    if (mode == 0) k_loop(PwMode<0>());
+    else k_loop(PwMode<1>());
   }
 
   // ---- epilogue ------------------------------------------------------------------
@@ -303,6 +404,31 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   }
 }
 
+
+// Buffer-descriptor addressing needs every feature-map part (elements of `esz` bytes) and the weight tables below 2^31 bytes.
+static bool pw_lean_ok(const PwParams& p, int esz) {
+  for (int i = 0; i < p.nsites; ++i) {
+    for (int q = 0; q < p.s[i].nparts; ++q)
+      if ((unsigned long long)p.s[i].M * p.s[i].cp[q] * (unsigned long long)esz >= 0x7fffff00ull) return false;
+    if ((unsigned long long)kGenCh * p.s[i].C * 4ull >= 0x7fffff00ull) return false;
+  }
+  return true;
+}
+
+#ifdef OFFK_PW_REDUCE_FEAT16
+bool pw_reduce_feat16_supported(const PwParams& p) { return !p.nhwc && pw_lean_ok(p, 2); }
+
+// Same grid, same block -> rows mapping and same K walk as pw_reduce_launch: only the map loader differs.
+hipError_t pw_reduce_feat16_launch(const PwParams& p, int feat_dtype, hipStream_t st) {
+  if (p.total_blocks <= 0) return hipSuccess;
+  if (!pw_reduce_feat16_supported(p)) return hipErrorInvalidValue;
+  if (feat_dtype == kFeatBf16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatBf16>), dim3(p.total_blocks), dim3(256), 0, st, p);
+  else if (feat_dtype == kFeatF16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatF16>), dim3(p.total_blocks), dim3(256), 0, st, p);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+#else
 hipError_t pw_reduce_launch(const PwParams& p_in, hipStream_t st) {
   PwParams p = p_in;
 #ifdef OFFK_TUNING_KNOBS
@@ -310,12 +436,7 @@ hipError_t pw_reduce_launch(const PwParams& p_in, hipStream_t st) {
 #endif
   if (p.total_blocks <= 0) return hipSuccess;
   constexpr int kNT = 0;     // product default (tools/sweep_pw.py, profiles/r02)
-  bool lean = true;          // buffer addressing: every byte offset below 2^31
-  for (int i = 0; i < p.nsites; ++i) {
-    for (int q = 0; q < p.s[i].nparts; ++q)
-      if ((unsigned long long)p.s[i].M * p.s[i].cp[q] * 4ull >= 0x7fffff00ull) lean = false;
-    if ((unsigned long long)kGenCh * p.s[i].C * 4ull >= 0x7fffff00ull) lean = false;
-  }
+  bool lean = pw_lean_ok(p, 4);   // buffer addressing: every byte offset below 2^31
 #ifdef OFFK_TUNING_KNOBS
   const char* e = getenv("OFFK_PW_NT");
   const int nt = e ? atoi(e) : kNT;
@@ -333,5 +454,6 @@ hipError_t pw_reduce_launch(const PwParams& p_in, hipStream_t st) {
 #endif
   return hipGetLastError();
 }
+#endif
 
 }  // namespace offk

@@ -264,6 +264,13 @@ __device__ __forceinline__ int wg_down_row(int f, int L, int P, int slice_mode) 
 }
 }  // namespace
 
+template <int V> struct WgVec { static constexpr int value = V; };   // X loader form known at compile time (-1: the runtime `vec`)
+
+// FEAT: element type of X (enum offk_feat_dtype).  The 16-bit forms fetch X rows of 16-bit elements (an 8-byte load per pixel quad
+// where HW % 4 == 0, four 2-byte loads at the 7x7 sites, whose 98-byte rows are only 2-byte aligned), keep them as loaded in the
+// prefetch registers and widen them to the exact fp32 values on the way into the fp32 loader's LDS positions.  Everything behind
+// the LDS store is this one text, so their slabs are bit-equal to the fp32 kernel's on the widened maps.
+template <int FEAT = kFeatF32>
 __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   // fp32 MFMA, LDS [row][k] fp32 (stride LDS_K)
   constexpr int LDS_BYTES = (WG_BM + WG_BN) * LDS_K * 4;
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
 
   // B loader: rows (tid>>3) + 32r of the slab, k quad tid&7; the four 32-channel groups may sit in different parts
   const float* xrow[4];   // block-uniform (SGPRs): first row of the 32-channel group inside its part
-  int xfs[4];             // frame stride of the part, in floats
+  int xfs[4];             // frame stride of the part, in elements
   bool xok[4];
   const int rowoff = (tid >> 3) * HW;
 #pragma unroll
@@ -316,7 +323,8 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       }
     }
     xok[r] = cb < C;
-    xrow[r] = xb + (size_t)kl * HW;
+    xrow[r] = FEAT == kFeatF32 ? xb + (size_t)kl * HW     // (16-bit maps: the same element offset in 2-byte units)
+                               : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + (size_t)kl * HW);
     xfs[r] = cpart * HW;
   }
   const bool wave_on = nt * WG_BN + 32 * wave < C;
@@ -324,6 +332,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   const int pq = tid & 7, cq = tid >> 3;     // gen A loader: pixel quad (fastest: conflict-free LDS stores), channel quad
   const int dpx = tid >> 3, dcq = tid & 7;   // down A loader: pixel, channel quad
   float4 rg[9];                              // 0-3 gen pixels, 4 down, 5-8 X rows
+  unsigned long long rx[4];                  // 16-bit maps, HW % 4 == 0: the X quads as loaded
   float4 bs_g = make_float4(0.f, 0.f, 0.f, 0.f), bs_d = make_float4(0.f, 0.f, 0.f, 0.f);
 
   int frame = kt0 / S.tpf, kin = (kt0 - frame * S.tpf) * BK;
@@ -332,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   // `if (ok) v = load` the compiler serialises the loads of one tile (s_waitcnt vmcnt(0) in front of every
   // load whose destination registers are also written on another control-flow path).
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 7x7 maps: rows are only 4-byte aligned
-  auto load_tile = [&]() {
+  auto load_tile = [&](auto VT) {
     const float* ga = S.dG + ((size_t)frame * HW + kin + 4 * pq) * kGenCh + 4 * cq;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -347,6 +356,33 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     // X quad k..k+3 of the row; a quad that straddles the row end (HW % 4 != 0) is read from HW-4 and shifted
     // into place by store_tile
     const int k = kin + 4 * (tid & 7), kk = min(k, HW - 4);
+    if constexpr (FEAT != kFeatF32) {
+      // 16-bit X: rx[] (a pixel quad per 8-byte load, kept whole: a 64-bit value that is split only behind the wait stays in one
+      // register pair around the loop) or rg[5..8] (2-byte loads) hold the elements as loaded; store_tile widens them.  The zero page
+      // reads as 16-bit zeros too; no quad is read early, so there is no tail to shift.  The form is a compile-time one here (the
+      // K loop below exists once per form): with both in one loop the copies that reconciled their register images behind the
+      // loads waited for the prefetch in front of the MFMAs
+      const unsigned short* z16 = reinterpret_cast<const unsigned short*>(p.zeros);
+      if constexpr (decltype(VT)::value == 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned short* q = (xok[r] && k < HW && !(p.dbg & 1))
+                                        ? reinterpret_cast<const unsigned short*>(xrow[r]) + (size_t)frame * xfs[r] + (rowoff + k) : z16;
+          rx[r] = *reinterpret_cast<const unsigned long long*>(q);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned short* row = reinterpret_cast<const unsigned short*>(xrow[r]) + (size_t)frame * xfs[r] + (rowoff + k);
+          const bool on = xok[r] && !(p.dbg & 1);
+          const unsigned e0 = *((on && k < HW) ? row : z16), e1 = *((on && k + 1 < HW) ? row + 1 : z16);
+          const unsigned e2 = *((on && k + 2 < HW) ? row + 2 : z16), e3 = *((on && k + 3 < HW) ? row + 3 : z16);
+          rg[5 + r] = make_float4(__uint_as_float(e0), __uint_as_float(e1), __uint_as_float(e2), __uint_as_float(e3));
+        }
+      }
+      kin_ld = kin;
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float* q = (xok[r] && k < HW && !(p.dbg & 1)) ? xrow[r] + (size_t)frame * xfs[r] + (rowoff + kk) : p.zeros;
@@ -366,8 +402,25 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       }
     }
   };
-  auto store_tile = [&]() {
-    if (!vec) fix_x_tail();
+  auto widen = [](unsigned h) {   // one 16-bit element (upper bits zero) -> the fp32 value it stands for
+    if (FEAT == kFeatBf16) return __uint_as_float(h << 16);
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);   // hardware conversion: keeps subnormals
+  };
+  auto store_tile = [&](auto VT) {
+    if constexpr (FEAT != kFeatF32) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (decltype(VT)::value == 1) {
+          const unsigned a = (unsigned)rx[r], b = (unsigned)(rx[r] >> 32);
+          rg[5 + r] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+        } else {
+          rg[5 + r] = make_float4(widen(__float_as_uint(rg[5 + r].x)), widen(__float_as_uint(rg[5 + r].y)),
+                                  widen(__float_as_uint(rg[5 + r].z)), widen(__float_as_uint(rg[5 + r].w)));
+        }
+      }
+    } else {
+      if (!vec) fix_x_tail();
+    }
     bs_g.x += (rg[0].x + rg[1].x) + (rg[2].x + rg[3].x); bs_g.y += (rg[0].y + rg[1].y) + (rg[2].y + rg[3].y);
     bs_g.z += (rg[0].z + rg[1].z) + (rg[2].z + rg[3].z); bs_g.w += (rg[0].w + rg[1].w) + (rg[2].w + rg[3].w);
     bs_d.x += rg[4].x; bs_d.y += rg[4].y; bs_d.z += rg[4].z; bs_d.w += rg[4].w;
@@ -389,36 +442,43 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  if (kt0 < kt1) load_tile();
-  for (int kt = kt0; kt < kt1; ++kt) {
-    store_tile();
-    __syncthreads();
-    if (kt + 1 < kt1) {
-      kin += BK;
-      if (kin >= HW) { kin = 0; ++frame; }
-      load_tile();
-    }
-    if (wave_on) {
-      const int r32 = lane & 31, h = lane >> 5;
-      const float* bsrc = Bs + (wave * 32 + r32) * LDS_K + 4 * h;
-      const float* asrc = As + r32 * LDS_K + 4 * h;
-#pragma unroll 1
-      for (int g = 0; g < BK / 8; ++g) {
-        const float4 b = *reinterpret_cast<const float4*>(bsrc + 8 * g);
-        float4 a[5];
-#pragma unroll
-        for (int t = 0; t < 5; ++t) a[t] = *reinterpret_cast<const float4*>(asrc + t * 32 * LDS_K + 8 * g);
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].x, b.x, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].y, b.y, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].z, b.z, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].w, b.w, acc[t], 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();
+  // the K loop; the 16-bit forms run it once per X loader form (see load_tile), a block-uniform choice.  (A macro: with the loop
+  // inside a lambda the fp32 form came out of the compiler changed.)
+#define OFFK_WG_K_LOOP(VT)                                                                                  \
+  if (kt0 < kt1) load_tile(VT);                                                                             \
+  for (int kt = kt0; kt < kt1; ++kt) {                                                                      \
+    store_tile(VT);                                                                                         \
+    __syncthreads();                                                                                        \
+    if (kt + 1 < kt1) {                                                                                     \
+      kin += BK;                                                                                            \
+      if (kin >= HW) { kin = 0; ++frame; }                                                                  \
+      load_tile(VT);                                                                                        \
+    }                                                                                                       \
+    if (wave_on) {                                                                                          \
+      const int r32 = lane & 31, h = lane >> 5;                                                             \
+      const float* bsrc = Bs + (wave * 32 + r32) * LDS_K + 4 * h;                                           \
+      const float* asrc = As + r32 * LDS_K + 4 * h;                                                         \
+      _Pragma("unroll 1")                                                                                   \
+      for (int g = 0; g < BK / 8; ++g) {                                                                    \
+        const float4 b = *reinterpret_cast<const float4*>(bsrc + 8 * g);                                    \
+        float4 a[5];                                                                                        \
+      _Pragma("unroll")                                                                                     \
+        for (int t = 0; t < 5; ++t) a[t] = *reinterpret_cast<const float4*>(asrc + t * 32 * LDS_K + 8 * g); \
+      _Pragma("unroll")                                                                                     \
+        for (int t = 0; t < 5; ++t) {                                                                       \
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].x, b.x, acc[t], 0, 0, 0);                      \
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].y, b.y, acc[t], 0, 0, 0);                      \
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].z, b.z, acc[t], 0, 0, 0);                      \
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t].w, b.w, acc[t], 0, 0, 0);                      \
+        }                                                                                                   \
+      }                                                                                                     \
+    }                                                                                                       \
+    __syncthreads();                                                                                        \
   }
+  if constexpr (FEAT == kFeatF32) { OFFK_WG_K_LOOP(WgVec<-1>()) }
+  else if (vec) { OFFK_WG_K_LOOP(WgVec<1>()) }
+  else { OFFK_WG_K_LOOP(WgVec<0>()) }
+#undef OFFK_WG_K_LOOP
 
   // ---- epilogue: partial tile -> slab [chunk][160][ntiles*128] -----------------------------------------
   const int cpad = S.ntiles * WG_BN;
@@ -450,10 +510,19 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   }
 }
 
+hipError_t pw_wgrad_feat16_launch(const WgParams& p, int feat_dtype, hipStream_t st) {
+  if (p.total_blocks <= 0) return hipSuccess;
+  if (p.precision != 0) return hipErrorInvalidValue;
+  if (feat_dtype == kFeatBf16) hipLaunchKernelGGL(pw_wgrad_kernel<kFeatBf16>, dim3(p.total_blocks), dim3(256), 0, st, p);
+  else if (feat_dtype == kFeatF16) hipLaunchKernelGGL(pw_wgrad_kernel<kFeatF16>, dim3(p.total_blocks), dim3(256), 0, st, p);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 hipError_t pw_wgrad_launch(const WgParams& p, hipStream_t st) {
   if (p.total_blocks <= 0) return hipSuccess;
   if (p.precision != 0) return hipErrorInvalidValue;      // (the bf16x3 core is no longer instantiated: retired in round 5)
-  hipLaunchKernelGGL(pw_wgrad_kernel, dim3(p.total_blocks), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(pw_wgrad_kernel<kFeatF32>, dim3(p.total_blocks), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 

@@ -127,7 +127,8 @@ class OFFSubNetwork(nn.Module):
 class _OFFUnitsFn(torch.autograd.Function):
     """autograd node around offk_off_units(_train) / offk_off_units_backward.  Inputs after the three
     bookkeeping arguments are the unit parameters in ``OFFUnits.param_keys`` order; the feature maps come from
-    the frozen backbone (train_off.py:39-56) and get no gradient."""
+    the frozen backbone (train_off.py:39-56) and get no gradient; they are kept in ``ctx.feats`` in the dtype they came in
+    (fp32, or bf16 / fp16 from an autocast backbone -- the typed entries read those without an fp32 copy)."""
 
     @staticmethod
     def forward(ctx, mod, feats, drop, *params):
@@ -140,10 +141,12 @@ class _OFFUnitsFn(torch.autograd.Function):
         ctx.gen = mod._generation
         ctx.versions = dict((k, (prm.data_ptr(), prm._version)) for k, prm in zip(mod.param_keys, params))
         P = rt.P
-        # copies: the workspace is rewritten by the next forward, autograd consumers may outlive it
+        # copies: the workspace is rewritten by the next forward, autograd consumers may outlive it.  (clone, not .contiguous():
+        # fusion_28 is all unit channels, so its slice is contiguous already and .contiguous() handed out the workspace itself --
+        # a forward between this one and the use of its m28 changed the values under the caller)
         outs = []
         for name, H, C, width in (("fusion_28", 28, 320, 320), ("fusion_14", 14, 1056, 800), ("fusion_7", 7, 832, 320)):
-            buf = rt.region(name, C).view(P, H, H, C)[..., :width].contiguous()
+            buf = rt.region(name, C).view(P, H, H, C)[..., :width].clone(memory_format=torch.contiguous_format)
             outs.append(buf.permute(0, 3, 1, 2))       # NCHW view of channels-last memory
         return tuple(outs)
 
@@ -171,7 +174,12 @@ class OFFUnits(nn.Module):
     = offk_off_units_backward.  Returns the three motion maps the fusion stages start from
     (cat(motion_3a, motion_3b) [P,320,28,28], cat(motion_3c..4d) [P,800,14,14], cat(motion_5a, motion_5b)
     [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The reference's fusion convolutions
-    and heads stay ordinary PyTorch modules in training."""
+    and heads stay ordinary PyTorch modules in training.
+
+    The nine maps may be fp32, or bf16 / fp16 of one dtype -- what a frozen backbone under ``torch.autocast`` emits.
+    16-bit maps are neither cast nor copied: the kernels read them as they are (offk_off_units_train_typed,
+    offk_off_units_backward_typed), the autograd node keeps the 16-bit tensors for its backward and for the
+    recompute of a stale generation, and outputs and gradients are fp32 and equal those from ``x.float()``."""
 
     def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8):
         super().__init__()

@@ -167,6 +167,15 @@ class OffForward:
             raise ValueError("bf16 / fp16 feature maps need a split-fp32 handle (precision=\"f32split\"); this one runs the fp32 pipe")
         return _FEAT_DTYPES[dt]
 
+    def _train16(self, feats):
+        """enum offk_feat_dtype of nine bf16 / fp16 maps for the training-side entries (offk_off_units_typed and its siblings), None for
+        fp32 ones.  No condition on the handle's precision here: that one belongs to the inference forward (_feat16)."""
+        if len(feats) != spec.NUM_SITES:
+            raise ValueError("need nine feature maps")
+        if any(not torch.is_tensor(f) for f in feats):
+            return None                                    # _feat_array names the offender
+        return _FEAT_DTYPES.get(feat_dtype(feats))
+
     def _feat_array(self, feats, check=_check_dev):
         if len(feats) != spec.NUM_SITES:
             raise ValueError("need nine feature maps")
@@ -242,6 +251,13 @@ class OffForward:
                                          _ptr(self.workspace)), self._h)
 
     def off_units(self, feats):
+        """K1 + K2 into the workspace.  feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (offk_off_units_typed: the values
+        of the same maps upcast, on any handle)."""
+        fdt = self._train16(feats)
+        if fdt is not None:
+            arr = self._feat_array(feats, _check_dev16)
+            _lib.check(self.lib.offk_off_units_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace)), self._h)
+            return
         arr = self._feat_array(feats)
         _lib.check(self.lib.offk_off_units(self._h, _stream(self.device), arr, _ptr(self.workspace)), self._h)
 
@@ -259,7 +275,14 @@ class OffForward:
     # ---- training side of the units ----------------------------
     def off_units_train(self, feats, drop_seed=0, drop_p=0.8):
         """K1+K2 in training mode: nn.Dropout(p) (RGB_OFF.py:356, :612) on the spatial gradients with the
-        reproducible mask of synth.dropout_keep; leaves G/D in the workspace for off_units_backward."""
+        reproducible mask of synth.dropout_keep; leaves G/D in the workspace for off_units_backward.
+        bf16 / fp16 maps of one dtype are taken as they are (offk_off_units_train_typed)."""
+        fdt = self._train16(feats)
+        if fdt is not None:
+            arr = self._feat_array(feats, _check_dev16)
+            _lib.check(self.lib.offk_off_units_train_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace),
+                                                           ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
+            return
         arr = self._feat_array(feats)
         _lib.check(self.lib.offk_off_units_train(self._h, _stream(self.device), arr, _ptr(self.workspace),
                                                  ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
@@ -284,10 +307,13 @@ class OffForward:
         """Gradients of the units' parameters.  grad_views: nine (tensor, coff) pairs -- a channels-last
         gradient buffer [P, H, W, Cs] (or [P*H*W, Cs]) and the first of the unit's 160 channels in it.
         Needs training=True (workspace superset) and the G/D state of the matching forward call.
+        feats: the maps of the matching forward call, fp32 or bf16 / fp16 of one dtype (offk_off_units_backward_typed; gradients
+        are fp32 and equal those from the upcast maps).
         Returns (flat grads tensor, dict key -> view in the reference's parameter shape)."""
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
-        arr = self._feat_array(feats)
+        fdt = self._train16(feats)
+        arr = self._feat_array(feats, _check_dev16 if fdt is not None else _check_dev)
         gv = (_lib.OffkGradView * spec.NUM_SITES)()
         for i, ((t, coff), (_n, _c, H)) in enumerate(zip(grad_views, spec.SITES)):
             _check_dev(t, "grad_views[%d]" % i, self.device)
@@ -297,9 +323,14 @@ class OffForward:
         if grads is None:
             grads = self.new_unit_grads()
         _check_dev(grads, "grads", self.device)
-        _lib.check(self.lib.offk_off_units_backward(self._h, _stream(self.device), arr, gv, _ptr(self.workspace),
-                                                    ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
-                                                    int(bool(accumulate))), self._h)
+        if fdt is not None:
+            _lib.check(self.lib.offk_off_units_backward_typed(self._h, _stream(self.device), fdt, arr, gv, _ptr(self.workspace),
+                                                              ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
+                                                              int(bool(accumulate))), self._h)
+        else:
+            _lib.check(self.lib.offk_off_units_backward(self._h, _stream(self.device), arr, gv, _ptr(self.workspace),
+                                                        ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
+                                                        int(bool(accumulate))), self._h)
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
 
@@ -308,6 +339,11 @@ class OffForward:
         _name, _C, H = spec.SITES[site]
         G = torch.empty(self.N * H * H, spec.GEN_CH, dtype=torch.float32, device=self.device)
         D = torch.zeros(self.P * H * H, spec.DOWN_CH, dtype=torch.float32, device=self.device)
+        if torch.is_tensor(feat) and feat.dtype in _FEAT_DTYPES:      # bf16 / fp16 map: offk_pw_reduce_typed
+            _check_dev16(feat, "feat", self.device)
+            _lib.check(self.lib.offk_pw_reduce_typed(self._h, _stream(self.device), _FEAT_DTYPES[feat.dtype], site, _ptr(feat),
+                                                     _ptr(G), _ptr(D)), self._h)
+            return G, D
         _check_dev(feat, "feat", self.device)
         _lib.check(self.lib.offk_pw_reduce(self._h, _stream(self.device), site, _ptr(feat), _ptr(G), _ptr(D)), self._h)
         return G, D

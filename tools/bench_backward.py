@@ -1,6 +1,8 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
-    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20]
+    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16]
+--feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
+.float() casts that path makes unnecessary are timed beside it.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -36,26 +38,31 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--variant", type=int, default=spec.VARIANT_RGB)
+    ap.add_argument("--feat-dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
     h = runtime.OffForward(B, L, a.variant, precision=a.precision, training=True)
     h.load_state_dict(synth.make_weights(a.variant))
-    feats = [torch.from_numpy(f).cuda() for f in synth.make_features(B, L, 2)]
+    fdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.feat_dtype]
+    feats = [torch.from_numpy(f).cuda().to(fdt).contiguous() for f in synth.make_features(B, L, 2)]
     gen = torch.Generator(device="cuda").manual_seed(5)
     bufs = [torch.randn(P, H, H, C, device="cuda", generator=gen) for H, C in ((28, 320), (14, 1056), (7, 832))]
     views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
     grads = h.new_unit_grads()
     t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8), a.iters)
     t_bwd = timed(lambda: h.off_units_backward(feats, views, 21, 0.8, grads=grads), a.iters)
+    t_cast = timed(lambda: [f.float() for f in feats], a.iters) if fdt != torch.float32 else 0.0
+    esz = 4 if fdt == torch.float32 else 2
     hw = sum(H * H for _n, _c, H in spec.SITES)
     # K2b: read dM (160 ch, P rows) + G (128, N) + D (32, P), write dG (128, N) + dD (32, P)
     k2b = B * hw * 4 * ((160 + 32 + 32) * (L - 1) + 256 * L)
     # K1b: read X once + dG + dD (ideal); FLOPs as the forward's K1
-    x_bytes = sum(N * C * H * H * 4 for _n, C, H in spec.SITES)
+    x_bytes = sum(N * C * H * H * esz for _n, C, H in spec.SITES)
     k1b = x_bytes + B * hw * 4 * (128 * L + 32 * (L - 1))
     flops = sum(2 * N * H * H * C * 128 + 2 * P * H * H * C * 32 for _n, C, H in spec.SITES)
-    print(json.dumps({"batch": B, "length": L, "precision_fwd": a.precision,
+    print(json.dumps({"batch": B, "length": L, "precision_fwd": a.precision, "feat_dtype": a.feat_dtype,
+                      "nine_float_casts_ms": round(t_cast, 4),
                       "units_train_forward_ms": round(t_fwd, 4), "units_backward_ms": round(t_bwd, 4),
                       "clips_per_s_fwd_bwd_units": round(B / (t_fwd + t_bwd) * 1e3, 1),
                       "k2b_algorithmic_bytes": k2b, "k1b_algorithmic_bytes": k1b, "k1b_flops": flops,
