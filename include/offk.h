@@ -70,13 +70,21 @@ enum offk_precision {
   OFFK_PRECISION_FP32 = 0,  /* v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate */
   /* (1 was OFFK_PRECISION_BF16X3 until ABI v8: each fp32 operand as TWO bf16 planes, three products, ~1e-5 of the fp32 path;
    *  retired in ABI v9 -- offk_create rejects it -- in favour of the exact three-plane mode below) */
-  OFFK_PRECISION_F32SPLIT = 2 /* fp32 arithmetic on the bf16 matrix pipe: each fp32 operand cut into THREE bf16 planes
-                               (8 + 8 + 8 significand bits = the fp32 value exactly), the six plane products above
-                               2^-24 of the leading one on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (units kernel:
-                               the leading product and the five small ones in two running accumulators, added once; batched
-                               GEMMs: summed per 32-k step from zero and added to the accumulator once per step).  Measured
-                               error against fp64 no larger than the fp32 pipe's own on every parity distribution
-                               (DESIGN.md); kernels that have no split form run exactly as in OFFK_PRECISION_FP32.
+  OFFK_PRECISION_F32SPLIT = 2 /* fp32 arithmetic on the bf16 matrix pipe: each fp32 operand cut into THREE bf16 planes by
+                               truncation (h = the upper 16 bits, the exact remainder cut again: 8 + 8 + 8 significand bits
+                               = the fp32 value exactly), six of the nine plane products (w_h x_h, w_h x_m, w_m x_h, w_m x_m,
+                               w_h x_l, w_l x_h) on v_mfma_f32_16x16x32_bf16 with fp32 accumulation -- in every split
+                               kernel (units, batched GEMMs, chains, the 1x1 of winograd_between) the leading product in
+                               one running accumulator and the five small ones in another, added once at the end.
+                               Contract: the dropped products w_m x_l + w_l x_m + w_l x_l are below
+                               (2^-21 + 2^-30) sum_k |w_k x_k| per output (|m| < 2^-7 |v|, |l| < 2^-15 |v| for the
+                               truncating cut; reached within 3 % when both operands carry mantissa 0x00FFFF), beside an
+                               fp32 accumulation error.  On the parity distributions (synthetic maps, 24-bit mantissas,
+                               heavy tail, cancellation) the measured error against fp64 is no larger than the fp32 pipe's
+                               own; on worst-case mantissas that comparison does not hold -- there the
+                               bound above is what is tested, dropped and accumulation parts separately
+                               (tests/test_split_contract.py on the CPU, tests/test_gpu_split.py::test_*_worst_case_mantissas).
+                               Kernels that have no split form run exactly as in OFFK_PRECISION_FP32.
                                Non-finite inputs: the cut of +-Inf leaves Inf - Inf = NaN in the lower planes, so every
                                output such an operand touches is NaN where the fp32 pipe gives +-Inf (or NaN): non-finite
                                in both modes, but not the same non-finite value.  Tiny inputs: a plane below the bf16
@@ -280,7 +288,11 @@ int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_c
  * branch_w == NULL: the residual chains 28b / 28c (Cin = 256 or 64; res may be NULL).  branch_w != NULL (Cin = 64, res must be NULL): chain 28a --
  * y = relu(c3(t2) + b3 + branch_w . x + branch_b) with the branch 1x1 [256][64] on the chain input BEFORE relu_in's ReLU, RGB_OFF.py:657-667.
  * Weights as for offk_bottleneck_chain14 (fp32, device); scratch: device memory for their plane images, at least
- * 6 * (64 * Cin + 64 * 576 + 2 * 256 * 64) bytes (cut on every call: a stage entry point, not a fast path). */
+ * 6 * (64 * Cin + 64 * 576 + 2 * 256 * 64) bytes (cut on every call: a stage entry point, not a fast path).
+ * Views and aliasing, checked before anything is enqueued (OFFK_ERR_INVALID otherwise): offsets >= 0, x_cstride >= x_coff + Cin,
+ * y_cstride >= y_coff + 256, res_cstride >= res_coff + 256 (res != NULL).  The chain does NOT run in place: y's bytes
+ * [y, y + n_img * 196 * y_cstride * 4) may overlap neither x's [x, x + n_img * 196 * x_cstride * 4) nor res's (a block stores y while the
+ * block of the image's other half still reads x's halo rows); res may be x itself (28b / 28c) or any view of x's buffer. */
 int offk_bottleneck_chain14_split(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Cin, int relu_in,
                                   const float* w1, const float* b1, const float* w2_packed, const float* b2,
                                   const float* w3, const float* b3, const float* branch_w, const float* branch_b,

@@ -2,7 +2,7 @@
 //
 // The chains of chain_fused.hip (reference RGB_OFF.py:670-676, :679-685: t1 = relu(c1(x)); t2 = relu(c2_3x3(t1)); y = relu(c3(t2) + x))
 // with every contraction in the arithmetic of pw_tdiff_split.hip / wino_gemm_split.hip: fp32 operands as three bf16 planes (h + m + l = the
-// value, exactly), the six plane products above 2^-24 of the leading one on v_mfma_f32_16x16x32_bf16 into two running fp32 accumulators per
+// value, exactly), six of the nine plane products (the dropped three: below (2^-21 + 2^-30) |w x|, include/offk.h) on v_mfma_f32_16x16x32_bf16 into two running fp32 accumulators per
 // tile (w_h x_h | the five small products), added once.  The fp32 kernel is latency-bound (sixteen barrier-separated phases, the 3x3 in
 // Winograd F(2x2, 3x3) form to halve its 32-cycle fp32 MFMAs: 0.47 of the fp32 pipe on executed FLOPs); here an MFMA is 16 cycles for eight
 // times the products, so the 3x3 runs DIRECT (no transforms, no extra barriers) and the block has four barriers in all.

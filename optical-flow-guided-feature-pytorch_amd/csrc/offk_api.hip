@@ -1796,6 +1796,23 @@ int offk_bottleneck_chain14_split(void* stream, const float* x, int x_cstride, i
   const char* who = "offk_bottleneck_chain14_split";
   if (!x || !w1 || !b1 || !w2_packed || !b2 || !w3 || !b3 || !y || !scratch || n_img < 1 || (Cin != 64 && Cin != 256) || (branch_w && !branch_b))
     return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument");
+  // the kernel loads x / res and stores y through raw pointers: every view must hold its slice, and y may alias neither input (a block's
+  // stores would race with the other half-image block's halo reads of x, and with later blocks' residual loads)
+  if (x_coff < 0 || y_coff < 0 || (res && res_coff < 0)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": negative channel offset");
+  if (x_cstride < x_coff + Cin) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x_cstride < x_coff + Cin");
+  if (y_cstride < y_coff + 256) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": y_cstride < y_coff + 256");
+  if (res && res_cstride < res_coff + 256) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": res_cstride < res_coff + 256");
+  if (branch_w && res) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": the branch form takes no residual (res must be NULL)");
+  {
+    const size_t rows = (size_t)n_img * 196 * sizeof(float);
+    const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + rows * (size_t)y_cstride;
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + rows * (size_t)x_cstride;
+    if (y0 < x1 && x0 < y1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": y overlaps x (the chain does not run in place)");
+    if (res) {
+      const uintptr_t r0 = reinterpret_cast<uintptr_t>(res), r1 = r0 + rows * (size_t)res_cstride;
+      if (y0 < r1 && r0 < y1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": y overlaps res (the chain does not run in place)");
+    }
+  }
   const size_t e1 = (size_t)64 * Cin, e2 = (size_t)64 * 576, e3 = (size_t)256 * 64;
   if (scratch_bytes < 6 * (e1 + e2 + 2 * e3)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small");
   hipStream_t st = static_cast<hipStream_t>(stream);

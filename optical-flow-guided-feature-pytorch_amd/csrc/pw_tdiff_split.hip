@@ -2,8 +2,8 @@
 // down rows, reference RGB_OFF.py:597-610) with every fp32 operand cut into THREE bf16 planes and multiplied on the bf16 matrix pipe.
 //
 // Arithmetic.  x = x_h + x_m + x_l exactly (8 + 8 + 8 significand bits: x_h = the upper 16 bits of x, the remainder is exact in
-// fp32, cut again, and again), the same for w; every product of two planes is exact in fp32.  Of the nine plane products the six
-// above 2^-24 of the leading one are formed on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, into TWO running accumulators per
+// fp32, cut again, and again), the same for w; every product of two planes is exact in fp32.  Of the nine plane products six
+// (the dropped three are below (2^-21 + 2^-30) |w x| for this truncating cut, include/offk.h) are formed on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, into TWO running accumulators per
 // output tile (round 6): A1 takes the leading product w_h x_h, A2 the five small ones (w_l x_h, w_h x_l, w_m x_m, w_m x_h, w_h x_m --
 // all below 2^-8 of the leading one, so A2's own roundings are 2^-8 of an fp32 chain's); out = A1 + A2 once, in the epilogue.
 // Measured against fp64 on MI355X (tools/probe_split_mfma.hip mode 6, "6 products, 2 acc (hh | rest)", profiles/r05/probe_split_mfma.txt):

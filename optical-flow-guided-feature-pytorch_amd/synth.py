@@ -141,3 +141,128 @@ def dropout_keep(seed, site_index, pairs, H, p):
     for c in range(4):
         keep[..., c] = ((x >> np.uint64(16 * c)) & np.uint64(0xFFFF)) >= thr
     return np.ascontiguousarray(keep.reshape(pairs, H, H, spec.DOWN_CH).transpose(0, 3, 1, 2))
+
+
+# ---- a CPU model of the split-fp32 arithmetic and its worst-case operands (tests/test_split_contract.py, tests/test_gpu_split.py) ----
+# The kernels cut every fp32 operand into three bf16 planes by TRUNCATION (h = the upper 16 bits of the word, the remainder is exact in fp32,
+# cut again; csrc/chain_split.hip cut4, pw_tdiff_split.hip, wino_gemm_split.hip, wino_mid.hip) and form six of the nine plane products.  For
+# that cut |m| < 2^-7 |v| and |l| < 2^-15 |v|, so the three dropped products w_m x_l + w_l x_m + w_l x_l are below
+# (2 * 2^-22 + 2^-30) |w x| = SPLIT_DROP_BOUND * 2^-24 |w x| -- and mantissa 0x00FFFF in both operands comes within 3 % of that.
+SPLIT_EPS = 2.0 ** -24
+SPLIT_DROP_BOUND = 8.015625            # (2^-21 + 2^-30) / 2^-24
+SPLIT_EXACT_MIN = 2.0 ** -109          # below this an operand's last plane falls under the last bf16 subnormal (2^-133) and is lost
+ADVERSARIAL_MANTISSAS = (0x7FFFFF, 0x7F7F7F, 0x00FFFF, 0x00FF7F, 0x007FFF)
+# (w plane, x plane) of the six kept products in the order the kernels issue them per 32-k step, planes 0 = h, 1 = m, 2 = l; the last one
+# (w_h x_h) goes to accumulator A1, the five small ones to A2
+SPLIT_PRODUCTS = ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))
+SPLIT_DROPPED = ((1, 2), (2, 1), (2, 2))
+
+
+def cut3(x):
+    """The kernels' cut of fp32 values into three bf16 planes (h, m, l), each returned as fp32 with its low 16 bits clear: mask the upper 16
+    bits, take the exact fp32 remainder, mask again, take the remainder and keep its upper 16 bits (the plane images hold 16-bit words).
+    h + m + l == x exactly for |x| >= 2^-109; below that the last plane is under 2^-133 and the sum misses x by less than 2^-133."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    mask = np.uint32(0xFFFF0000)
+    h = (x.view(np.uint32) & mask).view(np.float32)
+    r = x - h
+    m = (r.view(np.uint32) & mask).view(np.float32)
+    r2 = r - m
+    l = (r2.view(np.uint32) & mask).view(np.float32)
+    return h, m, l
+
+
+def make_adversarial(shape, pattern, signs="same", seed=0, relu=False, k_axis=-1, e_range=(-3, 3)):
+    """fp32 values +-2^e (1 + mant / 2^23) whose cut leaves the largest lower planes.  pattern: one of ADVERSARIAL_MANTISSAS (or any 23-bit
+    mantissa), or "mixed" (a seeded draw among the five per element); e uniform in e_range (the products vary in size); signs "same": all
+    positive (nothing cancels in a contraction of two such arrays), "alternating": the sign flips along k_axis (sum w x << sum |w x|);
+    relu: a seeded half of the values is zero (a post-ReLU feature map)."""
+    n = int(np.prod(shape))
+    bits = raw_u64(0xADE5 + 977 * int(seed), 0, n)
+    lo, hi = e_range
+    e = (bits % np.uint64(hi - lo + 1)).astype(np.int64) + lo
+    if pattern == "mixed":
+        mant = np.asarray(ADVERSARIAL_MANTISSAS, dtype=np.uint32)[((bits >> np.uint64(8)) % np.uint64(len(ADVERSARIAL_MANTISSAS))).astype(np.int64)]
+    else:
+        assert 0 <= int(pattern) < (1 << 23)
+        mant = np.full(n, int(pattern), dtype=np.uint32)
+    v = ((((e + 127).astype(np.uint32)) << np.uint32(23)) | mant).view(np.float32).reshape(shape).copy()
+    if relu:
+        v[(((bits >> np.uint64(16)) & np.uint64(1)) == 0).reshape(shape)] = 0.0
+    if signs == "alternating":
+        k = np.arange(v.shape[k_axis])
+        sg = np.where(k % 2 == 0, np.float32(1), np.float32(-1))
+        v *= sg.reshape([-1 if a == (k_axis % v.ndim) else 1 for a in range(v.ndim)])
+    elif signs != "same":
+        raise ValueError("unknown sign mode %r" % (signs,))
+    return v
+
+
+def split_terms(w, x):
+    """fp64 pieces of the contraction out[m, n] = sum_k x[m, k] w[n, k] of fp32 operands: (ref, dropped, mag) with ref the exact result,
+    dropped = w_m x_l + w_l x_m + w_l x_l (so kept = ref - dropped is the sum of the six kept plane products) and mag = sum_k |w_k x_k|."""
+    wp = [p.astype(np.float64) for p in cut3(w)]
+    xp = [p.astype(np.float64) for p in cut3(x)]
+    x64, w64 = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    ref = x64 @ w64.T
+    dropped = sum(xp[b] @ wp[a].T for a, b in SPLIT_DROPPED)
+    mag = np.abs(x64) @ np.abs(w64).T
+    return ref, dropped, mag
+
+
+def emulate_split_dot(w, x, form="units", skip=None, chunk_bytes=1 << 26):
+    """out[m, n] = sum_k x[m, k] w[n, k] (fp32, x [M, K], w [N, K]) in the arithmetic of the split kernels, on the CPU.
+
+    One v_mfma_f32_16x16x32_bf16 is modelled as DESIGN.md 5.1 / tools/probe_split_mfma.hip part 2 record it: plane products exact, the eight
+    products of a lane group (k = 8 g .. 8 g + 7) summed exactly, the four group sums added to the accumulator one after the other, each add
+    rounded to fp32 (nearest even).  ASSUMPTIONS: the group sum is exact (the instruction keeps ~24 bits below its largest product) and
+    the rounding is to nearest; the order of the 32 products inside an instruction beyond that is not specified, which is why the GPU
+    tests allow twice this model's accumulation error.
+    form "units": A1 += w_h x_h, A2 += the five small products (SPLIT_PRODUCTS order) per 32-k step, out = A1 + A2 once at the end -- what
+    every split kernel runs since round 6.  form "gemm": per 32-k step the six products are summed from zero, and that sum is added to
+    the one accumulator once per step (round 5's batched GEMM).  skip: index into SPLIT_PRODUCTS of a product to leave out (mutation)."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    (M, K), N = x.shape, w.shape[0]
+    assert w.shape[1] == K and form in ("units", "gemm")
+    Kp = (K + 31) // 32 * 32
+    if Kp != K:
+        w = np.pad(w, ((0, 0), (0, Kp - K)))
+        x = np.pad(x, ((0, 0), (0, Kp - K)))
+    G = Kp // 8
+    wp = [p.astype(np.float64).reshape(N, G, 8).transpose(1, 2, 0).copy() for p in cut3(w)]          # [G][8][N]
+    xpl = [p.astype(np.float64) for p in cut3(x)]
+    prods = [(i, a, b) for i, (a, b) in enumerate(SPLIT_PRODUCTS) if i != skip]
+    out = np.empty((M, N), dtype=np.float32)
+    mc = max(16, int(chunk_bytes // (8 * G * N)))
+    f32, f64 = np.float32, np.float64
+    for m0 in range(0, M, mc):
+        xs = [p[m0:m0 + mc].reshape(-1, G, 8).transpose(1, 0, 2) for p in xpl]                        # [G][mc][8]
+        S = dict((i, np.matmul(xs[b], wp[a])) for i, a, b in prods)                                    # [G][mc][N] exact group sums
+        rows = xs[0].shape[1]
+        if form == "units":
+            a1 = np.zeros((rows, N), dtype=f32)
+            a2 = np.zeros((rows, N), dtype=f32)
+            for g0 in range(0, G, 4):
+                for i, _a, _b in prods:
+                    for g in range(g0, g0 + 4):
+                        if i == 5:
+                            a1 = (a1.astype(f64) + S[i][g]).astype(f32)
+                        else:
+                            a2 = (a2.astype(f64) + S[i][g]).astype(f32)
+            out[m0:m0 + mc] = a1 + a2
+        else:
+            acc = np.zeros((rows, N), dtype=f32)
+            for g0 in range(0, G, 4):
+                t = np.zeros((rows, N), dtype=f32)
+                for i, _a, _b in prods:
+                    for g in range(g0, g0 + 4):
+                        t = (t.astype(f64) + S[i][g]).astype(f32)
+                acc = acc + t
+            out[m0:m0 + mc] = acc
+    return out
+
+
+def split_c_acc(emulated, ref, dropped, mag):
+    """c_acc per element: |emulated - kept| / (2^-24 sum |w x|), kept = ref - dropped (elements with mag = 0 give 0)."""
+    return np.abs(emulated.astype(np.float64) - (ref - dropped)) / np.maximum(SPLIT_EPS * mag, 1e-300)

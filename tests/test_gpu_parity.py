@@ -238,12 +238,7 @@ def test_pw_reduce_vs_oracle(rt, site, slice_mode, prec):
     assert rel_err(D.view(B * (L - 1), H, H, 32).permute(0, 3, 1, 2), d_ref) < RTOL
 
 
-@pytest.mark.parametrize("algo", [0, 1, 4])      # temporal difference by register rotation / wavefront shuffle / flat shifted stream
-@pytest.mark.parametrize("variant", [spec.VARIANT_RGB, spec.VARIANT_FLOW])
-@pytest.mark.parametrize("site", [0, 2, 7])
-def test_sobel_tdiff_vs_oracle(rt, site, variant, algo):
-    B, L = 2, 4
-    h, w = make_handle(rt, B, L, variant)
+def _check_sobel_tdiff(h, w, B, L, site, variant, algo):
     name, _C, H = spec.SITES[site]
     g = torch.Generator().manual_seed(site + 10 * variant)
     G = torch.relu(torch.randn(B * L, 128, H, H, generator=g))
@@ -257,9 +252,28 @@ def test_sobel_tdiff_vs_oracle(rt, site, variant, algo):
     M = torch.full((B * (L - 1) * H * H, 352), -3.0, device="cuda")
     h.sobel_tdiff(site, nhwc(G).view(-1, 128), nhwc(D).view(-1, 32), M, 160, algo)
     Mv = M.view(B * (L - 1), H, H, 352).permute(0, 3, 1, 2)
-    assert rel_err(Mv[:, 160:192], s_ref) < RTOL
-    assert rel_err(Mv[:, 192:320], t_ref) < 1e-6          # a single fp32 subtraction: exact
-    assert torch.all(Mv[:, :160] == -3.0) and torch.all(Mv[:, 320:] == -3.0)
+    assert rel_err(Mv[:, 160:192], s_ref) < RTOL, name
+    assert rel_err(Mv[:, 192:320], t_ref) < 1e-6, name          # a single fp32 subtraction: exact
+    assert torch.all(Mv[:, :160] == -3.0) and torch.all(Mv[:, 320:] == -3.0), name
+
+
+@pytest.mark.parametrize("algo", [0, 1, 4])      # temporal difference by register rotation / wavefront shuffle / flat shifted stream
+@pytest.mark.parametrize("variant", [spec.VARIANT_RGB, spec.VARIANT_FLOW])
+@pytest.mark.parametrize("site", range(spec.NUM_SITES))      # every site's own depthwise taps and map size, not only through whole-forward buffers
+def test_sobel_tdiff_vs_oracle(rt, site, variant, algo):
+    B, L = 2, 4
+    h, w = make_handle(rt, B, L, variant)
+    _check_sobel_tdiff(h, w, B, L, site, variant, algo)
+
+
+@pytest.mark.parametrize("algo", [0, 1, 4])
+@pytest.mark.parametrize("variant", [spec.VARIANT_RGB, spec.VARIANT_FLOW])
+@pytest.mark.parametrize("B,L", [(1, 2), (3, 5)])
+def test_sobel_tdiff_vs_oracle_clip_shapes(rt, B, L, variant, algo):
+    """A single pair (B = 1, L = 2: no neighbour pair on either side) and an odd batch of longer clips, all nine sites."""
+    h, w = make_handle(rt, B, L, variant)
+    for site in range(spec.NUM_SITES):
+        _check_sobel_tdiff(h, w, B, L, site, variant, algo)
 
 
 GOLDEN = ["rgb_b1_l7", "rgb_b2_l3", "rgb_b3_l7", "flow_b1_l7", "flow_b2_l3", "flow_b3_l7", "rgbv2_b2_l3"]

@@ -348,3 +348,224 @@ def test_bottleneck_chain14_split_vs_fp64(rt, case, n, kind):
     rms32 = (((got32.double().cpu() - want) ** 2).mean().sqrt() / s).item()
     print("chain %-15s n = %2d %-10s vs fp64: split max %.2e rms %.2e | fp32 pipe max %.2e rms %.2e" % (case, n, kind, e, rms, e32, rms32))
     assert e < 2e-6 and e <= 1.05 * e32 and rms <= 1.05 * rms32
+
+
+# ---- worst-case mantissas: the true dropped-term bound and the accumulation error, separated (tests/test_split_contract.py is the CPU side) ----
+#
+# Operands from synth.make_adversarial: +-2^e (1 + mant / 2^23), e in -3 .. 3, mant one of the patterns whose truncating cut leaves the
+# largest lower planes (0x00FFFF: dropped products 7.83 x 2^-24 |w x|, against the bound 8.015625).  Per output element
+#     |gpu - ref64| <= |ref64 - kept64| + A 2^-24 sum_k |w_k x_k|  (+ 2^-24 |value| per fp32 operation of the epilogue behind the accumulators)
+# where kept64 = the six kept plane products in fp64 (synth.split_terms: the EXACT dropped part, up to 7.83) and A = max(1, 2 c_acc) with
+# c_acc the maximum over elements of the CPU emulation's own accumulation error (synth.emulate_split_dot, two-accumulator form, against
+# kept64) ON THE SAME INPUTS: A is computed in the test from the emulation, never from the kernel's output.  The factor 2: the order and
+# rounding of the products inside one MFMA is recorded only as far as tools/probe_split_mfma.hip part 2 goes.
+# tests/test_split_contract.py::test_losing_any_kept_product_breaks_the_gpu_inequality shows that this inequality fails when any one of the
+# six products is lost (the smallest are 2^-16 of the leading one: c ~ 256).  On these inputs "split <= fp32 pipe" is NOT a property of the
+# arithmetic (the dropped part alone is up to 7.8 where a K = 64 fp32 chain stays near 1): the fp32 pipe is printed beside, not asserted.
+ADV_PATTERNS = [0x00FFFF, 0x7FFFFF, 0x7F7F7F]
+ADV_SIGNS = ["same", "alternating"]
+SECOND_ORDER = 2.0 ** -40          # x sum |w x|: an epilogue rounding is 2^-24 of the COMPUTED value, which is within ~2^-16 sum |w x| of the fp64 one
+
+
+def _pow2_scale(C):
+    """1 / sqrt(C) rounded to a power of two: scaling by it keeps the adversarial mantissas."""
+    return np.float32(2.0 ** -round(np.log2(C) / 2))
+
+
+def adversarial_units_inputs(B, L, pattern, signs, relu):
+    """Nine adversarial maps and the synthetic weights with every motion_conv_gen_* / motion_spatial_down_* weight adversarial too
+    (sign mode along C, scaled by ~1 / sqrt(C)); biases as synth makes them."""
+    feats = [synth.make_adversarial((B * L, C, H, H), pattern, "same", seed=10 + si, relu=relu, k_axis=1) for si, (_n, C, H) in enumerate(spec.SITES)]
+    w = synth.make_weights(spec.VARIANT_RGB)
+    for si, (name, C, _H) in enumerate(spec.SITES):
+        for j, key in enumerate(("motion_conv_gen_%s.weight" % name, "motion_spatial_down_%s.weight" % name)):
+            w[key] = synth.make_adversarial(w[key].shape, pattern, signs, seed=100 + 2 * si + j, k_axis=1) * _pow2_scale(C)
+    return feats, w
+
+
+def adversarial_units_model(feats, w, B, L):
+    """CPU side of the units test.  Per site the limits of T and D (see above) and the pieces the report prints; and the emulation's
+    c_acc maximum over every pre-epilogue sum the outputs use.  Epilogue (pw_tdiff_split.hip): G = relu((A1 + A2) + b) -- A1 + A2 belongs to
+    the emulation, the bias add is one fp32 operation --, T = G[t + 1] - G[t] one more; D = (A1 + A2) + b."""
+    P = B * (L - 1)
+    sites, c_acc = [], 0.0
+    for (name, C, H), x in zip(spec.SITES, feats):
+        HW = H * H
+        X = np.ascontiguousarray(x.transpose(0, 2, 3, 1)).reshape(B * L * HW, C)
+        W = np.concatenate([w["motion_conv_gen_%s.weight" % name].reshape(128, C), w["motion_spatial_down_%s.weight" % name].reshape(32, C)])
+        ref, dropped, mag = synth.split_terms(W, X)
+        c = synth.split_c_acc(synth.emulate_split_dot(W, X, "units"), ref, dropped, mag)
+        c_acc = max(c_acc, c[:, :128].max(), c[:P * HW, 128:].max())
+        bg = w["motion_conv_gen_%s.bias" % name].astype(np.float64)
+        bd = w["motion_spatial_down_%s.bias" % name].astype(np.float64)
+        nchw = lambda a, n, ch: torch.from_numpy(np.ascontiguousarray(a.reshape(n, H, H, ch).transpose(0, 3, 1, 2)))
+        pairs = lambda a: (a.reshape(B, L, HW, 128)[:, 1:], a.reshape(B, L, HW, 128)[:, :-1])
+        s, dr, mg = ref[:, :128], dropped[:, :128], mag[:, :128]
+        g1, g0 = pairs(np.maximum(s + bg, 0.0))
+        k1, k0 = pairs(np.maximum(s - dr + bg, 0.0))
+        m1, m0 = pairs(mg)
+        v1, v0 = pairs(np.abs(s + bg))
+        sd, dd, md = ref[:P * HW, 128:], dropped[:P * HW, 128:], mag[:P * HW, 128:]
+        sites.append({"T_kept": nchw((k1 - k0), P, 128), "T_mag": nchw(m1 + m0, P, 128),
+                      "T_epi": nchw(EPS * (v1 + v0 + np.abs(g1 - g0)) + SECOND_ORDER * (m1 + m0), P, 128),
+                      "D_kept": nchw(sd - dd + bd, P, 32), "D_mag": nchw(md, P, 32),
+                      "D_epi": nchw(EPS * np.abs(sd + bd) + SECOND_ORDER * md, P, 32)})
+    return sites, float(c_acc)
+
+
+def split_report(what, got, ref, kept, mag, epi, A):
+    """Prints the measured c = error / (2^-24 sum |w x|) split into its dropped and accumulation parts, returns the worst excess over the limit."""
+    e_drop, e_acc, e_tot = (ref - kept).abs(), (got - kept).abs(), (got - ref).abs()
+    unit = (EPS * mag).clamp_min(1e-300)
+    limit = e_drop + A * EPS * mag + epi
+    over = (e_tot - limit).max().item()
+    i = int((e_tot - limit).argmax())
+    print("%s: c_total max %.3f | dropped (exact, CPU) max %.3f | accumulation + epilogue (gpu - kept64) max %.3f, allowed A = %.3f | worst element %d: err %.3e limit %.3e"
+          % (what, (e_tot / unit).max().item(), (e_drop / unit).max().item(), (e_acc / unit).max().item(), A, i,
+             e_tot.reshape(-1)[i].item(), limit.reshape(-1)[i].item()))
+    return over
+
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("pattern", ADV_PATTERNS)
+@pytest.mark.parametrize("signs", ADV_SIGNS)
+def test_units_split_worst_case_mantissas(rt, signs, pattern, relu):
+    """h.off_units_fused, all nine sites, B = 2 x L = 7, every T and D element against units_reference_fp64 under the inequality above.
+    Emulated c_acc (CPU, maximum over the nine sites' sums) and A = max(1, 2 c_acc) per case; GPU columns: measured accumulation part
+    (gpu - kept64) / (2^-24 sum |w x|), the epilogue's bias add included, T and D maxima (first MI355X run; also DESIGN.md 5.1):
+
+        signs        pattern   relu   c_acc (emulation)   A       gpu accumulation max (T / D)
+        same         0x00FFFF  no     1.337               2.675   1.496 / 2.035
+        same         0x00FFFF  yes    1.295               2.590   1.773 / 2.013
+        same         0x7FFFFF  no     14.331              28.661  9.979 / 12.268
+        same         0x7FFFFF  yes    14.690              29.381  8.969 / 14.097
+        same         0x7F7F7F  no     13.773              27.547  9.570 / 13.173
+        same         0x7F7F7F  yes    15.586              31.173  9.349 / 13.388
+        alternating  0x00FFFF  no     0.459               1.000   0.511 / 0.767
+        alternating  0x00FFFF  yes    0.651               1.301   0.727 / 1.007
+        alternating  0x7FFFFF  no     2.668               5.337   1.341 / 2.507
+        alternating  0x7FFFFF  yes    4.221               8.443   2.443 / 4.076
+        alternating  0x7F7F7F  no     2.826               5.652   1.582 / 2.874
+        alternating  0x7F7F7F  yes    4.426               8.853   2.337 / 3.850
+    """
+    B, L = 2, 7
+    feats_np, w = adversarial_units_inputs(B, L, pattern, signs, relu)
+    model, c_acc = adversarial_units_model(feats_np, w, B, L)
+    A = max(1.0, 2.0 * c_acc)
+    print("units worst case %s 0x%06X relu %d: emulated c_acc %.3f -> A %.3f" % (signs, pattern, relu, c_acc, A))
+    ref = units_reference_fp64(feats_np, w, B, L)
+    outs, _ = run_units(rt, B, L, "f32split", feats_np, w)
+    outs32, _ = run_units(rt, B, L, "fp32", feats_np, w)
+    worst = []
+    for (name, _C, _H), (T, D), (T32, D32), (Tr, _mT, Dr, _mD), m in zip(spec.SITES, outs, outs32, ref, model):
+        tag = "units worst case %-11s 0x%06X relu %d site %s" % (signs, pattern, relu, name)
+        worst.append((split_report(tag + " T", T, Tr, m["T_kept"], m["T_mag"], m["T_epi"], A), name, "T"))
+        worst.append((split_report(tag + " D", D, Dr, m["D_kept"], m["D_mag"], m["D_epi"], A), name, "D"))
+        print("%s: fp32 pipe beside it (not a limit): c_total T %.3f D %.3f" % (tag, ((T32 - Tr).abs() / (EPS * m["T_mag"]).clamp_min(1e-300)).max().item(),
+                                                                               ((D32 - Dr).abs() / (EPS * m["D_mag"]).clamp_min(1e-300)).max().item()))
+    assert max(worst)[0] <= 0.0, max(worst)
+
+
+ADV_GEMM_SHAPES = [(3, 100, 64, 64), (5, 384, 832, 256), (3, 130, 1280, 192)]
+
+
+def adversarial_gemm_inputs(batch, M, K, Co, pattern, signs):
+    x = synth.make_adversarial((batch, M, K), pattern, "same", seed=500 + K)
+    w = synth.make_adversarial((batch, Co, K), pattern, signs, seed=501 + K) * _pow2_scale(K)
+    return x, w
+
+
+def adversarial_gemm_model(x, w):
+    """(ref, kept, mag) in fp64 and the emulation's c_acc maximum.  wino_gemm_split.hip runs the two-accumulator form (`acc += acs` once per
+    item: form "units" of the emulation); nothing follows the accumulators."""
+    terms = [synth.split_terms(w[b], x[b]) for b in range(x.shape[0])]
+    c_acc = max(synth.split_c_acc(synth.emulate_split_dot(w[b], x[b], "units"), *terms[b]).max() for b in range(x.shape[0]))
+    ref, dropped, mag = (torch.from_numpy(np.stack([t[i] for t in terms])) for i in range(3))
+    return ref, ref - dropped, mag, float(c_acc)
+
+
+@pytest.mark.parametrize("pattern", ADV_PATTERNS)
+@pytest.mark.parametrize("signs", ADV_SIGNS)
+@pytest.mark.parametrize("batch,M,K,Co", ADV_GEMM_SHAPES)
+def test_batched_gemm_split_worst_case_mantissas(rt, batch, M, K, Co, signs, pattern):
+    """batched_gemm_nt(..., "f32split") at the shortest K, a production shape, and the longest K with a row tail and the 64-channel form.
+    Emulated c_acc / A = max(1, 2 c_acc) / measured GPU accumulation part max (first MI355X run), per (shape, signs), patterns 0x00FFFF |
+    0x7FFFFF | 0x7F7F7F:
+
+        (batch, M, K, Co)     signs        c_acc (emulation)         A                         gpu accumulation max
+        (3, 100, 64, 64)      same         1.027 | 3.304 | 3.304     2.054 | 6.608 | 6.609     1.027 | 3.304 | 3.304
+        (3, 100, 64, 64)      alternating  0.608 | 1.875 | 1.640     1.215 | 3.750 | 3.280     0.608 | 1.875 | 2.130
+        (5, 384, 832, 256)    same         1.344 | 12.245 | 12.348   2.688 | 24.490 | 24.696   1.344 | 12.422 | 12.348
+        (5, 384, 832, 256)    alternating  0.327 | 2.442 | 2.712     1.000 | 4.884 | 5.424     0.327 | 2.442 | 2.712
+        (3, 130, 1280, 192)   same         1.305 | 15.148 | 15.579   2.610 | 30.297 | 31.158   1.305 | 15.148 | 15.579
+        (3, 130, 1280, 192)   alternating  0.192 | 1.838 | 1.879     1.000 | 3.677 | 3.757     0.222 | 1.838 | 1.879
+    """
+    x, w = adversarial_gemm_inputs(batch, M, K, Co, pattern, signs)
+    ref, kept, mag, c_acc = adversarial_gemm_model(x, w)
+    A = max(1.0, 2.0 * c_acc)
+    tag = "batched GEMM worst case (%d, %d, %d, %d) %-11s 0x%06X" % (batch, M, K, Co, signs, pattern)
+    print("%s: emulated c_acc %.3f -> A %.3f" % (tag, c_acc, A))
+    y = rt.batched_gemm_nt(dev(x), dev(w), "f32split").double().cpu()
+    y32 = rt.batched_gemm_nt(dev(x), dev(w), "fp32").double().cpu()
+    over = split_report(tag, y, ref, kept, mag, torch.zeros_like(mag), A)
+    print("%s: fp32 pipe beside it (not a limit): c_total %.3f" % (tag, ((y32 - ref).abs() / (EPS * mag)).max().item()))
+    assert over <= 0.0
+
+
+@pytest.mark.parametrize("pattern", ADV_PATTERNS)
+@pytest.mark.parametrize("signs", ADV_SIGNS)
+@pytest.mark.parametrize("case", ["28a_branch", "28b_residual"])
+def test_bottleneck_chain14_split_worst_case_mantissas(rt, case, signs, pattern):
+    """The chains with the FIRST contraction's operands (the chain input and c1's weight) adversarial; t1's bound is asserted indirectly,
+    through the whole chain against fp64 exactly as test_bottleneck_chain14_split_vs_fp64 measures it (max error / max |want| < 2e-6).  The
+    fp32-pipe kernel is printed beside it and is not a limit here."""
+    n, branch = 5, case == "28a_branch"
+    _x, _w1, b1, w2, b2, w3, b3, wb, bb = _chain_inputs(case, n, "normal", 900)
+    Cin, x_coff = (64, 64) if branch else (256, 0)
+    x = torch.from_numpy(synth.make_adversarial((n, 14, 14, Cin + x_coff), pattern, "same", seed=40))
+    w1 = torch.from_numpy(synth.make_adversarial((64, Cin), pattern, signs, seed=41) * _pow2_scale(Cin))
+    xin = x[..., x_coff:x_coff + Cin].permute(0, 3, 1, 2).double()
+    t1 = F.relu(F.conv2d(F.relu(xin) if branch else xin, w1.double()[:, :, None, None], b1.double()))
+    t2 = F.relu(F.conv2d(t1, w2.double(), b2.double(), padding=1))
+    want = F.conv2d(t2, w3.double()[:, :, None, None], b3.double())
+    want = want + (F.conv2d(xin, wb.double()[:, :, None, None], bb.double()) if branch else xin)
+    want = F.relu(want).permute(0, 2, 3, 1)
+    res = None if branch else dev(x)
+    got = rt.bottleneck_chain14_split(dev(x), dev(w1), dev(b1), dev(w2), dev(b2), dev(w3), dev(b3), res=res,
+                                      branch=(dev(wb), dev(bb)) if branch else None, relu_in=branch, x_coff=x_coff)
+    if branch:
+        got32 = rt.bottleneck_chain14(dev(x), dev(w1), dev(b1), dev(w2), dev(b2), dev(torch.cat([w3, wb], 1).contiguous()), dev(b3 + bb),
+                                      relu_in=True, x_coff=x_coff)
+    else:
+        got32 = rt.bottleneck_chain14(dev(x), dev(w1), dev(b1), dev(w2), dev(b2), dev(w3), dev(b3), res=res)
+    torch.cuda.synchronize()
+    s = want.abs().max()
+    e = ((got.double().cpu() - want).abs().max() / s).item()
+    e32 = ((got32.double().cpu() - want).abs().max() / s).item()
+    rms = (((got.double().cpu() - want) ** 2).mean().sqrt() / s).item()
+    print("chain worst case %-13s %-11s 0x%06X vs fp64: split max %.2e rms %.2e | fp32 pipe beside it (not a limit) max %.2e" % (case, signs, pattern, e, rms, e32))
+    assert e < 2e-6
+
+
+@pytest.mark.parametrize("pattern", ADV_PATTERNS)
+@pytest.mark.parametrize("signs", ADV_SIGNS)
+def test_winograd_between_split_worst_case_mantissas(rt, signs, pattern):
+    """winograd_between with its 1x1 conv in split arithmetic (Cin = Cmid = 128, n = 5): w1 adversarial, the Winograd-domain input too (the
+    activations the 1x1 contracts are its output transform); limits and normalisation of tests/test_gpu_paths.py::
+    test_winograd_between_vs_fp64, the fp32-pipe kernel printed beside it."""
+    from tests.test_gpu_paths import _between_reference, rel_err
+    n, cin = 5, 128
+    M = synth.make_adversarial((121, n, cin), pattern, "same", seed=60) * np.float32(0.125)
+    bias = synth.uniform_values(61, cin, 0.5)
+    w1 = synth.make_adversarial((cin, cin), pattern, signs, seed=62) * _pow2_scale(cin)
+    b1 = synth.uniform_values(63, cin, 0.1)
+    x_ref, v_ref = _between_reference(M.astype(np.float64), bias.astype(np.float64), 1, w1.astype(np.float64), b1.astype(np.float64))
+    errs = {}
+    for prec in ("f32split", "fp32"):
+        xbuf = torch.full((n, 7, 7, cin + 64), -3.0, device="cuda")
+        V = rt.winograd_between(dev(M), dev(bias), 1, dev(w1), dev(b1), x=xbuf, x_coff=32, precision=prec)
+        torch.cuda.synchronize()
+        errs[prec] = (rel_err(xbuf[..., 32:32 + cin], x_ref), rel_err(V, v_ref))
+    print("winograd between worst case %-11s 0x%06X: split x %.2e V %.2e | fp32 pipe beside it (not a limit) x %.2e V %.2e"
+          % ((signs, pattern) + errs["f32split"] + errs["fp32"]))
+    assert errs["f32split"][0] < 1e-5 and errs["f32split"][1] < 2e-5
