@@ -24,7 +24,8 @@
  *    give the same values (to 2e-6 in fp32: the fused kernel sums k in another grouping).
  *  - a handle is not thread-safe; distinct handles are independent.
  *  - fp32 everywhere (16-bit feature maps: offk_forward_typed).  Boundary tensors are NCHW contiguous exactly as the reference
- *    backbone produces them; INTERNAL activations (workspace, stage entry points) are
+ *    backbone produces them (a channels_last backbone's NHWC-strided maps, fp32 or 16-bit: offk_forward_cl, layout per call);
+ *    INTERNAL activations (workspace, stage entry points) are
  *    channels-last: [rows = image*H*W + y*W + x][channels], see DESIGN.md.
  */
 #ifndef OFFK_H_
@@ -190,6 +191,28 @@ int offk_forward_typed(offk_handle* h, void* stream, int feat_dtype, const void*
 int offk_forward_parts_typed(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES],
                              float* out7, float* out14, float* out28, void* workspace);
 
+/* Channels-last feature maps (ABI v10, additive).  A backbone run in torch.channels_last hands the nine maps over with NHWC
+ * strides; these entries take them as they are, with no copy, for every feat_dtype.  The layout is a property of the CALL:
+ * cfg.feat_layout keeps describing what the entries above are given and is ignored here.
+ *   feats / parts as in the _typed entries, but every map (part) is physically channels-last: [B*L*H_i*H_i][C_i] (part q:
+ *   [B*L*H_i*H_i][channels[q]]), elements of feat_dtype (OFFK_FEAT_F32 / _BF16 / _F16), 16-byte aligned.  Outputs, workspace
+ *   (offk_workspace_bytes is unchanged) and stream rules are offk_forward's: no synchronisation and no allocation on the call,
+ *   stream-capturable.
+ * Contract: for FINITE maps the three heads and the workspace regions the units fill are EQUAL, element for element, to what
+ * the same handle computes through offk_forward / offk_forward_typed from the NCHW copy of the same logical tensor -- not a
+ * new tolerance.  Why: the channels-last units kernel (csrc/pw_tdiff_cl.hip) puts the same k into the same operand slots
+ * (K-tile kt, lane group g, element e <-> channel 32 kt + 8 g + e of the part that holds it), cuts the values the same way,
+ * multiplies them with the same weight plane image in the same order into the same two accumulators (fp32 maps six MFMAs per
+ * tile and 32-k group, fp16 five, bf16 three) and ends in the same epilogue; only the loader differs: the eight k of a lane's
+ * B operand are 16 or 32 contiguous bytes of a channels-last map.  Every launch after the units is the existing path.
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: null arguments; an unknown feat_dtype; a handle that is not
+ * OFFK_PRECISION_F32SPLIT; a handle created with OFFK_FUSED_UNITS=0; any gen / down weight bound through offk_bind_weight; a
+ * data pointer that is not 16-byte aligned; channel groups offk_forward_parts refuses. */
+int offk_forward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                    float* out7, float* out14, float* out28, void* workspace);
+int offk_forward_parts_cl(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES],
+                          float* out7, float* out14, float* out28, void* workspace);
+
 /* Named regions of the workspace after offk_forward (for stage-level parity tests):
  * "G_<site>", "D_<site>", "fusion_28", "fusion_14", "fusion_7", "sum_7".  All channels-last. */
 int offk_workspace_region(const offk_handle* h, const char* name, size_t* offset_bytes, size_t* nbytes);
@@ -242,6 +265,9 @@ int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[
 /* The same stage for 16-bit maps (offk_forward_typed's dtypes, checks and contract). */
 int offk_off_units_fused_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
                                void* workspace);
+/* The same stage for channels-last maps of any feat_dtype (offk_forward_cl's layout, checks and contract). */
+int offk_off_units_fused_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                            void* workspace);
 
 /* K4. Generic channels-last convolution (the fusion convs, RGB_OFF.py:657-685,762-780,
  * 833-841): y = post( pre(conv(in(x)) + bias) + res ).  x,y,res are channel-sliced views

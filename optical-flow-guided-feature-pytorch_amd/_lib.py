@@ -53,6 +53,8 @@ SIGNATURES = {
     "offk_forward_parts": (_I, [_P, _P, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
     "offk_forward_typed": (_I, [_P, _P, _I, _c.POINTER(_P), _F, _F, _F, _P]),
     "offk_forward_parts_typed": (_I, [_P, _P, _I, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
+    "offk_forward_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _F, _F, _F, _P]),
+    "offk_forward_parts_cl": (_I, [_P, _P, _I, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
     "offk_workspace_region": (_I, [_P, _c.c_char_p, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
     "offk_set_profiling": (_I, [_P, _I]),
     "offk_stage_times": (_I, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _I]),
@@ -63,6 +65,7 @@ SIGNATURES = {
     "offk_off_units": (_I, [_P, _P, _c.POINTER(_F), _P]),
     "offk_off_units_fused": (_I, [_P, _P, _c.POINTER(_F), _P]),
     "offk_off_units_fused_typed": (_I, [_P, _P, _I, _c.POINTER(_P), _P]),
+    "offk_off_units_fused_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _P]),
     "offk_conv2d": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _F, _I, _I, _I, _F, _I, _I]),
     "offk_conv2d_ex": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _F, _I, _I, _I, _F, _I, _I,
                             _I, _I, _F, _c.c_size_t, _I]),

@@ -551,7 +551,10 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
 // Inference path of the units: K1 fused with the temporal difference (pw_tdiff.hip), then the S-blocks of K2 alone.
 // feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (split-fp32 handles, the library's own weight image: offk_forward_typed checks): the
 // 16-bit maps' units kernel (pw_tdiff_f16.hip), which writes the same regions with the same values.
-int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev, int feat_dtype = OFFK_FEAT_F32) {
+// cl (offk_forward_cl and its siblings, whose checks have passed): every part is physically channels-last, elements of feat_dtype --
+// the channels-last units kernel (pw_tdiff_cl.hip), the same regions with the same values again.
+int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev, int feat_dtype = OFFK_FEAT_F32,
+                        bool cl = false) {
   { int rc = finalize_pw(h, st); if (rc != OFFK_OK) return rc; }
   PtParams pt;
   memset(&pt, 0, sizeof(pt));
@@ -582,7 +585,12 @@ int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts fe
   }
   (void)blk;     // block layout (chunks, leftover blocks, blk_begin, total_blocks): pw_tdiff_launch
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
-  if (feat_dtype != OFFK_FEAT_F32) {
+  if (cl) {
+    { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16    ? "units:pw_tdiff (K1T, channels-last fp16 maps)"
+                                 : feat_dtype == OFFK_FEAT_BF16 ? "units:pw_tdiff (K1T, channels-last bf16 maps)"
+                                                                : "units:pw_tdiff (K1T, channels-last maps)"); if (rc != OFFK_OK) return rc; }
+    HIP_TRY(h, pw_tdiff_cl_launch(pt, feat_dtype, st));
+  } else if (feat_dtype != OFFK_FEAT_F32) {
     { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16 ? "units:pw_tdiff (K1T, fp16 maps)" : "units:pw_tdiff (K1T, bf16 maps)"); if (rc != OFFK_OK) return rc; }
     HIP_TRY(h, pw_tdiff_feat16_launch(pt, feat_dtype, st));
   } else {
@@ -1174,7 +1182,7 @@ int offk_forward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM
 }
 
 static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats[OFFK_NUM_SITES], float* out7, float* out14,
-                         float* out28, void* workspace, int feat_dtype);
+                         float* out28, void* workspace, int feat_dtype, bool cl = false);
 
 int offk_forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats[OFFK_NUM_SITES], float* out7, float* out14,
                        float* out28, void* workspace) {
@@ -1240,8 +1248,63 @@ int offk_off_units_fused_typed(offk_handle* h, void* stream, int feat_dtype, con
   return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, feat_dtype);
 }
 
+// ---- channels-last feature maps (offk_forward_cl and its siblings) ----
+// Everything such a call is refused for, checked before anything is enqueued.  The layout belongs to the call: cfg.feat_layout is
+// not looked at.
+static int check_feat_cl(offk_handle* h, int feat_dtype, const offk_feat_parts parts[], const char* fn) {
+  const std::string f(fn);
+  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  if (!h->f32split)
+    return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need an OFFK_PRECISION_F32SPLIT handle (precision=\"f32split\"); "
+                                         "this handle runs the fp32 pipe");
+  if (!h->fused_units)
+    return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need the fused units kernel (the handle was created with OFFK_FUSED_UNITS=0)");
+  for (int s = 0; s < kNumSites; ++s)
+    if (h->bnd_gen_w[s] || h->bnd_down_w[s])
+      return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need the library's own unit weights (a gen / down weight is bound "
+                                           "through offk_bind_weight: " + kSites[s].name + ")");
+  TRY(check_parts(h, parts));
+  for (int s = 0; s < kNumSites; ++s)
+    for (int q = 0; q < parts[s].n_parts; ++q)
+      if (reinterpret_cast<uintptr_t>(parts[s].data[q]) & 15)
+        return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature map pointers must be 16-byte aligned (site " + kSites[s].name + ")");
+  return OFFK_OK;
+}
+
+int offk_forward_parts_cl(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES], float* out7,
+                          float* out14, float* out28, void* workspace) {
+  if (!h || !parts || !out7 || !out14 || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null argument");
+  TRY(check_feat_cl(h, feat_dtype, parts, "offk_forward_cl"));
+  return forward_parts(h, stream, parts, out7, out14, out28, workspace, feat_dtype, true);
+}
+
+int offk_forward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], float* out7, float* out14,
+                    float* out28, void* workspace) {
+  if (!h || !feats) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null argument");
+  offk_feat_parts parts[kNumSites];
+  for (int s = 0; s < kNumSites; ++s) {
+    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null feature map");
+    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
+  }
+  return offk_forward_parts_cl(h, stream, feat_dtype, parts, out7, out14, out28, workspace);
+}
+
+int offk_off_units_fused_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_cl: null argument");
+  offk_feat_parts parts[kNumSites];
+  for (int s = 0; s < kNumSites; ++s) {
+    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_cl: null feature map");
+    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
+  }
+  TRY(check_feat_cl(h, feat_dtype, parts, "offk_off_units_fused_cl"));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, feat_dtype, true);
+}
+
 static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats[OFFK_NUM_SITES], float* out7, float* out14,
-                         float* out28, void* workspace, int feat_dtype) {
+                         float* out28, void* workspace, int feat_dtype, bool cl) {
   if (!h || !feats || !out7 || !out14 || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_forward: null argument");
   TRY(check_parts(h, feats));
   TRY(check_ready(h));
@@ -1263,7 +1326,8 @@ static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts fea
     if ((h->ev_used + 1) * per <= h->events.size()) ev = &h->events[h->ev_used++ * per];
   }
 
-  if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype));
+  if (cl) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype, true));       // (check_feat_cl: fused_units, whatever cfg.feat_layout)
+  else if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype));
   else TRY(run_off_units(h, st, feats, ws, ev));
 
   h->cur_splitk = region(h, ws, "splitk");

@@ -215,6 +215,9 @@ hipError_t pw_tdiff_split_launch(const PtParams& p, hipStream_t st);
 // pw_tdiff_f16.hip: the split-fp32 units kernel on 16-bit NCHW maps (feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16; the parts' data
 // pointers hold 16-bit elements); its own block layout
 hipError_t pw_tdiff_feat16_launch(const PtParams& p, int feat_dtype, hipStream_t st);
+// pw_tdiff_cl.hip: the split-fp32 units kernel on channels-last maps (every part [B L HW][cp], elements of feat_dtype kFeatF32 /
+// kFeatBf16 / kFeatF16, 16-byte aligned); pw_tdiff_feat16_launch's block layout
+hipError_t pw_tdiff_cl_launch(const PtParams& p, int feat_dtype, hipStream_t st);
 
 // ---- K2 ------------------------------------------------------------------------
 struct StSite {

@@ -109,17 +109,29 @@ class OFFSubNetwork(nn.Module):
         return self._rt
 
     # -- forward ----------------------------------------------------------------------
+    def _as_handed_over(self, rt, feats):
+        """A channels_last backbone's nine maps on a precision="f32split" module: the handle takes them with no copy
+        (runtime.OffForward.takes_channels_last decides); everything else is made contiguous as ever."""
+        if all(t.is_contiguous() for f in feats for t in ([f] if torch.is_tensor(f) else f)):
+            return False
+        try:
+            return rt.takes_channels_last(feats)
+        except ValueError:          # a mix of layouts, or an fp32-pipe module: the contiguous copies settle it, as ever
+            return False
+
     def forward(self, feats, want28=True):
         """feats: the nine ``inception_{3a..5b}_output_out`` maps [B*L, C, H, H] fp32 on a HIP
         device -- each either the concatenated tensor or the list of its inception branches in
         torch.cat order (then the concat never has to exist, offk_forward_parts).  bf16 / fp16 maps of one dtype (an autocast
-        backbone's) go through as they are on a precision="f32split" module (offk_forward_typed: the values of the maps upcast).  Returns (fc_action_motion_7, fc_action_motion_14, fc_action_motion_28):
+        backbone's) go through as they are on a precision="f32split" module (offk_forward_typed: the values of the maps upcast), and so
+        do the torch.channels_last maps of a channels_last backbone, in any of the three dtypes (offk_forward_cl: no copy, no cast).  Returns (fc_action_motion_7, fc_action_motion_14, fc_action_motion_28):
         [B*(L-1), classes] each, or [B, classes] with the consensus average."""
-        feats = [f.contiguous() if torch.is_tensor(f) else [g.contiguous() for g in f] for f in feats]
         first = feats[0] if torch.is_tensor(feats[0]) else feats[0][0]
         if not first.is_cuda:
             raise runtime._lib.OffkError("OFFSubNetwork has no CPU path: feature maps must live on an MI355X")
         rt = self._handle(first.device)
+        if not self._as_handed_over(rt, feats):
+            feats = [f.contiguous() if torch.is_tensor(f) else [g.contiguous() for g in f] for f in feats]
         with torch.no_grad():
             return rt.forward(feats, want28=want28)
 

@@ -51,6 +51,47 @@ def feat_dtype(feats):
     return dts.pop()
 
 
+# channels_last feature maps (offk_forward_cl): what a backbone run in torch.channels_last hands over, in any of the three dtypes
+_CL_DTYPES = {torch.float32: _lib.FEAT_F32, torch.bfloat16: _lib.FEAT_BF16, torch.float16: _lib.FEAT_F16}
+
+
+def feat_layout(feats, batch, length):
+    """The one physical layout of nine feature maps (tensors or lists of channel groups); works on CPU tensors.
+    "nchw": every tensor is_contiguous() (what every entry took so far; shapes are the entry's business).
+    "cl":   every tensor has the reference's logical shape [B*L, C, H, H] (a channel group: its own C) and is
+            contiguous in torch.channels_last, i.e. physically [B*L, H, H, C].
+    ValueError when the maps do not have one layout, or when a tensor is neither."""
+    if len(feats) != spec.NUM_SITES:
+        raise ValueError("need nine feature maps")
+    shapes = spec.feature_shapes(batch, length)
+    kinds = set()
+    for i, (f, s) in enumerate(zip(feats, shapes)):
+        for q, t in enumerate([f] if torch.is_tensor(f) else list(f)):
+            name = "feats[%d]" % i if torch.is_tensor(f) else "feats[%d][%d]" % (i, q)
+            if not torch.is_tensor(t):
+                raise ValueError("%s is not a tensor" % name)
+            if t.is_contiguous():
+                kinds.add("nchw")
+            elif t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+                want = (s[0], t.shape[1], s[2], s[3])
+                if tuple(t.shape) != want:
+                    raise ValueError("%s is channels_last with logical shape %s, expected %s" % (name, tuple(t.shape), want))
+                kinds.add("cl")
+            else:
+                raise ValueError("%s is neither contiguous nor torch.channels_last" % name)
+    if len(kinds) != 1:
+        raise ValueError("feature maps must all have one layout (all contiguous or all torch.channels_last), got a mix")
+    return kinds.pop()
+
+
+def _check_dev_cl(t, name, device):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype in _CL_DTYPES and t.dim() == 4
+            and t.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError("%s must be a channels_last fp32, bf16 or fp16 CUDA/HIP tensor" % name)
+    if t.device != device:
+        raise ValueError("%s lives on %s, handle on %s" % (name, t.device, device))
+
+
 class OffForward:
     """One liboffk handle for a fixed (batch, length, variant).
 
@@ -167,6 +208,30 @@ class OffForward:
             raise ValueError("bf16 / fp16 feature maps need a split-fp32 handle (precision=\"f32split\"); this one runs the fp32 pipe")
         return _FEAT_DTYPES[dt]
 
+    def takes_channels_last(self, feats):
+        """True when these nine maps go to the channels-last entries as they are (offk_forward_cl: no copy, no cast): every one a
+        torch.channels_last tensor of the reference's logical shape, on an NCHW-entry (feat_layout 0) split-fp32 handle.  Mixed
+        layouts raise (feat_layout); whatever else is not this case returns False and meets the checks it always met."""
+        if self.feat_layout != 0 or len(feats) != spec.NUM_SITES:
+            return False
+        ts = [t for f in feats for t in ([f] if torch.is_tensor(f) else list(f))]
+        if any(not torch.is_tensor(t) for t in ts) or all(t.is_contiguous() for t in ts):
+            return False
+        if not any(t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) for t in ts):
+            return False
+        if feat_layout(feats, self.batch, self.length) != "cl":
+            return False
+        if self.precision != _lib.PRECISION_F32SPLIT:
+            raise ValueError("feature maps must be contiguous fp32 CUDA/HIP tensors on this handle (the fp32 pipe): channels_last "
+                             "maps need a split-fp32 handle (precision=\"f32split\")")
+        return True
+
+    def _cl_dtype(self, feats):
+        dt = feat_dtype(feats)
+        if dt not in _CL_DTYPES:
+            raise ValueError("channels_last feature maps must be fp32, bf16 or fp16, got %s" % dt)
+        return _CL_DTYPES[dt]
+
     def _train16(self, feats):
         """enum offk_feat_dtype of nine bf16 / fp16 maps for the training-side entries (offk_off_units_typed and its siblings), None for
         fp32 ones.  No condition on the handle's precision here: that one belongs to the inference forward (_feat16)."""
@@ -208,7 +273,11 @@ class OffForward:
 
     def forward(self, feats, want28=True):
         """feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (split-fp32 handles: offk_forward_typed, the values of
-        the same maps upcast); each map a tensor or a list of its channel groups.  Logits are fp32 either way."""
+        the same maps upcast); each map a tensor or a list of its channel groups.  Logits are fp32 either way.
+        torch.channels_last maps of any of the three dtypes (all nine, logical shape as ever) are taken as they are on a split-fp32
+        handle (offk_forward_cl) and give the values of their contiguous copies."""
+        if self.takes_channels_last(feats):
+            return self._forward_cl(feats, want28)
         fdt = self._feat16(feats)
         if fdt is not None:
             return self._forward16(feats, fdt, want28)
@@ -245,6 +314,22 @@ class OffForward:
                                                    _ptr(self.workspace)), self._h)
         return out7, out14, out28
 
+    def _forward_cl(self, feats, want28):
+        fdt = self._cl_dtype(feats)
+        rows = self.out_rows()
+        out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
+        out14 = torch.empty_like(out7)
+        out28 = torch.empty_like(out7) if want28 else None
+        if any(not torch.is_tensor(f) for f in feats):
+            arr = self._parts_array(feats, _check_dev_cl)
+            _lib.check(self.lib.offk_forward_parts_cl(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
+                                                      _ptr(self.workspace)), self._h)
+        else:
+            arr = self._feat_array(feats, _check_dev_cl)
+            _lib.check(self.lib.offk_forward_cl(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
+                                                _ptr(self.workspace)), self._h)
+        return out7, out14, out28
+
     def forward_into(self, feat_array, out7, out14, out28):
         """Launch-only variant for benchmarking: pre-validated ctypes array + outputs."""
         _lib.check(self.lib.offk_forward(self._h, _stream(self.device), feat_array, _ptr(out7), _ptr(out14), _ptr(out28),
@@ -263,7 +348,12 @@ class OffForward:
 
     def off_units_fused(self, feats):
         """The units as forward() runs them (fused K1T + S-blocks, the handle's arithmetic); results in the fusion_* / D_* regions.
-        bf16 / fp16 maps (split-fp32 handles): offk_off_units_fused_typed."""
+        bf16 / fp16 maps (split-fp32 handles): offk_off_units_fused_typed; torch.channels_last maps: offk_off_units_fused_cl."""
+        if self.takes_channels_last(feats):
+            arr = self._feat_array(feats, _check_dev_cl)
+            _lib.check(self.lib.offk_off_units_fused_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace)),
+                       self._h)
+            return
         fdt = self._feat16(feats)
         if fdt is not None:
             arr = self._feat_array(feats, _check_dev16)
