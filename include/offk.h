@@ -177,7 +177,8 @@ int offk_forward_parts(offk_handle* h, void* stream, const offk_feat_parts parts
  * x.float() -- not a new tolerance.  Why: a bf16 value is exactly its own leading bf16 plane (x_m = x_l = +0), an fp16 value
  * (11 significant bits, subnormals included: each is a normal number in bf16's exponent range) exactly two (x_l = +0).  The
  * fp32-map units kernel issues per output tile and 32-k group, into A2: w_l x_h, w_h x_l, w_m x_m, w_m x_h, w_h x_m, then
- * into A1: w_h x_h; the products of a +0 plane are +-0.  The 16-bit kernel (csrc/pw_tdiff_f16.hip) issues the other MFMAs --
+ * into A1: w_h x_h; the products of a +0 plane are +-0.  The 16-bit kernel (csrc/pw_tdiff_f16.hip: its loader on the block
+ * body of csrc/pw_tdiff_staged.h, which the channels-last kernel below shares) issues the other MFMAs --
  * bf16 three, fp16 five -- with the same k in the same operand slots, in the same order, into the same two accumulators,
  * from the same weight plane image, and ends in the same epilogue; every launch after it is the fp32-map path's, on the
  * same buffers.  Non-finite maps are outside the equality: every output a non-finite value touches is non-finite, as in
@@ -200,7 +201,8 @@ int offk_forward_parts_typed(offk_handle* h, void* stream, int feat_dtype, const
  *   stream-capturable.
  * Contract: for FINITE maps the three heads and the workspace regions the units fill are EQUAL, element for element, to what
  * the same handle computes through offk_forward / offk_forward_typed from the NCHW copy of the same logical tensor -- not a
- * new tolerance.  Why: the channels-last units kernel (csrc/pw_tdiff_cl.hip) puts the same k into the same operand slots
+ * new tolerance.  Why: the channels-last units kernel (csrc/pw_tdiff_cl.hip: its loader on the block body of
+ * csrc/pw_tdiff_staged.h, the 16-bit kernel's) puts the same k into the same operand slots
  * (K-tile kt, lane group g, element e <-> channel 32 kt + 8 g + e of the part that holds it), cuts the values the same way,
  * multiplies them with the same weight plane image in the same order into the same two accumulators (fp32 maps six MFMAs per
  * tile and 32-k group, fp16 five, bf16 three) and ends in the same epilogue; only the loader differs: the eight k of a lane's

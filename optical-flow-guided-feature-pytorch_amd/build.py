@@ -20,7 +20,7 @@ SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "sobel_tdiff.hi
            "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip")
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",)}
-HEADERS = ("offk_common.h", "offk_internal.h", "winograd_common.h", os.path.join("..", "..", "include", "offk.h"))
+HEADERS = ("offk_common.h", "offk_internal.h", "pw_tdiff_staged.h", "winograd_common.h", os.path.join("..", "..", "include", "offk.h"))
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=fast"]
 # heads.hip: no SLP vectoriser.  It pairs the FC accumulators of neighbouring classes into v_pk_fma_f32 with

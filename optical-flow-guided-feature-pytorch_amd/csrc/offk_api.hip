@@ -487,6 +487,16 @@ offk_feat_parts whole_map(int site, const float* p) {
   return fp;
 }
 
+// nine non-null pointers -> nine whole maps, else "<fn>: null feature map"
+template <class T>
+int whole_maps(offk_handle* h, const T* const feats[], offk_feat_parts parts[], const char* fn) {
+  for (int s = 0; s < kNumSites; ++s) {
+    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null feature map");
+    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
+  }
+  return OFFK_OK;
+}
+
 int check_parts(offk_handle* h, const offk_feat_parts parts[]) {
   for (int s = 0; s < kNumSites; ++s) {
     const offk_feat_parts& fp = parts[s];
@@ -552,7 +562,8 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
 // feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (split-fp32 handles, the library's own weight image: offk_forward_typed checks): the
 // 16-bit maps' units kernel (pw_tdiff_f16.hip), which writes the same regions with the same values.
 // cl (offk_forward_cl and its siblings, whose checks have passed): every part is physically channels-last, elements of feat_dtype --
-// the channels-last units kernel (pw_tdiff_cl.hip), the same regions with the same values again.
+// the channels-last units kernel (pw_tdiff_cl.hip), the same regions with the same values again.  (Both: one block body,
+// pw_tdiff_staged.h, with a loader each.)
 int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev, int feat_dtype = OFFK_FEAT_F32,
                         bool cl = false) {
   { int rc = finalize_pw(h, st); if (rc != OFFK_OK) return rc; }
@@ -567,8 +578,7 @@ int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts fe
   for (int s = 0; s < kNumSites; ++s)
     if (h->bnd_gen_w[s] || h->bnd_down_w[s]) pt.bdirect = 0;
   const char* fus[3] = {"fusion_28", "fusion_14", "fusion_7"};
-  int blk = 0;
-  for (int i = 0; i < kNumSites; ++i) {
+  for (int i = 0; i < kNumSites; ++i) {      // (the block layout -- chunks, leftover blocks, blk_begin, total_blocks -- is the launchers')
     const int s = kPwOrder[i];
     PtSite& o = pt.s[i];
     const offk_feat_parts& fp = feats[s];
@@ -583,7 +593,6 @@ int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts fe
     o.m_cs = kFusionC[kSiteFusion[s]]; o.m_coff = kSiteCoff[s];
     o.C = kSites[s].C; o.HW = kSites[s].H * kSites[s].H;
   }
-  (void)blk;     // block layout (chunks, leftover blocks, blk_begin, total_blocks): pw_tdiff_launch
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
   if (cl) {
     { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16    ? "units:pw_tdiff (K1T, channels-last fp16 maps)"
@@ -1147,25 +1156,19 @@ int offk_sobel_tdiff_all(offk_handle* h, void* stream, void* workspace, int algo
 
 int offk_off_units(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace) {
   if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units: null argument");
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units: null feature map");
-    TRY(site_weights_ready(h, s, true, true));
-  }
-  DeviceGuard guard(h->cfg.device);
   offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) parts[s] = whole_map(s, feats[s]);
+  TRY(whole_maps(h, feats, parts, "offk_off_units"));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
   return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
 }
 
 int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace) {
   if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused: null argument");
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused: null feature map");
-    TRY(site_weights_ready(h, s, true, true));
-  }
-  DeviceGuard guard(h->cfg.device);
   offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) parts[s] = whole_map(s, feats[s]);
+  TRY(whole_maps(h, feats, parts, "offk_off_units_fused"));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
   if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
   return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
 }
@@ -1174,10 +1177,7 @@ int offk_forward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM
                  float* out28, void* workspace) {
   if (!h || !feats) return fail(h, OFFK_ERR_INVALID, "offk_forward: null argument");
   offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_forward: null feature map");
-    parts[s] = whole_map(s, feats[s]);
-  }
+  TRY(whole_maps(h, feats, parts, "offk_forward"));
   return offk_forward_parts(h, stream, parts, out7, out14, out28, workspace);
 }
 
@@ -1189,118 +1189,96 @@ int offk_forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats
   return forward_parts(h, stream, feats, out7, out14, out28, workspace, OFFK_FEAT_F32);
 }
 
-// ---- 16-bit feature maps (offk_forward_typed and its siblings) ----
-// Everything a 16-bit call is refused for, checked before anything is enqueued.
-static int check_feat16(offk_handle* h, int feat_dtype, const offk_feat_parts parts[], const char* fn) {
-  const std::string f(fn);
-  if (feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+// ---- 16-bit NCHW feature maps (offk_forward_typed and its siblings), channels-last feature maps (offk_forward_cl and its siblings) ----
+// What tells the two families apart.  Channels-last: the layout belongs to the call, cfg.feat_layout is not looked at.
+struct FeatKind {
+  const char* noun;      // in the messages
+  bool f32_ok;           // OFFK_FEAT_F32 is one of its dtypes
+  int align;             // of the map pointers, bytes
+  bool cl;               // channels-last parts (else NCHW, and an NHWC handle is refused)
+};
+constexpr FeatKind kKind16{"16-bit", false, 4, false}, kKindCl{"channels-last", true, 16, true};
+
+// Everything such a call is refused for, checked before anything is enqueued.
+static int check_feat(offk_handle* h, const FeatKind& k, int feat_dtype, const offk_feat_parts parts[], const char* fn) {
+  const std::string f(fn), maps = std::string(": ") + k.noun + " feature maps ";
+  if (!(feat_dtype == OFFK_FEAT_F32 && k.f32_ok) && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
     return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
   if (!h->f32split)
-    return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps need an OFFK_PRECISION_F32SPLIT handle (precision=\"f32split\"); "
-                                         "this handle runs the fp32 pipe");
-  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps are NCHW-only (this handle is NHWC)");
+    return fail(h, OFFK_ERR_INVALID, f + maps + "need an OFFK_PRECISION_F32SPLIT handle (precision=\"f32split\"); this handle runs the fp32 pipe");
+  if (!k.cl && h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + maps + "are NCHW-only (this handle is NHWC)");
   if (!h->fused_units)
-    return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps need the fused units kernel (the handle was created with OFFK_FUSED_UNITS=0)");
+    return fail(h, OFFK_ERR_INVALID, f + maps + "need the fused units kernel (the handle was created with OFFK_FUSED_UNITS=0)");
   for (int s = 0; s < kNumSites; ++s)
     if (h->bnd_gen_w[s] || h->bnd_down_w[s])
-      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps need the library's own unit weights (a gen / down weight is bound "
-                                           "through offk_bind_weight: " + kSites[s].name + ")");
+      return fail(h, OFFK_ERR_INVALID, f + maps + "need the library's own unit weights (a gen / down weight is bound through offk_bind_weight: " +
+                                           kSites[s].name + ")");
   TRY(check_parts(h, parts));
   for (int s = 0; s < kNumSites; ++s)
     for (int q = 0; q < parts[s].n_parts; ++q)
-      if (reinterpret_cast<uintptr_t>(parts[s].data[q]) & 3)
-        return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature map pointers must be 4-byte aligned (site " + kSites[s].name + ")");
+      if (reinterpret_cast<uintptr_t>(parts[s].data[q]) & (k.align - 1))
+        return fail(h, OFFK_ERR_INVALID, f + ": " + k.noun + " feature map pointers must be " + std::to_string(k.align) + "-byte aligned (site " +
+                                             kSites[s].name + ")");
   return OFFK_OK;
+}
+
+// the common tails of the two families' entries; fn: the name the messages carry
+static int forward_parts_kind(offk_handle* h, void* stream, const FeatKind& k, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES],
+                              float* out7, float* out14, float* out28, void* workspace, const char* fn) {
+  if (!h || !parts || !out7 || !out14 || !workspace) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  TRY(check_feat(h, k, feat_dtype, parts, fn));
+  return forward_parts(h, stream, parts, out7, out14, out28, workspace, feat_dtype, k.cl);
+}
+
+static int forward_kind(offk_handle* h, void* stream, const FeatKind& k, int feat_dtype, const void* const feats[OFFK_NUM_SITES], float* out7,
+                        float* out14, float* out28, void* workspace, const char* fn) {
+  if (!h || !feats) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
+  return forward_parts_kind(h, stream, k, feat_dtype, parts, out7, out14, out28, workspace, fn);
+}
+
+static int off_units_fused_kind(offk_handle* h, void* stream, const FeatKind& k, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                                void* workspace, const char* fn) {
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
+  TRY(check_feat(h, k, feat_dtype, parts, fn));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, feat_dtype, k.cl);
 }
 
 int offk_forward_parts_typed(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES], float* out7,
                              float* out14, float* out28, void* workspace) {
   if (feat_dtype == OFFK_FEAT_F32) return offk_forward_parts(h, stream, parts, out7, out14, out28, workspace);
-  if (!h || !parts || !out7 || !out14 || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_forward_typed: null argument");
-  TRY(check_feat16(h, feat_dtype, parts, "offk_forward_typed"));
-  return forward_parts(h, stream, parts, out7, out14, out28, workspace, feat_dtype);
+  return forward_parts_kind(h, stream, kKind16, feat_dtype, parts, out7, out14, out28, workspace, "offk_forward_typed");
 }
 
 int offk_forward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], float* out7,
                        float* out14, float* out28, void* workspace) {
   if (feat_dtype == OFFK_FEAT_F32)
     return offk_forward(h, stream, reinterpret_cast<const float* const*>(feats), out7, out14, out28, workspace);
-  if (!h || !feats) return fail(h, OFFK_ERR_INVALID, "offk_forward_typed: null argument");
-  offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_forward_typed: null feature map");
-    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
-  }
-  return offk_forward_parts_typed(h, stream, feat_dtype, parts, out7, out14, out28, workspace);
+  return forward_kind(h, stream, kKind16, feat_dtype, feats, out7, out14, out28, workspace, "offk_forward_typed");
 }
 
 int offk_off_units_fused_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
   if (feat_dtype == OFFK_FEAT_F32) return offk_off_units_fused(h, stream, reinterpret_cast<const float* const*>(feats), workspace);
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_typed: null argument");
-  offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_typed: null feature map");
-    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
-  }
-  TRY(check_feat16(h, feat_dtype, parts, "offk_off_units_fused_typed"));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, feat_dtype);
-}
-
-// ---- channels-last feature maps (offk_forward_cl and its siblings) ----
-// Everything such a call is refused for, checked before anything is enqueued.  The layout belongs to the call: cfg.feat_layout is
-// not looked at.
-static int check_feat_cl(offk_handle* h, int feat_dtype, const offk_feat_parts parts[], const char* fn) {
-  const std::string f(fn);
-  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
-    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
-  if (!h->f32split)
-    return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need an OFFK_PRECISION_F32SPLIT handle (precision=\"f32split\"); "
-                                         "this handle runs the fp32 pipe");
-  if (!h->fused_units)
-    return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need the fused units kernel (the handle was created with OFFK_FUSED_UNITS=0)");
-  for (int s = 0; s < kNumSites; ++s)
-    if (h->bnd_gen_w[s] || h->bnd_down_w[s])
-      return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature maps need the library's own unit weights (a gen / down weight is bound "
-                                           "through offk_bind_weight: " + kSites[s].name + ")");
-  TRY(check_parts(h, parts));
-  for (int s = 0; s < kNumSites; ++s)
-    for (int q = 0; q < parts[s].n_parts; ++q)
-      if (reinterpret_cast<uintptr_t>(parts[s].data[q]) & 15)
-        return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature map pointers must be 16-byte aligned (site " + kSites[s].name + ")");
-  return OFFK_OK;
+  return off_units_fused_kind(h, stream, kKind16, feat_dtype, feats, workspace, "offk_off_units_fused_typed");
 }
 
 int offk_forward_parts_cl(offk_handle* h, void* stream, int feat_dtype, const offk_feat_parts parts[OFFK_NUM_SITES], float* out7,
                           float* out14, float* out28, void* workspace) {
-  if (!h || !parts || !out7 || !out14 || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null argument");
-  TRY(check_feat_cl(h, feat_dtype, parts, "offk_forward_cl"));
-  return forward_parts(h, stream, parts, out7, out14, out28, workspace, feat_dtype, true);
+  return forward_parts_kind(h, stream, kKindCl, feat_dtype, parts, out7, out14, out28, workspace, "offk_forward_cl");
 }
 
 int offk_forward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], float* out7, float* out14,
                     float* out28, void* workspace) {
-  if (!h || !feats) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null argument");
-  offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_forward_cl: null feature map");
-    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
-  }
-  return offk_forward_parts_cl(h, stream, feat_dtype, parts, out7, out14, out28, workspace);
+  return forward_kind(h, stream, kKindCl, feat_dtype, feats, out7, out14, out28, workspace, "offk_forward_cl");
 }
 
 int offk_off_units_fused_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_cl: null argument");
-  offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units_fused_cl: null feature map");
-    parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
-  }
-  TRY(check_feat_cl(h, feat_dtype, parts, "offk_off_units_fused_cl"));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, feat_dtype, true);
+  return off_units_fused_kind(h, stream, kKindCl, feat_dtype, feats, workspace, "offk_off_units_fused_cl");
 }
 
 static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats[OFFK_NUM_SITES], float* out7, float* out14,
@@ -1326,7 +1304,7 @@ static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts fea
     if ((h->ev_used + 1) * per <= h->events.size()) ev = &h->events[h->ev_used++ * per];
   }
 
-  if (cl) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype, true));       // (check_feat_cl: fused_units, whatever cfg.feat_layout)
+  if (cl) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype, true));       // (check_feat: fused_units, whatever cfg.feat_layout)
   else if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype));
   else TRY(run_off_units(h, st, feats, ws, ev));
 
@@ -1623,13 +1601,10 @@ int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[
   if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train: null argument");
   DropCfg drop;
   TRY(make_drop(h, drop_seed, drop_p, &drop));
-  for (int s = 0; s < kNumSites; ++s) {
-    if (!feats[s]) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train: null feature map");
-    TRY(site_weights_ready(h, s, true, true));
-  }
-  DeviceGuard guard(h->cfg.device);
   offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) parts[s] = whole_map(s, feats[s]);
+  TRY(whole_maps(h, feats, parts, "offk_off_units_train"));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
   return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop);
 }
 
@@ -1724,7 +1699,7 @@ int offk_off_units_backward(offk_handle* h, void* stream, const float* const fea
 }
 
 // ---- 16-bit feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_typed and its siblings ----
-// Everything such a call is refused for, checked before anything is enqueued.  Unlike check_feat16 (the inference forward) there is
+// Everything such a call is refused for, checked before anything is enqueued.  Unlike check_feat (the inference forward) there is
 // no condition on the handle's precision, on bound weights or on OFFK_FUSED_UNITS: these entries run the fp32 kernels K1 / K1b.
 static int check_feat16_train(offk_handle* h, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
   const std::string f(fn);
@@ -1762,10 +1737,10 @@ int offk_pw_reduce_typed(offk_handle* h, void* stream, int feat_dtype, int site,
 static int off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
                            const DropCfg& drop, const char* fn) {
   TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, fn));
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
   for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
   DeviceGuard guard(h->cfg.device);
-  offk_feat_parts parts[kNumSites];
-  for (int s = 0; s < kNumSites; ++s) parts[s] = whole_map(s, static_cast<const float*>(feats[s]));
   return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop, feat_dtype);
 }
 

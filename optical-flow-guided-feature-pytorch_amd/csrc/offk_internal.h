@@ -212,11 +212,10 @@ hipError_t pw_pack_direct16_launch(const float* w160, int C, float* out, hipStre
 // pw_tdiff_split.hip: out = 160 * C * 6 bytes; p with the 16-pixel form's block layout (pw_tdiff_launch fills it and calls this)
 hipError_t pw_pack_split16_launch(const float* w160, int C, void* out, hipStream_t st);
 hipError_t pw_tdiff_split_launch(const PtParams& p, hipStream_t st);
-// pw_tdiff_f16.hip: the split-fp32 units kernel on 16-bit NCHW maps (feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16; the parts' data
-// pointers hold 16-bit elements); its own block layout
+// The split-fp32 units kernels that stage their maps through LDS: one block body and block layout (pw_tdiff_staged.h), a loader each.
+// pw_tdiff_f16.hip: 16-bit NCHW maps (feat_dtype kFeatBf16 / kFeatF16; the parts' data pointers hold 16-bit elements, 4-byte aligned)
 hipError_t pw_tdiff_feat16_launch(const PtParams& p, int feat_dtype, hipStream_t st);
-// pw_tdiff_cl.hip: the split-fp32 units kernel on channels-last maps (every part [B L HW][cp], elements of feat_dtype kFeatF32 /
-// kFeatBf16 / kFeatF16, 16-byte aligned); pw_tdiff_feat16_launch's block layout
+// pw_tdiff_cl.hip: channels-last maps (every part [B L HW][cp], elements of feat_dtype kFeatF32 / kFeatBf16 / kFeatF16, 16-byte aligned)
 hipError_t pw_tdiff_cl_launch(const PtParams& p, int feat_dtype, hipStream_t st);
 
 // ---- K2 ------------------------------------------------------------------------
