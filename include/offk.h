@@ -24,7 +24,8 @@
  *    give the same values (to 2e-6 in fp32: the fused kernel sums k in another grouping).
  *  - a handle is not thread-safe; distinct handles are independent.
  *  - fp32 everywhere (16-bit feature maps: offk_forward_typed).  Boundary tensors are NCHW contiguous exactly as the reference
- *    backbone produces them (a channels_last backbone's NHWC-strided maps, fp32 or 16-bit: offk_forward_cl, layout per call);
+ *    backbone produces them (a channels_last backbone's NHWC-strided maps, fp32 or 16-bit: offk_forward_cl, and on the
+ *    training side offk_off_units_train_cl / offk_off_units_backward_cl, layout per call);
  *    INTERNAL activations (workspace, stage entry points) are
  *    channels-last: [rows = image*H*W + y*W + x][channels], see DESIGN.md.
  */
@@ -441,7 +442,8 @@ int offk_unit_grad_slot(const offk_handle* h, const char* key, size_t* offset_fl
  * offk_off_units(_train) / offk_forward call on the same feats left them, and the same drop_seed / drop_p.
  * gm[s]: gradient w.r.t. motion_<site>.  grads: the flat buffer above; accumulate != 0 adds to it (the
  * reference calls backward three times per step, train_off.py:141-143), otherwise it is overwritten.
- * Every reduction has a fixed order: results are bit-reproducible.  NCHW feature maps only. */
+ * Every reduction has a fixed order: results are bit-reproducible.  NCHW feature maps only (channels-last maps:
+ * offk_off_units_backward_cl below). */
 int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                             const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                             float* grads, int accumulate);
@@ -483,6 +485,40 @@ int offk_off_units_train_typed(offk_handle* h, void* stream, int feat_dtype, con
 int offk_off_units_backward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
                                   const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed,
                                   double drop_p, float* grads, int accumulate);
+
+/* ---- channels-last feature maps on the training side (additive; ABI version unchanged) -----------
+ * A frozen backbone run in torch.channels_last hands over NHWC-strided maps.  These four entries are offk_pw_reduce,
+ * offk_off_units, offk_off_units_train and offk_off_units_backward on such maps as they are, argument for argument the
+ * _typed entries above:
+ *   feat_dtype OFFK_FEAT_F32 / _BF16 / _F16 (OFFK_FEAT_F32 is a form of its own here, not a forward to the untyped entry);
+ *   feats[i] (feat): the channels-last image [B*L*H_i*H_i][C_i] of the logical [B*L, C_i, H_i, H_i] map, elements of
+ *   feat_dtype, 16-byte aligned.
+ * The layout belongs to the call, as in offk_forward_cl: cfg.feat_layout keeps describing what the untyped entries are
+ * given and is not looked at here.  No condition on the handle either: both precisions, bound or set weights, any
+ * OFFK_FUSED_UNITS setting (K1 + K2, never the fused kernel).  Outputs, gradients and the workspace stay fp32;
+ * offk_train_workspace_bytes is unchanged.
+ *
+ * Contract: EQUAL VALUES, not a tolerance.  Everything a _cl call writes -- G_<site>, D_<site>, the unit channels of
+ * fusion_28/14/7, the whole flat gradient buffer in both accumulate modes -- is bit-equal to what the untyped / _typed
+ * call of the same feat_dtype writes from the NCHW copy of the same logical tensors.  Why: only the loaders of K1 and
+ * K1b differ.  K1 reads four consecutive channels of a row per load (fp32: 16 bytes, the kernel's existing channels-last
+ * loader, now chosen per call; 16-bit: 8 bytes through a buffer descriptor, widened on the way into LDS); K1b reads four
+ * consecutive channels of a pixel per load and transposes 4 x 4 in registers, as it always did for dG.  Both fill
+ * exactly the LDS image the NCHW loaders fill, in front of the same MFMA sequence, epilogue, slab layout and launch plan.
+ * Rows / pixels past the end of a site read zeros (K1 16-bit: an out-of-range buffer offset; K1b: the zero page).
+ *
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: an unknown feat_dtype; a null map; a map pointer that is
+ * not 16-byte aligned; a single 16-bit map of 2 GiB or more (K1's 16-bit loaders address through a buffer descriptor;
+ * fp32 maps have no such limit).  The untyped entries' own checks (dropout probability, gradient views) apply unchanged.
+ * The _typed entries keep refusing an NHWC handle: their maps are NCHW. */
+int offk_pw_reduce_cl(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D);
+int offk_off_units_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                      void* workspace);
+int offk_off_units_train_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                            void* workspace, uint64_t drop_seed, double drop_p);
+int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                               const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed,
+                               double drop_p, float* grads, int accumulate);
 
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);

@@ -524,13 +524,14 @@ int finalize_pw(offk_handle* h, hipStream_t st) {
 
 // feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (the typed training entries; check_feat16_train has passed): K1 runs its 16-bit map form
 // on the same grid; the parts' data pointers then address 16-bit elements.
-int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev,
+// nhwc: the maps of THIS call are channels-last (the untyped entries pass the handle's cfg.feat_layout, the _cl entries true).
+int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev, bool nhwc,
                   const DropCfg& drop = DropCfg(), int feat_dtype = OFFK_FEAT_F32) {
   { int rc = finalize_pw(h, st); if (rc != OFFK_OK) return rc; }
   PwParams pp;
   memset(&pp, 0, sizeof(pp));
   pp.nsites = kNumSites; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
-  pp.nhwc = h->cfg.feat_layout == OFFK_FEAT_NHWC;
+  pp.nhwc = nhwc;
   pp.zeros = h->zero_page;
   int blk = 0;
   for (int i = 0; i < kNumSites; ++i) {
@@ -544,7 +545,8 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
   if (feat_dtype != OFFK_FEAT_F32) {
     if (!pw_reduce_feat16_supported(pp)) return fail(h, OFFK_ERR_INVALID, "16-bit feature maps: a map of 2 GiB or more is not supported");
-    { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, fp16 maps)" : "units:pw_reduce (K1, bf16 maps)"); if (rc != OFFK_OK) return rc; }
+    { int rc = trace_mark(h, st, nhwc ? (feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, channels-last fp16 maps)" : "units:pw_reduce (K1, channels-last bf16 maps)")
+                                      : (feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, fp16 maps)" : "units:pw_reduce (K1, bf16 maps)")); if (rc != OFFK_OK) return rc; }
     HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, st));
   } else {
     { int rc = trace_mark(h, st, "units:pw_reduce (K1)"); if (rc != OFFK_OK) return rc; }
@@ -1160,7 +1162,7 @@ int offk_off_units(offk_handle* h, void* stream, const float* const feats[OFFK_N
   TRY(whole_maps(h, feats, parts, "offk_off_units"));
   for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
   DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, h->cfg.feat_layout == OFFK_FEAT_NHWC);
 }
 
 int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace) {
@@ -1170,7 +1172,7 @@ int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[
   for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
   DeviceGuard guard(h->cfg.device);
   if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) return run_off_units_fused(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, h->cfg.feat_layout == OFFK_FEAT_NHWC);
 }
 
 int offk_forward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], float* out7, float* out14,
@@ -1306,7 +1308,7 @@ static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts fea
 
   if (cl) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype, true));       // (check_feat: fused_units, whatever cfg.feat_layout)
   else if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype));
-  else TRY(run_off_units(h, st, feats, ws, ev));
+  else TRY(run_off_units(h, st, feats, ws, ev, h->cfg.feat_layout == OFFK_FEAT_NHWC));
 
   h->cur_splitk = region(h, ws, "splitk");
   float* F28 = region(h, ws, "fusion_28");
@@ -1605,15 +1607,15 @@ int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[
   TRY(whole_maps(h, feats, parts, "offk_off_units_train"));
   for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
   DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, h->cfg.feat_layout == OFFK_FEAT_NHWC, drop);
 }
 
 // feat_dtype != OFFK_FEAT_F32: feats[] address 16-bit elements and check_feat16_train has passed; only K1b reads them
+// nhwc: the maps of this call are channels-last (offk_off_units_backward_cl, check_feat_cl_train has passed): K1b's channels-last forms
 static int off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                               const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
-                              float* grads, int accumulate, int feat_dtype) {
+                              float* grads, int accumulate, int feat_dtype, bool nhwc) {
   if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: null argument");
-  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: NCHW feature maps only");
   DropCfg drop;
   TRY(make_drop(h, drop_seed, drop_p, &drop));
   for (int s = 0; s < kNumSites; ++s) {
@@ -1686,7 +1688,8 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
     r.C = w.C; r.cpad = w.ntiles * 128; r.nchunks = w.nchunks; r.nsblocks = nsblocks[s];
   }
   wp.total_blocks = blk;
-  if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_wgrad_feat16_launch(wp, feat_dtype, st));
+  if (nhwc) HIP_TRY(h, pw_wgrad_cl_launch(wp, feat_dtype, st));
+  else if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_wgrad_feat16_launch(wp, feat_dtype, st));
   else HIP_TRY(h, pw_wgrad_launch(wp, st));
   HIP_TRY(h, wgrad_reduce_launch(rp, st));
   return OFFK_OK;
@@ -1695,7 +1698,9 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
 int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                             const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                             float* grads, int accumulate) {
-  return off_units_backward(h, stream, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, OFFK_FEAT_F32);
+  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: null argument");
+  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: NCHW feature maps only");
+  return off_units_backward(h, stream, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, OFFK_FEAT_F32, false);
 }
 
 // ---- 16-bit feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_typed and its siblings ----
@@ -1741,7 +1746,7 @@ static int off_units_typed(offk_handle* h, void* stream, int feat_dtype, const v
   TRY(whole_maps(h, feats, parts, fn));
   for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
   DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, drop, feat_dtype);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, false, drop, feat_dtype);
 }
 
 int offk_off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
@@ -1767,7 +1772,75 @@ int offk_off_units_backward_typed(offk_handle* h, void* stream, int feat_dtype, 
   if (feat_dtype == OFFK_FEAT_F32) return offk_off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate);
   if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward_typed: null argument");
   TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, "offk_off_units_backward_typed"));
-  return off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype);
+  return off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype, false);
+}
+
+// ---- channels-last feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_cl and its siblings ----
+// The layout belongs to the call: cfg.feat_layout is not looked at, and as for the _typed entries above there is no condition on
+// the handle.  Everything such a call is refused for, checked before anything is enqueued.
+static int check_feat_cl_train(offk_handle* h, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
+  const std::string f(fn);
+  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  for (int i = 0; i < count; ++i) {
+    if (!feats[i]) return fail(h, OFFK_ERR_INVALID, f + ": null feature map");
+    if (reinterpret_cast<uintptr_t>(feats[i]) & 15)
+      return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature map pointers must be 16-byte aligned (site " + kSites[first + i].name + ")");
+    if (feat_dtype != OFFK_FEAT_F32 &&
+        (unsigned long long)h->N * kSites[first + i].H * kSites[first + i].H * kSites[first + i].C * 2ull >= 0x7fffff00ull)
+      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps of 2 GiB or more are not supported (site " + kSites[first + i].name + ")");
+  }
+  return OFFK_OK;
+}
+
+int offk_pw_reduce_cl(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D) {
+  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, "offk_pw_reduce_cl: bad argument");
+  TRY(check_feat_cl_train(h, feat_dtype, &feat, site, 1, "offk_pw_reduce_cl"));
+  TRY(site_weights_ready(h, site, true, false));
+  DeviceGuard guard(h->cfg.device);
+  PwParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
+  pp.nhwc = 1;
+  pp.zeros = h->zero_page;
+  TRY(finalize_pw(h, static_cast<hipStream_t>(stream)));
+  fill_pw_site(h, site, whole_map(site, static_cast<const float*>(feat)), G, D, &pp.s[0]);
+  pp.total_blocks = pw_blocks_for(pp.s[0].M);
+  if (feat_dtype == OFFK_FEAT_F32) HIP_TRY(h, pw_reduce_launch(pp, static_cast<hipStream_t>(stream)));
+  else HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, static_cast<hipStream_t>(stream)));
+  return OFFK_OK;
+}
+
+static int off_units_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                        const DropCfg& drop, const char* fn) {
+  TRY(check_feat_cl_train(h, feat_dtype, feats, 0, kNumSites, fn));
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, true, drop, feat_dtype);
+}
+
+int offk_off_units_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_cl: null argument");
+  return off_units_cl(h, stream, feat_dtype, feats, workspace, DropCfg(), "offk_off_units_cl");
+}
+
+int offk_off_units_train_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                            uint64_t drop_seed, double drop_p) {
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train_cl: null argument");
+  DropCfg drop;
+  TRY(make_drop(h, drop_seed, drop_p, &drop));
+  return off_units_cl(h, stream, feat_dtype, feats, workspace, drop, "offk_off_units_train_cl");
+}
+
+int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
+                               const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
+                               float* grads, int accumulate) {
+  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward_cl: null argument");
+  TRY(check_feat_cl_train(h, feat_dtype, feats, 0, kNumSites, "offk_off_units_backward_cl"));
+  return off_units_backward(h, stream, reinterpret_cast<const float* const*>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate,
+                            feat_dtype, true);
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

@@ -159,11 +159,14 @@ int pw_blocks_for(int M);
 hipError_t pw_reduce_launch(const PwParams& p, hipStream_t st);
 // enum offk_feat_dtype for device code (include/offk.h is not seen by the kernels)
 constexpr int kFeatF32 = 0, kFeatBf16 = 1, kFeatF16 = 2;
+constexpr int kFeatCl = 4;   // or-ed to the element type in a kernel's FEAT parameter: the channels-last loader form (K1, K1b)
 // K1 on 16-bit NCHW maps (feat_dtype kFeatBf16 / kFeatF16): xp[] carry pointers to 16-bit elements, 8-byte aligned.  Same grid and
-// the same arithmetic as pw_reduce_launch, so G / D equal the fp32 kernel's on the widened maps.  _supported: NCHW and every part
-// below 2^31 bytes (the 16-bit loaders exist in the buffer-descriptor form only).
+// the same arithmetic as pw_reduce_launch, so G / D equal the fp32 kernel's on the widened maps.  _supported: every part below
+// 2^31 bytes (the 16-bit loaders exist in the buffer-descriptor form only).  p.nhwc: the parts are channels-last [N*HW][cp], 16-byte
+// aligned -- pw_reduce_feat16_launch hands those to pw_reduce_cl16_launch (pw_reduce_cl.hip).
 bool pw_reduce_feat16_supported(const PwParams& p);
 hipError_t pw_reduce_feat16_launch(const PwParams& p, int feat_dtype, hipStream_t st);
+hipError_t pw_reduce_cl16_launch(const PwParams& p, int feat_dtype, hipStream_t st);
 
 // ---- K1T: K1 fused with the temporal difference (pw_tdiff.hip) -------------------------
 struct PtSite {
@@ -303,6 +306,9 @@ struct WgParams {
 hipError_t pw_wgrad_launch(const WgParams& p, hipStream_t st);
 // K1b on 16-bit NCHW maps: as pw_wgrad_launch with xp[] pointing at 16-bit elements (8-byte aligned); same blocks, same slabs
 hipError_t pw_wgrad_feat16_launch(const WgParams& p, int feat_dtype, hipStream_t st);
+// K1b on channels-last maps (units_bwd_cl.hip): xp[] point at [N*HW][cp] images of feat_dtype kFeatF32 / kFeatBf16 / kFeatF16
+// elements, 16-byte aligned; same blocks, same slabs, bit-equal to the NCHW forms
+hipError_t pw_wgrad_cl_launch(const WgParams& p, int feat_dtype, hipStream_t st);
 
 struct WrSite {
   const float* slab; const float* bpart; const float* dw_part;

@@ -15,9 +15,10 @@
 // [row][k] LDS image the MFMA core wants.  Outputs are channels-last:
 //   G [N*HW][128] (post-ReLU), D [P*HW][32] (row = output pair index).
 //
-// This file is compiled twice: as it is (the fp32 forms and pw_reduce_launch), and through pw_reduce_f16.hip with
-// OFFK_PW_REDUCE_FEAT16 defined (the bf16 / fp16 map forms and pw_reduce_feat16_launch alone).  Two objects, because the
-// 16-bit instantiations in the same code object changed the register allocation of the fp32 ones.
+// This file is compiled three times: as it is (the fp32 forms and pw_reduce_launch), through pw_reduce_f16.hip with
+// OFFK_PW_REDUCE_FEAT16 defined (the bf16 / fp16 NCHW map forms and pw_reduce_feat16_launch alone), and through pw_reduce_cl.hip
+// with OFFK_PW_REDUCE_CL16 defined (the bf16 / fp16 channels-last map forms and pw_reduce_cl16_launch alone).  Three objects,
+// because the 16-bit instantiations in the same code object changed the register allocation of the fp32 ones.
 #include <cstdlib>
 
 #include "offk_common.h"
@@ -27,7 +28,7 @@ namespace offk {
 
 constexpr int PW_BM = 128, PW_BN = 160, PW_TN = 5;
 
-#ifndef OFFK_PW_REDUCE_FEAT16
+#if !defined(OFFK_PW_REDUCE_FEAT16) && !defined(OFFK_PW_REDUCE_CL16)
 int pw_blocks_for(int M) { return (M + PW_BM - 1) / PW_BM; }
 #endif
 
@@ -90,7 +91,8 @@ __device__ __forceinline__ float4 widen16x4(unsigned lo, unsigned hi) {   // fou
 
 // LEAN: buffer-descriptor addressing of the weights and of the NCHW quad loader (mode 0), unconditional prefetch pinned
 // in front of the MFMAs -- as pw_tdiff.hip; needs every feature-map part and the weight tables below 2^31 bytes.
-// FEAT: element type of the feature map (enum offk_feat_dtype).  The 16-bit forms (NCHW only, LEAN only) differ from the
+// FEAT: element type of the feature map (enum offk_feat_dtype), for 16-bit maps | kFeatCl where they are channels-last (fp32
+// channels-last maps run mode 2 of the fp32 forms, p.nhwc).  The 16-bit forms (LEAN only) differ from the
 // fp32 kernel in the map loader alone: it fetches half the bytes, keeps them as they are in the prefetch registers and widens
 // them on the way into the SAME LDS positions; everything behind the LDS store is this one text, so their G / D are bit-equal
 // to the fp32 kernel's on the widened maps.  (One template, not a shared body behind three kernels: with the parameter block
@@ -100,6 +102,8 @@ template <int V> struct PwMode { static constexpr int value = V; };   // a loade
 template <int NT, int LEAN, int FEAT = kFeatF32>
 __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   static_assert(FEAT == kFeatF32 || LEAN, "the 16-bit loaders exist in the buffer-descriptor form only");
+  static_assert(FEAT != (kFeatF32 | kFeatCl), "fp32 channels-last maps: mode 2 of the fp32 forms");
+  constexpr int FT = FEAT & ~kFeatCl;             // the element type alone
   constexpr int ESZ = FEAT == kFeatF32 ? 4 : 2;   // bytes per feature-map element
   constexpr int LDS_BYTES = (PW_BM + PW_BN) * LDS_K * 4;
   __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   //         8-byte bf16 stores of a group fell into 4 bank positions (60 % of the LDS cycles were conflicts)
   // mode 1: NCHW, any HW      : thread = (pixel i = tid&127, k quads (tid>>7) + 2r)
   // mode 2: channels-last     : thread = (rows (tid>>3)+32r, k quad tid&7)
-  const int mode = (FEAT == kFeatF32 && p.nhwc) ? 2 : ((HW & 3) == 0 ? 0 : 1);
+  const int mode = ((FEAT & kFeatCl) || (FEAT == kFeatF32 && p.nhwc)) ? 2 : ((HW & 3) == 0 ? 0 : 1);
   int fr = 0, pix = 0;       // this thread's frame and pixel (modes 0 / 1)
   bool row_ok = true;
   if (mode == 0) {
@@ -305,11 +309,22 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
     // through its out-of-range offset); mode 1 (98-byte rows): 2-byte loads, zero-extended.  The mode is a compile-time one
     // (the K loop exists once per mode, a block-uniform choice): with both loaders in one loop the copies that reconciled
     // their register images behind the loads waited for the prefetch in front of the MFMAs.
+    // mode 2 (FEAT | kFeatCl, channels-last maps): mode 2's thread mapping; per row one 8-byte load of four consecutive channels
+    // through the descriptor of the part that holds the K-tile, rows past M at the out-of-range offset.
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     auto load_tile16 = [&](int k0, auto MT) {
       const float* xb; int cpart, kl;
       locate(k0, xb, cpart, kl);
-      if constexpr (decltype(MT)::value == 0) {
+      if constexpr (decltype(MT)::value == 2) {
+        const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, M * cpart * ESZ, 0x00020000);
+        const int row = m0 + (tid >> 3);
+        const int voff = (row * cpart + koff) * ESZ;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(xrs, row + 32 * r < M ? voff : (int)0x80000000, (kl + 32 * r * cpart) * ESZ, 0);
+          rg[r].x = __uint_as_float(v.x); rg[r].y = __uint_as_float(v.y);
+        }
+      } else if constexpr (decltype(MT)::value == 0) {
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, (M / HW) * cpart * HW * ESZ, 0x00020000);
         const int voff = fr * (cpart * HW * ESZ) + vA;
 #pragma unroll
@@ -332,10 +347,15 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
       rg[4 + PW_TN - 1] = ld_b(wdrs, woff, k0 * 4);
     };
     auto store_tile16 = [&](auto MT) {
-      if constexpr (decltype(MT)::value == 0) {
+      if constexpr (decltype(MT)::value == 2) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          *reinterpret_cast<float4*>(As + ((tid >> 3) + 32 * r) * LDS_K + 4 * (tid & 7)) =
+              widen16x4<FT>(__float_as_uint(rg[r].x), __float_as_uint(rg[r].y));
+      } else if constexpr (decltype(MT)::value == 0) {
         float4 w[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = widen16x4<FEAT>(__float_as_uint(rg[j].x), __float_as_uint(rg[j].y));
+        for (int j = 0; j < 4; ++j) w[j] = widen16x4<FT>(__float_as_uint(rg[j].x), __float_as_uint(rg[j].y));
         float* dst = As + 4 * (tid >> 3) * LDS_K + 4 * (tid & 7);
         *reinterpret_cast<float4*>(dst) = make_float4(w[0].x, w[1].x, w[2].x, w[3].x);
         *reinterpret_cast<float4*>(dst + LDS_K) = make_float4(w[0].y, w[1].y, w[2].y, w[3].y);
@@ -345,8 +365,8 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           *reinterpret_cast<float4*>(As + (tid & 127) * LDS_K + 4 * ((tid >> 7) + 2 * r)) =
-              make_float4(widen16<FEAT>(__float_as_uint(rg[r].x)), widen16<FEAT>(__float_as_uint(rg[r].y)),
-                          widen16<FEAT>(__float_as_uint(rg[r].z)), widen16<FEAT>(__float_as_uint(rg[r].w)));
+              make_float4(widen16<FT>(__float_as_uint(rg[r].x)), widen16<FT>(__float_as_uint(rg[r].y)),
+                          widen16<FT>(__float_as_uint(rg[r].z)), widen16<FT>(__float_as_uint(rg[r].w)));
       }
 #pragma unroll
       for (int r = 0; r < PW_TN; ++r)
@@ -364,7 +384,8 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
         __syncthreads();
       }
     };
-    if (mode == 0) k_loop(PwMode<0>());
+    if constexpr ((FEAT & kFeatCl) != 0) k_loop(PwMode<2>());
+    else if (mode == 0) k_loop(PwMode<0>());
     else k_loop(PwMode<1>());
   }
 
@@ -415,13 +436,25 @@ static bool pw_lean_ok(const PwParams& p, int esz) {
   return true;
 }
 
-#ifdef OFFK_PW_REDUCE_FEAT16
-bool pw_reduce_feat16_supported(const PwParams& p) { return !p.nhwc && pw_lean_ok(p, 2); }
+#if defined(OFFK_PW_REDUCE_CL16)
+// The channels-last 16-bit forms (pw_reduce_feat16_launch sends p.nhwc here; it has checked pw_reduce_feat16_supported).
+hipError_t pw_reduce_cl16_launch(const PwParams& p, int feat_dtype, hipStream_t st) {
+  if (p.total_blocks <= 0) return hipSuccess;
+  if (!p.nhwc || !pw_lean_ok(p, 2)) return hipErrorInvalidValue;
+  if (feat_dtype == kFeatBf16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatBf16 | kFeatCl>), dim3(p.total_blocks), dim3(256), 0, st, p);
+  else if (feat_dtype == kFeatF16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatF16 | kFeatCl>), dim3(p.total_blocks), dim3(256), 0, st, p);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+#elif defined(OFFK_PW_REDUCE_FEAT16)
+bool pw_reduce_feat16_supported(const PwParams& p) { return pw_lean_ok(p, 2); }
 
 // Same grid, same block -> rows mapping and same K walk as pw_reduce_launch: only the map loader differs.
 hipError_t pw_reduce_feat16_launch(const PwParams& p, int feat_dtype, hipStream_t st) {
   if (p.total_blocks <= 0) return hipSuccess;
   if (!pw_reduce_feat16_supported(p)) return hipErrorInvalidValue;
+  if (p.nhwc) return pw_reduce_cl16_launch(p, feat_dtype, st);
   if (feat_dtype == kFeatBf16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatBf16>), dim3(p.total_blocks), dim3(256), 0, st, p);
   else if (feat_dtype == kFeatF16) hipLaunchKernelGGL((pw_reduce_kernel<0, 1, kFeatF16>), dim3(p.total_blocks), dim3(256), 0, st, p);
   else return hipErrorInvalidValue;

@@ -13,15 +13,20 @@
 //   reduce kernels          slabs / partials summed in a fixed order into the caller's gradient buffer
 //                           in the reference's parameter layouts ([128,C,1,1], [32,C,1,1], [32,1,3,3]).
 // Every sum has a fixed order: the gradients are bit-reproducible run to run.
+//
+// This file is compiled twice: as it is, and through units_bwd_cl.hip with OFFK_UNITS_BWD_CL defined (the channels-last X loader
+// forms of pw_wgrad_kernel and pw_wgrad_cl_launch alone), so that the forms of this object keep the code they have.
 #include "offk_common.h"
 #include "offk_internal.h"
 
 namespace offk {
 
+#ifndef OFFK_UNITS_BWD_CL
 unsigned long long drop_stream_base(unsigned long long seed, int site) {
   const unsigned long long stream = ((seed & 0xFFFFFFFFFFFFull) << 8) | (unsigned long long)site;
   return mix64(stream * 0x9E3779B97F4A7C15ull + 0x9E3779B97F4A7C15ull);
 }
+#endif
 
 namespace {
 
@@ -55,6 +60,7 @@ __device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
 
 }  // namespace
 
+#ifndef OFFK_UNITS_BWD_CL
 // =====================================================================================================
 // K2b
 // =====================================================================================================
@@ -245,6 +251,7 @@ hipError_t units_bwd_launch(const UbParams& p, hipStream_t st) {
   hipLaunchKernelGGL(units_bwd_kernel, dim3(p.total_s + p.total_t), dim3(UB_THREADS), lds, st, p);
   return hipGetLastError();
 }
+#endif   // !OFFK_UNITS_BWD_CL
 
 // =====================================================================================================
 // K1b: weight gradient of the stacked 1x1 reduce convs
@@ -270,6 +277,10 @@ template <int V> struct WgVec { static constexpr int value = V; };   // X loader
 // where HW % 4 == 0, four 2-byte loads at the 7x7 sites, whose 98-byte rows are only 2-byte aligned), keep them as loaded in the
 // prefetch registers and widen them to the exact fp32 values on the way into the fp32 loader's LDS positions.  Everything behind
 // the LDS store is this one text, so their slabs are bit-equal to the fp32 kernel's on the widened maps.
+// FEAT | kFeatCl (all three element types): X is channels-last, [N*HW][C].  Four consecutive channels of one pixel are contiguous
+// there, so the loader is the transposing one of dG: thread = (pixel quad pq, channel quad cq), one load per pixel (16 bytes fp32,
+// 8 bytes 16-bit), a 4 x 4 register transpose (behind the widening) into the same Bs[channel][pixel] image.  cq >> 3 is the wave, so
+// the part and its row stride are wave-uniform.  No row tail to shift and no 2-byte loads: a pixel's row is C * esz bytes, C % 32 == 0.
 template <int FEAT = kFeatF32>
 __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   // fp32 MFMA, LDS [row][k] fp32 (stride LDS_K)
@@ -279,6 +290,8 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   float* lds = reinterpret_cast<float*>(lds_raw);
   float* As = lds;                   // [160][LDS_K]: rows = stacked output channel, k = pixel
   float* Bs = lds + WG_BM * LDS_K;   // [128][LDS_K]: rows = input channel of this slab
+  constexpr bool CL = (FEAT & kFeatCl) != 0;
+  constexpr int FT = FEAT & ~kFeatCl;   // the element type alone
 
   // XCD-aware order: consecutive logical blocks (the channel slabs of one K-chunk, which share the A operand)
   // land on the same XCD / L2
@@ -328,6 +341,22 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     xfs[r] = cpart * HW;
   }
   const bool wave_on = nt * WG_BN + 32 * wave < C;
+  // channels-last X: the part that holds this wave's 32-channel group, at the group's first channel, and its row stride (elements)
+  const float* xcl = nullptr;
+  int xcs = 0;
+  if constexpr (CL) {
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const float* xb = S.xp[0]; int cpart = S.cp[0], kl = nt * WG_BN + 32 * wv;
+    if (S.nparts > 1 && kl >= S.cp[0]) {
+      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
+      if (S.nparts > 2 && kl >= S.cp[1]) {
+        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
+        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
+      }
+    }
+    xcl = FT == kFeatF32 ? xb + kl : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + kl);
+    xcs = cpart;
+  }
 
   const int pq = tid & 7, cq = tid >> 3;     // gen A loader: pixel quad (fastest: conflict-free LDS stores), channel quad
   const int dpx = tid >> 3, dcq = tid & 7;   // down A loader: pixel, channel quad
@@ -356,6 +385,25 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     // X quad k..k+3 of the row; a quad that straddles the row end (HW % 4 != 0) is read from HW-4 and shifted
     // into place by store_tile
     const int k = kin + 4 * (tid & 7), kk = min(k, HW - 4);
+    if constexpr (CL) {
+      // channels-last X: pixel kin + 4 pq + j, channels 4 cq .. 4 cq + 3 of the slab (4 (cq & 7) .. of the wave's group); rg[5 + j]
+      // (fp32) or rx[j] (16-bit) hold pixel j's channel quad as loaded, store_tile transposes
+      const size_t px = (size_t)frame * HW + kin + 4 * pq;
+      const int cin = 4 * (cq & 7);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool on = wave_on && kin + 4 * pq + j < HW && !(p.dbg & 1);
+        if constexpr (FT == kFeatF32) {
+          rg[5 + j] = *reinterpret_cast<const float4*>(on ? xcl + (px + j) * xcs + cin : p.zeros);
+        } else {
+          const unsigned short* q = on ? reinterpret_cast<const unsigned short*>(xcl) + (px + j) * xcs + cin
+                                       : reinterpret_cast<const unsigned short*>(p.zeros);
+          rx[j] = *reinterpret_cast<const unsigned long long*>(q);
+        }
+      }
+      kin_ld = kin;
+      return;
+    }
     if constexpr (FEAT != kFeatF32) {
       // 16-bit X: rx[] (a pixel quad per 8-byte load, kept whole: a 64-bit value that is split only behind the wait stays in one
       // register pair around the loop) or rg[5..8] (2-byte loads) hold the elements as loaded; store_tile widens them.  The zero page
@@ -403,11 +451,31 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     }
   };
   auto widen = [](unsigned h) {   // one 16-bit element (upper bits zero) -> the fp32 value it stands for
-    if (FEAT == kFeatBf16) return __uint_as_float(h << 16);
+    if (FT == kFeatBf16) return __uint_as_float(h << 16);
     return (float)__builtin_bit_cast(_Float16, (unsigned short)h);   // hardware conversion: keeps subnormals
   };
   auto store_tile = [&](auto VT) {
-    if constexpr (FEAT != kFeatF32) {
+    if constexpr (CL) {
+      // pixel j's four channels -> channel i's four pixels, straight into LDS as for dG below (the prefetch registers are left as
+      // loaded: transposed in place, the copies between the two register images waited for the prefetch in front of the MFMAs)
+      float4 x[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if constexpr (FT != kFeatF32) {
+          const unsigned a = (unsigned)rx[j], b = (unsigned)(rx[j] >> 32);
+          x[j] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+        } else {
+          x[j] = rg[5 + j];
+          // (pins the quad here: without it hipcc gathers the transposed register quads right behind the loads, in front of the MFMAs)
+          asm volatile("" : "+v"(x[j].x), "+v"(x[j].y), "+v"(x[j].z), "+v"(x[j].w));
+        }
+      }
+      float* b = Bs + 4 * cq * LDS_K + 4 * pq;
+      *reinterpret_cast<float4*>(b) = make_float4(x[0].x, x[1].x, x[2].x, x[3].x);
+      *reinterpret_cast<float4*>(b + LDS_K) = make_float4(x[0].y, x[1].y, x[2].y, x[3].y);
+      *reinterpret_cast<float4*>(b + 2 * LDS_K) = make_float4(x[0].z, x[1].z, x[2].z, x[3].z);
+      *reinterpret_cast<float4*>(b + 3 * LDS_K) = make_float4(x[0].w, x[1].w, x[2].w, x[3].w);
+    } else if constexpr (FEAT != kFeatF32) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if constexpr (decltype(VT)::value == 1) {
@@ -432,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     float* dd = As + (kGenCh + 4 * dcq) * LDS_K + dpx;
     dd[0] = rg[4].x; dd[LDS_K] = rg[4].y; dd[2 * LDS_K] = rg[4].z; dd[3 * LDS_K] = rg[4].w;
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int r = 0; !CL && r < 4; ++r)
       *reinterpret_cast<float4*>(Bs + ((tid >> 3) + 32 * r) * LDS_K + 4 * (tid & 7)) = rg[5 + r];
   };
 
@@ -475,7 +543,8 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
     }                                                                                                       \
     __syncthreads();                                                                                        \
   }
-  if constexpr (FEAT == kFeatF32) { OFFK_WG_K_LOOP(WgVec<-1>()) }
+  if constexpr (CL) { OFFK_WG_K_LOOP(WgVec<2>()) }
+  else if constexpr (FEAT == kFeatF32) { OFFK_WG_K_LOOP(WgVec<-1>()) }
   else if (vec) { OFFK_WG_K_LOOP(WgVec<1>()) }
   else { OFFK_WG_K_LOOP(WgVec<0>()) }
 #undef OFFK_WG_K_LOOP
@@ -510,6 +579,18 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   }
 }
 
+#ifdef OFFK_UNITS_BWD_CL
+hipError_t pw_wgrad_cl_launch(const WgParams& p, int feat_dtype, hipStream_t st) {
+  if (p.total_blocks <= 0) return hipSuccess;
+  if (p.precision != 0) return hipErrorInvalidValue;
+  if (feat_dtype == kFeatF32) hipLaunchKernelGGL(pw_wgrad_kernel<kFeatF32 | kFeatCl>, dim3(p.total_blocks), dim3(256), 0, st, p);
+  else if (feat_dtype == kFeatBf16) hipLaunchKernelGGL(pw_wgrad_kernel<kFeatBf16 | kFeatCl>, dim3(p.total_blocks), dim3(256), 0, st, p);
+  else if (feat_dtype == kFeatF16) hipLaunchKernelGGL(pw_wgrad_kernel<kFeatF16 | kFeatCl>, dim3(p.total_blocks), dim3(256), 0, st, p);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+#else
 hipError_t pw_wgrad_feat16_launch(const WgParams& p, int feat_dtype, hipStream_t st) {
   if (p.total_blocks <= 0) return hipSuccess;
   if (p.precision != 0) return hipErrorInvalidValue;
@@ -626,5 +707,6 @@ hipError_t consensus_bwd_launch(const float* go, int B, int T, int C, float* gi,
   hipLaunchKernelGGL(consensus_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, go, B, T, C, gi);
   return hipGetLastError();
 }
+#endif   // OFFK_UNITS_BWD_CL
 
 }  // namespace offk

@@ -140,7 +140,8 @@ class _OFFUnitsFn(torch.autograd.Function):
     """autograd node around offk_off_units(_train) / offk_off_units_backward.  Inputs after the three
     bookkeeping arguments are the unit parameters in ``OFFUnits.param_keys`` order; the feature maps come from
     the frozen backbone (train_off.py:39-56) and get no gradient; they are kept in ``ctx.feats`` in the dtype they came in
-    (fp32, or bf16 / fp16 from an autocast backbone -- the typed entries read those without an fp32 copy)."""
+    (fp32, or bf16 / fp16 from an autocast backbone -- the typed entries read those without an fp32 copy) and in the layout
+    they came in where all nine are torch.channels_last (the _cl training entries read those without a contiguous copy)."""
 
     @staticmethod
     def forward(ctx, mod, feats, drop, *params):
@@ -191,7 +192,12 @@ class OFFUnits(nn.Module):
     The nine maps may be fp32, or bf16 / fp16 of one dtype -- what a frozen backbone under ``torch.autocast`` emits.
     16-bit maps are neither cast nor copied: the kernels read them as they are (offk_off_units_train_typed,
     offk_off_units_backward_typed), the autograd node keeps the 16-bit tensors for its backward and for the
-    recompute of a stale generation, and outputs and gradients are fp32 and equal those from ``x.float()``."""
+    recompute of a stale generation, and outputs and gradients are fp32 and equal those from ``x.float()``.
+
+    Nine ``torch.channels_last`` maps (logical shape as ever, any of the three dtypes) -- what a backbone run in channels_last
+    emits -- are not made contiguous either: offk_off_units_train_cl / offk_off_units_backward_cl read them as they are, the
+    autograd node keeps those very tensors, and outputs and gradients equal those from the contiguous copies.  Any other
+    layout, a mix included, is made contiguous as ever."""
 
     def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8):
         super().__init__()
@@ -255,8 +261,21 @@ class OFFUnits(nn.Module):
                 self._bound[key] = prm.data_ptr()
         return self._rt
 
+    def _as_handed_over(self, feats):
+        """Nine channels_last maps of the reference's logical shape and one fp32 / bf16 / fp16 dtype: the _cl training entries take
+        them without a copy."""
+        if len(feats) != spec.NUM_SITES or any(not torch.is_tensor(f) for f in feats):
+            return False
+        try:
+            return (runtime.train_feat_layout(feats, self.batch, self.length) == "cl"
+                    and runtime.feat_dtype(feats) in runtime._CL_DTYPES)
+        except ValueError:        # a mix of layouts or dtypes, a wrong shape: the contiguous path and its checks
+            return False
+
     def forward(self, feats, drop_seed=None):
-        feats = tuple(f.contiguous() for f in feats)
+        feats = tuple(feats)
+        if not self._as_handed_over(feats):
+            feats = tuple(f.contiguous() for f in feats)
         if not feats[0].is_cuda:
             raise runtime._lib.OffkError("OFFUnits has no CPU path: feature maps must live on an MI355X")
         if self.training and self.drop_p > 0.0:

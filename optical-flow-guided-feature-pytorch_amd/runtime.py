@@ -84,6 +84,21 @@ def feat_layout(feats, batch, length):
     return kinds.pop()
 
 
+def train_feat_layout(feats, batch, length):
+    """Where nine maps go on the training side of the units (off_units, off_units_train, off_units_backward): "cl" when every one is a
+    torch.channels_last tensor of the reference's logical shape (the offk_*_cl training entries, maps as they are), else "nchw" (the
+    entries and checks contiguous maps always met).  Works on CPU tensors.  A mix of layouts raises, as feat_layout does.  Unlike
+    OffForward.takes_channels_last there is no condition on the handle: the training side runs the fp32 kernels on either
+    precision, and the layout belongs to the call."""
+    if len(feats) != spec.NUM_SITES:
+        raise ValueError("need nine feature maps")
+    if any(not torch.is_tensor(f) for f in feats) or all(f.is_contiguous() for f in feats):
+        return "nchw"
+    if not any(f.dim() == 4 and f.is_contiguous(memory_format=torch.channels_last) for f in feats):
+        return "nchw"                                  # no channels_last map among them: the contiguity checks name the offender
+    return feat_layout(feats, batch, length)
+
+
 def _check_dev_cl(t, name, device):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype in _CL_DTYPES and t.dim() == 4
             and t.is_contiguous(memory_format=torch.channels_last)):
@@ -241,13 +256,18 @@ class OffForward:
             return None                                    # _feat_array names the offender
         return _FEAT_DTYPES.get(feat_dtype(feats))
 
+    def train_takes_channels_last(self, feats):
+        """True when these nine maps go to the channels-last training entries as they are (offk_off_units_cl and its siblings: no
+        copy, no cast, any handle); see train_feat_layout."""
+        return train_feat_layout(feats, self.batch, self.length) == "cl"
+
     def _feat_array(self, feats, check=_check_dev):
         if len(feats) != spec.NUM_SITES:
             raise ValueError("need nine feature maps")
         shapes = spec.feature_shapes(self.batch, self.length)
         for i, (f, s) in enumerate(zip(feats, shapes)):
             check(f, "feats[%d]" % i, self.device)
-            want = s if self.feat_layout == 0 else (s[0], s[2], s[3], s[1])
+            want = s if self.feat_layout == 0 or check is _check_dev_cl else (s[0], s[2], s[3], s[1])   # channels_last: the logical shape
             if tuple(f.shape) != tuple(want):
                 raise ValueError("feats[%d] has shape %s, expected %s" % (i, tuple(f.shape), tuple(want)))
         return (ctypes.c_void_p * spec.NUM_SITES)(*[f.data_ptr() for f in feats])
@@ -337,7 +357,12 @@ class OffForward:
 
     def off_units(self, feats):
         """K1 + K2 into the workspace.  feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (offk_off_units_typed: the values
-        of the same maps upcast, on any handle)."""
+        of the same maps upcast, on any handle).  Nine torch.channels_last maps of any of the three dtypes are taken as they are
+        (offk_off_units_cl, any handle) and give the values of their contiguous copies."""
+        if self.train_takes_channels_last(feats):
+            arr = self._feat_array(feats, _check_dev_cl)
+            _lib.check(self.lib.offk_off_units_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace)), self._h)
+            return
         fdt = self._train16(feats)
         if fdt is not None:
             arr = self._feat_array(feats, _check_dev16)
@@ -366,7 +391,13 @@ class OffForward:
     def off_units_train(self, feats, drop_seed=0, drop_p=0.8):
         """K1+K2 in training mode: nn.Dropout(p) (RGB_OFF.py:356, :612) on the spatial gradients with the
         reproducible mask of synth.dropout_keep; leaves G/D in the workspace for off_units_backward.
-        bf16 / fp16 maps of one dtype are taken as they are (offk_off_units_train_typed)."""
+        bf16 / fp16 maps of one dtype are taken as they are (offk_off_units_train_typed), and so are nine torch.channels_last maps
+        of any of the three dtypes (offk_off_units_train_cl)."""
+        if self.train_takes_channels_last(feats):
+            arr = self._feat_array(feats, _check_dev_cl)
+            _lib.check(self.lib.offk_off_units_train_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace),
+                                                        ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
+            return
         fdt = self._train16(feats)
         if fdt is not None:
             arr = self._feat_array(feats, _check_dev16)
@@ -398,12 +429,14 @@ class OffForward:
         gradient buffer [P, H, W, Cs] (or [P*H*W, Cs]) and the first of the unit's 160 channels in it.
         Needs training=True (workspace superset) and the G/D state of the matching forward call.
         feats: the maps of the matching forward call, fp32 or bf16 / fp16 of one dtype (offk_off_units_backward_typed; gradients
-        are fp32 and equal those from the upcast maps).
+        are fp32 and equal those from the upcast maps), contiguous or all nine torch.channels_last (offk_off_units_backward_cl;
+        equal to the gradients from the contiguous copies).
         Returns (flat grads tensor, dict key -> view in the reference's parameter shape)."""
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
-        fdt = self._train16(feats)
-        arr = self._feat_array(feats, _check_dev16 if fdt is not None else _check_dev)
+        cl = self.train_takes_channels_last(feats)
+        fdt = self._cl_dtype(feats) if cl else self._train16(feats)
+        arr = self._feat_array(feats, _check_dev_cl if cl else (_check_dev16 if fdt is not None else _check_dev))
         gv = (_lib.OffkGradView * spec.NUM_SITES)()
         for i, ((t, coff), (_n, _c, H)) in enumerate(zip(grad_views, spec.SITES)):
             _check_dev(t, "grad_views[%d]" % i, self.device)
@@ -413,7 +446,11 @@ class OffForward:
         if grads is None:
             grads = self.new_unit_grads()
         _check_dev(grads, "grads", self.device)
-        if fdt is not None:
+        if cl:
+            _lib.check(self.lib.offk_off_units_backward_cl(self._h, _stream(self.device), fdt, arr, gv, _ptr(self.workspace),
+                                                           ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
+                                                           int(bool(accumulate))), self._h)
+        elif fdt is not None:
             _lib.check(self.lib.offk_off_units_backward_typed(self._h, _stream(self.device), fdt, arr, gv, _ptr(self.workspace),
                                                               ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
                                                               int(bool(accumulate))), self._h)
@@ -426,9 +463,18 @@ class OffForward:
 
     # ---- stage entry points -----------------------------------------------------------
     def pw_reduce(self, site, feat):
-        _name, _C, H = spec.SITES[site]
+        """K1 of one site.  feat: the site's map, fp32 / bf16 / fp16, contiguous or torch.channels_last (offk_pw_reduce_cl)."""
+        _name, C, H = spec.SITES[site]
         G = torch.empty(self.N * H * H, spec.GEN_CH, dtype=torch.float32, device=self.device)
         D = torch.zeros(self.P * H * H, spec.DOWN_CH, dtype=torch.float32, device=self.device)
+        if (torch.is_tensor(feat) and feat.dim() == 4 and not feat.is_contiguous()
+                and feat.is_contiguous(memory_format=torch.channels_last)):      # channels_last map: offk_pw_reduce_cl
+            _check_dev_cl(feat, "feat", self.device)
+            if tuple(feat.shape) != (self.N, C, H, H):
+                raise ValueError("feat is channels_last with logical shape %s, expected %s" % (tuple(feat.shape), (self.N, C, H, H)))
+            _lib.check(self.lib.offk_pw_reduce_cl(self._h, _stream(self.device), _CL_DTYPES[feat.dtype], site, _ptr(feat),
+                                                  _ptr(G), _ptr(D)), self._h)
+            return G, D
         if torch.is_tensor(feat) and feat.dtype in _FEAT_DTYPES:      # bf16 / fp16 map: offk_pw_reduce_typed
             _check_dev16(feat, "feat", self.device)
             _lib.check(self.lib.offk_pw_reduce_typed(self._h, _stream(self.device), _FEAT_DTYPES[feat.dtype], site, _ptr(feat),

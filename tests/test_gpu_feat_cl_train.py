@@ -1,0 +1,567 @@
+"""torch.channels_last feature maps on the training side of the OFF units (offk_pw_reduce_cl, offk_off_units_cl,
+offk_off_units_train_cl, offk_off_units_backward_cl; the channels-last loaders of K1 in csrc/pw_reduce.hip and of K1b in
+csrc/units_bwd.hip).  The contract is equality, not a tolerance: everything a _cl call writes -- G, D, the unit channels of the
+fusion buffers, the flat gradient buffer -- is torch.equal to what the NCHW call of the same dtype writes from the contiguous
+copies of the same logical tensors (include/offk.h).  All inputs here are finite, so no case is left out of the equality."""
+import ctypes
+import functools
+
+import pytest
+import torch
+
+import offk_amd  # noqa: F401
+from offk_amd import _lib, spec, synth
+from oracle import off_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+VARIANTS = {"rgb": spec.VARIANT_RGB, "flow": spec.VARIANT_FLOW}
+SHAPES = [(1, 2), (2, 3), (3, 4), (5, 7), (2, 9)]
+RTOL = 2e-4          # tests/test_gpu_backward.py's bound for the fp32 path against the oracle
+DROP_SEED, DROP_P = 7, 0.8
+CLAST = torch.channels_last
+
+
+@pytest.fixture(scope="module")
+def rt():
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from offk_amd import runtime
+    return runtime
+
+
+def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, precision="fp32", **kw):
+    h = rt.OffForward(B, L, variant, slice_mode, precision=precision, training=True, **kw)
+    assert h.load_state_dict(synth.make_weights(variant)) == []
+    return h
+
+
+def to_cl(xs):
+    """The channels_last copies of contiguous maps: same logical tensors, physically [N, H, H, C]."""
+    out = [x.contiguous(memory_format=CLAST) for x in xs]
+    assert all(not c.is_contiguous() and c.is_contiguous(memory_format=CLAST) and torch.equal(c, x) for c, x in zip(out, xs))
+    return out
+
+
+# ---- inputs (the generators of tests/test_gpu_feat16_train.py, repeated here: test files do not import each other; the fp32
+#      forms of the bit-pattern kinds are the 16-bit patterns widened, plus low mantissa bits of their own) ----
+
+def relu_maps(B, L, dtype, seed):
+    """ReLU-like synthetic maps, made on the device and rounded to `dtype`."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return [torch.relu(torch.randn(B * L, C, H, H, device="cuda", generator=g)).to(dtype).contiguous() for _, C, H in spec.SITES]
+
+
+def bit_maps(B, L, dtype, seed, full_mantissa=False):
+    """Random finite bit patterns: both signs, every mantissa bit in play (or all set), exponents from the subnormals
+    (exponent field 0) up to 2^10.  fp32: bf16's sign / exponent / upper mantissa with sixteen more mantissa bits below."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    out = []
+    for _, C, H in spec.SITES:
+        n = B * L * C * H * H
+        r = torch.randint(0, 1 << 30, (n,), device="cuda", generator=g, dtype=torch.int64)
+        sign = (r & 1) << 15
+        if dtype == torch.float16:
+            mant = torch.full_like(r, 0x3ff) if full_mantissa else (r >> 1) & 0x3ff
+            e = (r >> 11) % 26                                        # 0 (subnormal) .. 25 (2^10)
+            bits = sign | (e << 10) | mant
+        else:
+            mant = torch.full_like(r, 0x7f) if full_mantissa else (r >> 1) & 0x7f
+            e = (r >> 11) % 38
+            e = torch.where(e == 0, e, e + 100)                       # 0 (subnormal) or 101 .. 137
+            bits = sign | (e << 7) | mant
+        if dtype == torch.float32:
+            low = torch.full_like(r, 0xffff) if full_mantissa else (r >> 14) & 0xffff
+            bits = (bits << 16) | low
+            bits = torch.where(bits >= 1 << 31, bits - (1 << 32), bits)
+            out.append(bits.to(torch.int32).view(torch.float32).view(B * L, C, H, H).contiguous())
+            continue
+        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
+        out.append(bits.to(torch.int16).view(dtype).view(B * L, C, H, H).contiguous())
+    return out
+
+
+def heavy_maps(B, L, dtype, seed):
+    """Heavy-tailed maps within fp16's range (expm1 of a scaled normal, up to ~1e4)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return [torch.expm1(1.5 * torch.randn(B * L, C, H, H, device="cuda", generator=g)).clamp(max=3e4).to(dtype).contiguous()
+            for _, C, H in spec.SITES]
+
+
+def maps_of_kind(kind, B, L, dtype, seed):
+    if kind == "relu":
+        return relu_maps(B, L, dtype, seed)
+    if kind == "heavy_tail":
+        return heavy_maps(B, L, dtype, seed)
+    x = bit_maps(B, L, dtype, seed, full_mantissa=kind == "full_mantissa")
+    if kind == "random_bits":                                   # the generator does reach the type's subnormals
+        tiny = 2.0 ** -14 if dtype == torch.float16 else 2.0 ** -126
+        assert any(bool(((t.float().abs() < tiny) & (t.float() != 0)).any()) for t in x)
+    return x
+
+
+# ---- what the calls write ----
+
+def written(h):
+    """Copies of everything K1 + K2 write: G_<site> and D_<site> of every site, and its 160 unit channels in the fusion buffer."""
+    P = h.P
+    out = []
+    for fkey, fd in spec.FUSION.items():
+        width = 160 * len(fd["sites"]) + fd["carry"]
+        buf = h.region("fusion_" + fkey, width).view(P, fd["H"], fd["H"], width)
+        for i, sname in enumerate(fd["sites"]):
+            out.append(("unit_" + sname, buf[..., 160 * i:160 * i + 160].clone()))
+            out.append(("G_" + sname, h.region("G_" + sname, 128).clone()))
+            out.append(("D_" + sname, h.region("D_" + sname, 32).clone()))
+    return out
+
+
+def run_units(h, x, train):
+    h.workspace.fill_(0xff)                            # (NaN in every float: what the units leave unwritten shows)
+    if train:
+        h.off_units_train(x, DROP_SEED, DROP_P)
+    else:
+        h.off_units(x)
+    return written(h)
+
+
+def assert_forward_equal(h, x):
+    """x: contiguous maps.  off_units and off_units_train on their channels_last copies write what they write on x."""
+    xcl = to_cl(x)
+    for train in (False, True):
+        ref = run_units(h, x, train)
+        got = run_units(h, xcl, train)
+        torch.cuda.synchronize()
+        assert len(got) == 27
+        for (name, a), (_n, b) in zip(got, ref):
+            assert a.dtype == torch.float32 and torch.isfinite(a).all(), (name, train)
+            assert torch.equal(a, b), (name, train)
+
+
+def cotangents(P):
+    return [torch.from_numpy(synth.uniform_values(0xC07 + i, P * spec.NUM_CLASSES, 1.0).reshape(P, spec.NUM_CLASSES))
+            for i in range(3)]
+
+
+def unit_drop(seed, P, p=DROP_P):
+    return [torch.from_numpy(synth.dropout_keep(seed, si, P, H, p)).float() / (1.0 - p)
+            for si, (_n, _c, H) in enumerate(spec.SITES)]
+
+
+def grad_views(dm):
+    """nine [P,160,H,H] -> the three fusion-buffer gradients, channels-last, + per-site (tensor, coff)."""
+    groups = ((0, 1), (2, 3, 4, 5, 6), (7, 8))
+    views = [None] * spec.NUM_SITES
+    for grp in groups:
+        buf = torch.cat([dm[i] for i in grp], dim=1).permute(0, 2, 3, 1).contiguous().cuda()
+        for k, i in enumerate(grp):
+            views[i] = (buf, 160 * k)
+    return views
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_dm(variant, B, L, slice_mode):
+    """dM as tests/test_gpu_backward.py makes it: the head cotangents of cotangents(P) taken back through the oracle's fusion
+    stages (on the synthetic fp32 maps; the equality below holds for any dM, so it need not belong to the maps under test).
+    Computed once per configuration and shared by every test that needs it."""
+    w = orc.to_torch_weights(synth.make_weights(variant))
+    tf = [torch.from_numpy(f) for f in synth.make_features(B, L, 9)]
+    P = B * (L - 1)
+    _g, dm = orc.unit_backward(tf, w, B, L, variant, slice_mode, cotangents(P), unit_drop(DROP_SEED, P), None)
+    return [d.detach() for d in dm]
+
+
+def assert_backward_equal(h, x, views):
+    """The flat gradient buffer of the backward on the channels_last copies equals the one on the contiguous maps x:
+    overwritten, and accumulated onto a pre-filled buffer.  Each backward follows the forward on the same maps."""
+    n = h.new_unit_grads().numel()
+    g = torch.Generator(device="cuda").manual_seed(n)
+    fill = torch.randn(n, device="cuda", generator=g)
+    res = {}
+    for tag, xs in (("nchw", x), ("cl", to_cl(x))):
+        h.off_units_train(xs, DROP_SEED, DROP_P)
+        over = torch.full((n,), float("nan"), device="cuda")
+        h.off_units_backward(xs, views, DROP_SEED, DROP_P, grads=over, accumulate=False)
+        acc = fill.clone()
+        h.off_units_backward(xs, views, DROP_SEED, DROP_P, grads=acc, accumulate=True)
+        res[tag] = (over, acc)
+    torch.cuda.synchronize()
+    for a, b in zip(res["cl"], res["nchw"]):
+        assert a.dtype == torch.float32 and torch.isfinite(a).all()
+        assert torch.equal(a, b)
+    assert not torch.equal(res["cl"][1], fill) and float(res["cl"][0].abs().max()) > 0
+
+
+# ---- 1. forward equality ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("slice_mode", [spec.SLICE_FLAT, spec.SLICE_PER_CLIP])
+@pytest.mark.parametrize("precision", ["fp32", "f32split"])
+@pytest.mark.parametrize("B,L", SHAPES)
+def test_forward_equals_contiguous_maps(rt, name, variant, slice_mode, precision, B, L):
+    """off_units and off_units_train (seed 7, p 0.8) on channels_last maps: G, D and the unit regions finite and equal to the run on
+    the contiguous copies; pw_reduce alone on every site."""
+    h = make_handle(rt, B, L, VARIANTS[variant], slice_mode, precision)
+    x = relu_maps(B, L, DTYPES[name], 11 * B + L)
+    assert_forward_equal(h, x)
+    xcl = to_cl(x)
+    for site in range(spec.NUM_SITES):
+        Gc, Dc = h.pw_reduce(site, xcl[site])
+        Gn, Dn = h.pw_reduce(site, x[site])
+        torch.cuda.synchronize()
+        assert torch.isfinite(Gc).all() and torch.equal(Gc, Gn) and torch.equal(Dc, Dn), site
+
+
+# ---- 2. backward equality ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("slice_mode", [spec.SLICE_FLAT, spec.SLICE_PER_CLIP])
+@pytest.mark.parametrize("precision", ["fp32", "f32split"])
+@pytest.mark.parametrize("B,L", SHAPES)
+def test_backward_equals_contiguous_maps(rt, name, variant, slice_mode, precision, B, L):
+    h = make_handle(rt, B, L, VARIANTS[variant], slice_mode, precision)
+    x = relu_maps(B, L, DTYPES[name], 13 * B + L)
+    assert_backward_equal(h, x, grad_views(oracle_dm(VARIANTS[variant], B, L, slice_mode)))
+
+
+# ---- 3. input kinds ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+@pytest.mark.parametrize("kind", ["relu", "random_bits", "full_mantissa", "heavy_tail"])
+def test_input_kinds(rt, name, kind):
+    """ReLU maps, random finite bit patterns (negative values, subnormals), every mantissa bit set, a heavy tail."""
+    B, L = 3, 4
+    h = make_handle(rt, B, L)
+    x = maps_of_kind(kind, B, L, DTYPES[name], 4)
+    assert all(bool(torch.isfinite(t.float()).all()) for t in x)
+    assert_forward_equal(h, x)
+    assert_backward_equal(h, x, grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT)))
+
+
+# ---- 4. an anchor that does not pass through the NCHW kernels ----
+
+def rel_err(got, ref):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    return float((got - ref).abs().max() / max(float(ref.abs().max()), 1e-30))
+
+
+def device_relu_masks(h, feats_cpu, w, B, L, slack=1e-5):
+    """The ReLU decisions the device took (saved G > 0), after checking that they differ from the oracle's own only for
+    pre-activations within rounding distance of zero (as tests/test_gpu_backward.py)."""
+    masks = []
+    for (site, _c, H), x in zip(spec.SITES, feats_cpu):
+        G = h.region("G_" + site, 128).view(B * L, H * H, 128).permute(0, 2, 1).reshape(B * L, 128, H, H).cpu()
+        with torch.no_grad():
+            pre = torch.nn.functional.conv2d(x, w["motion_conv_gen_%s.weight" % site], w["motion_conv_gen_%s.bias" % site])
+        mask = (G > 0)
+        flip = mask != (pre > 0)
+        assert int(flip.sum()) <= 5 + slack * flip.numel(), site
+        if flip.any():
+            assert float(pre[flip].abs().max()) < slack * max(1.0, float(pre.abs().max())), site
+        masks.append(mask.float())
+    return masks
+
+
+@pytest.mark.parametrize("name", ["bf16", "f16"])
+@pytest.mark.parametrize("variant,seed", [("rgb", DROP_SEED), ("flow", None)])
+def test_backward_channels_last_maps_vs_oracle(rt, name, variant, seed):
+    """Gradients from channels_last 16-bit maps against oracle.unit_backward on the same values, within the fp32 path's own RTOL."""
+    B, L = 2, 3
+    P = B * (L - 1)
+    v = VARIANTS[variant]
+    h = make_handle(rt, B, L, v)
+    w = orc.to_torch_weights(synth.make_weights(v))
+    xcl = to_cl([torch.from_numpy(f).cuda().to(DTYPES[name]).contiguous() for f in synth.make_features(B, L, 2)])
+    tf = [x.float().cpu().contiguous() for x in xcl]
+    drops = None if seed is None else unit_drop(seed, P)
+    if seed is None:
+        h.off_units(xcl)
+    else:
+        h.off_units_train(xcl, seed, DROP_P)
+    ref, dm = orc.unit_backward(tf, w, B, L, v, spec.SLICE_FLAT, cotangents(P), drops, device_relu_masks(h, tf, w, B, L))
+    _flat, got = h.off_units_backward(xcl, grad_views(dm), 0 if seed is None else seed, 0.0 if seed is None else DROP_P)
+    torch.cuda.synchronize()
+    assert set(got) == set(ref)
+    errs = dict((k, rel_err(got[k], ref[k])) for k in ref)
+    bad = dict((k, "%.2e" % e) for k, e in errs.items() if not e < RTOL or got[k].shape != ref[k].shape)
+    assert not bad, bad
+
+
+# ---- 5. OFFUnits behind a channels_last backbone ----
+
+class ToyBackbone(torch.nn.Module):
+    """Nine maps of the inception shapes out of a 3-channel 28 x 28 input (1x1 convs after average pooling), handed over in
+    torch.channels_last as a backbone run in that memory format does."""
+
+    def __init__(self):
+        super().__init__()
+        self.convs = torch.nn.ModuleList(torch.nn.Conv2d(3, C, 1) for _, C, _ in spec.SITES)
+
+    def forward(self, x):
+        return [torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous(memory_format=CLAST)
+                for (_, _C, H), conv in zip(spec.SITES, self.convs)]
+
+
+def _units_node(out):
+    """The autograd node of OFFUnits behind one of its outputs (the object the forward stored its ctx attributes on)."""
+    node = out.grad_fn
+    while node is not None and not hasattr(node, "feats"):
+        node = node.next_functions[0][0]
+    assert node is not None
+    return node
+
+
+@pytest.mark.parametrize("name", ["none", "bf16", "f16"])
+def test_off_units_behind_channels_last_backbone(rt, name):
+    from offk_amd.off_module import OFFUnits
+    import contextlib
+    B, L = 2, 3
+    P = B * (L - 1)
+    dt = torch.float32 if name == "none" else DTYPES[name]
+    autocast = (lambda: contextlib.nullcontext()) if name == "none" else (lambda: torch.autocast("cuda", dtype=dt))
+    torch.manual_seed(0)
+    bb = ToyBackbone().cuda().requires_grad_(False)                 # the frozen backbone
+    wnp = synth.make_weights(spec.VARIANT_RGB)
+    wg = {k: t.cuda() for k, t in orc.to_torch_weights(wnp).items()}
+    cot = [c.cuda() for c in cotangents(P)]
+    x = torch.randn(B * L, 3, 28, 28, device="cuda")
+    with torch.no_grad(), autocast():
+        other = [f * 0.5 for f in bb(x.flip(0))]                    # a second set of maps for the interleaved forward
+        feats_cl = bb(x)
+    assert all(f.dtype == dt and not f.is_contiguous() and f.is_contiguous(memory_format=CLAST) for f in feats_cl + other)
+
+    def new_units():
+        u = OFFUnits(B, L, "rgb").cuda()
+        u.load_state_dict({k: torch.from_numpy(a) for k, a in wnp.items() if k in u.state_dict()}, strict=True)
+        return u.train()
+
+    def loss_of(m28, m14, m7):
+        # the reference's fusion stages and heads as ordinary torch ops (the oracle's functions are plain torch)
+        s28 = orc.fusion_28(m28, wg)
+        s14 = orc.fusion_14(torch.cat((m14, s28), 1), wg)
+        s7 = orc.fusion_7(torch.cat((m7, s14), 1), wg)
+        return (orc.head(s7, wg, "fc_action_motion", False) * cot[0]).sum() + (orc.head(s14, wg, "fc_action_motion_14", False) * cot[1]).sum() \
+            + (orc.head(s28, wg, "fc_action_motion_28", True) * cot[2]).sum()
+
+    def step(units, layout, interleave):
+        """One training step: units on the backbone's maps (as handed over, their contiguous copies, or a mix), torch fusion
+        stages, loss.backward().  Returns the maps given, the maps the autograd node holds, the outputs and the parameter gradients."""
+        for p in units.parameters():
+            p.grad = None
+        feats = list(feats_cl)
+        if layout == "nchw":
+            feats = [f.contiguous() for f in feats]
+        elif layout == "mix":
+            feats = [f.contiguous() if i % 2 else f for i, f in enumerate(feats)]
+        with autocast():
+            outs = units(feats, drop_seed=DROP_SEED)
+        saved = list(_units_node(outs[0]).feats)
+        if interleave:                                              # an eval forward between the forward and its backward
+            units.eval()
+            with torch.no_grad():
+                units([f.contiguous() for f in other] if layout == "nchw" else other)
+            units.train()
+        loss = loss_of(*outs)
+        loss.backward()
+        return feats, saved, [o.detach().clone() for o in outs], {k: p.grad.clone() for k, p in units.named_parameters() if p.grad is not None}
+
+    det = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True                       # the torch stages between the units and the loss, run twice
+    try:
+        ucl, unc = new_units(), new_units()
+        given, saved_cl, out_cl, g_cl = step(ucl, "cl", False)
+        _f, saved_nc, out_nc, g_nc = step(unc, "nchw", False)
+        # no copy was made: the node holds the very tensors the backbone handed over
+        assert [s.data_ptr() for s in saved_cl] == [f.data_ptr() for f in given] == [f.data_ptr() for f in feats_cl]
+        assert all(s.dtype == dt and s.is_contiguous(memory_format=CLAST) and not s.is_contiguous() for s in saved_cl)
+        assert all(s.is_contiguous() for s in saved_nc)
+        assert all(o.dtype == torch.float32 for o in out_cl)
+        assert all(torch.equal(a, b) for a, b in zip(out_cl, out_nc))
+        assert g_cl.keys() == g_nc.keys() and len(g_cl) == 54
+        for k in g_cl:
+            assert g_cl[k].dtype == torch.float32 and torch.equal(g_cl[k], g_nc[k]), k
+        # the interleaved forward: the backward finds a foreign generation and recomputes K1 + K2 from the saved channels_last maps
+        _f, _s, _o, g_cli = step(ucl, "cl", True)
+        _f, _s, _o, g_nci = step(unc, "nchw", True)
+        for k in g_cl:
+            assert torch.equal(g_cli[k], g_cl[k]) and torch.equal(g_cli[k], g_nci[k]), k
+        # a mix of layouts still works, through contiguous copies
+        _f, saved_mix, out_mix, g_mix = step(ucl, "mix", False)
+        assert all(s.is_contiguous() for s in saved_mix)
+        assert all(torch.equal(a, b) for a, b in zip(out_mix, out_nc))
+        for k in g_cl:
+            assert torch.equal(g_mix[k], g_nc[k]), k
+    finally:
+        torch.backends.cudnn.deterministic = det
+
+
+# ---- 6. stream capture ----
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_train_and_backward_capture(rt, name):
+    """off_units_train followed by off_units_backward on channels_last maps, captured in a torch.cuda.graph on one stream and
+    replayed twice: bit-identical to the eager run."""
+    B, L = 3, 4
+    h = make_handle(rt, B, L)
+    xcl = to_cl(relu_maps(B, L, DTYPES[name], 21))
+    views = grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT))
+    grads = h.new_unit_grads()
+
+    def launch():
+        h.off_units_train(xcl, DROP_SEED, DROP_P)
+        h.off_units_backward(xcl, views, DROP_SEED, DROP_P, grads=grads, accumulate=False)
+
+    launch()
+    torch.cuda.synchronize()
+    eager_g, eager_w = grads.clone(), written(h)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        launch()                                       # warm-up on the capture stream
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        launch()
+    for _ in range(2):
+        grads.fill_(float("nan"))
+        h.workspace.fill_(0xff)
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(grads, eager_g)
+        for (n, a), (_n, b) in zip(written(h), eager_w):
+            assert torch.equal(a, b), n
+
+
+# ---- 7. what is refused, before any launch; and which handles are not ----
+
+ENTRIES = ("offk_pw_reduce", "offk_off_units", "offk_off_units_train", "offk_off_units_backward")      # + "_cl" (or "_typed")
+
+
+def _raw_calls(h, rt, fdt, ptrs, views, grads, entries, suffix="_cl"):
+    """The entries named in `entries` (+ suffix) straight through ctypes (no Python-side checks); [(entry, rc, message)]."""
+    arr = (ctypes.c_void_p * spec.NUM_SITES)(*ptrs)
+    gv = (_lib.OffkGradView * spec.NUM_SITES)()
+    for i, (t, coff) in enumerate(views):
+        gv[i].data, gv[i].cstride, gv[i].coff = t.data_ptr(), t.shape[-1], int(coff)
+    ws, st = ctypes.c_void_p(h.workspace.data_ptr()), rt._stream(h.device)
+    G = torch.zeros(h.N * 28 * 28, 128, device="cuda")
+    D = torch.zeros(h.P * 28 * 28, 32, device="cuda")
+    fn = lambda stem: getattr(h.lib, stem + suffix)
+    out = []
+    for entry, call in (
+            ("offk_pw_reduce" + suffix, lambda: fn("offk_pw_reduce")(h._h, st, fdt, 0, ctypes.c_void_p(ptrs[0]),
+                                                                    ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(D.data_ptr()))),
+            ("offk_off_units" + suffix, lambda: fn("offk_off_units")(h._h, st, fdt, arr, ws)),
+            ("offk_off_units_train" + suffix, lambda: fn("offk_off_units_train")(h._h, st, fdt, arr, ws, DROP_SEED, DROP_P)),
+            ("offk_off_units_backward" + suffix, lambda: fn("offk_off_units_backward")(h._h, st, fdt, arr, gv, ws, DROP_SEED, DROP_P,
+                                                                                      ctypes.c_void_p(grads.data_ptr()), 0))):
+        if entry[:-len(suffix)] not in entries:
+            continue
+        rc = call()
+        out.append((entry, rc, h.lib.offk_last_error(h._h).decode()))
+    torch.cuda.synchronize()
+    assert not G.any() and not D.any()
+    return out
+
+
+def _assert_refused(h, rt, fdt, ptrs, views, needle, entries=ENTRIES, suffix="_cl"):
+    h.workspace.fill_(0x5a)
+    grads = torch.full((h.new_unit_grads().numel(),), 3.25, device="cuda")
+    torch.cuda.synchronize()
+    seen = 0
+    for entry, rc, msg in _raw_calls(h, rt, fdt, ptrs, views, grads, entries, suffix):
+        assert rc == -1 and needle in msg and entry in msg, (entry, rc, msg)
+        seen += 1
+    assert seen == len(entries)
+    torch.cuda.synchronize()
+    assert bool((h.workspace == 0x5a).all()) and bool((grads == 3.25).all())      # nothing was enqueued
+
+
+def test_refusals(rt):
+    B, L = 2, 3
+    x = relu_maps(B, L, torch.float32, 1)
+    xcl = to_cl(x)
+    ptrs = [t.data_ptr() for t in xcl]
+    views = grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT))
+    h = make_handle(rt, B, L)
+    # an unknown dtype
+    _assert_refused(h, rt, 7, ptrs, views, "unknown feat_dtype")
+    # a null map: site 3a for pw_reduce (its own wording), the last site for the nine-map entries
+    _assert_refused(h, rt, _lib.FEAT_F32, [None] + ptrs[1:], views, "bad argument", ENTRIES[:1])
+    _assert_refused(h, rt, _lib.FEAT_BF16, ptrs[:8] + [None], views, "null feature map", ENTRIES[1:])
+    # a map whose pointer is 4 mod 16: site 3a for pw_reduce, and another site for the nine-map entries
+    for site in (0, 4):
+        s = x[site]
+        N, C, H, _ = s.shape
+        buf = torch.empty(s.numel() + 8, dtype=s.dtype, device="cuda")
+        off = buf[1:1 + s.numel()].view(N, H, H, C).permute(0, 3, 1, 2)
+        off.copy_(s)
+        assert off.data_ptr() % 16 == 4 and off.is_contiguous(memory_format=CLAST) and not off.is_contiguous()
+        bad = list(xcl)
+        bad[site] = off
+        for fdt in (_lib.FEAT_F32, _lib.FEAT_F16):
+            _assert_refused(h, rt, fdt, [t.data_ptr() for t in bad], views, "16-byte aligned (site %s)" % spec.SITES[site][0],
+                            ENTRIES if site == 0 else ENTRIES[1:])
+        with pytest.raises(_lib.OffkError, match="16-byte aligned"):
+            h.off_units_train(bad, DROP_SEED, DROP_P)
+        if site == 0:
+            with pytest.raises(_lib.OffkError, match="16-byte aligned"):
+                h.pw_reduce(0, off)
+    # mixed layouts (Python), on every entry that takes nine maps
+    h.workspace.fill_(0x5a)
+    mixed = xcl[:8] + [x[8]]
+    for call in (lambda: h.off_units(mixed), lambda: h.off_units_train(mixed, DROP_SEED, DROP_P),
+                 lambda: h.off_units_backward(mixed, views, DROP_SEED, DROP_P)):
+        with pytest.raises(ValueError, match="one layout"):
+            call()
+    # a channels_last tensor of the wrong logical shape: another batch; H and C swapped
+    wrong = list(xcl)
+    wrong[3] = torch.zeros((B * L + 1,) + tuple(x[3].shape[1:]), device="cuda").contiguous(memory_format=CLAST)
+    for call in (lambda: h.off_units(wrong), lambda: h.off_units_train(wrong, DROP_SEED, DROP_P),
+                 lambda: h.off_units_backward(wrong, views, DROP_SEED, DROP_P)):
+        with pytest.raises(ValueError, match=r"feats\[3\].*logical shape"):
+            call()
+    with pytest.raises(ValueError, match="logical shape"):
+        h.pw_reduce(3, wrong[3])
+    with pytest.raises(ValueError, match="logical shape"):
+        h.pw_reduce(3, torch.zeros(B * L, 14, 14, 576, device="cuda").contiguous(memory_format=CLAST))
+    torch.cuda.synchronize()
+    assert bool((h.workspace == 0x5a).all())
+    # an NHWC handle's _typed calls are refused as before, and so is its untyped backward
+    hn = make_handle(rt, B, L, feat_layout=1)
+    x16 = [t.to(torch.bfloat16) for t in x]
+    _assert_refused(hn, rt, _lib.FEAT_BF16, [t.data_ptr() for t in x16], views, "NCHW", suffix="_typed")
+    nhwc = [t.permute(0, 2, 3, 1).contiguous() for t in x]
+    with pytest.raises(_lib.OffkError, match="NCHW feature maps only"):
+        hn.off_units_backward(nhwc, views, DROP_SEED, DROP_P)
+    # and none of this disturbed the handles: the next call runs
+    assert_forward_equal(h, x)
+
+
+@pytest.mark.parametrize("name", list(DTYPES))
+def test_layout_belongs_to_the_call_not_the_handle(rt, name):
+    """The _cl entries on an NHWC handle (cfg.feat_layout is not looked at): forward and backward equal those of an NCHW handle
+    with the same weights; and the NHWC handle's own untyped forward on the same memory still runs mode 2 as before."""
+    B, L = 2, 3
+    x = relu_maps(B, L, DTYPES[name], 5)
+    xcl = to_cl(x)
+    views = grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT))
+    res = []
+    for layout in (0, 1):
+        h = make_handle(rt, B, L, feat_layout=layout)
+        w = run_units(h, xcl, True)
+        grads = torch.full((h.new_unit_grads().numel(),), float("nan"), device="cuda")
+        h.off_units_backward(xcl, views, DROP_SEED, DROP_P, grads=grads)
+        if layout == 1 and name == "f32":
+            nhwc = [t.permute(0, 2, 3, 1) for t in xcl]
+            assert all(t.is_contiguous() and t.data_ptr() == c.data_ptr() for t, c in zip(nhwc, xcl))
+            for (n, a), (_n, b) in zip(run_units(h, nhwc, True), w):
+                assert torch.equal(a, b), n
+        torch.cuda.synchronize()
+        res.append((w, grads))
+    for (n, a), (_n, b) in zip(res[0][0], res[1][0]):
+        assert torch.equal(a, b), n
+    assert torch.isfinite(res[0][1]).all() and torch.equal(res[0][1], res[1][1])

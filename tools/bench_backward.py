@@ -1,8 +1,11 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
-    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16]
+    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy]
 --feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
 .float() casts that path makes unnecessary are timed beside it.
+--feat-layout cl: the maps are torch.channels_last tensors and go in as they are (offk_off_units_train_cl / offk_off_units_backward_cl);
+copy: the same channels_last maps made contiguous inside the timed region of the forward (nine .contiguous() calls, what a caller
+without the _cl entries does; the backward then reads the copies); nchw (default): contiguous maps.  units_step_ms is forward + backward.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--precision", default="fp32")
     ap.add_argument("--variant", type=int, default=spec.VARIANT_RGB)
     ap.add_argument("--feat-dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--feat-layout", default="nchw", choices=["nchw", "cl", "copy"])
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
@@ -50,8 +54,21 @@ def main():
     bufs = [torch.randn(P, H, H, C, device="cuda", generator=gen) for H, C in ((28, 320), (14, 1056), (7, 832))]
     views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
     grads = h.new_unit_grads()
-    t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8), a.iters)
-    t_bwd = timed(lambda: h.off_units_backward(feats, views, 21, 0.8, grads=grads), a.iters)
+    if a.feat_layout != "nchw":
+        feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
+    if a.feat_layout == "copy":
+        held = [None]
+
+        def fwd():
+            held[0] = [f.contiguous() for f in feats]        # the copies live until the backward has run, as in an autograd node
+            h.off_units_train(held[0], 21, 0.8)
+        t_fwd = timed(fwd, a.iters)
+        t_copy = timed(lambda: [f.contiguous() for f in feats], a.iters)
+        t_bwd = timed(lambda: h.off_units_backward(held[0], views, 21, 0.8, grads=grads), a.iters)
+    else:
+        t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8), a.iters)
+        t_copy = 0.0
+        t_bwd = timed(lambda: h.off_units_backward(feats, views, 21, 0.8, grads=grads), a.iters)
     t_cast = timed(lambda: [f.float() for f in feats], a.iters) if fdt != torch.float32 else 0.0
     esz = 4 if fdt == torch.float32 else 2
     hw = sum(H * H for _n, _c, H in spec.SITES)
@@ -62,8 +79,10 @@ def main():
     k1b = x_bytes + B * hw * 4 * (128 * L + 32 * (L - 1))
     flops = sum(2 * N * H * H * C * 128 + 2 * P * H * H * C * 32 for _n, C, H in spec.SITES)
     print(json.dumps({"batch": B, "length": L, "precision_fwd": a.precision, "feat_dtype": a.feat_dtype,
+                      "feat_layout": a.feat_layout, "nine_contiguous_copies_ms": round(t_copy, 4),
                       "nine_float_casts_ms": round(t_cast, 4),
                       "units_train_forward_ms": round(t_fwd, 4), "units_backward_ms": round(t_bwd, 4),
+                      "units_step_ms": round(t_fwd + t_bwd, 4),
                       "clips_per_s_fwd_bwd_units": round(B / (t_fwd + t_bwd) * 1e3, 1),
                       "k2b_algorithmic_bytes": k2b, "k1b_algorithmic_bytes": k1b, "k1b_flops": flops,
                       "backward_floor_ms_hbm_8TBs": round((k2b + k1b) / 8e12 * 1e3, 4),
