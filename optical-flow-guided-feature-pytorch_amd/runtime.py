@@ -29,6 +29,21 @@ def _check_dev(t, name, device):
         raise ValueError("%s lives on %s, handle on %s" % (name, t.device, device))
 
 
+def _given(t, shape, name, device, dtype=torch.float32):
+    """A buffer the caller supplies instead of the one the wrapper would allocate (tests that guard the memory around it):
+    contiguous, on `device`, of `dtype` and of EXACTLY the documented element count; None: allocate as ever."""
+    n = int(np.prod(shape))
+    if t is None:
+        return torch.empty(n, dtype=dtype, device=device).view(*shape)
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s CUDA/HIP tensor" % (name, dtype))
+    if t.device != torch.device(device):
+        raise ValueError("%s lives on %s, the call runs on %s" % (name, t.device, device))
+    if t.numel() != n:
+        raise ValueError("%s holds %d elements, the documented size is %d %s" % (name, t.numel(), n, tuple(shape)))
+    return t.view(*shape)
+
+
 # 16-bit feature maps (offk_forward_typed): what an autocast backbone hands over
 _FEAT_DTYPES = {torch.bfloat16: _lib.FEAT_BF16, torch.float16: _lib.FEAT_F16}
 
@@ -201,6 +216,16 @@ class OffForward:
             self._ws = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def set_workspace(self, t):
+        """Use the caller's buffer (uint8, on the handle's device, at least workspace_bytes) instead of the cached allocation."""
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise ValueError("the workspace must be a contiguous uint8 CUDA/HIP tensor")
+        if t.device != self.device:
+            raise ValueError("the workspace lives on %s, handle on %s" % (t.device, self.device))
+        if t.numel() < self.workspace_bytes:
+            raise ValueError("the workspace holds %d bytes, the handle needs %d" % (t.numel(), self.workspace_bytes))
+        self._ws = t
+
     def region(self, name, channels):
         """View of a named workspace region as [rows, channels] fp32 (channels-last)."""
         off, nb = ctypes.c_size_t(), ctypes.c_size_t()
@@ -291,39 +316,42 @@ class OffForward:
                 arr[i].data[q] = t.data_ptr()
         return arr
 
-    def forward(self, feats, want28=True):
+    def _outs(self, out, want28):
+        """The three logits buffers: fresh ones, or the caller's (out7, out14, out28) -- out28 None means no 28 head."""
+        shape = (self.out_rows(), self.num_classes)
+        if out is None:
+            out7 = torch.empty(shape, dtype=torch.float32, device=self.device)
+            return out7, torch.empty_like(out7), torch.empty_like(out7) if want28 else None
+        out7, out14, out28 = out
+        return (_given(out7, shape, "out7", self.device), _given(out14, shape, "out14", self.device),
+                _given(out28, shape, "out28", self.device) if out28 is not None else None)
+
+    def forward(self, feats, want28=True, out=None):
         """feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (split-fp32 handles: offk_forward_typed, the values of
         the same maps upcast); each map a tensor or a list of its channel groups.  Logits are fp32 either way.
+        out: the caller's (out7, out14, out28) instead of fresh tensors (out28 None: no 28 head).
         torch.channels_last maps of any of the three dtypes (all nine, logical shape as ever) are taken as they are on a split-fp32
         handle (offk_forward_cl) and give the values of their contiguous copies."""
+        kw = {} if out is None else {"out": out}       # (the default call reaches the two forms below exactly as it always did)
         if self.takes_channels_last(feats):
-            return self._forward_cl(feats, want28)
+            return self._forward_cl(feats, want28, **kw)
         fdt = self._feat16(feats)
         if fdt is not None:
-            return self._forward16(feats, fdt, want28)
+            return self._forward16(feats, fdt, want28, **kw)
         if any(not torch.is_tensor(f) for f in feats):
             arr = self._parts_array(feats)
-            rows = self.out_rows()
-            out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
-            out14 = torch.empty_like(out7)
-            out28 = torch.empty_like(out7) if want28 else None
+            out7, out14, out28 = self._outs(out, want28)
             _lib.check(self.lib.offk_forward_parts(self._h, _stream(self.device), arr, _ptr(out7), _ptr(out14), _ptr(out28),
                                                    _ptr(self.workspace)), self._h)
             return out7, out14, out28
         arr = self._feat_array(feats)
-        rows = self.out_rows()
-        out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
-        out14 = torch.empty_like(out7)
-        out28 = torch.empty_like(out7) if want28 else None
+        out7, out14, out28 = self._outs(out, want28)
         _lib.check(self.lib.offk_forward(self._h, _stream(self.device), arr, _ptr(out7), _ptr(out14), _ptr(out28),
                                          _ptr(self.workspace)), self._h)
         return out7, out14, out28
 
-    def _forward16(self, feats, fdt, want28):
-        rows = self.out_rows()
-        out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
-        out14 = torch.empty_like(out7)
-        out28 = torch.empty_like(out7) if want28 else None
+    def _forward16(self, feats, fdt, want28, out=None):
+        out7, out14, out28 = self._outs(out, want28)
         if any(not torch.is_tensor(f) for f in feats):
             arr = self._parts_array(feats, _check_dev16)
             _lib.check(self.lib.offk_forward_parts_typed(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14),
@@ -334,12 +362,9 @@ class OffForward:
                                                    _ptr(self.workspace)), self._h)
         return out7, out14, out28
 
-    def _forward_cl(self, feats, want28):
+    def _forward_cl(self, feats, want28, out=None):
         fdt = self._cl_dtype(feats)
-        rows = self.out_rows()
-        out7 = torch.empty(rows, self.num_classes, dtype=torch.float32, device=self.device)
-        out14 = torch.empty_like(out7)
-        out28 = torch.empty_like(out7) if want28 else None
+        out7, out14, out28 = self._outs(out, want28)
         if any(not torch.is_tensor(f) for f in feats):
             arr = self._parts_array(feats, _check_dev_cl)
             _lib.check(self.lib.offk_forward_parts_cl(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
@@ -462,11 +487,12 @@ class OffForward:
         return grads, views
 
     # ---- stage entry points -----------------------------------------------------------
-    def pw_reduce(self, site, feat):
-        """K1 of one site.  feat: the site's map, fp32 / bf16 / fp16, contiguous or torch.channels_last (offk_pw_reduce_cl)."""
+    def pw_reduce(self, site, feat, G=None, D=None):
+        """K1 of one site.  feat: the site's map, fp32 / bf16 / fp16, contiguous or torch.channels_last (offk_pw_reduce_cl).
+        G / D: the caller's buffers instead of fresh ones."""
         _name, C, H = spec.SITES[site]
-        G = torch.empty(self.N * H * H, spec.GEN_CH, dtype=torch.float32, device=self.device)
-        D = torch.zeros(self.P * H * H, spec.DOWN_CH, dtype=torch.float32, device=self.device)
+        G = _given(G, (self.N * H * H, spec.GEN_CH), "G", self.device)
+        D = _given(D, (self.P * H * H, spec.DOWN_CH), "D", self.device)
         if (torch.is_tensor(feat) and feat.dim() == 4 and not feat.is_contiguous()
                 and feat.is_contiguous(memory_format=torch.channels_last)):      # channels_last map: offk_pw_reduce_cl
             _check_dev_cl(feat, "feat", self.device)
@@ -522,20 +548,21 @@ class OffForward:
         return dict((n, (ms[i], int(calls[i]))) for i, n in enumerate(_lib.STAGE_NAMES))
 
 
-def segment_consensus_backward(grad_out, length_m1):
+def segment_consensus_backward(grad_out, length_m1, out=None):
     """basic_ops.py:29-33: grad_out [B, C] -> grad_in [B*(L-1), C] = grad_out / (L-1), repeated."""
     lib = _lib.load()
     B, C = grad_out.shape
-    gi = torch.empty(B * length_m1, C, dtype=torch.float32, device=grad_out.device)
+    gi = _given(out, (B * length_m1, C), "out", grad_out.device)
     _lib.check(lib.offk_segment_consensus_backward(_stream(grad_out.device), _ptr(grad_out.contiguous()), B, int(length_m1), C, _ptr(gi)))
     return gi
 
 
 # ---- handle-less stage kernels (channels-last tensors) ----------------------------------
 def conv2d_nhwc(x, w_oihw, bias, stride, pad, res=None, flags=0, x_coff=0, ci=None, y=None, y_coff=0,
-                tile_cfg=-1, splitk=0, w_packed=None, precision=0):
+                tile_cfg=-1, splitk=0, w_packed=None, precision=0, partial=None):
     """x: [n, H, W, Cs] fp32 CUDA; uses channels [x_coff, x_coff+Ci).  Returns y [n, Ho, Wo, Co]
-    (or writes channels [y_coff, y_coff+Co) of the given y)."""
+    (or writes channels [y_coff, y_coff+Co) of the given y).  partial: the caller's split-K slab buffer, exactly
+    splitk * M * Co floats (splitk > 1)."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     Co, Ci, KH, KW = w_oihw.shape
@@ -550,50 +577,53 @@ def conv2d_nhwc(x, w_oihw, bias, stride, pad, res=None, flags=0, x_coff=0, ci=No
     part, nfl = None, 0
     if splitk > 1:
         nfl = splitk * n * Ho * Wo * Co
-        part = torch.empty(nfl, dtype=torch.float32, device=x.device)
+        part = _given(partial, (nfl,), "partial", x.device)
     _lib.check(lib.offk_conv2d_ex(_stream(x.device), _ptr(x), cs, x_coff, n, H, W, Ci, _ptr(wp), _ptr(bias), Co, KH, KW,
                                   stride, pad, _ptr(res), res.shape[-1] if res is not None else 0, 0, flags,
                                   _ptr(y), y.shape[-1], y_coff, tile_cfg, splitk, _ptr(part), nfl, precision))
     return y
 
 
-def pack_conv_weight(w_oihw):
-    """[Co][Ci][KH][KW] -> the library's K order [Co][Ci/32][KH*KW][32] (device tensor)."""
+def pack_conv_weight(w_oihw, out=None):
+    """[Co][Ci][KH][KW] -> the library's K order [Co][Ci/32][KH*KW][32] (device tensor; out: the caller's buffer of that size)."""
     lib = _lib.load()
     Co, Ci, KH, KW = w_oihw.shape
-    wp = torch.empty(Co, KH, KW, Ci, dtype=torch.float32, device=w_oihw.device)
+    wp = _given(out, (Co, KH, KW, Ci), "out", w_oihw.device)
     _lib.check(lib.offk_pack_conv_weight(_stream(w_oihw.device), _ptr(w_oihw.contiguous()), Co, Ci, KH, KW, _ptr(wp)))
     return wp
 
 
-def bottleneck_chain14(x, w1, b1, w2_oihw, b2, w3, b3, res=None, relu_in=False, x_coff=0, y=None, y_coff=0):
+def bottleneck_chain14(x, w1, b1, w2_oihw, b2, w3, b3, res=None, relu_in=False, x_coff=0, y=None, y_coff=0, w2_packed=None):
     """One 1x1 -> 3x3 -> 1x1 (+ residual) chain of fusion@28 in one launch (offk_bottleneck_chain14).  x: [n, 14, 14, Cs] fp32 CUDA,
     the chain reads channels [x_coff, x_coff + Cin); w1 [64, Cin], w2_oihw [64, 64, 3, 3], w3 [256, K3] (K3 = 128: contracts
-    [t2 | x]); res: [n, 14, 14, 256] or None.  Returns y [n, 14, 14, 256] (or writes channels [y_coff, y_coff + 256) of y)."""
+    [t2 | x]); res: [n, 14, 14, 256] or None.  Returns y [n, 14, 14, 256] (or writes channels [y_coff, y_coff + 256) of y).
+    w2_packed: pack_conv_weight(w2_oihw) where the caller already holds it."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     assert H == 14 and W == 14
     Cin, K3 = w1.shape[1], w3.shape[1]
     if y is None:
         y = torch.empty(n, 14, 14, 256, dtype=torch.float32, device=x.device)
-    w2p = pack_conv_weight(w2_oihw)
+    w2p = pack_conv_weight(w2_oihw) if w2_packed is None else w2_packed
     _lib.check(lib.offk_bottleneck_chain14(_stream(x.device), _ptr(x), cs, x_coff, n, Cin, int(relu_in), _ptr(w1.contiguous()),
                                            _ptr(b1), _ptr(w2p), _ptr(b2), _ptr(w3.contiguous()), _ptr(b3), K3, _ptr(res),
                                            res.shape[-1] if res is not None else 0, 0, _ptr(y), y.shape[-1], y_coff))
     return y
 
 
-def bottleneck_chain14_split(x, w1, b1, w2_oihw, b2, w3, b3, res=None, branch=None, relu_in=False, x_coff=0, y=None, y_coff=0):
+def bottleneck_chain14_split(x, w1, b1, w2_oihw, b2, w3, b3, res=None, branch=None, relu_in=False, x_coff=0, y=None, y_coff=0,
+                             w2_packed=None, scratch=None):
     """offk_bottleneck_chain14_split: the chain in split-fp32 arithmetic (chain_split.hip).  w3 [256, 64]; branch = (w [256, 64], b [256]):
-    chain 28a's branch 1x1 on the chain input before relu_in's ReLU (then Cin = 64 and no res)."""
+    chain 28a's branch 1x1 on the chain input before relu_in's ReLU (then Cin = 64 and no res).  scratch: the caller's uint8 buffer
+    of exactly the header's 6 * (64 * Cin + 64 * 576 + 2 * 256 * 64) bytes; w2_packed: pack_conv_weight(w2_oihw)."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     assert H == 14 and W == 14 and w3.shape[1] == 64
     Cin = w1.shape[1]
     if y is None:
         y = torch.empty(n, 14, 14, 256, dtype=torch.float32, device=x.device)
-    w2p = pack_conv_weight(w2_oihw)
-    scratch = torch.empty(6 * (64 * Cin + 64 * 576 + 2 * 256 * 64), dtype=torch.uint8, device=x.device)
+    w2p = pack_conv_weight(w2_oihw) if w2_packed is None else w2_packed
+    scratch = _given(scratch, (6 * (64 * Cin + 64 * 576 + 2 * 256 * 64),), "scratch", x.device, torch.uint8)
     bw, bb = (branch[0].contiguous(), branch[1].contiguous()) if branch is not None else (None, None)
     _lib.check(lib.offk_bottleneck_chain14_split(_stream(x.device), _ptr(x), cs, x_coff, n, Cin, int(relu_in), _ptr(w1.contiguous()), _ptr(b1),
                                                  _ptr(w2p), _ptr(b2), _ptr(w3.contiguous()), _ptr(b3), _ptr(bw), _ptr(bb), _ptr(res),
@@ -602,9 +632,11 @@ def bottleneck_chain14_split(x, w1, b1, w2_oihw, b2, w3, b3, res=None, branch=No
     return y
 
 
-def winograd_conv3x3(x, w_oihw, bias, res=None, flags=0, x_coff=0, y=None, y_coff=0, want_pool=False):
+def winograd_conv3x3(x, w_oihw, bias, res=None, flags=0, x_coff=0, y=None, y_coff=0, want_pool=False, w_packed=None, scratch=None,
+                     pool=None):
     """3x3 / stride 1 / pad 1 conv on 7x7 maps as Winograd F(4x4, 3x3) (offk_winograd_conv3x3).  x: [n, 7, 7, Cs]; returns y
-    [n, 7, 7, Co] (and, want_pool, the per-tile sums [4 n, Co])."""
+    [n, 7, 7, Co] (and, want_pool, the per-tile sums [4 n, Co]).  w_packed / scratch / pool: the caller's packed weight, scratch
+    (exactly the header's 121 * (Co * Ci + n * (Ci + Co)) floats) and pool buffer ([4 n, Co]) instead of fresh ones."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     assert H == 7 and W == 7
@@ -612,17 +644,18 @@ def winograd_conv3x3(x, w_oihw, bias, res=None, flags=0, x_coff=0, y=None, y_cof
     if y is None:
         y = torch.empty(n, 7, 7, Co, dtype=torch.float32, device=x.device)
     nfl = 121 * (Co * Ci + n * (Ci + Co))
-    scratch = torch.empty(nfl, dtype=torch.float32, device=x.device)
-    pool = torch.empty(4 * n, Co, dtype=torch.float32, device=x.device) if want_pool else None
-    _lib.check(lib.offk_winograd_conv3x3(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(pack_conv_weight(w_oihw)), _ptr(bias), Co,
+    scratch = _given(scratch, (nfl,), "scratch", x.device)
+    pool = _given(pool, (4 * n, Co), "pool", x.device) if want_pool else None
+    wp = pack_conv_weight(w_oihw) if w_packed is None else w_packed
+    _lib.check(lib.offk_winograd_conv3x3(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(wp), _ptr(bias), Co,
                                          _ptr(res), res.shape[-1] if res is not None else 0, 0, flags, _ptr(y), y.shape[-1], y_coff,
                                          _ptr(scratch), nfl, _ptr(pool)))
     return (y, pool) if want_pool else y
 
 
-def winograd_conv5x5s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0):
+def winograd_conv5x5s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0, w_packed=None, scratch=None):
     """5x5 / stride 2 / pad 2 conv on 14x14 maps in polyphase Winograd form (offk_winograd_conv5x5s2).  x: [n, 14, 14, Cs]; returns
-    y [n, 7, 7, Co]."""
+    y [n, 7, 7, Co].  w_packed / scratch (exactly the header's 400 * Ci * (Co + n) + 121 * n * Co floats): the caller's."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     assert H == 14 and W == 14
@@ -630,15 +663,17 @@ def winograd_conv5x5s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0):
     if y is None:
         y = torch.empty(n, 7, 7, Co, dtype=torch.float32, device=x.device)
     nfl = 400 * Ci * (Co + n) + 121 * n * Co
-    scratch = torch.empty(nfl, dtype=torch.float32, device=x.device)
-    _lib.check(lib.offk_winograd_conv5x5s2(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(pack_conv_weight(w_oihw)), _ptr(bias), Co,
+    scratch = _given(scratch, (nfl,), "scratch", x.device)
+    wp = pack_conv_weight(w_oihw) if w_packed is None else w_packed
+    _lib.check(lib.offk_winograd_conv5x5s2(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(wp), _ptr(bias), Co,
                                            None, 0, 0, flags, _ptr(y), y.shape[-1], y_coff, _ptr(scratch), nfl))
     return y
 
 
-def winograd_conv7x7s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0):
+def winograd_conv7x7s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0, w_packed=None, scratch=None):
     """7x7 / stride 2 / pad 3 conv on 28x28 maps in polyphase Winograd form F(5x5, 4x4) (offk_winograd_conv7x7s2).
-    x: [n, 28, 28, Cs]; returns y [n, 14, 14, Co]."""
+    x: [n, 28, 28, Cs]; returns y [n, 14, 14, Co].  w_packed / scratch (exactly the header's 225 * Ci * (Co + 9 n) + 64 * 9 n * Co floats):
+    the caller's."""
     lib = _lib.load()
     n, H, W, cs = x.shape
     assert H == 28 and W == 28
@@ -646,23 +681,25 @@ def winograd_conv7x7s2(x, w_oihw, bias, flags=0, x_coff=0, y=None, y_coff=0):
     if y is None:
         y = torch.empty(n, 14, 14, Co, dtype=torch.float32, device=x.device)
     nfl = 225 * Ci * (Co + 9 * n) + 64 * 9 * n * Co
-    scratch = torch.empty(nfl, dtype=torch.float32, device=x.device)
-    _lib.check(lib.offk_winograd_conv7x7s2(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(pack_conv_weight(w_oihw)), _ptr(bias), Co,
+    scratch = _given(scratch, (nfl,), "scratch", x.device)
+    wp = pack_conv_weight(w_oihw) if w_packed is None else w_packed
+    _lib.check(lib.offk_winograd_conv7x7s2(_stream(x.device), _ptr(x), cs, x_coff, n, Ci, _ptr(wp), _ptr(bias), Co,
                                            flags, _ptr(y), y.shape[-1], y_coff, _ptr(scratch), nfl))
     return y
 
 
-def winograd_between(M, bias_in, phases_in, w1=None, b1=None, x=None, x_coff=0, precision="fp32"):
+def winograd_between(M, bias_in, phases_in, w1=None, b1=None, x=None, x_coff=0, precision="fp32", V=None, scratch=None):
     """offk_winograd_between: M [121, n, Cin] (Winograd-domain GEMM output of the conv in front) -> V [121, n, Cmid] (GEMM input of
     the conv behind), through relu(A^T M A + bias_in), optionally a 1x1 conv w1 [Cmid, Cin] + b1 + ReLU, and B^T . B.  x: optional
-    [n, 7, 7, Cs] buffer that also receives relu(A^T M A + bias_in) at channels [x_coff, x_coff + Cin)."""
+    [n, 7, 7, Cs] buffer that also receives relu(A^T M A + bias_in) at channels [x_coff, x_coff + Cin).  V / scratch (split-fp32: exactly
+    the header's Cmid * Cin * 6 bytes): the caller's buffers instead of fresh ones."""
     lib = _lib.load()
     pts, n, cin = M.shape
     assert pts == 121
     cmid = w1.shape[0] if w1 is not None else cin
-    V = torch.empty(121, n, cmid, dtype=torch.float32, device=M.device)
+    V = _given(V, (121, n, cmid), "V", M.device)
     if precision == "f32split":      # offk_winograd_between_ex: stage B (the 1x1 conv) in split-fp32 arithmetic
-        scratch = torch.empty(cmid * cin * 6, dtype=torch.uint8, device=M.device)
+        scratch = _given(scratch, (cmid * cin * 6,), "scratch", M.device, torch.uint8)
         _lib.check(lib.offk_winograd_between_ex(_stream(M.device), _ptr(M.contiguous()), _ptr(bias_in), int(phases_in), n, cin, _ptr(x),
                                                 x.shape[-1] if x is not None else 0, x_coff, _ptr(w1.contiguous()), _ptr(b1), cmid, _ptr(V),
                                                 _lib.PRECISIONS[precision], _ptr(scratch), scratch.numel()))
@@ -673,66 +710,70 @@ def winograd_between(M, bias_in, phases_in, w1=None, b1=None, x=None, x_coff=0, 
     return V
 
 
-def batched_gemm_nt(x, w, precision="fp32"):
+def batched_gemm_nt(x, w, precision="fp32", y=None, scratch=None):
     """offk_batched_gemm_nt: y[b] = x[b] @ w[b].T for x [batch, M, K], w [batch, Co, K] (the GEMMs of a conv on a Winograd path);
-    precision "f32split": split-fp32 arithmetic on the bf16 matrix pipe (wino_gemm_split.hip)."""
+    precision "f32split": split-fp32 arithmetic on the bf16 matrix pipe (wino_gemm_split.hip).  y / scratch (split-fp32: exactly the
+    header's batch * Co * K * 6 bytes): the caller's buffers instead of fresh ones."""
     lib = _lib.load()
     batch, m, k = x.shape
     co = w.shape[1]
     assert w.shape == (batch, co, k)
-    y = torch.empty(batch, m, co, dtype=torch.float32, device=x.device)
-    scratch = torch.empty(batch * co * k * 6 if precision == "f32split" else 16, dtype=torch.uint8, device=x.device)
+    y = _given(y, (batch, m, co), "y", x.device)
+    if precision == "f32split":
+        scratch = _given(scratch, (batch * co * k * 6,), "scratch", x.device, torch.uint8)
+    else:
+        scratch = torch.empty(16, dtype=torch.uint8, device=x.device)      # (the fp32 form takes none)
     _lib.check(lib.offk_batched_gemm_nt(_stream(x.device), _ptr(x.contiguous()), _ptr(w.contiguous()), _ptr(y), batch, m, k, co,
                                         _lib.PRECISIONS[precision], _ptr(scratch), scratch.numel()))
     return y
 
 
-def head(x, fc_w, fc_b, maxpool, x_coff=0, c=None):
+def head(x, fc_w, fc_b, maxpool, x_coff=0, c=None, out=None):
     lib = _lib.load()
     n, H, W, cs = x.shape
     C = cs if c is None else c
-    out = torch.empty(n, fc_w.shape[0], dtype=torch.float32, device=x.device)
+    out = _given(out, (n, fc_w.shape[0]), "out", x.device)
     _lib.check(lib.offk_head(_stream(x.device), _ptr(x), cs, x_coff, n, H, W, C, int(maxpool), _ptr(fc_w.contiguous()),
                              _ptr(fc_b.contiguous()), fc_w.shape[0], _ptr(out)))
     return out
 
 
-def segment_consensus(x, batch):
+def segment_consensus(x, batch, out=None):
     lib = _lib.load()
     T = x.shape[0] // batch
-    out = torch.empty(batch, x.shape[1], dtype=torch.float32, device=x.device)
+    out = _given(out, (batch, x.shape[1]), "out", x.device)
     _lib.check(lib.offk_segment_consensus(_stream(x.device), _ptr(x.contiguous()), batch, T, x.shape[1], _ptr(out)))
     return out
 
 
-def nchw_to_nhwc(x):
+def nchw_to_nhwc(x, out=None):
     lib = _lib.load()
     n, C, H, W = x.shape
-    out = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device)
+    out = _given(out, (n, H, W, C), "out", x.device)
     _lib.check(lib.offk_nchw_to_nhwc(_stream(x.device), _ptr(x.contiguous()), n, C, H * W, _ptr(out)))
     return out
 
 
-def nhwc_to_nchw(x, coff=0, c=None):
+def nhwc_to_nchw(x, coff=0, c=None, out=None):
     lib = _lib.load()
     n, H, W, cs = x.shape
     C = cs - coff if c is None else c
-    out = torch.empty(n, C, H, W, dtype=torch.float32, device=x.device)
+    out = _given(out, (n, C, H, W), "out", x.device)
     _lib.check(lib.offk_nhwc_to_nchw(_stream(x.device), _ptr(x), cs, coff, n, C, H * W, _ptr(out)))
     return out
 
 
-def score_fusion(score_sets, weights, want_pred=True):
+def score_fusion(score_sets, weights, want_pred=True, out=None):
     """score_sets: list of [videos, crops, classes] (or [videos, classes]) fp32 CUDA tensors.
-    Returns (fused [videos, classes], pred [videos] int32 or None) -- K7, include/offk.h."""
+    Returns (fused [videos, classes], pred [videos] int32 or None) -- K7, include/offk.h.  out: the caller's (fused, pred)."""
     lib = _lib.load()
     sets = [s.contiguous() if s.dim() == 3 else s.contiguous().unsqueeze(1) for s in score_sets]
     v, k, c = sets[0].shape
     for s in sets:
         if tuple(s.shape) != (v, k, c) or not s.is_cuda or s.dtype != torch.float32:
             raise ValueError("score sets must be same-shape fp32 CUDA tensors")
-    fused = torch.empty(v, c, dtype=torch.float32, device=sets[0].device)
-    pred = torch.empty(v, dtype=torch.int32, device=sets[0].device) if want_pred else None
+    fused = _given(out[0] if out is not None else None, (v, c), "fused", sets[0].device)
+    pred = _given(out[1] if out is not None else None, (v,), "pred", sets[0].device, torch.int32) if want_pred else None
     ptrs = (ctypes.c_void_p * len(sets))(*[s.data_ptr() for s in sets])
     w = (ctypes.c_float * len(sets))(*[float(x) for x in weights])
     _lib.check(lib.offk_score_fusion(_stream(sets[0].device), ptrs, w, len(sets), v, k, c, _ptr(fused), _ptr(pred)))
