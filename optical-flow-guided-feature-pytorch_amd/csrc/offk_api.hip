@@ -15,6 +15,8 @@
 
 using namespace offk;
 
+typedef const void* const* MapPtrs;      // nine maps of any element type, as the _typed / _cl entries take them
+
 // The batched GEMMs of a conv on a Winograd path (M[point] = V[point] . U[point]^T): one persistent launch of wino_gemm_kernel
 // (wino_gemm.hip), or -- persistent == false, OFFK_WINO_GEMM=0 -- gridDim.y problems of the generic 1x1 kernel (conv_igemm.hip, 64 x 64
 // LDS-DMA tile).  Bit-identical.  grp / ngrp: winograd.hip's wino_groups / winograd7.hip's wino7_groups; rows = rows of every V[point].
@@ -234,6 +236,11 @@ int fail_hip(offk_handle* h, hipError_t e, const char* what) {
   do {                                                     \
     hipError_t e__ = (expr);                               \
     if (e__ != hipSuccess) return fail_hip(h, e__, #expr); \
+  } while (0)
+#define TRY(expr)            \
+  do {                       \
+    int rc__ = (expr);       \
+    if (rc__ != OFFK_OK) return rc__; \
   } while (0)
 
 // per-launch trace (offk_set_profiling(h, 2)): an event on `st` in front of the launch group `name`; name == nullptr closes
@@ -522,7 +529,55 @@ int finalize_pw(offk_handle* h, hipStream_t st) {
   return OFFK_OK;
 }
 
-// feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (the typed training entries; check_feat16_train has passed): K1 runs its 16-bit map form
+// ---- the kinds of feature maps beside contiguous fp32: 16-bit NCHW (the _typed entries), channels-last in any dtype (the _cl entries) ----
+// One table for both sides.  Channels-last: the layout belongs to the call, cfg.feat_layout is not looked at.
+struct FeatKind {
+  const char* noun;      // in the messages
+  bool f32_ok;           // OFFK_FEAT_F32 is one of its dtypes (the _typed entries forward it to the untyped entry instead)
+  int align;             // of the map pointers, bytes: the inference side (K1T)
+  int align_train;       // ... the training side (K1, K1b)
+  bool cl;               // channels-last parts (else NCHW, and an NHWC handle is refused)
+};
+// Pointer alignments, bytes, each from the widest load of the kernels behind it:
+constexpr int kAlign16Infer = 4;    // 16-bit NCHW, K1T: the 28x28 and 14x14 sites are read as pixel pairs (pw_tdiff_f16.hip)
+constexpr int kAlign16Train = 8;    // 16-bit NCHW, K1 / K1b: four pixels per load there (pw_reduce.hip, units_bwd.hip) -- intended, not drift from 4
+constexpr int kAlignCl = 16;        // channels-last, every loader on either side: 16-byte pieces of a pixel's channel row
+constexpr FeatKind kKind16{"16-bit", false, kAlign16Infer, kAlign16Train, false}, kKindCl{"channels-last", true, kAlignCl, kAlignCl, true};
+// one 16-bit map, bytes (either kind, training side): K1 / K1b address such maps through a buffer descriptor (pw_reduce.hip, 2 GiB less a guard)
+constexpr unsigned long long kFeat16MaxBytes = 0x7fffff00ull;
+
+// The launchers of K1, K1T and K1b by (channels-last, feat_dtype), each with the name its launch goes under in the per-launch
+// trace: [channels-last][enum offk_feat_dtype].  K1 on channels-last fp32 maps is the plain kernel (its nhwc form) under the plain name.
+constexpr const char* kK1Plain = "units:pw_reduce (K1)";
+const char* const kK1Name[2][3] = {{kK1Plain, "units:pw_reduce (K1, bf16 maps)", "units:pw_reduce (K1, fp16 maps)"},
+                                   {kK1Plain, "units:pw_reduce (K1, channels-last bf16 maps)", "units:pw_reduce (K1, channels-last fp16 maps)"}};
+const char* const kK1TName[2][3] = {{"units:pw_tdiff (K1T)", "units:pw_tdiff (K1T, bf16 maps)", "units:pw_tdiff (K1T, fp16 maps)"},
+                                    {"units:pw_tdiff (K1T, channels-last maps)", "units:pw_tdiff (K1T, channels-last bf16 maps)",
+                                     "units:pw_tdiff (K1T, channels-last fp16 maps)"}};
+// K1 (pw_reduce.hip; pp.nhwc says channels-last).  traced: false for the stage entries offk_pw_reduce*, which leave no mark.
+int launch_k1(offk_handle* h, hipStream_t st, const PwParams& pp, int feat_dtype, bool traced) {
+  if (traced) TRY(trace_mark(h, st, kK1Name[pp.nhwc ? 1 : 0][feat_dtype]));
+  if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, st));
+  else HIP_TRY(h, pw_reduce_launch(pp, st));
+  return OFFK_OK;
+}
+// K1T (pw_tdiff.hip / pw_tdiff_split.hip; pw_tdiff_f16.hip; pw_tdiff_cl.hip)
+int launch_k1t(offk_handle* h, hipStream_t st, const PtParams& pt, int feat_dtype, bool cl) {
+  TRY(trace_mark(h, st, kK1TName[cl][feat_dtype]));
+  if (cl) HIP_TRY(h, pw_tdiff_cl_launch(pt, feat_dtype, st));
+  else if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_tdiff_feat16_launch(pt, feat_dtype, st));
+  else HIP_TRY(h, pw_tdiff_launch(pt, st));
+  return OFFK_OK;
+}
+// K1b (units_bwd.hip, units_bwd_cl.hip); the backward leaves no marks in the trace
+int launch_k1b(offk_handle* h, hipStream_t st, const WgParams& wp, int feat_dtype, bool cl) {
+  if (cl) HIP_TRY(h, pw_wgrad_cl_launch(wp, feat_dtype, st));
+  else if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_wgrad_feat16_launch(wp, feat_dtype, st));
+  else HIP_TRY(h, pw_wgrad_launch(wp, st));
+  return OFFK_OK;
+}
+
+// feat_dtype OFFK_FEAT_BF16 / OFFK_FEAT_F16 (the typed training entries; check_feat_train has passed): K1 runs its 16-bit map form
 // on the same grid; the parts' data pointers then address 16-bit elements.
 // nhwc: the maps of THIS call are channels-last (the untyped entries pass the handle's cfg.feat_layout, the _cl entries true).
 int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, hipEvent_t* ev, bool nhwc,
@@ -543,15 +598,9 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
   }
   pp.total_blocks = blk;
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
-  if (feat_dtype != OFFK_FEAT_F32) {
-    if (!pw_reduce_feat16_supported(pp)) return fail(h, OFFK_ERR_INVALID, "16-bit feature maps: a map of 2 GiB or more is not supported");
-    { int rc = trace_mark(h, st, nhwc ? (feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, channels-last fp16 maps)" : "units:pw_reduce (K1, channels-last bf16 maps)")
-                                      : (feat_dtype == OFFK_FEAT_F16 ? "units:pw_reduce (K1, fp16 maps)" : "units:pw_reduce (K1, bf16 maps)")); if (rc != OFFK_OK) return rc; }
-    HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, st));
-  } else {
-    { int rc = trace_mark(h, st, "units:pw_reduce (K1)"); if (rc != OFFK_OK) return rc; }
-    HIP_TRY(h, pw_reduce_launch(pp, st));
-  }
+  if (feat_dtype != OFFK_FEAT_F32 && !pw_reduce_feat16_supported(pp))
+    return fail(h, OFFK_ERR_INVALID, "16-bit feature maps: a map of 2 GiB or more is not supported");
+  TRY(launch_k1(h, st, pp, feat_dtype, true));
   if (ev) HIP_TRY(h, hipEventRecord(ev[1], st));
 
   { int rc = trace_mark(h, st, "units:sobel_tdiff (K2)"); if (rc != OFFK_OK) return rc; }
@@ -596,23 +645,65 @@ int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts fe
     o.C = kSites[s].C; o.HW = kSites[s].H * kSites[s].H;
   }
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
-  if (cl) {
-    { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16    ? "units:pw_tdiff (K1T, channels-last fp16 maps)"
-                                 : feat_dtype == OFFK_FEAT_BF16 ? "units:pw_tdiff (K1T, channels-last bf16 maps)"
-                                                                : "units:pw_tdiff (K1T, channels-last maps)"); if (rc != OFFK_OK) return rc; }
-    HIP_TRY(h, pw_tdiff_cl_launch(pt, feat_dtype, st));
-  } else if (feat_dtype != OFFK_FEAT_F32) {
-    { int rc = trace_mark(h, st, feat_dtype == OFFK_FEAT_F16 ? "units:pw_tdiff (K1T, fp16 maps)" : "units:pw_tdiff (K1T, bf16 maps)"); if (rc != OFFK_OK) return rc; }
-    HIP_TRY(h, pw_tdiff_feat16_launch(pt, feat_dtype, st));
-  } else {
-    { int rc = trace_mark(h, st, "units:pw_tdiff (K1T)"); if (rc != OFFK_OK) return rc; }
-    HIP_TRY(h, pw_tdiff_launch(pt, st));
-  }
+  TRY(launch_k1t(h, st, pt, feat_dtype, cl));
   if (ev) HIP_TRY(h, hipEventRecord(ev[1], st));
   { int rc = trace_mark(h, st, "units:sobel S-blocks (K2 spatial half)"); if (rc != OFFK_OK) return rc; }
   { int rc = run_sobel_tdiff_all(h, st, ws, 3); if (rc != OFFK_OK) return rc; }   // S-blocks only: M[.., coff .. coff+32)
   if (ev) HIP_TRY(h, hipEventRecord(ev[2], st));
   return OFFK_OK;
+}
+
+// ---- the training side of the kinds (K1 + K2, K1b): what offk_pw_reduce_typed / _cl and their siblings refuse, and the bodies they share ----
+// Everything such a call is refused for, checked before anything is enqueued.  Unlike check_feat (the inference forward) there is no
+// condition on the handle's precision, on bound weights or on OFFK_FUSED_UNITS: these entries run the fp32 kernels K1 / K1b.
+int check_feat_train(offk_handle* h, const FeatKind& k, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
+  const std::string f(fn), maps = std::string(": ") + k.noun + " feature map";
+  if (!(feat_dtype == OFFK_FEAT_F32 && k.f32_ok) && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  if (!k.cl && h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + maps + "s are NCHW-only (this handle is NHWC)");
+  for (int i = 0; i < count; ++i) {
+    const SiteSpec& site = kSites[first + i];
+    if (!feats[i]) return fail(h, OFFK_ERR_INVALID, f + ": null feature map");
+    if (reinterpret_cast<uintptr_t>(feats[i]) & (k.align_train - 1))
+      return fail(h, OFFK_ERR_INVALID, f + maps + " pointers must be " + std::to_string(k.align_train) + "-byte aligned (site " + site.name + ")");
+    if (feat_dtype != OFFK_FEAT_F32 && (unsigned long long)h->N * site.H * site.H * site.C * 2ull >= kFeat16MaxBytes)
+      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps of 2 GiB or more are not supported (site " + site.name + ")");
+  }
+  return OFFK_OK;
+}
+
+// K1 of one site into the caller's G / D: offk_pw_reduce (k == nullptr: the handle's layout, fp32) and its _typed / _cl forms
+int pw_reduce_site(offk_handle* h, void* stream, const FeatKind* k, int feat_dtype, int site, const void* feat, float* G, float* D, const char* fn) {
+  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": bad argument");
+  if (k) TRY(check_feat_train(h, *k, feat_dtype, &feat, site, 1, fn));
+  TRY(site_weights_ready(h, site, true, false));
+  DeviceGuard guard(h->cfg.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  PwParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
+  pp.nhwc = k ? k->cl : h->cfg.feat_layout == OFFK_FEAT_NHWC;
+  pp.zeros = h->zero_page;
+  TRY(finalize_pw(h, st));
+  fill_pw_site(h, site, whole_map(site, static_cast<const float*>(feat)), G, D, &pp.s[0]);
+  pp.total_blocks = pw_blocks_for(pp.s[0].M);
+  return launch_k1(h, st, pp, feat_dtype, false);
+}
+
+// K1 + K2 of nine whole maps into the workspace: offk_off_units, offk_off_units_train (train: with the dropout of drop_seed / drop_p)
+// and their _typed / _cl forms (k == nullptr: the plain entries -- the handle's layout, fp32)
+int off_units_whole(offk_handle* h, void* stream, const FeatKind* k, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                    bool train, uint64_t drop_seed, double drop_p, const char* fn) {
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  DropCfg drop;
+  if (train) TRY(make_drop(h, drop_seed, drop_p, &drop));
+  if (k) TRY(check_feat_train(h, *k, feat_dtype, feats, 0, kNumSites, fn));
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, k ? k->cl : h->cfg.feat_layout == OFFK_FEAT_NHWC, drop,
+                       feat_dtype);
 }
 
 struct View { const float* p; int cs, coff; };
@@ -727,12 +818,6 @@ int finalize_wino(offk_handle* h, hipStream_t st) {
   h->wino_dirty = false;
   return OFFK_OK;
 }
-#define TRY(expr)            \
-  do {                       \
-    int rc__ = (expr);       \
-    if (rc__ != OFFK_OK) return rc__; \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -1111,19 +1196,7 @@ int offk_stage_times(offk_handle* h, double ms[OFFK_NUM_STAGES], int64_t calls[O
 }
 
 int offk_pw_reduce(offk_handle* h, void* stream, int site, const float* feat, float* G, float* D) {
-  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, "offk_pw_reduce: bad argument");
-  TRY(site_weights_ready(h, site, true, false));
-  DeviceGuard guard(h->cfg.device);
-  PwParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
-  pp.nhwc = h->cfg.feat_layout == OFFK_FEAT_NHWC;
-  pp.zeros = h->zero_page;
-  TRY(finalize_pw(h, static_cast<hipStream_t>(stream)));
-  fill_pw_site(h, site, whole_map(site, feat), G, D, &pp.s[0]);
-  pp.total_blocks = pw_blocks_for(pp.s[0].M);
-  HIP_TRY(h, pw_reduce_launch(pp, static_cast<hipStream_t>(stream)));
-  return OFFK_OK;
+  return pw_reduce_site(h, stream, nullptr, OFFK_FEAT_F32, site, feat, G, D, "offk_pw_reduce");
 }
 
 int offk_sobel_tdiff(offk_handle* h, void* stream, int site, const float* G, const float* D, float* M, int m_cstride,
@@ -1157,12 +1230,7 @@ int offk_sobel_tdiff_all(offk_handle* h, void* stream, void* workspace, int algo
 }
 
 int offk_off_units(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace) {
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units: null argument");
-  offk_feat_parts parts[kNumSites];
-  TRY(whole_maps(h, feats, parts, "offk_off_units"));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, h->cfg.feat_layout == OFFK_FEAT_NHWC);
+  return off_units_whole(h, stream, nullptr, OFFK_FEAT_F32, reinterpret_cast<MapPtrs>(feats), workspace, false, 0, 0.0, "offk_off_units");
 }
 
 int offk_off_units_fused(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace) {
@@ -1191,16 +1259,7 @@ int offk_forward_parts(offk_handle* h, void* stream, const offk_feat_parts feats
   return forward_parts(h, stream, feats, out7, out14, out28, workspace, OFFK_FEAT_F32);
 }
 
-// ---- 16-bit NCHW feature maps (offk_forward_typed and its siblings), channels-last feature maps (offk_forward_cl and its siblings) ----
-// What tells the two families apart.  Channels-last: the layout belongs to the call, cfg.feat_layout is not looked at.
-struct FeatKind {
-  const char* noun;      // in the messages
-  bool f32_ok;           // OFFK_FEAT_F32 is one of its dtypes
-  int align;             // of the map pointers, bytes
-  bool cl;               // channels-last parts (else NCHW, and an NHWC handle is refused)
-};
-constexpr FeatKind kKind16{"16-bit", false, 4, false}, kKindCl{"channels-last", true, 16, true};
-
+// ---- 16-bit NCHW feature maps (offk_forward_typed and its siblings), channels-last feature maps (offk_forward_cl and its siblings): FeatKind ----
 // Everything such a call is refused for, checked before anything is enqueued.
 static int check_feat(offk_handle* h, const FeatKind& k, int feat_dtype, const offk_feat_parts parts[], const char* fn) {
   const std::string f(fn), maps = std::string(": ") + k.noun + " feature maps ";
@@ -1600,18 +1659,11 @@ int offk_unit_grad_slot(const offk_handle* h, const char* key, size_t* offset_fl
 
 int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace,
                          uint64_t drop_seed, double drop_p) {
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train: null argument");
-  DropCfg drop;
-  TRY(make_drop(h, drop_seed, drop_p, &drop));
-  offk_feat_parts parts[kNumSites];
-  TRY(whole_maps(h, feats, parts, "offk_off_units_train"));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, h->cfg.feat_layout == OFFK_FEAT_NHWC, drop);
+  return off_units_whole(h, stream, nullptr, OFFK_FEAT_F32, reinterpret_cast<MapPtrs>(feats), workspace, true, drop_seed, drop_p, "offk_off_units_train");
 }
 
-// feat_dtype != OFFK_FEAT_F32: feats[] address 16-bit elements and check_feat16_train has passed; only K1b reads them
-// nhwc: the maps of this call are channels-last (offk_off_units_backward_cl, check_feat_cl_train has passed): K1b's channels-last forms
+// feat_dtype != OFFK_FEAT_F32: feats[] address 16-bit elements; nhwc: the maps of this call are channels-last (offk_off_units_backward_cl).
+// Either way check_feat_train has passed, and only K1b reads the maps.
 static int off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                               const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                               float* grads, int accumulate, int feat_dtype, bool nhwc) {
@@ -1688,159 +1740,74 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
     r.C = w.C; r.cpad = w.ntiles * 128; r.nchunks = w.nchunks; r.nsblocks = nsblocks[s];
   }
   wp.total_blocks = blk;
-  if (nhwc) HIP_TRY(h, pw_wgrad_cl_launch(wp, feat_dtype, st));
-  else if (feat_dtype != OFFK_FEAT_F32) HIP_TRY(h, pw_wgrad_feat16_launch(wp, feat_dtype, st));
-  else HIP_TRY(h, pw_wgrad_launch(wp, st));
+  TRY(launch_k1b(h, st, wp, feat_dtype, nhwc));
   HIP_TRY(h, wgrad_reduce_launch(rp, st));
   return OFFK_OK;
+}
+
+// the common prologue of the three offk_off_units_backward* entries (k == nullptr: the plain one, NCHW handles only)
+static int off_units_backward_kind(offk_handle* h, void* stream, const FeatKind* k, int feat_dtype, MapPtrs feats, const offk_grad_view gm[OFFK_NUM_SITES],
+                                   void* workspace, uint64_t drop_seed, double drop_p, float* grads, int accumulate, const char* fn) {
+  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  if (!k && h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": NCHW feature maps only");
+  if (k) TRY(check_feat_train(h, *k, feat_dtype, feats, 0, kNumSites, fn));
+  return off_units_backward(h, stream, reinterpret_cast<const float* const*>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype,
+                            k && k->cl);
 }
 
 int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                             const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                             float* grads, int accumulate) {
-  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: null argument");
-  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: NCHW feature maps only");
-  return off_units_backward(h, stream, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, OFFK_FEAT_F32, false);
+  return off_units_backward_kind(h, stream, nullptr, OFFK_FEAT_F32, reinterpret_cast<MapPtrs>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate,
+                                 "offk_off_units_backward");
 }
 
-// ---- 16-bit feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_typed and its siblings ----
-// Everything such a call is refused for, checked before anything is enqueued.  Unlike check_feat (the inference forward) there is
-// no condition on the handle's precision, on bound weights or on OFFK_FUSED_UNITS: these entries run the fp32 kernels K1 / K1b.
-static int check_feat16_train(offk_handle* h, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
-  const std::string f(fn);
-  if (feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
-    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
-  if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps are NCHW-only (this handle is NHWC)");
-  for (int i = 0; i < count; ++i) {
-    if (!feats[i]) return fail(h, OFFK_ERR_INVALID, f + ": null feature map");
-    if (reinterpret_cast<uintptr_t>(feats[i]) & 7)
-      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature map pointers must be 8-byte aligned (site " + kSites[first + i].name + ")");
-    if ((unsigned long long)h->N * kSites[first + i].H * kSites[first + i].H * kSites[first + i].C * 2ull >= 0x7fffff00ull)
-      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps of 2 GiB or more are not supported (site " + kSites[first + i].name + ")");
-  }
-  return OFFK_OK;
-}
-
+// ---- 16-bit feature maps on the training side: the _typed entries forward OFFK_FEAT_F32 to the untyped entry ----
 int offk_pw_reduce_typed(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D) {
   if (feat_dtype == OFFK_FEAT_F32) return offk_pw_reduce(h, stream, site, static_cast<const float*>(feat), G, D);
-  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, "offk_pw_reduce_typed: bad argument");
-  TRY(check_feat16_train(h, feat_dtype, &feat, site, 1, "offk_pw_reduce_typed"));
-  TRY(site_weights_ready(h, site, true, false));
-  DeviceGuard guard(h->cfg.device);
-  PwParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
-  pp.nhwc = 0;
-  pp.zeros = h->zero_page;
-  TRY(finalize_pw(h, static_cast<hipStream_t>(stream)));
-  fill_pw_site(h, site, whole_map(site, static_cast<const float*>(feat)), G, D, &pp.s[0]);
-  pp.total_blocks = pw_blocks_for(pp.s[0].M);
-  HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, static_cast<hipStream_t>(stream)));
-  return OFFK_OK;
-}
-
-static int off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
-                           const DropCfg& drop, const char* fn) {
-  TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, fn));
-  offk_feat_parts parts[kNumSites];
-  TRY(whole_maps(h, feats, parts, fn));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, false, drop, feat_dtype);
+  return pw_reduce_site(h, stream, &kKind16, feat_dtype, site, feat, G, D, "offk_pw_reduce_typed");
 }
 
 int offk_off_units_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
   if (feat_dtype == OFFK_FEAT_F32) return offk_off_units(h, stream, reinterpret_cast<const float* const*>(feats), workspace);
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_typed: null argument");
-  return off_units_typed(h, stream, feat_dtype, feats, workspace, DropCfg(), "offk_off_units_typed");
+  return off_units_whole(h, stream, &kKind16, feat_dtype, feats, workspace, false, 0, 0.0, "offk_off_units_typed");
 }
 
 int offk_off_units_train_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
                                uint64_t drop_seed, double drop_p) {
   if (feat_dtype == OFFK_FEAT_F32)
     return offk_off_units_train(h, stream, reinterpret_cast<const float* const*>(feats), workspace, drop_seed, drop_p);
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train_typed: null argument");
-  DropCfg drop;
-  TRY(make_drop(h, drop_seed, drop_p, &drop));
-  return off_units_typed(h, stream, feat_dtype, feats, workspace, drop, "offk_off_units_train_typed");
+  return off_units_whole(h, stream, &kKind16, feat_dtype, feats, workspace, true, drop_seed, drop_p, "offk_off_units_train_typed");
 }
 
 int offk_off_units_backward_typed(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
                                   const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                                   float* grads, int accumulate) {
-  const float* const* f32 = reinterpret_cast<const float* const*>(feats);
-  if (feat_dtype == OFFK_FEAT_F32) return offk_off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate);
-  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward_typed: null argument");
-  TRY(check_feat16_train(h, feat_dtype, feats, 0, kNumSites, "offk_off_units_backward_typed"));
-  return off_units_backward(h, stream, f32, gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype, false);
+  if (feat_dtype == OFFK_FEAT_F32)
+    return offk_off_units_backward(h, stream, reinterpret_cast<const float* const*>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate);
+  return off_units_backward_kind(h, stream, &kKind16, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate,
+                                 "offk_off_units_backward_typed");
 }
 
-// ---- channels-last feature maps on the training side (K1 + K2, K1b): offk_pw_reduce_cl and its siblings ----
-// The layout belongs to the call: cfg.feat_layout is not looked at, and as for the _typed entries above there is no condition on
-// the handle.  Everything such a call is refused for, checked before anything is enqueued.
-static int check_feat_cl_train(offk_handle* h, int feat_dtype, const void* const* feats, int first, int count, const char* fn) {
-  const std::string f(fn);
-  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
-    return fail(h, OFFK_ERR_INVALID, f + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
-  for (int i = 0; i < count; ++i) {
-    if (!feats[i]) return fail(h, OFFK_ERR_INVALID, f + ": null feature map");
-    if (reinterpret_cast<uintptr_t>(feats[i]) & 15)
-      return fail(h, OFFK_ERR_INVALID, f + ": channels-last feature map pointers must be 16-byte aligned (site " + kSites[first + i].name + ")");
-    if (feat_dtype != OFFK_FEAT_F32 &&
-        (unsigned long long)h->N * kSites[first + i].H * kSites[first + i].H * kSites[first + i].C * 2ull >= 0x7fffff00ull)
-      return fail(h, OFFK_ERR_INVALID, f + ": 16-bit feature maps of 2 GiB or more are not supported (site " + kSites[first + i].name + ")");
-  }
-  return OFFK_OK;
-}
-
+// ---- channels-last feature maps on the training side ----
 int offk_pw_reduce_cl(offk_handle* h, void* stream, int feat_dtype, int site, const void* feat, float* G, float* D) {
-  if (!h || site < 0 || site >= kNumSites || !feat || !G || !D) return fail(h, OFFK_ERR_INVALID, "offk_pw_reduce_cl: bad argument");
-  TRY(check_feat_cl_train(h, feat_dtype, &feat, site, 1, "offk_pw_reduce_cl"));
-  TRY(site_weights_ready(h, site, true, false));
-  DeviceGuard guard(h->cfg.device);
-  PwParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.nsites = 1; pp.L = h->cfg.length; pp.P = h->P; pp.slice_mode = h->cfg.slice_mode;
-  pp.nhwc = 1;
-  pp.zeros = h->zero_page;
-  TRY(finalize_pw(h, static_cast<hipStream_t>(stream)));
-  fill_pw_site(h, site, whole_map(site, static_cast<const float*>(feat)), G, D, &pp.s[0]);
-  pp.total_blocks = pw_blocks_for(pp.s[0].M);
-  if (feat_dtype == OFFK_FEAT_F32) HIP_TRY(h, pw_reduce_launch(pp, static_cast<hipStream_t>(stream)));
-  else HIP_TRY(h, pw_reduce_feat16_launch(pp, feat_dtype, static_cast<hipStream_t>(stream)));
-  return OFFK_OK;
-}
-
-static int off_units_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
-                        const DropCfg& drop, const char* fn) {
-  TRY(check_feat_cl_train(h, feat_dtype, feats, 0, kNumSites, fn));
-  offk_feat_parts parts[kNumSites];
-  TRY(whole_maps(h, feats, parts, fn));
-  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
-  DeviceGuard guard(h->cfg.device);
-  return run_off_units(h, static_cast<hipStream_t>(stream), parts, workspace, nullptr, true, drop, feat_dtype);
+  return pw_reduce_site(h, stream, &kKindCl, feat_dtype, site, feat, G, D, "offk_pw_reduce_cl");
 }
 
 int offk_off_units_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace) {
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_cl: null argument");
-  return off_units_cl(h, stream, feat_dtype, feats, workspace, DropCfg(), "offk_off_units_cl");
+  return off_units_whole(h, stream, &kKindCl, feat_dtype, feats, workspace, false, 0, 0.0, "offk_off_units_cl");
 }
 
 int offk_off_units_train_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES], void* workspace,
                             uint64_t drop_seed, double drop_p) {
-  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_off_units_train_cl: null argument");
-  DropCfg drop;
-  TRY(make_drop(h, drop_seed, drop_p, &drop));
-  return off_units_cl(h, stream, feat_dtype, feats, workspace, drop, "offk_off_units_train_cl");
+  return off_units_whole(h, stream, &kKindCl, feat_dtype, feats, workspace, true, drop_seed, drop_p, "offk_off_units_train_cl");
 }
 
 int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
                                const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                                float* grads, int accumulate) {
-  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward_cl: null argument");
-  TRY(check_feat_cl_train(h, feat_dtype, feats, 0, kNumSites, "offk_off_units_backward_cl"));
-  return off_units_backward(h, stream, reinterpret_cast<const float* const*>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate,
-                            feat_dtype, true);
+  return off_units_backward_kind(h, stream, &kKindCl, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate,
+                                 "offk_off_units_backward_cl");
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

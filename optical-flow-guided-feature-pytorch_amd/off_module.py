@@ -109,14 +109,12 @@ class OFFSubNetwork(nn.Module):
         return self._rt
 
     # -- forward ----------------------------------------------------------------------
-    def _as_handed_over(self, rt, feats):
+    def _as_handed_over(self, feats):
         """A channels_last backbone's nine maps on a precision="f32split" module: the handle takes them with no copy
-        (runtime.OffForward.takes_channels_last decides); everything else is made contiguous as ever."""
-        if all(t.is_contiguous() for f in feats for t in ([f] if torch.is_tensor(f) else f)):
-            return False
+        (runtime.feat_route decides); everything else is made contiguous as ever."""
         try:
-            return rt.takes_channels_last(feats)
-        except ValueError:          # a mix of layouts, or an fp32-pipe module: the contiguous copies settle it, as ever
+            return runtime.feat_route(feats, self.batch, self.length, self.feat_layout, self.precision, "infer").route == "cl"
+        except ValueError:          # a mix of layouts or dtypes, an fp32-pipe module: the contiguous copies settle it, as ever
             return False
 
     def forward(self, feats, want28=True):
@@ -130,7 +128,7 @@ class OFFSubNetwork(nn.Module):
         if not first.is_cuda:
             raise runtime._lib.OffkError("OFFSubNetwork has no CPU path: feature maps must live on an MI355X")
         rt = self._handle(first.device)
-        if not self._as_handed_over(rt, feats):
+        if not self._as_handed_over(feats):
             feats = [f.contiguous() if torch.is_tensor(f) else [g.contiguous() for g in f] for f in feats]
         with torch.no_grad():
             return rt.forward(feats, want28=want28)
@@ -264,12 +262,9 @@ class OFFUnits(nn.Module):
     def _as_handed_over(self, feats):
         """Nine channels_last maps of the reference's logical shape and one fp32 / bf16 / fp16 dtype: the _cl training entries take
         them without a copy."""
-        if len(feats) != spec.NUM_SITES or any(not torch.is_tensor(f) for f in feats):
-            return False
-        try:
-            return (runtime.train_feat_layout(feats, self.batch, self.length) == "cl"
-                    and runtime.feat_dtype(feats) in runtime._CL_DTYPES)
-        except ValueError:        # a mix of layouts or dtypes, a wrong shape: the contiguous path and its checks
+        try:                      # (training side: the handle plays no part in the route)
+            return runtime.feat_route(feats, self.batch, self.length, 0, 0, "train").route == "cl"
+        except ValueError:        # a mix of layouts or dtypes, a wrong shape or count: the contiguous path and its checks
             return False
 
     def forward(self, feats, drop_seed=None):

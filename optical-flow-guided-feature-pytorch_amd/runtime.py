@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, the current HIP stream); all arithmetic
 in liboffk's HIP kernels.  Nothing in this file computes on the CPU and nothing falls
 back to torch ops.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -99,27 +100,76 @@ def feat_layout(feats, batch, length):
     return kinds.pop()
 
 
-def train_feat_layout(feats, batch, length):
-    """Where nine maps go on the training side of the units (off_units, off_units_train, off_units_backward): "cl" when every one is a
-    torch.channels_last tensor of the reference's logical shape (the offk_*_cl training entries, maps as they are), else "nchw" (the
-    entries and checks contiguous maps always met).  Works on CPU tensors.  A mix of layouts raises, as feat_layout does.  Unlike
-    OffForward.takes_channels_last there is no condition on the handle: the training side runs the fp32 kernels on either
-    precision, and the layout belongs to the call."""
-    if len(feats) != spec.NUM_SITES:
-        raise ValueError("need nine feature maps")
-    if any(not torch.is_tensor(f) for f in feats) or all(f.is_contiguous() for f in feats):
-        return "nchw"
-    if not any(f.dim() == 4 and f.is_contiguous(memory_format=torch.channels_last) for f in feats):
-        return "nchw"                                  # no channels_last map among them: the contiguity checks name the offender
-    return feat_layout(feats, batch, length)
-
-
 def _check_dev_cl(t, name, device):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype in _CL_DTYPES and t.dim() == 4
             and t.is_contiguous(memory_format=torch.channels_last)):
         raise ValueError("%s must be a channels_last fp32, bf16 or fp16 CUDA/HIP tensor" % name)
     if t.device != device:
         raise ValueError("%s lives on %s, handle on %s" % (name, t.device, device))
+
+
+# ---- where nine maps go: ONE rule for every entry that takes them ("Feature-map kinds") ----
+Route = collections.namedtuple("Route", "route fdt parts")   # "cl" / "typed" / "plain"; enum offk_feat_dtype; any map in channel groups
+# route -> (suffix of the C entry, the check every map pointer passes before the call)
+_KINDS = {"plain": ("", _check_dev), "typed": ("_typed", _check_dev16), "cl": ("_cl", _check_dev_cl)}
+# operation -> the side of the rule it follows; a side is the ladder below with ("infer") or without ("train") conditions on the handle
+_SIDES = {"forward": "infer", "forward_parts": "infer", "off_units_fused": "infer",
+          "off_units": "train", "off_units_train": "train", "off_units_backward": "train", "pw_reduce": "train"}
+# {operation: {route: (entry name, pointer check)}}
+_ENTRIES = {op: {route: ("offk_" + op + sfx, check) for route, (sfx, check) in _KINDS.items()} for op in _SIDES}
+
+
+def _is_channels_last(t):
+    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def _all_channels_last(feats, batch, length, side, split):
+    """The first rung: every map a torch.channels_last tensor of the reference's logical shape.  Mixed layouts raise (feat_layout);
+    whatever else is not this case is False and meets the checks it always met.  The inference side looks into channel groups and
+    needs a split-fp32 handle; the training side has no parts form (a list is not this case) and no condition on the handle."""
+    ts = list(feats) if side == "train" else [t for f in feats for t in ([f] if torch.is_tensor(f) else list(f))]
+    if any(not torch.is_tensor(t) for t in ts) or all(t.is_contiguous() for t in ts) or not any(_is_channels_last(t) for t in ts):
+        return False                                   # no channels_last map among them: the contiguity checks name the offender
+    if feat_layout(feats, batch, length) != "cl":
+        return False
+    if side == "infer" and not split:
+        raise ValueError("feature maps must be contiguous fp32 CUDA/HIP tensors on this handle (the fp32 pipe): channels_last "
+                         "maps need a split-fp32 handle (precision=\"f32split\")")
+    return True
+
+
+def feat_route(feats, batch, length, handle_layout, handle_precision, side):
+    """Route(route, fdt, parts) of nine feature maps (tensors or lists of channel groups); a pure function of dtypes, shapes and
+    strides, so it works on CPU tensors.  side "infer" (forward, off_units_fused) or "train" (off_units, off_units_train,
+    off_units_backward).  The ladder:
+      "cl"     all nine torch.channels_last: the _cl entries, maps as they are.  Inference: on a feat_layout 0 handle only, and a
+               ValueError unless it is split-fp32; training: any handle.
+      "typed"  bf16 / fp16 maps of one dtype: the _typed entries.  Inference: a ValueError unless the handle is split-fp32.
+      "plain"  everything else: the untyped entries and the checks they always made (parts: some map came as channel groups)."""
+    if len(feats) != spec.NUM_SITES:
+        raise ValueError("need nine feature maps")
+    split = handle_precision in (_lib.PRECISION_F32SPLIT, "f32split")      # (the code or its name in _lib.PRECISIONS)
+    parts = any(not torch.is_tensor(f) for f in feats)
+    if (side == "train" or handle_layout == 0) and _all_channels_last(feats, batch, length, side, split):
+        dt = feat_dtype(feats)
+        if dt not in _CL_DTYPES:
+            raise ValueError("channels_last feature maps must be fp32, bf16 or fp16, got %s" % dt)
+        return Route("cl", _CL_DTYPES[dt], parts)
+    if side == "infer" or not parts:                   # (training side, a non-tensor among the nine: _feat_array names the offender)
+        dt = feat_dtype(feats)
+        if dt in _FEAT_DTYPES:
+            if side == "infer" and not split:
+                raise ValueError("bf16 / fp16 feature maps need a split-fp32 handle (precision=\"f32split\"); this one runs the fp32 pipe")
+            return Route("typed", _FEAT_DTYPES[dt], parts)
+    return Route("plain", _lib.FEAT_F32, parts)
+
+
+def train_feat_layout(feats, batch, length):
+    """"cl" where feat_route(side="train") sends nine maps to the offk_*_cl training entries, else "nchw"; the dtype plays no part
+    here.  Works on CPU tensors.  A mix of layouts raises, as feat_layout does."""
+    if len(feats) != spec.NUM_SITES:
+        raise ValueError("need nine feature maps")
+    return "cl" if _all_channels_last(feats, batch, length, "train", True) else "nchw"
 
 
 class OffForward:
@@ -237,54 +287,29 @@ class OffForward:
     def out_rows(self):
         return self.batch if self.consensus else self.P
 
-    def _feat16(self, feats):
-        """enum offk_feat_dtype of 16-bit maps, None for fp32 ones (the untyped entries, exactly as before)."""
-        if len(feats) != spec.NUM_SITES:
-            raise ValueError("need nine feature maps")
-        dt = feat_dtype(feats)
-        if dt not in _FEAT_DTYPES:
-            return None
-        if self.precision != _lib.PRECISION_F32SPLIT:
-            raise ValueError("bf16 / fp16 feature maps need a split-fp32 handle (precision=\"f32split\"); this one runs the fp32 pipe")
-        return _FEAT_DTYPES[dt]
+    def _route(self, feats, side):
+        return feat_route(feats, self.batch, self.length, self.feat_layout, self.precision, side)
 
     def takes_channels_last(self, feats):
-        """True when these nine maps go to the channels-last entries as they are (offk_forward_cl: no copy, no cast): every one a
-        torch.channels_last tensor of the reference's logical shape, on an NCHW-entry (feat_layout 0) split-fp32 handle.  Mixed
-        layouts raise (feat_layout); whatever else is not this case returns False and meets the checks it always met."""
-        if self.feat_layout != 0 or len(feats) != spec.NUM_SITES:
-            return False
-        ts = [t for f in feats for t in ([f] if torch.is_tensor(f) else list(f))]
-        if any(not torch.is_tensor(t) for t in ts) or all(t.is_contiguous() for t in ts):
-            return False
-        if not any(t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) for t in ts):
-            return False
-        if feat_layout(feats, self.batch, self.length) != "cl":
-            return False
-        if self.precision != _lib.PRECISION_F32SPLIT:
-            raise ValueError("feature maps must be contiguous fp32 CUDA/HIP tensors on this handle (the fp32 pipe): channels_last "
-                             "maps need a split-fp32 handle (precision=\"f32split\")")
-        return True
-
-    def _cl_dtype(self, feats):
-        dt = feat_dtype(feats)
-        if dt not in _CL_DTYPES:
-            raise ValueError("channels_last feature maps must be fp32, bf16 or fp16, got %s" % dt)
-        return _CL_DTYPES[dt]
-
-    def _train16(self, feats):
-        """enum offk_feat_dtype of nine bf16 / fp16 maps for the training-side entries (offk_off_units_typed and its siblings), None for
-        fp32 ones.  No condition on the handle's precision here: that one belongs to the inference forward (_feat16)."""
-        if len(feats) != spec.NUM_SITES:
-            raise ValueError("need nine feature maps")
-        if any(not torch.is_tensor(f) for f in feats):
-            return None                                    # _feat_array names the offender
-        return _FEAT_DTYPES.get(feat_dtype(feats))
+        """True when these nine maps go to the channels-last entries as they are (offk_forward_cl: no copy, no cast): the "cl" rung
+        of feat_route's inference side, whatever their dtype."""
+        return (self.feat_layout == 0 and len(feats) == spec.NUM_SITES
+                and _all_channels_last(feats, self.batch, self.length, "infer", self.precision == _lib.PRECISION_F32SPLIT))
 
     def train_takes_channels_last(self, feats):
         """True when these nine maps go to the channels-last training entries as they are (offk_off_units_cl and its siblings: no
         copy, no cast, any handle); see train_feat_layout."""
         return train_feat_layout(feats, self.batch, self.length) == "cl"
+
+    def _call(self, op, r, *args):
+        """offk_<op>, offk_<op>_typed or offk_<op>_cl by the route; args: what follows (h, stream[, feat_dtype])."""
+        head = (self._h, _stream(self.device)) + (() if r.route == "plain" else (r.fdt,))
+        _lib.check(getattr(self.lib, _ENTRIES[op][r.route][0])(*(head + args)), self._h)
+
+    def _units_call(self, op, feats, *tail):
+        """resolve, build the array, call: the entries that take nine whole maps and the workspace"""
+        r = self._route(feats, _SIDES[op])
+        self._call(op, r, self._feat_array(feats, _ENTRIES[op][r.route][1]), _ptr(self.workspace), *tail)
 
     def _feat_array(self, feats, check=_check_dev):
         if len(feats) != spec.NUM_SITES:
@@ -332,48 +357,21 @@ class OffForward:
         out: the caller's (out7, out14, out28) instead of fresh tensors (out28 None: no 28 head).
         torch.channels_last maps of any of the three dtypes (all nine, logical shape as ever) are taken as they are on a split-fp32
         handle (offk_forward_cl) and give the values of their contiguous copies."""
-        kw = {} if out is None else {"out": out}       # (the default call reaches the two forms below exactly as it always did)
-        if self.takes_channels_last(feats):
-            return self._forward_cl(feats, want28, **kw)
-        fdt = self._feat16(feats)
-        if fdt is not None:
-            return self._forward16(feats, fdt, want28, **kw)
-        if any(not torch.is_tensor(f) for f in feats):
-            arr = self._parts_array(feats)
-            out7, out14, out28 = self._outs(out, want28)
-            _lib.check(self.lib.offk_forward_parts(self._h, _stream(self.device), arr, _ptr(out7), _ptr(out14), _ptr(out28),
-                                                   _ptr(self.workspace)), self._h)
-            return out7, out14, out28
-        arr = self._feat_array(feats)
-        out7, out14, out28 = self._outs(out, want28)
-        _lib.check(self.lib.offk_forward(self._h, _stream(self.device), arr, _ptr(out7), _ptr(out14), _ptr(out28),
-                                         _ptr(self.workspace)), self._h)
-        return out7, out14, out28
+        r = self._route(feats, "infer")
+        if r.route == "cl":
+            return self._forward_cl(feats, want28, **({} if out is None else {"out": out}))
+        return self._forward(feats, want28, out, r)
 
-    def _forward16(self, feats, fdt, want28, out=None):
+    def _forward(self, feats, want28, out, r):
+        op = "forward_parts" if r.parts else "forward"
+        arr = (self._parts_array if r.parts else self._feat_array)(feats, _ENTRIES[op][r.route][1])
         out7, out14, out28 = self._outs(out, want28)
-        if any(not torch.is_tensor(f) for f in feats):
-            arr = self._parts_array(feats, _check_dev16)
-            _lib.check(self.lib.offk_forward_parts_typed(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14),
-                                                         _ptr(out28), _ptr(self.workspace)), self._h)
-        else:
-            arr = self._feat_array(feats, _check_dev16)
-            _lib.check(self.lib.offk_forward_typed(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
-                                                   _ptr(self.workspace)), self._h)
+        self._call(op, r, arr, _ptr(out7), _ptr(out14), _ptr(out28), _ptr(self.workspace))
         return out7, out14, out28
 
     def _forward_cl(self, feats, want28, out=None):
-        fdt = self._cl_dtype(feats)
-        out7, out14, out28 = self._outs(out, want28)
-        if any(not torch.is_tensor(f) for f in feats):
-            arr = self._parts_array(feats, _check_dev_cl)
-            _lib.check(self.lib.offk_forward_parts_cl(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
-                                                      _ptr(self.workspace)), self._h)
-        else:
-            arr = self._feat_array(feats, _check_dev_cl)
-            _lib.check(self.lib.offk_forward_cl(self._h, _stream(self.device), fdt, arr, _ptr(out7), _ptr(out14), _ptr(out28),
-                                                _ptr(self.workspace)), self._h)
-        return out7, out14, out28
+        """forward() of nine channels_last maps, under a name of its own: what the mirror class's test hooks to see them arrive"""
+        return self._forward(feats, want28, out, self._route(feats, "infer"))
 
     def forward_into(self, feat_array, out7, out14, out28):
         """Launch-only variant for benchmarking: pre-validated ctypes array + outputs."""
@@ -384,33 +382,12 @@ class OffForward:
         """K1 + K2 into the workspace.  feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (offk_off_units_typed: the values
         of the same maps upcast, on any handle).  Nine torch.channels_last maps of any of the three dtypes are taken as they are
         (offk_off_units_cl, any handle) and give the values of their contiguous copies."""
-        if self.train_takes_channels_last(feats):
-            arr = self._feat_array(feats, _check_dev_cl)
-            _lib.check(self.lib.offk_off_units_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace)), self._h)
-            return
-        fdt = self._train16(feats)
-        if fdt is not None:
-            arr = self._feat_array(feats, _check_dev16)
-            _lib.check(self.lib.offk_off_units_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace)), self._h)
-            return
-        arr = self._feat_array(feats)
-        _lib.check(self.lib.offk_off_units(self._h, _stream(self.device), arr, _ptr(self.workspace)), self._h)
+        self._units_call("off_units", feats)
 
     def off_units_fused(self, feats):
         """The units as forward() runs them (fused K1T + S-blocks, the handle's arithmetic); results in the fusion_* / D_* regions.
         bf16 / fp16 maps (split-fp32 handles): offk_off_units_fused_typed; torch.channels_last maps: offk_off_units_fused_cl."""
-        if self.takes_channels_last(feats):
-            arr = self._feat_array(feats, _check_dev_cl)
-            _lib.check(self.lib.offk_off_units_fused_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace)),
-                       self._h)
-            return
-        fdt = self._feat16(feats)
-        if fdt is not None:
-            arr = self._feat_array(feats, _check_dev16)
-            _lib.check(self.lib.offk_off_units_fused_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace)), self._h)
-            return
-        arr = self._feat_array(feats)
-        _lib.check(self.lib.offk_off_units_fused(self._h, _stream(self.device), arr, _ptr(self.workspace)), self._h)
+        self._units_call("off_units_fused", feats)
 
     # ---- training side of the units (SURVEY.md 8(f) rank 4) ----------------------------
     def off_units_train(self, feats, drop_seed=0, drop_p=0.8):
@@ -418,20 +395,7 @@ class OffForward:
         reproducible mask of synth.dropout_keep; leaves G/D in the workspace for off_units_backward.
         bf16 / fp16 maps of one dtype are taken as they are (offk_off_units_train_typed), and so are nine torch.channels_last maps
         of any of the three dtypes (offk_off_units_train_cl)."""
-        if self.train_takes_channels_last(feats):
-            arr = self._feat_array(feats, _check_dev_cl)
-            _lib.check(self.lib.offk_off_units_train_cl(self._h, _stream(self.device), self._cl_dtype(feats), arr, _ptr(self.workspace),
-                                                        ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
-            return
-        fdt = self._train16(feats)
-        if fdt is not None:
-            arr = self._feat_array(feats, _check_dev16)
-            _lib.check(self.lib.offk_off_units_train_typed(self._h, _stream(self.device), fdt, arr, _ptr(self.workspace),
-                                                           ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
-            return
-        arr = self._feat_array(feats)
-        _lib.check(self.lib.offk_off_units_train(self._h, _stream(self.device), arr, _ptr(self.workspace),
-                                                 ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
+        self._units_call("off_units_train", feats, ctypes.c_uint64(int(drop_seed)), float(drop_p))
 
     def unit_grad_slots(self):
         """OrderedDict key -> (offset, shape) of every unit parameter in the flat gradient buffer."""
@@ -459,9 +423,8 @@ class OffForward:
         Returns (flat grads tensor, dict key -> view in the reference's parameter shape)."""
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
-        cl = self.train_takes_channels_last(feats)
-        fdt = self._cl_dtype(feats) if cl else self._train16(feats)
-        arr = self._feat_array(feats, _check_dev_cl if cl else (_check_dev16 if fdt is not None else _check_dev))
+        r = self._route(feats, "train")
+        arr = self._feat_array(feats, _ENTRIES["off_units_backward"][r.route][1])
         gv = (_lib.OffkGradView * spec.NUM_SITES)()
         for i, ((t, coff), (_n, _c, H)) in enumerate(zip(grad_views, spec.SITES)):
             _check_dev(t, "grad_views[%d]" % i, self.device)
@@ -471,18 +434,8 @@ class OffForward:
         if grads is None:
             grads = self.new_unit_grads()
         _check_dev(grads, "grads", self.device)
-        if cl:
-            _lib.check(self.lib.offk_off_units_backward_cl(self._h, _stream(self.device), fdt, arr, gv, _ptr(self.workspace),
-                                                           ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
-                                                           int(bool(accumulate))), self._h)
-        elif fdt is not None:
-            _lib.check(self.lib.offk_off_units_backward_typed(self._h, _stream(self.device), fdt, arr, gv, _ptr(self.workspace),
-                                                              ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
-                                                              int(bool(accumulate))), self._h)
-        else:
-            _lib.check(self.lib.offk_off_units_backward(self._h, _stream(self.device), arr, gv, _ptr(self.workspace),
-                                                        ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
-                                                        int(bool(accumulate))), self._h)
+        self._call("off_units_backward", r, arr, gv, _ptr(self.workspace), ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
+                   int(bool(accumulate)))
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
 
@@ -493,21 +446,12 @@ class OffForward:
         _name, C, H = spec.SITES[site]
         G = _given(G, (self.N * H * H, spec.GEN_CH), "G", self.device)
         D = _given(D, (self.P * H * H, spec.DOWN_CH), "D", self.device)
-        if (torch.is_tensor(feat) and feat.dim() == 4 and not feat.is_contiguous()
-                and feat.is_contiguous(memory_format=torch.channels_last)):      # channels_last map: offk_pw_reduce_cl
-            _check_dev_cl(feat, "feat", self.device)
-            if tuple(feat.shape) != (self.N, C, H, H):
-                raise ValueError("feat is channels_last with logical shape %s, expected %s" % (tuple(feat.shape), (self.N, C, H, H)))
-            _lib.check(self.lib.offk_pw_reduce_cl(self._h, _stream(self.device), _CL_DTYPES[feat.dtype], site, _ptr(feat),
-                                                  _ptr(G), _ptr(D)), self._h)
-            return G, D
-        if torch.is_tensor(feat) and feat.dtype in _FEAT_DTYPES:      # bf16 / fp16 map: offk_pw_reduce_typed
-            _check_dev16(feat, "feat", self.device)
-            _lib.check(self.lib.offk_pw_reduce_typed(self._h, _stream(self.device), _FEAT_DTYPES[feat.dtype], site, _ptr(feat),
-                                                     _ptr(G), _ptr(D)), self._h)
-            return G, D
-        _check_dev(feat, "feat", self.device)
-        _lib.check(self.lib.offk_pw_reduce(self._h, _stream(self.device), site, _ptr(feat), _ptr(G), _ptr(D)), self._h)
+        tensor = torch.is_tensor(feat)                 # one map: the ladder of feat_route's training side on it alone
+        route = "cl" if tensor and not feat.is_contiguous() and _is_channels_last(feat) else "typed" if tensor and feat.dtype in _FEAT_DTYPES else "plain"
+        _ENTRIES["pw_reduce"][route][1](feat, "feat", self.device)
+        if route == "cl" and tuple(feat.shape) != (self.N, C, H, H):
+            raise ValueError("feat is channels_last with logical shape %s, expected %s" % (tuple(feat.shape), (self.N, C, H, H)))
+        self._call("pw_reduce", Route(route, _CL_DTYPES.get(feat.dtype), False), site, _ptr(feat), _ptr(G), _ptr(D))
         return G, D
 
     def sobel_tdiff(self, site, G, D, M, m_coff, algo=0):

@@ -55,6 +55,7 @@ import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
 from .arena import SENTINEL, Arena, bits, same_bits
+from .featmaps import DTYPES
 from .test_gpu_parity import HANDLE_PRECISIONS, rt  # noqa: F401
 from .test_gpu_paths import forced_handle
 from .test_gpu_split import _chain_inputs
@@ -64,7 +65,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2), (3, 3)]      # one pair, 49-row 7x7 sites; P = 6: 294 rows at 7x7 -- partial against 16-, 32-, 96- and 128-row tiles
 VARIANTS = [spec.VARIANT_RGB, spec.VARIANT_FLOW]
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 # unit channels (9 x [S 32 | T 128]) of the three fusion buffers: (region, channels per pixel, unit channels)
 FUSION = (("fusion_28", 320, 320), ("fusion_14", 1056, 800), ("fusion_7", 832, 320))
 PATHS = {"default": {}, "unfused_units": {"OFFK_FUSED_UNITS": "0"}, "direct_convs": {"OFFK_WINOGRAD": "0", "OFFK_CHAIN": "0"},

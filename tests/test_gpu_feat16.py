@@ -9,71 +9,12 @@ import torch
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
+from .featmaps import (  # noqa: F401
+    bit_maps, heavy_maps, relu_maps, rt, unit_regions, make_handle)
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, consensus=None, precision="f32split", **kw):
-    h = rt.OffForward(B, L, variant, slice_mode, consensus, precision=precision, **kw)
-    assert h.load_state_dict(synth.make_weights(variant)) == []
-    return h
-
-
-def relu_maps(B, L, dtype, seed):
-    """ReLU-like synthetic maps, made on the device and rounded to `dtype`."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.relu(torch.randn(B * L, C, H, H, device="cuda", generator=g)).to(dtype).contiguous() for _, C, H in spec.SITES]
-
-
-def bit_maps(B, L, dtype, seed, full_mantissa=False):
-    """Random finite 16-bit patterns: both signs, every mantissa bit in play (or all set), exponents from the subnormals
-    (exponent field 0) up to 2^10 (fp16) / 2^10 (bf16, from 2^-27)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = []
-    for _, C, H in spec.SITES:
-        n = B * L * C * H * H
-        r = torch.randint(0, 1 << 30, (n,), device="cuda", generator=g, dtype=torch.int64)
-        sign = (r & 1) << 15
-        if dtype == torch.float16:
-            mant = torch.full_like(r, 0x3ff) if full_mantissa else (r >> 1) & 0x3ff
-            e = (r >> 11) % 26                                        # 0 (subnormal) .. 25 (2^10)
-            bits = sign | (e << 10) | mant
-        else:
-            mant = torch.full_like(r, 0x7f) if full_mantissa else (r >> 1) & 0x7f
-            e = (r >> 11) % 38
-            e = torch.where(e == 0, e, e + 100)                       # 0 (subnormal) or 101 .. 137
-            bits = sign | (e << 7) | mant
-        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
-        out.append(bits.to(torch.int16).view(dtype).view(B * L, C, H, H).contiguous())
-    return out
-
-
-def heavy_maps(B, L, dtype, seed):
-    """Heavy-tailed maps within fp16's range (expm1 of a scaled normal, up to ~1e4)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.expm1(1.5 * torch.randn(B * L, C, H, H, device="cuda", generator=g)).clamp(max=3e4).to(dtype).contiguous()
-            for _, C, H in spec.SITES]
-
-
-def unit_regions(h):
-    """Copies of what the units write: the 160 unit channels of every site in its fusion buffer, and D_<site>."""
-    P = h.P
-    out = []
-    for fkey, fd in spec.FUSION.items():
-        width = 160 * len(fd["sites"]) + fd["carry"]
-        buf = h.region("fusion_" + fkey, width).view(P, fd["H"], fd["H"], width)
-        for i, sname in enumerate(fd["sites"]):
-            out.append(buf[..., 160 * i:160 * i + 160].clone())
-            out.append(h.region("D_" + sname, 32).clone())
-    return out
 
 
 def units_equal(h, x16):

@@ -9,18 +9,14 @@ import torch
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
+from .featmaps import (  # noqa: F401
+    bit_maps, bit_maps32, heavy_maps, relu_maps, rt, unit_regions, make_handle)
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 FDT = {"f32": _lib.FEAT_F32, "bf16": _lib.FEAT_BF16, "f16": _lib.FEAT_F16}
 RTOL = 2e-4                                            # tests/test_gpu_parity.py's, of the tensor's max magnitude
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 def to_cl(x):
@@ -29,80 +25,6 @@ def to_cl(x):
 
 def to_nchw(x):
     return x.contiguous()
-
-
-def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, consensus=None, precision="f32split", **kw):
-    h = rt.OffForward(B, L, variant, slice_mode, consensus, precision=precision, **kw)
-    assert h.load_state_dict(synth.make_weights(variant)) == []
-    return h
-
-
-def relu_maps(B, L, dtype, seed):
-    """ReLU-like synthetic maps, made on the device and rounded to `dtype`."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.relu(torch.randn(B * L, C, H, H, device="cuda", generator=g)).to(dtype).contiguous() for _, C, H in spec.SITES]
-
-
-def bit_maps(B, L, dtype, seed, full_mantissa=False):
-    """Random finite 16-bit patterns: both signs, every mantissa bit in play (or all set), exponents from the subnormals
-    (exponent field 0) up to 2^10 (fp16) / 2^10 (bf16, from 2^-27)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = []
-    for _, C, H in spec.SITES:
-        n = B * L * C * H * H
-        r = torch.randint(0, 1 << 30, (n,), device="cuda", generator=g, dtype=torch.int64)
-        sign = (r & 1) << 15
-        if dtype == torch.float16:
-            mant = torch.full_like(r, 0x3ff) if full_mantissa else (r >> 1) & 0x3ff
-            e = (r >> 11) % 26                                        # 0 (subnormal) .. 25 (2^10)
-            bits = sign | (e << 10) | mant
-        else:
-            mant = torch.full_like(r, 0x7f) if full_mantissa else (r >> 1) & 0x7f
-            e = (r >> 11) % 38
-            e = torch.where(e == 0, e, e + 100)                       # 0 (subnormal) or 101 .. 137
-            bits = sign | (e << 7) | mant
-        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
-        out.append(bits.to(torch.int16).view(dtype).view(B * L, C, H, H).contiguous())
-    return out
-
-
-def bit_maps32(B, L, seed, full_mantissa=False):
-    """Random finite fp32 patterns: both signs, all 23 mantissa bits in play (or all set), exponents over +-30 octaves around 1, and
-    one value in eight below 2^-109 (exponent fields 0 .. 17, the subnormals among them): there the lower planes of the cut run
-    into the subnormals."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = []
-    for _, C, H in spec.SITES:
-        n = B * L * C * H * H
-        r = torch.randint(0, 1 << 62, (n,), device="cuda", generator=g, dtype=torch.int64)
-        sign = (r & 1) << 31
-        mant = torch.full_like(r, 0x7fffff) if full_mantissa else (r >> 1) & 0x7fffff
-        e = 97 + (r >> 24) % 61                                       # 2^-30 .. 2^30
-        e = torch.where((r >> 32) % 8 == 0, (r >> 36) % 18, e)        # 0 (subnormal) .. 17 (2^-110)
-        bits = sign | (e << 23) | mant
-        bits = torch.where(bits >= 1 << 31, bits - (1 << 32), bits)
-        out.append(bits.to(torch.int32).view(torch.float32).view(B * L, C, H, H).contiguous())
-    return out
-
-
-def heavy_maps(B, L, dtype, seed):
-    """Heavy-tailed maps within fp16's range (expm1 of a scaled normal, up to ~1e4)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.expm1(1.5 * torch.randn(B * L, C, H, H, device="cuda", generator=g)).clamp(max=3e4).to(dtype).contiguous()
-            for _, C, H in spec.SITES]
-
-
-def unit_regions(h):
-    """Copies of what the units write: the 160 unit channels of every site in its fusion buffer, and D_<site>."""
-    P = h.P
-    out = []
-    for fkey, fd in spec.FUSION.items():
-        width = 160 * len(fd["sites"]) + fd["carry"]
-        buf = h.region("fusion_" + fkey, width).view(P, fd["H"], fd["H"], width)
-        for i, sname in enumerate(fd["sites"]):
-            out.append(buf[..., 160 * i:160 * i + 160].clone())
-            out.append(h.region("D_" + sname, 32).clone())
-    return out
 
 
 def units_equal(h, x):

@@ -4,7 +4,6 @@ csrc/units_bwd.hip).  The contract is equality, not a tolerance: everything a _c
 fusion buffers, the flat gradient buffer -- is torch.equal to what the NCHW call of the same dtype writes from the contiguous
 copies of the same logical tensors (include/offk.h).  All inputs here are finite, so no case is left out of the equality."""
 import ctypes
-import functools
 
 import pytest
 import torch
@@ -13,27 +12,17 @@ import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 from oracle import off_oracle as orc
 
+from .featmaps import (  # noqa: F401
+    DROP_P, DROP_SEED, _units_node, cotangents, device_relu_masks, grad_views, maps_of_kind, oracle_dm, rel_err,
+    relu_maps, rt, run_units, unit_drop, written, make_train_handle as make_handle)
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 VARIANTS = {"rgb": spec.VARIANT_RGB, "flow": spec.VARIANT_FLOW}
 SHAPES = [(1, 2), (2, 3), (3, 4), (5, 7), (2, 9)]
 RTOL = 2e-4          # tests/test_gpu_backward.py's bound for the fp32 path against the oracle
-DROP_SEED, DROP_P = 7, 0.8
 CLAST = torch.channels_last
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, precision="fp32", **kw):
-    h = rt.OffForward(B, L, variant, slice_mode, precision=precision, training=True, **kw)
-    assert h.load_state_dict(synth.make_weights(variant)) == []
-    return h
 
 
 def to_cl(xs):
@@ -41,88 +30,6 @@ def to_cl(xs):
     out = [x.contiguous(memory_format=CLAST) for x in xs]
     assert all(not c.is_contiguous() and c.is_contiguous(memory_format=CLAST) and torch.equal(c, x) for c, x in zip(out, xs))
     return out
-
-
-# ---- inputs (the generators of tests/test_gpu_feat16_train.py, repeated here: test files do not import each other; the fp32
-#      forms of the bit-pattern kinds are the 16-bit patterns widened, plus low mantissa bits of their own) ----
-
-def relu_maps(B, L, dtype, seed):
-    """ReLU-like synthetic maps, made on the device and rounded to `dtype`."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.relu(torch.randn(B * L, C, H, H, device="cuda", generator=g)).to(dtype).contiguous() for _, C, H in spec.SITES]
-
-
-def bit_maps(B, L, dtype, seed, full_mantissa=False):
-    """Random finite bit patterns: both signs, every mantissa bit in play (or all set), exponents from the subnormals
-    (exponent field 0) up to 2^10.  fp32: bf16's sign / exponent / upper mantissa with sixteen more mantissa bits below."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = []
-    for _, C, H in spec.SITES:
-        n = B * L * C * H * H
-        r = torch.randint(0, 1 << 30, (n,), device="cuda", generator=g, dtype=torch.int64)
-        sign = (r & 1) << 15
-        if dtype == torch.float16:
-            mant = torch.full_like(r, 0x3ff) if full_mantissa else (r >> 1) & 0x3ff
-            e = (r >> 11) % 26                                        # 0 (subnormal) .. 25 (2^10)
-            bits = sign | (e << 10) | mant
-        else:
-            mant = torch.full_like(r, 0x7f) if full_mantissa else (r >> 1) & 0x7f
-            e = (r >> 11) % 38
-            e = torch.where(e == 0, e, e + 100)                       # 0 (subnormal) or 101 .. 137
-            bits = sign | (e << 7) | mant
-        if dtype == torch.float32:
-            low = torch.full_like(r, 0xffff) if full_mantissa else (r >> 14) & 0xffff
-            bits = (bits << 16) | low
-            bits = torch.where(bits >= 1 << 31, bits - (1 << 32), bits)
-            out.append(bits.to(torch.int32).view(torch.float32).view(B * L, C, H, H).contiguous())
-            continue
-        bits = torch.where(bits >= 1 << 15, bits - (1 << 16), bits)
-        out.append(bits.to(torch.int16).view(dtype).view(B * L, C, H, H).contiguous())
-    return out
-
-
-def heavy_maps(B, L, dtype, seed):
-    """Heavy-tailed maps within fp16's range (expm1 of a scaled normal, up to ~1e4)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    return [torch.expm1(1.5 * torch.randn(B * L, C, H, H, device="cuda", generator=g)).clamp(max=3e4).to(dtype).contiguous()
-            for _, C, H in spec.SITES]
-
-
-def maps_of_kind(kind, B, L, dtype, seed):
-    if kind == "relu":
-        return relu_maps(B, L, dtype, seed)
-    if kind == "heavy_tail":
-        return heavy_maps(B, L, dtype, seed)
-    x = bit_maps(B, L, dtype, seed, full_mantissa=kind == "full_mantissa")
-    if kind == "random_bits":                                   # the generator does reach the type's subnormals
-        tiny = 2.0 ** -14 if dtype == torch.float16 else 2.0 ** -126
-        assert any(bool(((t.float().abs() < tiny) & (t.float() != 0)).any()) for t in x)
-    return x
-
-
-# ---- what the calls write ----
-
-def written(h):
-    """Copies of everything K1 + K2 write: G_<site> and D_<site> of every site, and its 160 unit channels in the fusion buffer."""
-    P = h.P
-    out = []
-    for fkey, fd in spec.FUSION.items():
-        width = 160 * len(fd["sites"]) + fd["carry"]
-        buf = h.region("fusion_" + fkey, width).view(P, fd["H"], fd["H"], width)
-        for i, sname in enumerate(fd["sites"]):
-            out.append(("unit_" + sname, buf[..., 160 * i:160 * i + 160].clone()))
-            out.append(("G_" + sname, h.region("G_" + sname, 128).clone()))
-            out.append(("D_" + sname, h.region("D_" + sname, 32).clone()))
-    return out
-
-
-def run_units(h, x, train):
-    h.workspace.fill_(0xff)                            # (NaN in every float: what the units leave unwritten shows)
-    if train:
-        h.off_units_train(x, DROP_SEED, DROP_P)
-    else:
-        h.off_units(x)
-    return written(h)
 
 
 def assert_forward_equal(h, x):
@@ -136,39 +43,6 @@ def assert_forward_equal(h, x):
         for (name, a), (_n, b) in zip(got, ref):
             assert a.dtype == torch.float32 and torch.isfinite(a).all(), (name, train)
             assert torch.equal(a, b), (name, train)
-
-
-def cotangents(P):
-    return [torch.from_numpy(synth.uniform_values(0xC07 + i, P * spec.NUM_CLASSES, 1.0).reshape(P, spec.NUM_CLASSES))
-            for i in range(3)]
-
-
-def unit_drop(seed, P, p=DROP_P):
-    return [torch.from_numpy(synth.dropout_keep(seed, si, P, H, p)).float() / (1.0 - p)
-            for si, (_n, _c, H) in enumerate(spec.SITES)]
-
-
-def grad_views(dm):
-    """nine [P,160,H,H] -> the three fusion-buffer gradients, channels-last, + per-site (tensor, coff)."""
-    groups = ((0, 1), (2, 3, 4, 5, 6), (7, 8))
-    views = [None] * spec.NUM_SITES
-    for grp in groups:
-        buf = torch.cat([dm[i] for i in grp], dim=1).permute(0, 2, 3, 1).contiguous().cuda()
-        for k, i in enumerate(grp):
-            views[i] = (buf, 160 * k)
-    return views
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_dm(variant, B, L, slice_mode):
-    """dM as tests/test_gpu_backward.py makes it: the head cotangents of cotangents(P) taken back through the oracle's fusion
-    stages (on the synthetic fp32 maps; the equality below holds for any dM, so it need not belong to the maps under test).
-    Computed once per configuration and shared by every test that needs it."""
-    w = orc.to_torch_weights(synth.make_weights(variant))
-    tf = [torch.from_numpy(f) for f in synth.make_features(B, L, 9)]
-    P = B * (L - 1)
-    _g, dm = orc.unit_backward(tf, w, B, L, variant, slice_mode, cotangents(P), unit_drop(DROP_SEED, P), None)
-    return [d.detach() for d in dm]
 
 
 def assert_backward_equal(h, x, views):
@@ -242,28 +116,6 @@ def test_input_kinds(rt, name, kind):
 
 # ---- 4. an anchor that does not pass through the NCHW kernels ----
 
-def rel_err(got, ref):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    return float((got - ref).abs().max() / max(float(ref.abs().max()), 1e-30))
-
-
-def device_relu_masks(h, feats_cpu, w, B, L, slack=1e-5):
-    """The ReLU decisions the device took (saved G > 0), after checking that they differ from the oracle's own only for
-    pre-activations within rounding distance of zero (as tests/test_gpu_backward.py)."""
-    masks = []
-    for (site, _c, H), x in zip(spec.SITES, feats_cpu):
-        G = h.region("G_" + site, 128).view(B * L, H * H, 128).permute(0, 2, 1).reshape(B * L, 128, H, H).cpu()
-        with torch.no_grad():
-            pre = torch.nn.functional.conv2d(x, w["motion_conv_gen_%s.weight" % site], w["motion_conv_gen_%s.bias" % site])
-        mask = (G > 0)
-        flip = mask != (pre > 0)
-        assert int(flip.sum()) <= 5 + slack * flip.numel(), site
-        if flip.any():
-            assert float(pre[flip].abs().max()) < slack * max(1.0, float(pre.abs().max())), site
-        masks.append(mask.float())
-    return masks
-
-
 @pytest.mark.parametrize("name", ["bf16", "f16"])
 @pytest.mark.parametrize("variant,seed", [("rgb", DROP_SEED), ("flow", None)])
 def test_backward_channels_last_maps_vs_oracle(rt, name, variant, seed):
@@ -302,15 +154,6 @@ class ToyBackbone(torch.nn.Module):
     def forward(self, x):
         return [torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous(memory_format=CLAST)
                 for (_, _C, H), conv in zip(spec.SITES, self.convs)]
-
-
-def _units_node(out):
-    """The autograd node of OFFUnits behind one of its outputs (the object the forward stored its ctx attributes on)."""
-    node = out.grad_fn
-    while node is not None and not hasattr(node, "feats"):
-        node = node.next_functions[0][0]
-    assert node is not None
-    return node
 
 
 @pytest.mark.parametrize("name", ["none", "bf16", "f16"])
