@@ -17,6 +17,27 @@ using namespace offk;
 
 typedef const void* const* MapPtrs;      // nine maps of any element type, as the _typed / _cl entries take them
 
+// A path switch of the library (the list: offk_create): unset or anything else = on, "0" = off, an integer n > 1 = on from n frame
+// pairs (*min_p = n; left alone otherwise).
+static bool path_switch(const char* name, int* min_p = nullptr) {
+  const char* e = getenv(name);
+  if (e && min_p && atoi(e) > 1) *min_p = atoi(e);
+  return !(e && *e == '0');
+}
+
+// One conv launch: views, weights and plan (the last five: ConvDesc's own defaults); the batched / grouped / pooling fields are the caller's.
+static ConvDesc conv_desc(const float* x, int x_cs, int x_coff, int n_img, int H, int W, int Ci, const float* w, const float* bias, int Co, int KH,
+                          int KW, int stride, int pad, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff,
+                          int tile_cfg = -1, int splitk = 0, float* partial = nullptr, size_t partial_floats = 0, int precision = 0) {
+  ConvDesc d;
+  d.x = x; d.x_cs = x_cs; d.x_coff = x_coff; d.n_img = n_img; d.H = H; d.W = W; d.Ci = Ci;
+  d.w = w; d.bias = bias; d.Co = Co; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad;
+  d.res = res; d.res_cs = res_cs; d.res_coff = res_coff; d.flags = flags;
+  d.y = y; d.y_cs = y_cs; d.y_coff = y_coff;
+  d.tile_cfg = tile_cfg; d.splitk = splitk; d.partial = partial; d.partial_floats = partial_floats; d.precision = precision;
+  return d;
+}
+
 // The batched GEMMs of a conv on a Winograd path (M[point] = V[point] . U[point]^T): one persistent launch of wino_gemm_kernel
 // (wino_gemm.hip), or -- persistent == false, OFFK_WINO_GEMM=0 -- gridDim.y problems of the generic 1x1 kernel (conv_igemm.hip, 64 x 64
 // LDS-DMA tile).  Bit-identical.  grp / ngrp: winograd.hip's wino_groups / winograd7.hip's wino7_groups; rows = rows of every V[point].
@@ -35,12 +56,7 @@ static hipError_t wino_gemms_launch(const WinoGroup* grp, int ngrp, int npoints,
     // a shape the persistent kernel does not take: the generic one
   }
   const int K0 = grp[0].kmul * Ci;
-  ConvDesc d;
-  d.x = V; d.x_cs = K0; d.x_coff = 0; d.n_img = rows; d.H = 1; d.W = 1; d.Ci = K0;
-  d.w = U; d.bias = nullptr; d.Co = Co; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0;
-  d.res = nullptr; d.res_cs = 0; d.res_coff = 0; d.flags = 0;
-  d.y = M; d.y_cs = Co; d.y_coff = 0;
-  d.tile_cfg = 3; d.splitk = 1; d.precision = 0;
+  ConvDesc d = conv_desc(V, K0, 0, rows, 1, 1, K0, U, nullptr, Co, 1, 1, 1, 0, nullptr, 0, 0, 0, M, Co, 0, 3, 1);
 #ifdef OFFK_TUNING_KNOBS
   { const char* e = getenv("OFFK_WINO_CFG"); if (e && (Co % 128 == 0 || atoi(e) == 1 || atoi(e) == 2)) d.tile_cfg = atoi(e); }     // tools: one tile for every Winograd GEMM launch
 #endif
@@ -56,7 +72,7 @@ static hipError_t wino_gemms_launch(const WinoGroup* grp, int ngrp, int npoints,
 }
 // stage entry points have no handle: OFFK_WINO_GEMM is read once per process for them (offk_create reads it per handle)
 static bool wino_gemm_stage_default() {
-  static const bool on = [] { const char* e = getenv("OFFK_WINO_GEMM"); return !(e && *e == '0'); }();
+  static const bool on = path_switch("OFFK_WINO_GEMM");
   return on;
 }
 
@@ -129,6 +145,19 @@ struct Slot {
   bool set = false;
 };
 
+// What is derived from the weights of one fusion conv (slot kNumConvs + m: of merged conv m); kDerived below names every image, where it
+// exists, how large it is and how it is packed.  The plane images (6 bytes per element) are those of split-fp32 handles.
+struct Derived {
+  float* u = nullptr;            // transformed weights of the conv on its Winograd path
+  float* u_planes = nullptr;     // the plane image of u (wino_gemm_split.hip); nullptr: fp32 GEMMs
+  float* u2 = nullptr;           // F(2x2, 3x3) weights [16][64][64] of a chain's 3x3 conv (chain_fused.hip, OFFK_CHAIN_WINO)
+  float* planes = nullptr;       // the plane image of the [Co][K] weights for the fused kernel that runs the conv: chain_split.hip (c1 / c2 in
+                                 // the packed K order / c3 / the branch of chain 28a), wino_mid.hip (its 1x1 conv)
+  float* gemm_planes = nullptr;  // ... for the conv as a launch of its own on wino_gemm_split.hip's kernel with its conv epilogue
+};
+constexpr int kNumDerived = kNumConvs + 3;
+constexpr int merged_slot(int m) { return kNumConvs + m; }
+
 thread_local std::string g_err;
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -145,7 +174,9 @@ struct offk_handle {
   float* pw_wt16[kNumSites] = {};   // the same matrix in the operand order of the fused units kernel's 16-pixel form (fp32)
   float* pw_wt16s[kNumSites] = {};  // ... as three bf16 planes for the split-fp32 form (OFFK_PRECISION_F32SPLIT; 1.5 x the floats)
   bool split_gemm = false;          // a split-fp32 handle runs the Winograd GEMMs with Co % 128 == 0 in split-fp32 too (OFFK_SPLIT_GEMM=0: fp32 pipe)
-  int split_gemm_skip = 0;          // (tuning builds: OFFK_SPLIT_GEMM_SKIP, bit k = wino_u[k] stays on the fp32 pipe)
+  int split_gemm_skip = 0;          // (tuning builds: OFFK_SPLIT_GEMM_SKIP, the bit of a kDerived row = that image stays on the fp32 pipe)
+  bool split_chain = false;         // a split-fp32 handle runs the bottleneck chains on chain_split.hip (OFFK_SPLIT_CHAIN=0: chain_fused.hip)
+  bool split_mid = false;           // ... and the 1x1 convs inside wino_mid in split-fp32 (OFFK_SPLIT_MID=0: fp32 pipe)
   bool f32split = false;            // created with OFFK_PRECISION_F32SPLIT: cfg.precision is OFFK_PRECISION_FP32 inside the library, the
                                     // kernels that have a split form take it
   bool pw_dirty = true;
@@ -167,8 +198,6 @@ struct offk_handle {
   float* fc_b[3] = {};
   // residual-branch 1x1 convs merged into their sibling: out = W3*t + Wb*x == [W3|Wb] * [t|x] (K-concatenated)
   float* merged_w[3] = {};
-  float* merged_ws[3] = {};      // split-fp32 handles: the plane images of merged_w[1], [2] and of motion_conv1_trans_14b's weights
-  float* c1_14b_ws = nullptr;    // (the 1x1 convs on 7x7 maps that run on wino_gemm_split.hip's kernel with its conv epilogue)
   float* merged_b[3] = {};
   int merged_cfg[3] = {3, 3, 3}, merged_sk[3] = {1, 1, 1};   // kMergedPlan at offk_create
   bool merged_dirty = true;
@@ -177,19 +206,11 @@ struct offk_handle {
   float* zero_page = nullptr;    // 256 B of zeros (target of masked-out loads)
   bool fused_units = true;       // forward: K1 fused with the temporal difference (OFFK_FUSED_UNITS=0 at offk_create: K1 + K2)
   bool winograd = true;          // fp32: Winograd F(4x4, 3x3) for the three 3x3 / stride 1 convs on 7x7 maps (winograd.hip); OFFK_WINOGRAD=0: direct
-  float* wino_u7 = nullptr;      // transformed weights of C_T28 in the four groups of winograd7.hip (225 x Co x Ci floats)
   bool wino_7x7 = true;          // the 7x7 / stride 2 conv of fusion@28 in polyphase Winograd form F(5x5, 4x4) (OFFK_WINOGRAD_7X7=0: direct)
   int wino7_min_p = 12;          // ... from this many pairs (OFFK_WINOGRAD_7X7=<n> with n > 1 at offk_create: tools)
-  float* wino_u7s = nullptr;     // the same for wino_u7 (Co = 64: the 64-channel form of the kernel)
-  float* wino_us[6] = {};        // split-fp32 handles: the plane images of wino_u (wino_gemm_split.hip), 6 bytes per element; nullptr: fp32 GEMMs
-  float* wino_u[6] = {};         // transformed weights [121][Co][Ci] of C3_14B, C_T7, C2_7, C2_14A, C2_14B; 400 x Co x Ci floats of C_T14 (polyphase 5x5 / 2)
-  bool wino_dirty = true;
-  float* mid_ws[2] = {};         // split-fp32 handles (OFFK_SPLIT_MID=0: off): plane images of the 1x1 convs inside wino_mid (motion_conv1_trans_14a, motion_conv1_trans)
-  float* chain_ws[3][4] = {};    // split-fp32 handles (OFFK_SPLIT_CHAIN=0: off): plane images of the chains' c1 / c2 (packed K order) / c3 weights
-                                 // (chain_split.hip), [chain 28a, 28b, 28c][conv]; [0][3]: motion_conv_branch_28a, which such a handle runs as a
-                                 // 1x1 conv of its own in front of chain 28a (its output is the chain's residual)
-  float* chain_u2[3] = {};       // F(2x2, 3x3) weights [16][64][64] of the chains' 3x3 convs C2_28A / B / C (chain_fused.hip, OFFK_CHAIN_WINO)
-  bool chain_wino = false;
+  Derived derived[kNumDerived];  // the weight images of the Winograd, chain and split-fp32 paths, per conv (kDerived)
+  bool derived_dirty = true;
+  bool chain_wino = false;       // the 3x3 conv inside a bottleneck chain in Winograd F(2x2, 3x3) form (OFFK_CHAIN_WINO=0: direct)
   int wino5_min_p = 40;          // ... from this many pairs (OFFK_WINOGRAD_5X5=<n> with n > 1 at offk_create: tools)
   bool wino_5x5 = true;          // the 5x5 / stride 2 conv of fusion@14 in polyphase Winograd form (OFFK_WINOGRAD_5X5=0: direct)
   bool wino_gemm = true;         // the batched GEMMs of a Winograd conv as one persistent launch (wino_gemm.hip); false: the generic 1x1 kernel
@@ -205,8 +226,6 @@ struct offk_handle {
   int conv_cfg[kNumConvs];       // tile plan per fusion conv (-1 = automatic)
   int conv_splitk[kNumConvs];    // K-split per fusion conv (0 = automatic)
   size_t splitk_floats = 0;      // size of the "splitk" workspace region
-  float* cur_splitk = nullptr;   // that region inside the workspace of the forward being enqueued
-  float* cur_pool_part = nullptr;   // set around the one conv launch whose epilogue also emits pooled partial sums (heads)
   bool fold_pool = true;         // 7- / 14-head: average pool in the producing conv's epilogue + MFMA FC (OFFK_FOLD_POOL=0: pool + fc kernels)
   std::vector<void*> allocs;
   // workspace plan
@@ -708,116 +727,444 @@ int off_units_whole(offk_handle* h, void* stream, const FeatKind* k, int feat_dt
 
 struct View { const float* p; int cs, coff; };
 
-int conv_raw(offk_handle* h, hipStream_t st, const char* name, int Co, int Ci, int K, int stride, int pad, const float* w,
-             const float* bias, int cfg, int sk, int n_img, int H, View x, const float* res, int res_cs, int res_coff,
-             int flags, float* y, int y_cs, int y_coff, const void* w_planes = nullptr) {
-  if (w_planes && K == 1 && stride == 1 && pad == 0 && !res && !(flags & OFFK_CONV_RELU_IN_)) {
-    // a 1x1 conv of a split-fp32 handle: wino_gemm_split.hip's kernel with its conv epilogue (bias, ReLU, the folded pool)
-    WinoGemmArgs a{};
-    a.x = x.p; a.w = w; a.y = y; a.M = n_img * H * H; a.Co = Co; a.ngroups = 1; a.g_batch[0] = 1; a.g_K[0] = Ci;
-    a.w_planes = w_planes;
-    a.epilogue = 1; a.x_rs = x.cs; a.x_coff = x.coff; a.y_rs = y_cs; a.y_coff = y_coff; a.bias = bias;
-    a.relu = (flags & (OFFK_CONV_RELU_PRE_ | OFFK_CONV_RELU_POST_)) ? 1 : 0;
-    a.pool_part = h->cur_pool_part; a.pool_hw = h->cur_pool_part ? H * H : 0;
-    if (wino_gemm_split_supported(a)) {
-      { int rc = trace_mark(h, st, name); if (rc != OFFK_OK) return rc; }
-      hipError_t e = wino_gemm_split_launch(a, st);
-      if (e != hipSuccess) return fail_hip(h, e, name);
-      return OFFK_OK;
+// ---- what is derived from the fusion convs' weights: ONE table.  offk_create walks it to allocate, finalize_derived to pack, and the
+// forward asks h->derived[conv] (Derived, above) for what a launch needs. ----
+enum DerivedKind {
+  DK_U_F43,        // Winograd F(4, 3) x F(3, 3) U of a 3x3 / stride 1 conv on 7x7 maps: 121 points (winograd.hip)
+  DK_U_POLY,       // U of the 5x5 / stride 2 conv in polyphase form: 400 row-Ci units in four K groups (winograd.hip, phases = 4)
+  DK_U_F54,        // F(5x5, 4x4) U of the 7x7 / stride 2 conv: 225 units in four groups (winograd7.hip)
+  DK_CHAIN_U2,     // F(2x2, 3x3) U2 of a bottleneck chain's 3x3 conv (chain_fused.hip)
+  DK_PLANES,       // split-fp32 plane image of a [Co][K] matrix (wino_pack_split_launch, one problem)
+  DK_U_PLANES      // split-fp32 plane image of the conv's U, group by group
+};
+DerivedKind u_kind(const ConvSpec& c) { return c.K == 7 ? DK_U_F54 : c.K == 5 ? DK_U_POLY : DK_U_F43; }
+int u_units(DerivedKind k) { return k == DK_U_F54 ? kWino7Units : k == DK_U_POLY ? kWinoUnits4 : kWinoPoints; }
+size_t u_elems(const ConvSpec& c) { return (size_t)u_units(u_kind(c)) * c.Co * c.Ci; }
+int wino_phases(const ConvSpec& c) { return u_kind(c) == DK_U_POLY ? 4 : 1; }      // winograd.hip's `phases` of a conv on that path
+// the K groups of the conv's batched GEMMs with `rows` rows per V[point] (winograd.hip / winograd7.hip; the offsets into U do not depend on rows)
+int wino_conv_groups(const ConvSpec& c, long long rows, WinoGroup grp[4]) {
+  return u_kind(c) == DK_U_F54 ? wino7_groups(rows, c.Ci, c.Co, grp) : wino_groups(wino_phases(c), rows, c.Ci, c.Co, grp);
+}
+size_t plane_floats(size_t elems) { return (elems * 3 + 1) / 2; }                  // three bf16 planes: 6 bytes per element
+
+// the handle switches an image needs: all of a row's bits, each stated once in derived_exists, and h->winograd (every image belongs to
+// a path OFFK_WINOGRAD=0 turns off -- the chain and wino_mid plane images too: such a handle runs chain_fused.hip's direct form and no wino_mid)
+enum { ON_7X7 = 1, ON_SPLIT_GEMM = 2, ON_CHAIN_WINO = 4, ON_SPLIT_CHAIN = 8, ON_SPLIT_MID = 16 };
+struct DerivedRow {
+  int slot;                      // ConvId, or merged_slot(m)
+  DerivedKind kind;
+  float* Derived::*image;        // where the image lives in h->derived[slot]
+  int needs = 0;                 // ON_* bits
+  int skip_bit = 0;              // tuning builds: its bit in OFFK_SPLIT_GEMM_SKIP
+  int alloc_K = 0;               // > 0: DK_PLANES sized for this K (chain 28a's c1 has always been allocated like its siblings' 256-channel c1)
+};
+bool derived_exists(const offk_handle* h, const DerivedRow& r) {
+  const int on = h->wino_7x7 * ON_7X7 | h->split_gemm * ON_SPLIT_GEMM | h->chain_wino * ON_CHAIN_WINO | (h->chain && h->split_chain) * ON_SPLIT_CHAIN |
+                 (h->wino_mid && h->split_mid) * ON_SPLIT_MID;
+  const bool shape = r.kind != DK_U_PLANES || (kConvs[r.slot].Co % 64 == 0 && kConvs[r.slot].Ci >= 64);      // (Co = 64: the kernel's 64-channel form)
+  return h->winograd && !(r.needs & ~on) && shape && !(h->split_gemm_skip & r.skip_bit);
+}
+
+const DerivedRow kDerived[] = {      // (a conv's U in front of the plane image of that U: finalize_derived packs in this order)
+    {C3_14B, DK_U_F43, &Derived::u}, {C_T7, DK_U_F43, &Derived::u}, {C2_7, DK_U_F43, &Derived::u}, {C2_14A, DK_U_F43, &Derived::u},
+    {C2_14B, DK_U_F43, &Derived::u}, {C_T14, DK_U_POLY, &Derived::u}, {C_T28, DK_U_F54, &Derived::u, ON_7X7},
+    {C3_14B, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 1}, {C_T7, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 2},
+    {C2_7, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 4}, {C2_14A, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 8},
+    {C2_14B, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 16}, {C_T14, DK_U_PLANES, &Derived::u_planes, ON_SPLIT_GEMM, 32},
+    {C_T28, DK_U_PLANES, &Derived::u_planes, ON_7X7 | ON_SPLIT_GEMM, 64},
+    // the 1x1 convs on 7x7 maps as launches of their own on wino_gemm_split.hip
+    {merged_slot(1), DK_PLANES, &Derived::gemm_planes, ON_SPLIT_GEMM, 128}, {merged_slot(2), DK_PLANES, &Derived::gemm_planes, ON_SPLIT_GEMM, 128},
+    {C1_14B, DK_PLANES, &Derived::gemm_planes, ON_SPLIT_GEMM, 128},
+    {C2_28A, DK_CHAIN_U2, &Derived::u2, ON_CHAIN_WINO}, {C2_28B, DK_CHAIN_U2, &Derived::u2, ON_CHAIN_WINO}, {C2_28C, DK_CHAIN_U2, &Derived::u2, ON_CHAIN_WINO},
+    // chain_split.hip: c1, c2, c3 of the three chains, and the branch 1x1 that chain 28a runs on its pre-ReLU input
+    {C1_28A, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN, 0, 256}, {C2_28A, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C3_28A, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
+    {CB_28A, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
+    {C1_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C2_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C3_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
+    {C1_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C2_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C3_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
+    // the 1x1 convs inside wino_mid
+    {C1_14A, DK_PLANES, &Derived::planes, ON_SPLIT_MID}, {C1_7, DK_PLANES, &Derived::planes, ON_SPLIT_MID}};
+
+// the [Co][K] weights behind a slot: a conv's (library K order, K = Ci k k) or a merged conv's ([Co][Ci_main | Ci_branch])
+struct Matrix { const float* w; int Co, K; };
+Matrix slot_matrix(const offk_handle* h, int slot) {
+  if (slot < kNumConvs) return Matrix{h->conv_w[slot], kConvs[slot].Co, kConvs[slot].Ci * kConvs[slot].K * kConvs[slot].K};
+  const MergedSpec& m = kMerged[slot - kNumConvs];
+  return Matrix{h->merged_w[slot - kNumConvs], kConvs[m.main_id].Co, kConvs[m.main_id].Ci + kConvs[m.branch_id].Ci};
+}
+size_t derived_floats(const offk_handle* h, const DerivedRow& r) {
+  switch (r.kind) {
+    case DK_U_F43: case DK_U_POLY: case DK_U_F54: return (size_t)u_units(r.kind) * kConvs[r.slot].Co * kConvs[r.slot].Ci;
+    case DK_CHAIN_U2: return (size_t)16 * 64 * 64;
+    case DK_PLANES: { const Matrix m = slot_matrix(h, r.slot); return plane_floats((size_t)m.Co * (r.alloc_K ? r.alloc_K : m.K)); }
+    case DK_U_PLANES: return plane_floats(u_elems(kConvs[r.slot]));
+  }
+  return 0;
+}
+int pack_derived(offk_handle* h, const DerivedRow& r, hipStream_t st) {
+  const Derived& d = h->derived[r.slot];
+  switch (r.kind) {
+    case DK_U_F43: case DK_U_POLY:
+      HIP_TRY(h, wino_weight_launch(h->conv_w[r.slot], kConvs[r.slot].Co, kConvs[r.slot].Ci, wino_phases(kConvs[r.slot]), d.u, st));
+      break;
+    case DK_U_F54: HIP_TRY(h, wino7_weight_launch(h->conv_w[r.slot], kConvs[r.slot].Co, kConvs[r.slot].Ci, d.u, st)); break;
+    case DK_CHAIN_U2: HIP_TRY(h, chain_wino_weight_launch(h->conv_w[r.slot], d.u2, st)); break;
+    case DK_PLANES: {
+      const Matrix m = slot_matrix(h, r.slot);
+      HIP_TRY(h, wino_pack_split_launch(m.w, d.*r.image, m.Co, m.K, 1, st));
+      break;
+    }
+    case DK_U_PLANES: {
+      const ConvSpec& c = kConvs[r.slot];
+      WinoGroup grp[4];
+      const int ngrp = wino_conv_groups(c, 1, grp);
+      for (int g = 0; g < ngrp; ++g)
+        HIP_TRY(h, wino_pack_split_launch(d.u + grp[g].u_off, reinterpret_cast<char*>(d.u_planes) + grp[g].u_off * 6, c.Co, grp[g].kmul * c.Ci, grp[g].batch, st));
+      break;
     }
   }
-  ConvDesc d;
-  d.x = x.p; d.x_cs = x.cs; d.x_coff = x.coff; d.n_img = n_img; d.H = H; d.W = H; d.Ci = Ci;
-  d.w = w; d.bias = bias; d.Co = Co; d.KH = K; d.KW = K; d.stride = stride; d.pad = pad;
-  d.res = res; d.res_cs = res_cs; d.res_coff = res_coff; d.flags = flags;
-  d.y = y; d.y_cs = y_cs; d.y_coff = y_coff;
-  d.tile_cfg = cfg; d.splitk = sk;
-  d.partial = h->cur_splitk; d.partial_floats = h->splitk_floats;
-  d.precision = h->cfg.precision;
-  d.pool_part = h->cur_pool_part; d.pool_hw = h->cur_pool_part ? H * H / (stride * stride) : 0;
-  const char* why = nullptr;
-  { int rc = trace_mark(h, st, name); if (rc != OFFK_OK) return rc; }
-  hipError_t e = conv2d_launch(d, st, &why);
-  if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(name) + ": " + (why ? why : hipGetErrorString(e)));
   return OFFK_OK;
 }
 
-int conv(offk_handle* h, hipStream_t st, ConvId id, int n_img, int H, View x, const float* res, int res_cs, int res_coff,
-         int flags, float* y, int y_cs, int y_coff) {
-  const ConvSpec& c = kConvs[id];
-  const float* w = h->conv_w[id];
-  return conv_raw(h, st, c.key, c.Co, c.Ci, c.K, c.stride, c.pad, w, h->conv_b[id], h->conv_cfg[id], h->conv_splitk[id], n_img,
-                  H, x, res, res_cs, res_coff, flags, y, y_cs, y_coff, id == C1_14B ? h->c1_14b_ws : nullptr);
-}
-
-// main 1x1 + branch 1x1 as ONE conv over the channel-concatenated input [t | x]
-int conv_merged(offk_handle* h, hipStream_t st, int m, int n_img, int H, View x, int flags, float* y, int y_cs, int y_coff) {
-  const ConvSpec& a = kConvs[kMerged[m].main_id];
-  const ConvSpec& b = kConvs[kMerged[m].branch_id];
-  const float* w = h->merged_w[m];
-  return conv_raw(h, st, kMerged[m].name, a.Co, a.Ci + b.Ci, 1, 1, 0, w, h->merged_b[m], h->merged_cfg[m], h->merged_sk[m], n_img,
-                  H, x, nullptr, 0, 0, flags, y, y_cs, y_coff, h->merged_ws[m]);
-}
-
-// (re)build the merged weights after any conv weight changed: [Co][Ci_main | Ci_branch], bias = b_main + b_branch
+// (re)build the merged weights after any conv weight or bias changed: [Co][Ci_main | Ci_branch], bias = b_main + b_branch
 int finalize_merged(offk_handle* h, hipStream_t st) {
   if (!h->merged_dirty) return OFFK_OK;
   for (int m = 0; m < 3; ++m) {
     const ConvSpec& a = kConvs[kMerged[m].main_id];
     const ConvSpec& b = kConvs[kMerged[m].branch_id];
     const size_t K = (size_t)a.Ci + b.Ci;
-    HIP_TRY(h, hipMemcpy2DAsync(h->merged_w[m], K * 4, h->conv_w[kMerged[m].main_id], (size_t)a.Ci * 4, (size_t)a.Ci * 4, a.Co,
-                                hipMemcpyDeviceToDevice, st));
-    HIP_TRY(h, hipMemcpy2DAsync(h->merged_w[m] + a.Ci, K * 4, h->conv_w[kMerged[m].branch_id], (size_t)b.Ci * 4, (size_t)b.Ci * 4,
-                                a.Co, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(h, hipMemcpy2DAsync(h->merged_w[m], K * 4, h->conv_w[kMerged[m].main_id], (size_t)a.Ci * 4, (size_t)a.Ci * 4, a.Co, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(h, hipMemcpy2DAsync(h->merged_w[m] + a.Ci, K * 4, h->conv_w[kMerged[m].branch_id], (size_t)b.Ci * 4, (size_t)b.Ci * 4, a.Co, hipMemcpyDeviceToDevice, st));
     HIP_TRY(h, vec_add_launch(h->conv_b[kMerged[m].main_id], h->conv_b[kMerged[m].branch_id], h->merged_b[m], a.Co, st));
-    if (h->merged_ws[m]) HIP_TRY(h, wino_pack_split_launch(h->merged_w[m], h->merged_ws[m], a.Co, (int)K, 1, st));
   }
-  if (h->c1_14b_ws) HIP_TRY(h, wino_pack_split_launch(h->conv_w[C1_14B], h->c1_14b_ws, kConvs[C1_14B].Co, kConvs[C1_14B].Ci, 1, st));
   h->merged_dirty = false;
   return OFFK_OK;
 }
-int finalize_wino(offk_handle* h, hipStream_t st) {
-  if (!h->winograd || !h->wino_dirty) return OFFK_OK;
-  const ConvId wid[6] = {C3_14B, C_T7, C2_7, C2_14A, C2_14B, C_T14};
-  for (int k = 0; k < 6; ++k) {
-    const ConvSpec& c = kConvs[wid[k]];
-    HIP_TRY(h, wino_weight_launch(h->conv_w[wid[k]], c.Co, c.Ci, k == 5 ? 4 : 1, h->wino_u[k], st));
-    if (!h->wino_us[k]) continue;
-    WinoGroup grp[4];
-    const int ngrp = wino_groups(k == 5 ? 4 : 1, 1, c.Ci, c.Co, grp);
-    for (int g = 0; g < ngrp; ++g)
-      HIP_TRY(h, wino_pack_split_launch(h->wino_u[k] + grp[g].u_off, reinterpret_cast<char*>(h->wino_us[k]) + grp[g].u_off * 6, c.Co,
-                                        grp[g].kmul * c.Ci, grp[g].batch, st));
-  }
-  if (h->wino_u7) HIP_TRY(h, wino7_weight_launch(h->conv_w[C_T28], kConvs[C_T28].Co, kConvs[C_T28].Ci, h->wino_u7, st));
-  if (h->wino_u7 && h->wino_u7s) {
-    const ConvSpec& c = kConvs[C_T28];
-    WinoGroup grp[4];
-    const int ngrp = wino7_groups(1, c.Ci, c.Co, grp);
-    for (int g = 0; g < ngrp; ++g)
-      HIP_TRY(h, wino_pack_split_launch(h->wino_u7 + grp[g].u_off, reinterpret_cast<char*>(h->wino_u7s) + grp[g].u_off * 6, c.Co,
-                                        grp[g].kmul * c.Ci, grp[g].batch, st));
-  }
-  {
-    const ConvId c2[3] = {C2_28A, C2_28B, C2_28C};
-    for (int k = 0; k < 3; ++k)
-      if (h->chain_u2[k]) HIP_TRY(h, chain_wino_weight_launch(h->conv_w[c2[k]], h->chain_u2[k], st));
-    const ConvId c1[3] = {C1_28A, C1_28B, C1_28C}, c3[3] = {C3_28A, C3_28B, C3_28C};
-    for (int k = 0; k < 3; ++k) {
-      if (!h->chain_ws[k][0]) continue;
-      HIP_TRY(h, wino_pack_split_launch(h->conv_w[c1[k]], h->chain_ws[k][0], 64, kConvs[c1[k]].Ci, 1, st));
-      HIP_TRY(h, wino_pack_split_launch(h->conv_w[c2[k]], h->chain_ws[k][1], 64, 576, 1, st));
-      HIP_TRY(h, wino_pack_split_launch(h->conv_w[c3[k]], h->chain_ws[k][2], 256, 64, 1, st));
-    }
-    if (h->chain_ws[0][3]) HIP_TRY(h, wino_pack_split_launch(h->conv_w[CB_28A], h->chain_ws[0][3], 256, 64, 1, st));
-    const ConvId midc[2] = {C1_14A, C1_7};
-    for (int k = 0; k < 2; ++k)
-      if (h->mid_ws[k]) HIP_TRY(h, wino_pack_split_launch(h->conv_w[midc[k]], h->mid_ws[k], kConvs[midc[k]].Co, kConvs[midc[k]].Ci, 1, st));
-  }
-  h->wino_dirty = false;
+// (re)pack every derived image after any conv weight changed (behind finalize_merged: the merged matrices are sources too)
+int finalize_derived(offk_handle* h, hipStream_t st) {
+  if (!h->derived_dirty) return OFFK_OK;
+  for (const DerivedRow& r : kDerived)
+    if (h->derived[r.slot].*r.image) TRY(pack_derived(h, r, st));
+  h->derived_dirty = false;
   return OFFK_OK;
 }
+
+// ---- the forward behind the units: one call's context, the launches of a conv on each path, one function per stage ----
+constexpr int RI = OFFK_CONV_RELU_IN_, RP = OFFK_CONV_RELU_PRE_, RO = OFFK_CONV_RELU_POST_;
+// a launch name in two pieces, put together only when the per-launch trace is on
+int trace_mark(offk_handle* h, hipStream_t st, const char* key, const char* what) {
+  return h->profiling != 2 ? OFFK_OK : trace_mark(h, st, (std::string(key) + what).c_str());
+}
+// the fields of a wino_mid launch (the order of offk_winograd_between's parameters); w1p: the plane image of w1, or nullptr
+WinoMidArgs wino_mid_args(const float* M, const float* bias_in, int phases_in, int n_img, int Cin, float* x, int x_cs, int x_coff, const float* w1,
+                          const float* b1, int Cmid, float* V, const void* w1p = nullptr) {
+  WinoMidArgs m;
+  m.M = M; m.bias_in = bias_in; m.phases_in = phases_in; m.x = x; m.x_cs = x_cs; m.x_coff = x_coff;
+  m.w1 = w1; m.b1 = b1; m.Cin = Cin; m.Cmid = Cmid; m.n_img = n_img; m.V = V; m.w1p = w1p;
+  return m;
+}
+// the view, weight and x_bytes fields of a chain launch; u2 and the plane images are the caller's
+ChainArgs chain_args(const float* x, int x_cs, int x_coff, int n_img, int Cin, int relu_in, const float* w1, const float* b1, const float* w2,
+                     const float* b2, const float* w3, const float* b3, int K3, const float* res, int res_cs, int res_coff, float* y, int y_cs,
+                     int y_coff) {
+  ChainArgs a{};
+  a.x = x; a.x_cs = x_cs; a.x_coff = x_coff; a.Cin = Cin; a.relu_in = relu_in ? 1 : 0;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.K3 = K3;
+  a.res = res; a.res_cs = res_cs; a.res_coff = res_coff; a.y = y; a.y_cs = y_cs; a.y_coff = y_coff;
+  a.n_img = n_img; a.relu_out = 1;
+  const unsigned long long xb = ((unsigned long long)n_img * 196 * x_cs - x_coff) * 4ull;
+  a.x_bytes = xb < 0x7fffffffull ? (unsigned)xb : 0u;
+  return a;
+}
+
+struct Fwd {
+  offk_handle* h;
+  hipStream_t s;
+  void* ws;
+  int n;                           // = P: every launch covers all P pairs (the buffers are pair-major)
+  hipEvent_t* ev = nullptr;        // profiling == 1: the stage events of this call
+  float *F14, *F7;                 // fusion_14 / fusion_7: written by the stage in front, read by the stage behind
+  float *wino_V, *wino_M;          // Winograd domain: GEMM input and output (nullptr without the Winograd paths)
+  float* splitk;                   // split-K partial slabs
+  float *out7, *out14, *out28;     // the caller's (out28 nullptr: no 28-head)
+  float *l7, *l14, *l28;           // where the heads write: those, or the per-pair regions consensus averages afterwards
+  FcPooledJobs fcj{};              // the folded-pool FCs of the heads, launched together behind the last stage (fc_pooled_multi_kernel)
+  bool wino, w7, mid, w5, chained, fold, fold14t;      // the paths of this call (init)
+
+  float* reg(const char* name) const { return region(h, ws, name); }
+
+  int init(offk_handle* handle, hipStream_t st, void* workspace, float* o7, float* o14, float* o28) {
+    h = handle; s = st; ws = workspace; n = h->P; out7 = o7; out14 = o14; out28 = o28;
+    if (h->profiling == 1) {
+      const size_t per = OFFK_NUM_STAGES + 1;
+      if ((h->ev_used + 1) * per > h->events.size() && h->events.size() < 4096 * per) {
+        for (size_t i = 0; i < per; ++i) {
+          hipEvent_t e;
+          HIP_TRY(h, hipEventCreate(&e));
+          h->events.push_back(e);
+        }
+      }
+      if ((h->ev_used + 1) * per <= h->events.size()) ev = &h->events[h->ev_used++ * per];
+    }
+    wino = h->winograd;
+    // the 7x7 / stride 2 conv in polyphase Winograd form
+    // (from P = 12 pairs -- B = 2: 0.495 against 0.503 ms, B = 8: 0.813 against 0.874, B = 64: 3.88 against 4.24; B = 1: equal)
+    w7 = h->derived[C_T28].u && wino && h->wino_7x7 && n >= h->wino7_min_p;
+    mid = wino && h->wino_mid;
+    // (from P = 40 pairs: below, its 132-K-tile GEMMs have too few row tiles to fill the chip and the split-K direct conv wins --
+    // B = 1: 0.435 vs 0.50 ms, B = 4: 0.672 vs 0.695, B = 8: 0.892 vs 0.874, B = 12: 1.157 vs 1.12; OFFK_WINOGRAD_5X5=<pairs> moves the gate)
+    w5 = wino && h->wino_5x5 && n >= h->wino5_min_p;
+    // (from P = 72 pairs: a chain block walks its three convs alone -- 45 us per launch however few blocks there are; B = 8: three
+    //  convs per chain 0.885 ms per forward against 0.90, B = 16: 1.37 against 1.345; OFFK_CHAIN=<pairs> moves the gate)
+    chained = h->chain && n >= h->chain_min_p && (unsigned long long)n * 196 * 256 * 4ull < 0x7fffffffull;
+    // (fold: the conv's epilogue also leaves per-slab column sums of its output: the head's average pool)
+    auto generic = [](int cfg) { return cfg != 6 && cfg != 7 && cfg != 10; };      // the LDS-patch kernels have no pooling epilogue
+    fold = h->fold_pool && generic(h->conv_cfg[C3_14B]) && generic(h->merged_cfg[2]);
+    fold14t = wino && h->fold_pool;      // (the Winograd output transform of sum_14b leaves per-tile sums)
+    F14 = reg("fusion_14"); F7 = reg("fusion_7"); splitk = reg("splitk");
+    wino_V = wino ? reg("wino_v") : nullptr;
+    wino_M = wino ? reg("wino_m") : nullptr;
+    const bool cons = h->cfg.consensus == OFFK_CONSENSUS_AVG;
+    l7 = cons ? reg("logit_7") : out7; l14 = cons ? reg("logit_14") : out14; l28 = cons ? reg("logit_28") : out28;
+    fcj.n_img = n; fcj.ncls = h->cfg.num_classes;
+    return OFFK_OK;
+  }
+
+  // pool_part: the launch's epilogue also emits the pooled partial sums of a head there
+  int conv_raw(const char* name, int Co, int Ci, int K, int stride, int pad, const float* w, const float* bias, int cfg, int sk, int H, View x,
+               const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, const void* w_planes, float* pool_part) {
+    if (w_planes && K == 1 && stride == 1 && pad == 0 && !res && !(flags & OFFK_CONV_RELU_IN_)) {
+      // a 1x1 conv of a split-fp32 handle: wino_gemm_split.hip's kernel with its conv epilogue (bias, ReLU, the folded pool)
+      WinoGemmArgs a{};
+      a.x = x.p; a.w = w; a.y = y; a.M = n * H * H; a.Co = Co; a.ngroups = 1; a.g_batch[0] = 1; a.g_K[0] = Ci;
+      a.w_planes = w_planes;
+      a.epilogue = 1; a.x_rs = x.cs; a.x_coff = x.coff; a.y_rs = y_cs; a.y_coff = y_coff; a.bias = bias;
+      a.relu = (flags & (OFFK_CONV_RELU_PRE_ | OFFK_CONV_RELU_POST_)) ? 1 : 0;
+      a.pool_part = pool_part; a.pool_hw = pool_part ? H * H : 0;
+      if (wino_gemm_split_supported(a)) {
+        TRY(trace_mark(h, s, name));
+        hipError_t e = wino_gemm_split_launch(a, s);
+        if (e != hipSuccess) return fail_hip(h, e, name);
+        return OFFK_OK;
+      }
+    }
+    ConvDesc d = conv_desc(x.p, x.cs, x.coff, n, H, H, Ci, w, bias, Co, K, K, stride, pad, res, res_cs, res_coff, flags, y, y_cs, y_coff, cfg, sk,
+                           splitk, h->splitk_floats, h->cfg.precision);
+    d.pool_part = pool_part; d.pool_hw = pool_part ? H * H / (stride * stride) : 0;
+    const char* why = nullptr;
+    TRY(trace_mark(h, s, name));
+    hipError_t e = conv2d_launch(d, s, &why);
+    if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(name) + ": " + (why ? why : hipGetErrorString(e)));
+    return OFFK_OK;
+  }
+  int conv(ConvId id, int H, View x, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_part = nullptr) {
+    const ConvSpec& c = kConvs[id];
+    return conv_raw(c.key, c.Co, c.Ci, c.K, c.stride, c.pad, h->conv_w[id], h->conv_b[id], h->conv_cfg[id], h->conv_splitk[id], H, x, res, res_cs,
+                    res_coff, flags, y, y_cs, y_coff, h->derived[id].gemm_planes, pool_part);
+  }
+  // main 1x1 + branch 1x1 as ONE conv over the channel-concatenated input [t | x]
+  int conv_merged(int m, int H, View x, int flags, float* y, int y_cs, int y_coff, float* pool_part = nullptr) {
+    const Matrix w = slot_matrix(h, merged_slot(m));
+    return conv_raw(kMerged[m].name, w.Co, w.K, 1, 1, 0, w.w, h->merged_b[m], h->merged_cfg[m], h->merged_sk[m], H, x, nullptr, 0, 0, flags, y, y_cs,
+                    y_coff, h->derived[merged_slot(m)].gemm_planes, pool_part);
+  }
+
+  // A conv on its Winograd path in three steps: V = B^T x B (wino_V), M = V U per point (wino_M), y = epilogue(A^T M A).  winograd.hip: a
+  // 3x3 / stride 1 conv on 7x7 maps (phases = 1), the 5x5 / stride 2 conv on 14x14 maps in polyphase form (phases = 4); winograd7.hip: the
+  // 7x7 / stride 2 conv on 28x28 maps in polyphase form F(5x5, 4x4), nine tiles per image (no residual, no pooled sums).
+  // (7x7: the input transform INSIDE the GEMM kernel was built and measured in round 4 -- tools/experiments/winograd7_fused.hip, out of the
+  //  product build since round 5: 0.84 ms against 0.54 ms for these two launches; profiles/r04/wino7_fused_attempt.txt)
+  int wino_in(ConvId id, View x) {
+    const ConvSpec& c = kConvs[id];
+    TRY(trace_mark(h, s, c.key, " [winograd: input transform]"));
+    if (u_kind(c) == DK_U_F54) HIP_TRY(h, wino7_input_launch(x.p, x.cs, x.coff, n, c.Ci, wino_V, s));
+    else HIP_TRY(h, wino_input_launch(x.p, x.cs, x.coff, n, c.Ci, wino_phases(c), wino_V, s));
+    return OFFK_OK;
+  }
+  // the batched GEMMs: ONE launch, the K groups ride on gridDim.y (four launches left the short groups alone on the chip: slower than
+  // not skipping their zero products)
+  int wino_mm(ConvId id) {
+    const ConvSpec& c = kConvs[id];
+    const bool f54 = u_kind(c) == DK_U_F54;
+    TRY(trace_mark(h, s, c.key, f54 ? " [winograd: 64 GEMMs]" : " [winograd: 121 GEMMs]"));
+    const int rows = f54 ? kWino7Tiles * n : n;
+    WinoGroup grp[4];
+    const int ngrp = wino_conv_groups(c, rows, grp);
+    const char* why = nullptr;
+    hipError_t e = wino_gemms_launch(grp, ngrp, f54 ? kWino7Points : kWinoPoints, rows, c.Ci, c.Co, wino_V, h->derived[id].u, wino_M, h->wino_gemm, s, &why,
+                                     h->derived[id].u_planes);
+    if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(c.key) + " (winograd): " + (why ? why : hipGetErrorString(e)));
+    return OFFK_OK;
+  }
+  int wino_out(ConvId id, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t) {
+    const ConvSpec& c = kConvs[id];
+    TRY(trace_mark(h, s, c.key, " [winograd: output transform]"));
+    if (u_kind(c) == DK_U_F54) HIP_TRY(h, wino7_output_launch(wino_M, n, c.Co, h->conv_b[id], flags, y, y_cs, y_coff, s));
+    else HIP_TRY(h, wino_output_launch(wino_M, n, c.Co, wino_phases(c), h->conv_b[id], res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t, s));
+    return OFFK_OK;
+  }
+  int wino_conv(ConvId id, View x, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t) {
+    TRY(wino_in(id, x));
+    TRY(wino_mm(id));
+    return wino_out(id, res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t);
+  }
+  // What sits between two convs on that path, in ONE launch (wino_mid.hip): the output transform (+ bias, ReLU) of conv `a` from
+  // wino_M, optionally the 1x1 conv `c1` (+ bias, ReLU; kNumConvs: none), the input transform of the conv behind into wino_V.  xa: where
+  // the activation of conv `a` is ALSO stored (the merged convs read x1 / x2 from there later); nullptr: nowhere.
+  int wino_between(ConvId a, ConvId c1, float* xa, int xa_cs, int xa_coff, const char* name) {
+    const bool has = c1 != kNumConvs;
+    const WinoMidArgs m = wino_mid_args(wino_M, h->conv_b[a], wino_phases(kConvs[a]), n, kConvs[a].Co, xa, xa_cs, xa_coff, has ? h->conv_w[c1] : nullptr,
+                                        has ? h->conv_b[c1] : nullptr, kConvs[has ? c1 : a].Co, wino_V, has ? h->derived[c1].planes : nullptr);
+    TRY(trace_mark(h, s, name));
+    HIP_TRY(h, wino_mid_launch(m, s));
+    return OFFK_OK;
+  }
+  // x = relu(conv k x k (F)) -> c1 (1x1) -> c2 (3x3), the head of fusion@14 and fusion@7: xx = [c2's output | x] per pixel, t: c1's output.
+  // wino_t: `ct` on its Winograd path; with wino_mid the 1x1 conv then sits between the two Winograd GEMM launches.
+  int conv_t_c1_c2(ConvId ct, bool wino_t, int H, View F, ConvId c1, ConvId c2, float* xx, int cs, float* t, const char* between) {
+    const int half = cs / 2;
+    if (wino_t && mid) {
+      TRY(wino_in(ct, F));
+      TRY(wino_mm(ct));
+      TRY(wino_between(ct, c1, xx, cs, half, between));
+      TRY(wino_mm(c2));
+      return wino_out(c2, nullptr, 0, 0, RP, xx, cs, 0, nullptr);
+    }
+    if (wino_t) TRY(wino_conv(ct, F, nullptr, 0, 0, RP, xx, cs, half, nullptr));
+    else TRY(conv(ct, H, F, nullptr, 0, 0, RP, xx, cs, half));
+    TRY(conv(c1, 7, View{xx, cs, half}, nullptr, 0, 0, RP, t, half, 0));
+    if (wino) return wino_conv(c2, View{t, half, 0}, nullptr, 0, 0, RP, xx, cs, 0, nullptr);
+    return conv(c2, 7, View{t, half, 0}, nullptr, 0, 0, RP, xx, cs, 0);
+  }
+
+  // 1x1 -> 3x3 -> 1x1 (+ residual) as ONE launch per chain (a block owns half an image, t1 / t2 stay in LDS).  m >= 0: chain 28a, whose c3
+  // is summed with the branch 1x1 kMerged[m] on the chain input -- merged into c3's K (K3 = 128, the fp32 kernel), or, split_branch, as
+  // a 1x1 conv of its own inside chain_split.hip's kernel (c3 with K3 = 64; its output passes through y as the chain's residual).
+  int chain(const char* name, View x, int Cin, int relu_in, ConvId c1, ConvId c2, ConvId c3, int m, bool split_branch, const float* res, float* y, int y_cs, int y_coff) {
+    const bool merged = m >= 0 && !split_branch;
+    ChainArgs a = chain_args(x.p, x.cs, x.coff, n, Cin, relu_in, h->conv_w[c1], h->conv_b[c1], h->conv_w[c2], h->conv_b[c2],
+                             merged ? h->merged_w[m] : h->conv_w[c3], merged ? h->merged_b[m] : h->conv_b[c3], merged ? 128 : 64, res, 256, 0, y, y_cs, y_coff);
+    a.u2 = h->derived[c2].u2;
+    a.w1p = h->derived[c1].planes; a.w2p = h->derived[c2].planes; a.w3p = h->derived[c3].planes;
+    if (split_branch) { a.wbp = h->derived[kMerged[m].branch_id].planes; a.bbr = h->conv_b[kMerged[m].branch_id]; }
+    TRY(trace_mark(h, s, name));
+    const char* why = nullptr;
+    hipError_t e = chain14_split_supported(a) ? chain14_split_launch(a, s, &why) : chain14_launch(a, s, &why);
+    if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(name) + ": " + (why ? why : hipGetErrorString(e)));
+    return OFFK_OK;
+  }
+
+  // head k (kHeads order) from the pooled partial sums `part` its producing launch left (heads.hip: fc_pooled), or -- part == nullptr: the
+  // paths that cannot fold the pool into that launch (LDS-patch tiles, OFFK_FOLD_POOL=0) -- pool_kernel + fc_kernel on its output x
+  int head(int k, float* logits, const float* part, int tiles, const float* x, int x_cs, int x_coff, int Hh, int maxpool, const char* pooled_name) {
+    const int C = kHeads[k].C;
+    if (part) { fcj.job[fcj.njobs++] = FcPooledJob{part, 49, tiles, C, h->fc_w[k], h->fc_b[k], logits}; return OFFK_OK; }
+    float* pooled = reg(pooled_name);
+    TRY(trace_mark(h, s, k == 0 ? "head_7 (pool + fc)" : k == 1 ? "head_28 (pool + fc)" : "head_14 (pool + fc)"));
+    hipError_t e = pool_launch(x, x_cs, x_coff, n, Hh, Hh, C, maxpool, pooled, s);
+    if (e == hipSuccess) e = fc_launch(pooled, n, C, h->fc_w[k], h->fc_b[k], h->cfg.num_classes, logits, s);
+    if (e != hipSuccess) return fail_hip(h, e, "head");
+    return OFFK_OK;
+  }
+
+  int units(const offk_feat_parts feats[], int feat_dtype, bool cl) {
+    if (cl) return run_off_units_fused(h, s, feats, ws, ev, feat_dtype, true);       // (check_feat: fused_units, whatever cfg.feat_layout)
+    if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) return run_off_units_fused(h, s, feats, ws, ev, feat_dtype);
+    return run_off_units(h, s, feats, ws, ev, h->cfg.feat_layout == OFFK_FEAT_NHWC);
+  }
+
+  // ---- fusion @28 -> 14x14 (RGB_OFF.py:655-685) and the 28-head (:782-787) ----
+  int fusion28() {
+    float *F28 = reg("fusion_28"), *xt = reg("xt_28"), *t1 = reg("t1_28"), *sa = reg("sa_28"), *sb = reg("sb_28");
+    // xt = [t2 | x0] per pixel: c3(t2) + branch(x0) (:663-666) is then ONE 1x1 conv over 128 channels
+    // :657 x0, pre-ReLU kept for the branch
+    if (w7) TRY(wino_conv(C_T28, View{F28, 320, 0}, nullptr, 0, 0, 0, xt, 128, 64, nullptr));
+    else TRY(conv(C_T28, 28, View{F28, 320, 0}, nullptr, 0, 0, 0, xt, 128, 64));
+    if (chained) {
+      // split-fp32 (chain_split.hip, BR form): the branch 1x1 on the pre-ReLU chain input inside the kernel -- RGB_OFF.py:663-667; in the
+      // fp32 kernel the branch is merged into c3's K
+      TRY(chain("chain_28a = motion_conv1_trans_28a + motion_conv2_trans_28a + merged_28a", View{xt, 128, 64}, 64, 1, C1_28A, C2_28A, C3_28A, 0,
+                h->derived[CB_28A].planes != nullptr, nullptr, sa, 256, 0));                                                       // :658-667
+      TRY(chain("chain_28b = motion_conv1_trans_28b + motion_conv2_trans_28b + motion_conv3_trans_28b", View{sa, 256, 0}, 256, 0, C1_28B, C2_28B, C3_28B,
+                -1, false, sa, sb, 256, 0));                                                                                       // :670-676
+      TRY(chain("chain_28c = motion_conv1_trans_28c + motion_conv2_trans_28c + motion_conv3_trans_28c", View{sb, 256, 0}, 256, 0, C1_28C, C2_28C, C3_28C,
+                -1, false, sb, F14, 1056, 800));                                                                    // :679-685 -> cat at :760
+    } else {
+      TRY(conv(C1_28A, 14, View{xt, 128, 64}, nullptr, 0, 0, RI | RP, t1, 64, 0));            // :658-660
+      TRY(conv(C2_28A, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));                  // :661-662 t2
+      TRY(conv_merged(0, 14, View{xt, 128, 0}, RO, sa, 256, 0));                               // :663-667
+      TRY(conv(C1_28B, 14, View{sa, 256, 0}, nullptr, 0, 0, RP, t1, 64, 0));                  // :670-671
+      TRY(conv(C2_28B, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));                  // :672-673
+      TRY(conv(C3_28B, 14, View{xt, 128, 0}, sa, 256, 0, RO, sb, 256, 0));                     // :674-676
+      TRY(conv(C1_28C, 14, View{sb, 256, 0}, nullptr, 0, 0, RP, t1, 64, 0));                  // :679-680
+      TRY(conv(C2_28C, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));                  // :681-682
+      TRY(conv(C3_28C, 14, View{xt, 128, 0}, sb, 256, 0, RO, F14, 1056, 800));                 // :683-685 -> cat at :760
+    }
+    if (ev) HIP_TRY(h, hipEventRecord(ev[3], s));
+    if (!out28) return OFFK_OK;
+    float* pp = nullptr;     // the 28-head only reads sum_28c: pool-row partial sums + the FC as an MFMA GEMM instead of pool_kernel + fc_kernel
+    if (h->fold_pool) {
+      pp = reg("poolpart_28");
+      TRY(trace_mark(h, s, "head_28 (max pool rows)"));
+      HIP_TRY(h, maxpool_rows_launch(F14, 1056, 800, n, 14, 14, 256, pp, s));
+    }
+    return head(1, l28, pp, 1, F14, 1056, 800, 14, 1, "pooled_28");
+  }
+
+  // ---- fusion @14 -> 7x7 (RGB_OFF.py:759-780) and the 14-head (:789-793) ----
+  int fusion14() {
+    float *xu = reg("xu_14"), *u1 = reg("u1_14"), *s14 = reg("sa_14");                           // xu = [u2 | x1]
+    TRY(conv_t_c1_c2(C_T14, w5, 14, View{F14, 1056, 0}, C1_14A, C2_14A, xu, 256, u1,                // :762-767
+                     "motion_conv_trans_14 out + motion_conv1_trans_14a + motion_conv2_trans_14a in [winograd: between]"));
+    TRY(conv_merged(1, 7, View{xu, 256, 0}, RO, s14, 512, 0));                                   // :768-771
+    TRY(conv(C1_14B, 7, View{s14, 512, 0}, nullptr, 0, 0, RP, u1, 128, 0));                     // :773-774
+    // the 14-head's average pool of sum_14b: per-tile sums from the Winograd output transform (fold14t), or per-slab column sums from
+    // the direct conv's epilogue (fold)
+    float* pp14t = fold14t ? reg("poolpart_14t") : nullptr;
+    float* pp14 = !wino && fold ? reg("poolpart_14") : nullptr;
+    if (mid) {            // :775-780: c2_14b's output feeds c3_14b alone -- output transform, ReLU and input transform in one launch
+      TRY(wino_in(C2_14B, View{u1, 128, 0}));
+      TRY(wino_mm(C2_14B));
+      TRY(wino_between(C2_14B, kNumConvs, nullptr, 0, 0, "motion_conv2_trans_14b out + motion_conv3_trans_14b in [winograd: between]"));
+      TRY(wino_mm(C3_14B));
+      TRY(wino_out(C3_14B, s14, 512, 0, RP | RO, F7, 832, 320, pp14t));                          // :777-780 -> cat at :832
+    } else if (wino) {
+      TRY(wino_conv(C2_14B, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0, nullptr));          // :775-776
+      TRY(wino_conv(C3_14B, View{xu, 256, 0}, s14, 512, 0, RP | RO, F7, 832, 320, pp14t));       // :777-780 -> cat at :832
+    } else {
+      TRY(conv(C2_14B, 7, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0));                     // :775-776
+      TRY(conv(C3_14B, 7, View{xu, 256, 0}, s14, 512, 0, RP | RO, F7, 832, 320, pp14));          // :777-780 -> cat at :832
+    }
+    if (ev) HIP_TRY(h, hipEventRecord(ev[4], s));
+    return head(2, l14, pp14t ? pp14t : pp14, pp14t ? 1 : 0, F7, 832, 320, 7, 0, "pooled_14");      // only reads sum_14b
+  }
+
+  // ---- fusion @7 (RGB_OFF.py:831-841) and the 7-head (:843-847) ----
+  int fusion7() {
+    float *xv = reg("xv_7"), *v1 = reg("v1_7"), *s7 = reg("sum_7");                              // xv = [v2 | x2]
+    TRY(conv_t_c1_c2(C_T7, wino, 7, View{F7, 832, 0}, C1_7, C2_7, xv, 512, v1,                      // :833-838
+                     "motion_conv_trans out + motion_conv1_trans + motion_conv2_trans in [winograd: between]"));
+    float* pp7 = fold ? reg("poolpart_7") : nullptr;      // the 7-head's average pool in the merged conv's epilogue
+    TRY(conv_merged(2, 7, View{xv, 512, 0}, 0, s7, 1024, 0, pp7));                               // :839-841 (no ReLU)
+    if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
+    return head(0, l7, pp7, 0, s7, 1024, 0, 7, 0, "pooled_7");
+  }
+
+  // ---- the folded-pool FCs of all heads in one launch, segment consensus (Flow_OFF.py:874-876) ----
+  int heads() {
+    if (fcj.njobs > 0) {
+      TRY(trace_mark(h, s, "heads (fc on folded pools, one launch)"));
+      HIP_TRY(h, fc_pooled_multi_launch(fcj, s));
+    }
+    if (h->cfg.consensus == OFFK_CONSENSUS_AVG) {
+      TRY(trace_mark(h, s, "consensus (K6)"));
+      const float* const cx[3] = {l7, l14, out28 ? l28 : l14};                                    // one launch
+      float* const co[3] = {out7, out14, out28 ? out28 : out14};
+      HIP_TRY(h, consensus_multi_launch(cx, co, out28 ? 3 : 2, h->cfg.batch, h->cfg.length - 1, h->cfg.num_classes, s));
+    }
+    if (ev) HIP_TRY(h, hipEventRecord(ev[6], s));
+    return trace_mark(h, s, nullptr);
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -907,16 +1254,7 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
     if (rc == OFFK_OK) rc = dev_alloc(h, &h->fc_b[k], cfg->num_classes);
 
   }
-  if (rc != OFFK_OK) {
-    g_err = h->err;
-    offk_destroy(h);
-    return rc;
-  }
-  if (dev_alloc(h, &h->zero_page, 64) != OFFK_OK) {
-    g_err = h->err;
-    offk_destroy(h);
-    return OFFK_ERR_HIP;
-  }
+  if (rc == OFFK_OK) rc = dev_alloc(h, &h->zero_page, 64);
   // The path switches of the product library, all read HERE and nowhere else (INTEGRATION.md lists them): each names one
   // algorithm choice of the exact-fp32 forward; "0" = off, a number > 1 = use it from that many frame pairs P = B (L - 1).
   //   OFFK_FUSED_UNITS   K1 fused with the temporal difference (pw_tdiff.hip); 0: K1 + K2 (what training always runs)
@@ -929,56 +1267,34 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
   //   OFFK_CHAIN_WINO    the 3x3 conv inside a bottleneck chain in Winograd F(2x2, 3x3) form (chain_fused.hip); 0: direct (also with OFFK_WINOGRAD=0)
   //   OFFK_WINO_GEMM     the batched GEMMs of a Winograd conv as one persistent launch (wino_gemm.hip); 0: one block of the generic 1x1 kernel per
   //                      tile (bit-identical).  The handle-less stage entry points read it once per process.
-  { const char* e = getenv("OFFK_FUSED_UNITS"); h->fused_units = !(e && *e == '0'); }
-  { const char* e = getenv("OFFK_CHAIN"); h->chain = !(e && *e == '0'); if (e && atoi(e) > 1) h->chain_min_p = atoi(e);
+  h->fused_units = path_switch("OFFK_FUSED_UNITS");
+  h->split_chain = h->f32split && path_switch("OFFK_SPLIT_CHAIN");
+  h->split_mid = h->f32split && path_switch("OFFK_SPLIT_MID");
+  {
+    int from = 0;
+    h->chain = path_switch("OFFK_CHAIN", &from);
+    if (from) h->chain_min_p = from;
     // split-fp32 handles: chain14_split_kernel from the first pair on (a block of it alone on a CU is ~25 us per chain where the fp32 kernel's
     // sixteen phases are 45 us: B = 1 .. 4 0.432 / 0.482 / 0.565 -> 0.425 / 0.477 / 0.555 ms, B = 8 level; profiles/r06/small_batch_gates.txt)
-    else if (h->f32split) { const char* c = getenv("OFFK_SPLIT_CHAIN"); if (!(c && *c == '0')) h->chain_min_p = 1; } }
-  { const char* e = getenv("OFFK_FOLD_POOL"); h->fold_pool = !(e && *e == '0'); }
-  { const char* e = getenv("OFFK_WINO_MID"); h->wino_mid = !(e && *e == '0'); }
-  { const char* e = getenv("OFFK_WINO_GEMM"); h->wino_gemm = !(e && *e == '0'); }
-  { const char* e = getenv("OFFK_WINOGRAD"); h->winograd = !(e && *e == '0') && cfg->precision == OFFK_PRECISION_FP32; }
-  { const char* e = getenv("OFFK_WINOGRAD_5X5"); h->wino_5x5 = !(e && *e == '0'); if (e && atoi(e) > 1) h->wino5_min_p = atoi(e); }
-  { const char* e = getenv("OFFK_WINOGRAD_7X7"); h->wino_7x7 = !(e && *e == '0'); if (e && atoi(e) > 1) h->wino7_min_p = atoi(e); }
-  if (h->winograd) {
-    const ConvId wid[6] = {C3_14B, C_T7, C2_7, C2_14A, C2_14B, C_T14};
-    for (int k = 0; k < 6; ++k)
-      if (dev_alloc(h, &h->wino_u[k], (size_t)(k == 5 ? kWinoUnits4 : kWinoPoints) * kConvs[wid[k]].Co * kConvs[wid[k]].Ci) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    { const char* e = getenv("OFFK_SPLIT_GEMM"); h->split_gemm = h->f32split && !(e && *e == '0'); }
+    else if (h->split_chain) h->chain_min_p = 1;
+  }
+  h->fold_pool = path_switch("OFFK_FOLD_POOL");
+  h->wino_mid = path_switch("OFFK_WINO_MID");
+  h->wino_gemm = path_switch("OFFK_WINO_GEMM");
+  h->winograd = path_switch("OFFK_WINOGRAD") && cfg->precision == OFFK_PRECISION_FP32;
+  h->wino_5x5 = path_switch("OFFK_WINOGRAD_5X5", &h->wino5_min_p);
+  h->wino_7x7 = path_switch("OFFK_WINOGRAD_7X7", &h->wino7_min_p);
+  h->split_gemm = h->winograd && h->f32split && path_switch("OFFK_SPLIT_GEMM");
 #ifdef OFFK_TUNING_KNOBS
-    { const char* e = getenv("OFFK_SPLIT_GEMM_SKIP"); if (e) h->split_gemm_skip = atoi(e); }
+  { const char* e = getenv("OFFK_SPLIT_GEMM_SKIP"); if (e) h->split_gemm_skip = atoi(e); }
 #endif
-    if (h->split_gemm)
-      for (int k = 0; k < 6; ++k) {
-        const size_t elems = (size_t)(k == 5 ? kWinoUnits4 : kWinoPoints) * kConvs[wid[k]].Co * kConvs[wid[k]].Ci;
-        if (kConvs[wid[k]].Co % 64 == 0 && kConvs[wid[k]].Ci >= 64 && !(h->split_gemm_skip & (1 << k)) &&
-            dev_alloc(h, &h->wino_us[k], (elems * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-      }
-    if (h->split_gemm && !(h->split_gemm_skip & 128)) {      // the 1x1 convs on 7x7 maps
-      for (int m = 1; m < 3; ++m) {
-        const size_t elems = (size_t)kConvs[kMerged[m].main_id].Co * (kConvs[kMerged[m].main_id].Ci + kConvs[kMerged[m].branch_id].Ci);
-        if (dev_alloc(h, &h->merged_ws[m], (elems * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-      }
-      if (dev_alloc(h, &h->c1_14b_ws, ((size_t)kConvs[C1_14B].Co * kConvs[C1_14B].Ci * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    }
-    if (h->wino_7x7 && h->split_gemm && !(h->split_gemm_skip & 64) &&
-        dev_alloc(h, &h->wino_u7s, ((size_t)kWino7Units * kConvs[C_T28].Co * kConvs[C_T28].Ci * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    if (h->wino_7x7 && dev_alloc(h, &h->wino_u7, (size_t)kWino7Units * kConvs[C_T28].Co * kConvs[C_T28].Ci) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    { const char* e = getenv("OFFK_CHAIN_WINO"); h->chain_wino = h->chain && !(e && *e == '0'); }
-    if (h->chain_wino)
-      for (int k = 0; k < 3; ++k)
-        if (dev_alloc(h, &h->chain_u2[k], (size_t)16 * 64 * 64) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    { const char* e = getenv("OFFK_SPLIT_CHAIN"); if (h->chain && h->winograd && h->f32split && !(e && *e == '0')) {      // (h->winograd: finalize_wino packs them)
-      const size_t elems[4] = {(size_t)64 * 256, (size_t)64 * 576, (size_t)256 * 64, (size_t)256 * 64};
-      for (int k = 0; k < 3; ++k)
-        for (int q = 0; q < (k == 0 ? 4 : 3); ++q)
-          if (dev_alloc(h, &h->chain_ws[k][q], (elems[q] * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    } }
-    { const char* e = getenv("OFFK_SPLIT_MID"); if (h->wino_mid && h->winograd && h->f32split && !(e && *e == '0')) {
-      const ConvId midc[2] = {C1_14A, C1_7};
-      for (int k = 0; k < 2; ++k)
-        if (dev_alloc(h, &h->mid_ws[k], ((size_t)kConvs[midc[k]].Co * kConvs[midc[k]].Ci * 3 + 1) / 2) != OFFK_OK) { g_err = h->err; offk_destroy(h); return OFFK_ERR_HIP; }
-    } }
+  h->chain_wino = h->winograd && h->chain && path_switch("OFFK_CHAIN_WINO");
+  for (const DerivedRow& r : kDerived)
+    if (rc == OFFK_OK && derived_exists(h, r)) rc = dev_alloc(h, &(h->derived[r.slot].*r.image), derived_floats(h, r));
+  if (rc != OFFK_OK) {
+    g_err = h->err;
+    offk_destroy(h);
+    return rc;
   }
   plan_workspace(h);
   *out = h;
@@ -1071,7 +1387,7 @@ int offk_set_weight(offk_handle* h, const char* key, const float* data, const in
     }
   }
   if (s.kind == SK_CONV_W || s.kind == SK_CONV_B) h->merged_dirty = true;
-  if (s.kind == SK_CONV_W) h->wino_dirty = true;
+  if (s.kind == SK_CONV_W) h->derived_dirty = true;
   if (s.kind == SK_GEN_W || s.kind == SK_DOWN_W) h->pw_dirty = true;
   return rc;
 }
@@ -1349,296 +1665,15 @@ static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts fea
   TRY(check_ready(h));
   DeviceGuard guard(h->cfg.device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  void* ws = workspace;
-  const int P = h->P, ncls = h->cfg.num_classes;
-
-  hipEvent_t* ev = nullptr;
-  if (h->profiling == 1) {
-    const size_t per = OFFK_NUM_STAGES + 1;
-    if ((h->ev_used + 1) * per > h->events.size() && h->events.size() < 4096 * per) {
-      for (size_t i = 0; i < per; ++i) {
-        hipEvent_t e;
-        HIP_TRY(h, hipEventCreate(&e));
-        h->events.push_back(e);
-      }
-    }
-    if ((h->ev_used + 1) * per <= h->events.size()) ev = &h->events[h->ev_used++ * per];
-  }
-
-  if (cl) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype, true));       // (check_feat: fused_units, whatever cfg.feat_layout)
-  else if (h->fused_units && h->cfg.feat_layout != OFFK_FEAT_NHWC) TRY(run_off_units_fused(h, st, feats, ws, ev, feat_dtype));
-  else TRY(run_off_units(h, st, feats, ws, ev, h->cfg.feat_layout == OFFK_FEAT_NHWC));
-
-  h->cur_splitk = region(h, ws, "splitk");
-  float* F28 = region(h, ws, "fusion_28");
-  float* F14 = region(h, ws, "fusion_14");
-  float* F7 = region(h, ws, "fusion_7");
-  const int RI = OFFK_CONV_RELU_IN_, RP = OFFK_CONV_RELU_PRE_, RO = OFFK_CONV_RELU_POST_;
-
+  Fwd f;
+  TRY(f.init(h, st, workspace, out7, out14, out28));
+  TRY(f.units(feats, feat_dtype, cl));
   TRY(finalize_merged(h, st));
-  TRY(finalize_wino(h, st));
-  const bool cons = h->cfg.consensus == OFFK_CONSENSUS_AVG;
-  float* l7 = cons ? region(h, ws, "logit_7") : out7;
-  float* l14 = cons ? region(h, ws, "logit_14") : out14;
-  float* l28 = cons ? region(h, ws, "logit_28") : out28;
-  const int n = P;                 // every launch below covers all P pairs (the buffers are pair-major)
-  hipStream_t s = st;
-  // pool_kernel + fc_kernel: the heads of the paths that cannot fold the average pool into the producing conv (LDS-patch tiles
-  // of the bf16x3 plans, OFFK_FOLD_POOL=0)
-  auto run_head = [&](int k, const float* x, int x_cs, int x_coff, int Hh, int C, int maxpool, const char* pooled_name,
-                      float* logits) -> int {
-    float* pooled = region(h, ws, pooled_name);
-    { int rc = trace_mark(h, s, k == 0 ? "head_7 (pool + fc)" : k == 1 ? "head_28 (pool + fc)" : "head_14 (pool + fc)"); if (rc != OFFK_OK) return rc; }
-    hipError_t e = pool_launch(x, x_cs, x_coff, n, Hh, Hh, C, maxpool, pooled, s);
-    if (e == hipSuccess) e = fc_launch(pooled, n, C, h->fc_w[k], h->fc_b[k], ncls, logits, s);
-    if (e != hipSuccess) return fail_hip(h, e, "head");
-    return OFFK_OK;
-  };
-  // the folded-pool FCs of the heads are collected and launched together behind the last stage (heads.hip: fc_pooled_multi_kernel)
-  FcPooledJobs fcj{};
-  fcj.n_img = n; fcj.ncls = ncls;
-  auto fc_pooled_later = [&](const float* part, int hw, int tiles, int C, int k, float* logits) {
-    fcj.job[fcj.njobs++] = FcPooledJob{part, hw, tiles, C, h->fc_w[k], h->fc_b[k], logits};
-  };
-  float *xt = region(h, ws, "xt_28"), *t1 = region(h, ws, "t1_28");
-  float *sa = region(h, ws, "sa_28"), *sb = region(h, ws, "sb_28");
-  float *xu = region(h, ws, "xu_14"), *u1 = region(h, ws, "u1_14"), *s14 = region(h, ws, "sa_14");   // xu = [u2 | x1]
-  float *xv = region(h, ws, "xv_7"), *v1 = region(h, ws, "v1_7"), *s7 = region(h, ws, "sum_7");   // xv = [v2 | x2]
-  // the batched GEMMs of a conv on a Winograd path: ONE launch of the 1x1 kernel, the K groups ride on gridDim.y (four launches
-  // left the short groups alone on the chip: slower than not skipping their zero products)
-  auto wino_gemms = [&](const char* key, const WinoGroup* grp, int ngrp, int npoints, int rows, int Ci, int Co, const float* V,
-                        const float* U, float* M) -> int {
-    const char* why = nullptr;
-    const void* planes = nullptr;
-    for (int k = 0; k < 6; ++k) if (U == h->wino_u[k]) planes = h->wino_us[k];
-    if (U == h->wino_u7) planes = h->wino_u7s;
-    hipError_t e = wino_gemms_launch(grp, ngrp, npoints, rows, Ci, Co, V, U, M, h->wino_gemm, s, &why, planes);
-    if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(key) + " (winograd): " + (why ? why : hipGetErrorString(e)));
-    return OFFK_OK;
-  };
-  // 3x3 / stride 1 conv on 7x7 maps (phases = 1) or the 5x5 / stride 2 conv on 14x14 maps in polyphase form (phases = 4) on the
-  // Winograd path: input transform, batched GEMMs, output transform with the conv's epilogue (winograd.hip)
-  const bool wino = h->winograd;
-  float* const wino_V = wino ? region(h, ws, "wino_v") : nullptr;
-  float* const wino_M = wino ? region(h, ws, "wino_m") : nullptr;
-  // the three steps of a conv on that path: V = B^T x B (wino_V), M = V U per point (wino_M), y = epilogue(A^T M A)
-  auto wino_in = [&](ConvId id, View x) -> int {
-    const ConvSpec& c = kConvs[id];
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: input transform]").c_str()));
-    HIP_TRY(h, wino_input_launch(x.p, x.cs, x.coff, n, c.Ci, c.K == 5 ? 4 : 1, wino_V, s));
-    return OFFK_OK;
-  };
-  auto wino_mm = [&](ConvId id, int uidx) -> int {
-    const ConvSpec& c = kConvs[id];
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: 121 GEMMs]").c_str()));
-    WinoGroup grp[4];
-    const int ngrp = wino_groups(c.K == 5 ? 4 : 1, n, c.Ci, c.Co, grp);
-    return wino_gemms(c.key, grp, ngrp, kWinoPoints, n, c.Ci, c.Co, wino_V, h->wino_u[uidx], wino_M);
-  };
-  auto wino_out = [&](ConvId id, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t) -> int {
-    const ConvSpec& c = kConvs[id];
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: output transform]").c_str()));
-    HIP_TRY(h, wino_output_launch(wino_M, n, c.Co, c.K == 5 ? 4 : 1, h->conv_b[id], res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t, s));
-    return OFFK_OK;
-  };
-  auto wino_conv = [&](ConvId id, int uidx, View x, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs,
-                       int y_coff, float* pool_t) -> int {
-    TRY(wino_in(id, x));
-    TRY(wino_mm(id, uidx));
-    return wino_out(id, res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t);
-  };
-  // What sits between two convs on that path, in ONE launch (wino_mid.hip): the output transform (+ bias, ReLU) of conv `a` from
-  // wino_M, optionally the 1x1 conv `mid` (+ bias, ReLU), the input transform of the conv behind into wino_V.  xa: where the
-  // activation of conv `a` is ALSO stored (the merged convs read x1 / x2 from there later); nullptr: nowhere.
-  auto wino_between = [&](ConvId a, const ConvId* mid, float* xa, int xa_cs, int xa_coff, const char* name) -> int {
-    WinoMidArgs m;
-    m.M = wino_M; m.bias_in = h->conv_b[a]; m.phases_in = kConvs[a].K == 5 ? 4 : 1;
-    m.x = xa; m.x_cs = xa_cs; m.x_coff = xa_coff;
-    m.w1 = mid ? h->conv_w[*mid] : nullptr; m.b1 = mid ? h->conv_b[*mid] : nullptr;
-    m.Cin = kConvs[a].Co; m.Cmid = mid ? kConvs[*mid].Co : kConvs[a].Co; m.n_img = n;
-    m.V = wino_V;
-    if (mid) m.w1p = *mid == C1_14A ? h->mid_ws[0] : *mid == C1_7 ? h->mid_ws[1] : nullptr;
-    TRY(trace_mark(h, s, name));
-    HIP_TRY(h, wino_mid_launch(m, s));
-    return OFFK_OK;
-  };
-  const bool mid = wino && h->wino_mid;
-  // ---- fusion @28 -> 14x14 (RGB_OFF.py:655-685) -----------------------------------
-  // xt = [t2 | x0] per pixel: c3(t2) + branch(x0) (:663-666) is then ONE 1x1 conv over 128 channels
-  // :657 x0, pre-ReLU kept for the branch.  fp32: polyphase Winograd F(5x5, 4x4) (winograd7.hip) -- input transform, 64 batched
-  // GEMMs in four K groups as ONE launch of the 1x1 kernel, output transform
-  // (from P = 12 pairs -- B = 2: 0.495 against 0.503 ms, B = 8: 0.813 against 0.874, B = 64: 3.88 against 4.24; B = 1: equal)
-  if (h->wino_u7 && wino && h->wino_7x7 && P >= h->wino7_min_p) {
-    const ConvSpec& c = kConvs[C_T28];
-    const int T = kWino7Tiles * n;
-    // (the input transform INSIDE the GEMM kernel was built and measured in round 4 -- tools/experiments/winograd7_fused.hip, out of the
-    //  product build since round 5: 0.84 ms against 0.54 ms for these two launches; profiles/r04/wino7_fused_attempt.txt)
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: input transform]").c_str()));
-    HIP_TRY(h, wino7_input_launch(F28, 320, 0, n, c.Ci, wino_V, s));
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: 64 GEMMs]").c_str()));
-    WinoGroup grp[4];
-    const int ngrp = wino7_groups(T, c.Ci, c.Co, grp);
-    TRY(wino_gemms(c.key, grp, ngrp, kWino7Points, T, c.Ci, c.Co, wino_V, h->wino_u7, wino_M));
-    TRY(trace_mark(h, s, (std::string(c.key) + " [winograd: output transform]").c_str()));
-    HIP_TRY(h, wino7_output_launch(wino_M, n, c.Co, h->conv_b[C_T28], 0, xt, 128, 64, s));
-  } else {
-    TRY(conv(h, s, C_T28, n, 28, View{F28, 320, 0}, nullptr, 0, 0, 0, xt, 128, 64));
-  }
-  // 1x1 -> 3x3 -> 1x1 (+ residual) as ONE launch per chain (a block owns half an image, t1 / t2 stay in LDS)
-  bool split_branch = false;
-  auto chain = [&](const char* name, const float* x, int x_cs, int x_coff, int Cin, int relu_in, ConvId c1, ConvId c2,
-                   const float* w3, const float* b3, int K3, const float* res, float* y, int y_cs, int y_coff) -> int {
-    ChainArgs a;
-    a.x = x; a.x_cs = x_cs; a.x_coff = x_coff; a.Cin = Cin; a.relu_in = relu_in;
-    a.w1 = h->conv_w[c1]; a.b1 = h->conv_b[c1]; a.w2 = h->conv_w[c2]; a.b2 = h->conv_b[c2];
-    a.u2 = h->chain_wino ? h->chain_u2[c2 == C2_28A ? 0 : c2 == C2_28B ? 1 : 2] : nullptr;
-    a.w3 = w3; a.b3 = b3; a.K3 = K3;
-    a.res = res; a.res_cs = 256; a.res_coff = 0;
-    a.y = y; a.y_cs = y_cs; a.y_coff = y_coff;
-    a.n_img = n; a.relu_out = 1;
-    const unsigned long long xb = ((unsigned long long)n * 196 * x_cs - x_coff) * 4ull;
-    a.x_bytes = xb < 0x7fffffffull ? (unsigned)xb : 0u;
-    { int rc = trace_mark(h, s, name); if (rc != OFFK_OK) return rc; }
-    const char* why = nullptr;
-    const int ck = c2 == C2_28A ? 0 : c2 == C2_28B ? 1 : 2;
-    a.w1p = h->chain_ws[ck][0]; a.w2p = h->chain_ws[ck][1]; a.w3p = h->chain_ws[ck][2];
-    if (split_branch) { a.wbp = h->chain_ws[0][3]; a.bbr = h->conv_b[CB_28A]; }
-    hipError_t e = chain14_split_supported(a) ? chain14_split_launch(a, s, &why) : chain14_launch(a, s, &why);
-    if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(name) + ": " + (why ? why : hipGetErrorString(e)));
-    return OFFK_OK;
-  };
-  // (from P = 72 pairs: a chain block walks its three convs alone -- 45 us per launch however few blocks there are; B = 8: three
-  //  convs per chain 0.885 ms per forward against 0.90, B = 16: 1.37 against 1.345; OFFK_CHAIN=<pairs> moves the gate)
-  const bool chained = h->chain && P >= h->chain_min_p && (unsigned long long)n * 196 * 256 * 4ull < 0x7fffffffull;
-  if (chained) {
-    if (h->chain_ws[0][3]) {
-      // split-fp32 (chain_split.hip, BR form): c3 with K3 = 64, the branch 1x1 on the pre-ReLU chain input inside the kernel (its output
-      // passes through y as the chain's residual) -- RGB_OFF.py:663-667; in the fp32 kernel the branch is merged into c3's K
-      split_branch = true;
-      TRY(chain("chain_28a = motion_conv1_trans_28a + motion_conv2_trans_28a + merged_28a", xt, 128, 64, 64, 1, C1_28A, C2_28A, h->conv_w[C3_28A],
-                h->conv_b[C3_28A], 64, nullptr, sa, 256, 0));
-      split_branch = false;
-    } else {
-      TRY(chain("chain_28a = motion_conv1_trans_28a + motion_conv2_trans_28a + merged_28a", xt, 128, 64, 64, 1, C1_28A, C2_28A, h->merged_w[0], h->merged_b[0], 128,
-                nullptr, sa, 256, 0));                                                              // :658-667
-    }
-    TRY(chain("chain_28b = motion_conv1_trans_28b + motion_conv2_trans_28b + motion_conv3_trans_28b", sa, 256, 0, 256, 0, C1_28B, C2_28B, h->conv_w[C3_28B], h->conv_b[C3_28B], 64, sa, sb, 256, 0));   // :670-676
-    TRY(chain("chain_28c = motion_conv1_trans_28c + motion_conv2_trans_28c + motion_conv3_trans_28c", sb, 256, 0, 256, 0, C1_28C, C2_28C, h->conv_w[C3_28C], h->conv_b[C3_28C], 64, sb, F14, 1056, 800)); // :679-685 -> cat at :760
-  } else {
-    TRY(conv(h, s, C1_28A, n, 14, View{xt, 128, 64}, nullptr, 0, 0, RI | RP, t1, 64, 0));         // :658-660
-    TRY(conv(h, s, C2_28A, n, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));               // :661-662 t2
-    TRY(conv_merged(h, s, 0, n, 14, View{xt, 128, 0}, RO, sa, 256, 0));                            // :663-667
-    TRY(conv(h, s, C1_28B, n, 14, View{sa, 256, 0}, nullptr, 0, 0, RP, t1, 64, 0));               // :670-671
-    TRY(conv(h, s, C2_28B, n, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));               // :672-673
-    TRY(conv(h, s, C3_28B, n, 14, View{xt, 128, 0}, sa, 256, 0, RO, sb, 256, 0));                  // :674-676
-    TRY(conv(h, s, C1_28C, n, 14, View{sb, 256, 0}, nullptr, 0, 0, RP, t1, 64, 0));               // :679-680
-    TRY(conv(h, s, C2_28C, n, 14, View{t1, 64, 0}, nullptr, 0, 0, RP, xt, 128, 0));               // :681-682
-    TRY(conv(h, s, C3_28C, n, 14, View{xt, 128, 0}, sb, 256, 0, RO, F14, 1056, 800));              // :683-685 -> cat at :760
-  }
-  if (ev) HIP_TRY(h, hipEventRecord(ev[3], s));
-  if (out28) {   // 28-head (:782-787): only reads sum_28c
-    if (h->fold_pool) {     // pool-row partial sums + the FC as an MFMA GEMM (heads.hip) instead of pool_kernel + fc_kernel
-      float* pp = region(h, ws, "poolpart_28");
-      TRY(trace_mark(h, s, "head_28 (max pool rows)"));
-      HIP_TRY(h, maxpool_rows_launch(F14, 1056, 800, n, 14, 14, 256, pp, s));
-      fc_pooled_later(pp, 49, 1, 256, 1, l28);
-    } else {
-      TRY(run_head(1, F14, 1056, 800, 14, 256, 1, "pooled_28", l28));
-    }
-  }
-  // ---- fusion @14 -> 7x7 (RGB_OFF.py:759-780) ---------------------------------------
-  // (from P = 40 pairs: below, its 132-K-tile GEMMs have too few row tiles to fill the chip and the split-K direct conv wins --
-  // B = 1: 0.435 vs 0.50 ms, B = 4: 0.672 vs 0.695, B = 8: 0.892 vs 0.874, B = 12: 1.157 vs 1.12; OFFK_WINOGRAD_5X5=<pairs> moves the gate)
-  const bool w5 = wino && h->wino_5x5 && P >= h->wino5_min_p;
-  if (w5 && mid) {      // :762-767: x1 = relu(conv5x5(F14)) -> c1_14a -> c2_14a, the 1x1 conv between the two Winograd GEMM launches
-    const ConvId c1 = C1_14A;
-    TRY(wino_in(C_T14, View{F14, 1056, 0}));
-    TRY(wino_mm(C_T14, 5));
-    TRY(wino_between(C_T14, &c1, xu, 256, 128, "motion_conv_trans_14 out + motion_conv1_trans_14a + motion_conv2_trans_14a in [winograd: between]"));
-    TRY(wino_mm(C2_14A, 3));
-    TRY(wino_out(C2_14A, nullptr, 0, 0, RP, xu, 256, 0, nullptr));                                 // :766-767 u2
-  } else {
-    if (w5) TRY(wino_conv(C_T14, 5, View{F14, 1056, 0}, nullptr, 0, 0, RP, xu, 256, 128, nullptr));   // :762-763 x1 (polyphase)
-    else TRY(conv(h, s, C_T14, n, 14, View{F14, 1056, 0}, nullptr, 0, 0, RP, xu, 256, 128));      // :762-763 x1
-    TRY(conv(h, s, C1_14A, n, 7, View{xu, 256, 128}, nullptr, 0, 0, RP, u1, 128, 0));             // :764-765
-    if (wino) TRY(wino_conv(C2_14A, 3, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0, nullptr));  // :766-767 u2
-    else TRY(conv(h, s, C2_14A, n, 7, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0));          // :766-767 u2
-  }
-  TRY(conv_merged(h, s, 1, n, 7, View{xu, 256, 0}, RO, s14, 512, 0));                              // :768-771
-  TRY(conv(h, s, C1_14B, n, 7, View{s14, 512, 0}, nullptr, 0, 0, RP, u1, 128, 0));                // :773-774
-  if (mid) {            // :775-780: c2_14b's output feeds c3_14b alone -- output transform, ReLU and input transform in one launch
-    TRY(wino_in(C2_14B, View{u1, 128, 0}));
-    TRY(wino_mm(C2_14B, 4));
-    TRY(wino_between(C2_14B, nullptr, nullptr, 0, 0, "motion_conv2_trans_14b out + motion_conv3_trans_14b in [winograd: between]"));
-  } else if (wino) TRY(wino_conv(C2_14B, 4, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0, nullptr));  // :775-776
-  else TRY(conv(h, s, C2_14B, n, 7, View{u1, 128, 0}, nullptr, 0, 0, RP, xu, 256, 0));            // :775-776
-  // (fold: the conv's epilogue also leaves per-slab column sums of sum_14b: the 14-head's average pool)
-  auto generic = [](int cfg) { return cfg != 6 && cfg != 7 && cfg != 10; };      // the LDS-patch kernels have no pooling epilogue
-  const bool fold = h->fold_pool && generic(h->conv_cfg[C3_14B]) && generic(h->merged_cfg[2]);
-  float* pp14 = region(h, ws, "poolpart_14");
-  float* pp7 = region(h, ws, "poolpart_7");
-  float* pp14t = wino ? region(h, ws, "poolpart_14t") : nullptr;
-  const bool fold14t = wino && h->fold_pool;
-  if (mid) {
-    TRY(wino_mm(C3_14B, 0));
-    TRY(wino_out(C3_14B, s14, 512, 0, RP | RO, F7, 832, 320, fold14t ? pp14t : nullptr));          // :777-780 -> cat at :832
-  } else if (wino) {
-    TRY(wino_conv(C3_14B, 0, View{xu, 256, 0}, s14, 512, 0, RP | RO, F7, 832, 320, fold14t ? pp14t : nullptr));   // :777-780 -> cat at :832
-  } else {
-    h->cur_pool_part = fold ? pp14 : nullptr;
-    int rc_ = conv(h, s, C3_14B, n, 7, View{xu, 256, 0}, s14, 512, 0, RP | RO, F7, 832, 320);   // :777-780 -> cat at :832
-    h->cur_pool_part = nullptr;
-    if (rc_ != OFFK_OK) return rc_;
-  }
-  if (ev) HIP_TRY(h, hipEventRecord(ev[4], s));
-  // 14-head (:789-793): only reads sum_14b
-  if (fold14t) {
-    fc_pooled_later(pp14t, 49, 1, 512, 2, l14);
-  } else if (fold && !wino) {
-    fc_pooled_later(pp14, 49, 0, 512, 2, l14);
-  } else {
-    TRY(run_head(2, F7, 832, 320, 7, 512, 0, "pooled_14", l14));
-  }
-  // ---- fusion @7 (RGB_OFF.py:831-841) -------------------------------------------------
-  if (mid) {            // :833-838: x2 = relu(conv3x3(F7)) -> c1 -> c2, as fusion@14's first three convs
-    const ConvId c1 = C1_7;
-    TRY(wino_in(C_T7, View{F7, 832, 0}));
-    TRY(wino_mm(C_T7, 1));
-    TRY(wino_between(C_T7, &c1, xv, 512, 256, "motion_conv_trans out + motion_conv1_trans + motion_conv2_trans in [winograd: between]"));
-    TRY(wino_mm(C2_7, 2));
-    TRY(wino_out(C2_7, nullptr, 0, 0, RP, xv, 512, 0, nullptr));                                   // :837-838 v2
-  } else {
-    if (wino) TRY(wino_conv(C_T7, 1, View{F7, 832, 0}, nullptr, 0, 0, RP, xv, 512, 256, nullptr));  // :833-834 x2
-    else TRY(conv(h, s, C_T7, n, 7, View{F7, 832, 0}, nullptr, 0, 0, RP, xv, 512, 256));          // :833-834 x2
-    TRY(conv(h, s, C1_7, n, 7, View{xv, 512, 256}, nullptr, 0, 0, RP, v1, 256, 0));               // :835-836
-    if (wino) TRY(wino_conv(C2_7, 2, View{v1, 256, 0}, nullptr, 0, 0, RP, xv, 512, 0, nullptr));  // :837-838 v2
-    else TRY(conv(h, s, C2_7, n, 7, View{v1, 256, 0}, nullptr, 0, 0, RP, xv, 512, 0));            // :837-838 v2
-  }
-  h->cur_pool_part = fold ? pp7 : nullptr;
-  { int rc_ = conv_merged(h, s, 2, n, 7, View{xv, 512, 0}, 0, s7, 1024, 0);                        // :839-841 (no ReLU)
-    h->cur_pool_part = nullptr;
-    if (rc_ != OFFK_OK) return rc_; }
-  if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
-  // ---- 7-head (:843-847)
-  if (fold) {
-    fc_pooled_later(pp7, 49, 0, 1024, 0, l7);
-  } else {
-    TRY(run_head(0, s7, 1024, 0, 7, 1024, 0, "pooled_7", l7));
-  }
-  if (fcj.njobs > 0) {
-    TRY(trace_mark(h, s, "heads (fc on folded pools, one launch)"));
-    HIP_TRY(h, fc_pooled_multi_launch(fcj, s));
-  }
-  if (cons) {
-    const int B = h->cfg.batch, T = h->cfg.length - 1;
-    TRY(trace_mark(h, st, "consensus (K6)"));
-    const float* const cx[3] = {l7, l14, out28 ? l28 : l14};                                      // Flow_OFF.py:874-876, one launch
-    float* const co[3] = {out7, out14, out28 ? out28 : out14};
-    HIP_TRY(h, consensus_multi_launch(cx, co, out28 ? 3 : 2, B, T, ncls, st));
-  }
-  if (ev) HIP_TRY(h, hipEventRecord(ev[6], st));
-  TRY(trace_mark(h, st, nullptr));
-  return OFFK_OK;
+  TRY(finalize_derived(h, st));
+  TRY(f.fusion28());
+  TRY(f.fusion14());
+  TRY(f.fusion7());
+  return f.heads();
 }
 
 // ---- training side of the OFF units -----------------------------------
@@ -1821,14 +1856,8 @@ int offk_conv2d(void* stream, const float* x, int x_cstride, int x_coff, int n_i
                 const float* bias, int Co, int KH, int KW, int stride, int pad, const float* res, int res_cstride,
                 int res_coff, int flags, float* y, int y_cstride, int y_coff) {
   if (!x || !w || !y || n_img < 1 || H < 1 || W < 1) return fail(nullptr, OFFK_ERR_INVALID, "offk_conv2d: bad argument");
-  ConvDesc d;
-  d.x = x; d.x_cs = x_cstride; d.x_coff = x_coff; d.n_img = n_img; d.H = H; d.W = W; d.Ci = Ci;
-  d.w = w; d.bias = bias; d.Co = Co; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad;
-  d.res = res; d.res_cs = res_cstride; d.res_coff = res_coff; d.flags = flags; d.y = y; d.y_cs = y_cstride; d.y_coff = y_coff;
-  const char* why = nullptr;
-  hipError_t e = conv2d_launch(d, static_cast<hipStream_t>(stream), &why);
-  if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, why ? why : hipGetErrorString(e));
-  return OFFK_OK;
+  return offk_conv2d_ex(stream, x, x_cstride, x_coff, n_img, H, W, Ci, w, bias, Co, KH, KW, stride, pad, res, res_cstride, res_coff, flags, y,
+                        y_cstride, y_coff, -1, 0, nullptr, 0, 0);      // ConvDesc's own defaults
 }
 
 int offk_conv2d_ex(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int Ci, const float* w,
@@ -1836,12 +1865,8 @@ int offk_conv2d_ex(void* stream, const float* x, int x_cstride, int x_coff, int 
                    int res_coff, int flags, float* y, int y_cstride, int y_coff, int tile_cfg, int splitk, float* partial,
                    size_t partial_floats, int precision) {
   if (!x || !w || !y || n_img < 1 || H < 1 || W < 1) return fail(nullptr, OFFK_ERR_INVALID, "offk_conv2d_ex: bad argument");
-  ConvDesc d;
-  d.x = x; d.x_cs = x_cstride; d.x_coff = x_coff; d.n_img = n_img; d.H = H; d.W = W; d.Ci = Ci;
-  d.w = w; d.bias = bias; d.Co = Co; d.KH = KH; d.KW = KW; d.stride = stride; d.pad = pad;
-  d.res = res; d.res_cs = res_cstride; d.res_coff = res_coff; d.flags = flags; d.y = y; d.y_cs = y_cstride; d.y_coff = y_coff;
-  d.tile_cfg = tile_cfg; d.splitk = splitk; d.partial = partial; d.partial_floats = partial_floats;
-  d.precision = precision;
+  const ConvDesc d = conv_desc(x, x_cstride, x_coff, n_img, H, W, Ci, w, bias, Co, KH, KW, stride, pad, res, res_cstride, res_coff, flags, y,
+                               y_cstride, y_coff, tile_cfg, splitk, partial, partial_floats, precision);
   const char* why = nullptr;
   hipError_t e = conv2d_launch(d, static_cast<hipStream_t>(stream), &why);
   if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, why ? why : hipGetErrorString(e));
@@ -1854,14 +1879,9 @@ int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_c
                             int y_coff) {
   if (!x || !w1 || !b1 || !w2_packed || !b2 || !w3 || !b3 || !y || n_img < 1)
     return fail(nullptr, OFFK_ERR_INVALID, "offk_bottleneck_chain14: bad argument");
-  ChainArgs a;
-  a.u2 = nullptr;     // (the stage entry point runs the direct 3x3: it has no place for transformed weights)
-  a.x = x; a.x_cs = x_cstride; a.x_coff = x_coff; a.Cin = Cin; a.relu_in = relu_in ? 1 : 0;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2_packed; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.K3 = K3;
-  a.res = res; a.res_cs = res_cstride; a.res_coff = res_coff; a.y = y; a.y_cs = y_cstride; a.y_coff = y_coff;
-  a.n_img = n_img; a.relu_out = 1;
-  const unsigned long long xb = ((unsigned long long)n_img * 196 * x_cstride - x_coff) * 4ull;
-  a.x_bytes = xb < 0x7fffffffull ? (unsigned)xb : 0u;
+  // (u2 stays nullptr: the stage entry point runs the direct 3x3, it has no place for transformed weights)
+  const ChainArgs a = chain_args(x, x_cstride, x_coff, n_img, Cin, relu_in, w1, b1, w2_packed, b2, w3, b3, K3, res, res_cstride, res_coff, y,
+                                 y_cstride, y_coff);
   const char* why = nullptr;
   hipError_t e = chain14_launch(a, static_cast<hipStream_t>(stream), &why);
   if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, why ? why : hipGetErrorString(e));
@@ -1896,14 +1916,8 @@ int offk_bottleneck_chain14_split(void* stream, const float* x, int x_cstride, i
   if (scratch_bytes < 6 * (e1 + e2 + 2 * e3)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* sp = static_cast<char*>(scratch);
-  ChainArgs a;
-  a.u2 = nullptr;
-  a.x = x; a.x_cs = x_cstride; a.x_coff = x_coff; a.Cin = Cin; a.relu_in = relu_in ? 1 : 0;
-  a.w1 = w1; a.b1 = b1; a.w2 = w2_packed; a.b2 = b2; a.w3 = w3; a.b3 = b3; a.K3 = 64;
-  a.res = res; a.res_cs = res_cstride; a.res_coff = res_coff; a.y = y; a.y_cs = y_cstride; a.y_coff = y_coff;
-  a.n_img = n_img; a.relu_out = 1;
-  const unsigned long long xb = ((unsigned long long)n_img * 196 * x_cstride - x_coff) * 4ull;
-  a.x_bytes = xb < 0x7fffffffull ? (unsigned)xb : 0u;
+  ChainArgs a = chain_args(x, x_cstride, x_coff, n_img, Cin, relu_in, w1, b1, w2_packed, b2, w3, b3, 64, res, res_cstride, res_coff, y, y_cstride,
+                           y_coff);
   a.w1p = sp; a.w2p = sp + 6 * e1; a.w3p = sp + 6 * (e1 + e2);
   hipError_t e = wino_pack_split_launch(w1, const_cast<void*>(a.w1p), 64, Cin, 1, st);
   if (e == hipSuccess) e = wino_pack_split_launch(w2_packed, const_cast<void*>(a.w2p), 64, 576, 1, st);
@@ -1920,30 +1934,34 @@ int offk_bottleneck_chain14_split(void* stream, const float* x, int x_cstride, i
 }
 
 namespace {
-// shared body of the two Winograd entry points: phases = 1 (3x3 / stride 1 on 7x7) or 4 (polyphase 5x5 / stride 2 on 14x14)
+// shared body of the three Winograd entry points: phases = 1 (3x3 / stride 1 on 7x7), 4 (polyphase 5x5 / stride 2 on 14x14) -- winograd.hip --
+// or 7: the polyphase 7x7 / stride 2 conv on 28x28 maps, nine tiles per image (winograd7.hip; no residual, no pooled sums)
 int winograd_entry(const char* who, void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Ci, int phases,
                    const float* w_packed, const float* bias, int Co, const float* res, int res_cstride, int res_coff, int flags,
                    float* y, int y_cstride, int y_coff, float* scratch, size_t scratch_floats, float* pool_part) {
   if (!x || !w_packed || !y || !scratch || n_img < 1 || Ci < 32 || (Ci & 31) || Co < 64 || (Co & 63) || (flags & OFFK_CONV_RELU_IN_))
     return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (Ci % 32 == 0, Co % 64 == 0, no RELU_IN)");
-  const size_t T = (size_t)n_img, units = phases == 4 ? kWinoUnits4 : kWinoPoints;      // rows per batch entry; row-Ci units of U / V
-  const size_t need = units * Ci * ((size_t)Co + T) + (size_t)kWinoPoints * T * Co;
+  const bool f54 = phases == 7;
+  const size_t T = f54 ? (size_t)kWino7Tiles * n_img : (size_t)n_img;      // rows per batch entry
+  const size_t units = f54 ? kWino7Units : phases == 4 ? kWinoUnits4 : kWinoPoints, points = f54 ? kWino7Points : kWinoPoints;   // row-Ci units of U / V
+  const size_t need = units * Ci * ((size_t)Co + T) + points * T * Co;
   if (scratch_floats < need) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small");
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* U = scratch;
   float* V = U + units * Co * Ci;
   float* M = V + units * T * Ci;
-  hipError_t e = wino_weight_launch(w_packed, Co, Ci, phases, U, st);
-  if (e == hipSuccess) e = wino_input_launch(x, x_cstride, x_coff, n_img, Ci, phases, V, st);
+  hipError_t e = f54 ? wino7_weight_launch(w_packed, Co, Ci, U, st) : wino_weight_launch(w_packed, Co, Ci, phases, U, st);
+  if (e == hipSuccess) e = f54 ? wino7_input_launch(x, x_cstride, x_coff, n_img, Ci, V, st) : wino_input_launch(x, x_cstride, x_coff, n_img, Ci, phases, V, st);
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
   WinoGroup grp[4];
-  const int ngrp = wino_groups(phases, (long long)T, Ci, Co, grp);
+  const int ngrp = f54 ? wino7_groups((long long)T, Ci, Co, grp) : wino_groups(phases, (long long)T, Ci, Co, grp);
   {
     const char* why = nullptr;
-    e = wino_gemms_launch(grp, ngrp, kWinoPoints, (int)T, Ci, Co, V, U, M, wino_gemm_stage_default(), st, &why);
+    e = wino_gemms_launch(grp, ngrp, (int)points, (int)T, Ci, Co, V, U, M, wino_gemm_stage_default(), st, &why);
     if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, why ? why : hipGetErrorString(e));
   }
-  e = wino_output_launch(M, n_img, Co, phases, bias, res, res_cstride, res_coff, flags, y, y_cstride, y_coff, pool_part, st);
+  e = f54 ? wino7_output_launch(M, n_img, Co, bias, flags, y, y_cstride, y_coff, st)
+          : wino_output_launch(M, n_img, Co, phases, bias, res, res_cstride, res_coff, flags, y, y_cstride, y_coff, pool_part, st);
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
   return OFFK_OK;
 }
@@ -1966,27 +1984,8 @@ int offk_winograd_conv5x5s2(void* stream, const float* x, int x_cstride, int x_c
 int offk_winograd_conv7x7s2(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Ci, const float* w_packed,
                             const float* bias, int Co, int flags, float* y, int y_cstride, int y_coff, float* scratch,
                             size_t scratch_floats) {
-  const char* who = "offk_winograd_conv7x7s2";
-  if (!x || !w_packed || !y || !scratch || n_img < 1 || Ci < 32 || (Ci & 31) || Co < 64 || (Co & 63) || (flags & OFFK_CONV_RELU_IN_))
-    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (Ci % 32 == 0, Co % 64 == 0, no RELU_IN)");
-  const size_t T = (size_t)kWino7Tiles * n_img;
-  const size_t need = (size_t)kWino7Units * Ci * (Co + T) + (size_t)kWino7Points * T * Co;
-  if (scratch_floats < need) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* U = scratch;
-  float* V = U + (size_t)kWino7Units * Co * Ci;
-  float* M = V + (size_t)kWino7Units * T * Ci;
-  hipError_t e = wino7_weight_launch(w_packed, Co, Ci, U, st);
-  if (e == hipSuccess) e = wino7_input_launch(x, x_cstride, x_coff, n_img, Ci, V, st);
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  WinoGroup grp[4];
-  const int ngrp = wino7_groups((long long)T, Ci, Co, grp);
-  const char* why = nullptr;
-  e = wino_gemms_launch(grp, ngrp, kWino7Points, (int)T, Ci, Co, V, U, M, wino_gemm_stage_default(), st, &why);
-  if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, why ? why : hipGetErrorString(e));
-  e = wino7_output_launch(M, n_img, Co, bias, flags, y, y_cstride, y_coff, st);
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return winograd_entry("offk_winograd_conv7x7s2", stream, x, x_cstride, x_coff, n_img, Ci, 7, w_packed, bias, Co, nullptr, 0, 0, flags, y, y_cstride,
+                        y_coff, scratch, scratch_floats, nullptr);
 }
 
 int offk_winograd_between(void* stream, const float* M, const float* bias_in, int phases_in, int n_img, int Cin, float* x,
@@ -1996,10 +1995,7 @@ int offk_winograd_between(void* stream, const float* M, const float* bias_in, in
     return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument");
   if (!wino_mid_supported(Cin, Cmid, w1 != nullptr, phases_in))
     return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": shape not built ((Cin, Cmid) = (128, 128) / (256, 256); phases_in 1, or 4 with Cin 128)");
-  WinoMidArgs m;
-  m.M = M; m.bias_in = bias_in; m.phases_in = phases_in; m.x = x; m.x_cs = x_cstride; m.x_coff = x_coff;
-  m.w1 = w1; m.b1 = b1; m.Cin = Cin; m.Cmid = Cmid; m.n_img = n_img; m.V = V;
-  hipError_t e = wino_mid_launch(m, static_cast<hipStream_t>(stream));
+  hipError_t e = wino_mid_launch(wino_mid_args(M, bias_in, phases_in, n_img, Cin, x, x_cstride, x_coff, w1, b1, Cmid, V), static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
   return OFFK_OK;
 }
@@ -2018,10 +2014,7 @@ int offk_winograd_between_ex(void* stream, const float* M, const float* bias_in,
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = wino_pack_split_launch(w1, scratch, Cmid, Cin, 1, st);
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  WinoMidArgs m;
-  m.M = M; m.bias_in = bias_in; m.phases_in = phases_in; m.x = x; m.x_cs = x_cstride; m.x_coff = x_coff;
-  m.w1 = w1; m.b1 = b1; m.Cin = Cin; m.Cmid = Cmid; m.n_img = n_img; m.V = V; m.w1p = scratch;
-  e = wino_mid_launch(m, st);
+  e = wino_mid_launch(wino_mid_args(M, bias_in, phases_in, n_img, Cin, x, x_cstride, x_coff, w1, b1, Cmid, V, scratch), st);
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
   return OFFK_OK;
 }
