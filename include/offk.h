@@ -217,8 +217,19 @@ int offk_forward_parts_cl(offk_handle* h, void* stream, int feat_dtype, const of
                           float* out7, float* out14, float* out28, void* workspace);
 
 /* Named regions of the workspace after offk_forward (for stage-level parity tests):
- * "G_<site>", "D_<site>", "fusion_28", "fusion_14", "fusion_7", "sum_7".  All channels-last. */
+ * "G_<site>", "D_<site>", "fusion_28", "fusion_14", "fusion_7", "sum_7".  All channels-last.
+ * "sum_7" (motion_sum of RGB_OFF.py:839-841) is filled after a forward, or -- on a handle at or above the gate of
+ * OFFK_POOL_FIRST_7 (96 frame pairs by default), whose forward takes the 7-head from pooled sums of "xv_7" and never forms
+ * motion_sum -- after offk_stage_tensors. */
 int offk_workspace_region(const offk_handle* h, const char* name, size_t* offset_bytes, size_t* nbytes);
+
+/* Fills the stage tensors the last forward on `h` left out: today "sum_7" on handles that take the 7-head pool-first
+ * (RGB_OFF.py:839-847 is linear from [t2 | x2] to the logits; the merged 1x1 conv then runs only here, from "xv_7" in
+ * `workspace`, the launch and plan the forward would have used, so the bits are those of a handle below the gate).  Enqueued on
+ * `stream`, which must be ordered behind that forward.  Every forward that skipped the launch sets a pending flag on the
+ * handle, this call clears it; with nothing pending it enqueues nothing and returns OFFK_OK.  (A forward replayed from a
+ * captured graph does not pass through the library and sets no flag.) */
+int offk_stage_tensors(offk_handle* h, void* stream, void* workspace);
 
 /* Per-stage device timing.  When enabled, offk_forward brackets each stage with HIP
  * events on the caller's stream; offk_stage_times synchronises those events and

@@ -56,6 +56,7 @@ SIGNATURES = {
     "offk_forward_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _F, _F, _F, _P]),
     "offk_forward_parts_cl": (_I, [_P, _P, _I, _c.POINTER(OffkFeatParts), _F, _F, _F, _P]),
     "offk_workspace_region": (_I, [_P, _c.c_char_p, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
+    "offk_stage_tensors": (_I, [_P, _P, _P]),
     "offk_set_profiling": (_I, [_P, _I]),
     "offk_stage_times": (_I, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _I]),
     "offk_launch_times": (_I, [_P, _c.c_char_p, _c.c_size_t, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _I, _I]),

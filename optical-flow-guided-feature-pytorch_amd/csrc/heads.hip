@@ -353,6 +353,25 @@ hipError_t vec_add_launch(const float* a, const float* b, float* o, int n, hipSt
   return hipGetLastError();
 }
 
+// blockIdx.y = class, a thread = one column k of w_out (k == K: the bias); wm rows are read coalesced, fw[cls][j] is a broadcast
+__global__ __launch_bounds__(256) void head_compose_kernel(const float* __restrict__ fw, const float* __restrict__ fb, const float* __restrict__ wm,
+                                                           const float* __restrict__ bm, int Cm, int K, float* __restrict__ w_out,
+                                                           float* __restrict__ b_out) {
+  const int cls = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+  if (k > K) return;
+  const float* f = fw + (size_t)cls * Cm;
+  double acc = 0.0;
+  for (int j = 0; j < Cm; ++j) acc += (double)f[j] * (double)(k < K ? wm[(size_t)j * K + k] : bm[j]);
+  if (k < K) w_out[(size_t)cls * K + k] = (float)acc;
+  else b_out[cls] = (float)(acc + (double)fb[cls]);
+}
+hipError_t head_compose_launch(const float* fw, const float* fb, int ncls, const float* wm, const float* bm, int Cm, int K, float* w_out,
+                               float* b_out, hipStream_t st) {
+  if (ncls <= 0 || Cm <= 0 || K <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(head_compose_kernel, dim3((K + 1 + 255) / 256, ncls), dim3(256), 0, st, fw, fb, wm, bm, Cm, K, w_out, b_out);
+  return hipGetLastError();
+}
+
 __global__ void consensus_kernel(const float* __restrict__ x, int T, int C, float* __restrict__ out) {
   const int b = blockIdx.x;
   for (int c = threadIdx.x; c < C; c += blockDim.x) {

@@ -154,6 +154,7 @@ struct Derived {
   float* planes = nullptr;       // the plane image of the [Co][K] weights for the fused kernel that runs the conv: chain_split.hip (c1 / c2 in
                                  // the packed K order / c3 / the branch of chain 28a), wino_mid.hip (its 1x1 conv)
   float* gemm_planes = nullptr;  // ... for the conv as a launch of its own on wino_gemm_split.hip's kernel with its conv epilogue
+  float* head = nullptr;         // merged_7 only: the 7-head composed with it, W' = Wfc Wm [num_classes][512], then b' = Wfc bm + bfc [num_classes]
 };
 constexpr int kNumDerived = kNumConvs + 3;
 constexpr int merged_slot(int m) { return kNumConvs + m; }
@@ -226,6 +227,11 @@ struct offk_handle {
   int conv_cfg[kNumConvs];       // tile plan per fusion conv (-1 = automatic)
   int conv_splitk[kNumConvs];    // K-split per fusion conv (0 = automatic)
   size_t splitk_floats = 0;      // size of the "splitk" workspace region
+  // 7-head, pool first: motion_sum = merged_7(xv) feeds the head's average pool and FC alone and has no ReLU (RGB_OFF.py:839-847), so
+  // logits_7 = (Wfc Wm) mean49(xv) + (Wfc bm + bfc): the producers of xv_7 leave its per-tile sums, the FC launch reads those with the composed
+  // weights, and merged_7 (19.7 GFLOP at P = 384) runs only when sum_7 is asked for (offk_stage_tensors)
+  bool pool_first7 = false;      // this handle takes that path: winograd, wino_mid, fold_pool on and P >= the gate of OFFK_POOL_FIRST_7 (96 pairs)
+  bool sum7_pending = false;     // a forward skipped merged_7 and offk_stage_tensors has not run it since
   bool fold_pool = true;         // 7- / 14-head: average pool in the producing conv's epilogue + MFMA FC (OFFK_FOLD_POOL=0: pool + fc kernels)
   std::vector<void*> allocs;
   // workspace plan
@@ -359,6 +365,7 @@ void plan_workspace(offk_handle* h) {
     add_region(h, "wino_v", std::max((size_t)kWinoUnits4 * P * 1056, (size_t)kWino7Tiles * P * kWino7Units * 320));
     add_region(h, "wino_m", (size_t)kWinoPoints * P * 512);    // (7x7: 64 x 9 P x 64 is smaller)
     add_region(h, "poolpart_14t", (size_t)4 * P * 512);
+    if (h->pool_first7) add_region(h, "poolpart_7t", (size_t)4 * P * 512);      // per-tile sums of xv_7 = [v2 | x2]
   }
   // split-K partial slabs: room for 8 slices of the widest large-K conv output (7x7: [P*196, 64], 3x3 @7: [P*49, 256]) -- up
   // to 64 at small P, where the plans split deeper (conv2d_auto_plan); a conv whose plan needs more gets as many as fit
@@ -735,7 +742,8 @@ enum DerivedKind {
   DK_U_F54,        // F(5x5, 4x4) U of the 7x7 / stride 2 conv: 225 units in four groups (winograd7.hip)
   DK_CHAIN_U2,     // F(2x2, 3x3) U2 of a bottleneck chain's 3x3 conv (chain_fused.hip)
   DK_PLANES,       // split-fp32 plane image of a [Co][K] matrix (wino_pack_split_launch, one problem)
-  DK_U_PLANES      // split-fp32 plane image of the conv's U, group by group
+  DK_U_PLANES,     // split-fp32 plane image of the conv's U, group by group
+  DK_HEAD_COMPOSED // the 7-head's FC composed with merged conv 7 (heads.hip: head_compose_launch); its sources are biases and FC slots too
 };
 DerivedKind u_kind(const ConvSpec& c) { return c.K == 7 ? DK_U_F54 : c.K == 5 ? DK_U_POLY : DK_U_F43; }
 int u_units(DerivedKind k) { return k == DK_U_F54 ? kWino7Units : k == DK_U_POLY ? kWinoUnits4 : kWinoPoints; }
@@ -749,7 +757,7 @@ size_t plane_floats(size_t elems) { return (elems * 3 + 1) / 2; }               
 
 // the handle switches an image needs: all of a row's bits, each stated once in derived_exists, and h->winograd (every image belongs to
 // a path OFFK_WINOGRAD=0 turns off -- the chain and wino_mid plane images too: such a handle runs chain_fused.hip's direct form and no wino_mid)
-enum { ON_7X7 = 1, ON_SPLIT_GEMM = 2, ON_CHAIN_WINO = 4, ON_SPLIT_CHAIN = 8, ON_SPLIT_MID = 16 };
+enum { ON_7X7 = 1, ON_SPLIT_GEMM = 2, ON_CHAIN_WINO = 4, ON_SPLIT_CHAIN = 8, ON_SPLIT_MID = 16, ON_POOL_FIRST7 = 32 };
 struct DerivedRow {
   int slot;                      // ConvId, or merged_slot(m)
   DerivedKind kind;
@@ -760,7 +768,7 @@ struct DerivedRow {
 };
 bool derived_exists(const offk_handle* h, const DerivedRow& r) {
   const int on = h->wino_7x7 * ON_7X7 | h->split_gemm * ON_SPLIT_GEMM | h->chain_wino * ON_CHAIN_WINO | (h->chain && h->split_chain) * ON_SPLIT_CHAIN |
-                 (h->wino_mid && h->split_mid) * ON_SPLIT_MID;
+                 (h->wino_mid && h->split_mid) * ON_SPLIT_MID | h->pool_first7 * ON_POOL_FIRST7;
   const bool shape = r.kind != DK_U_PLANES || (kConvs[r.slot].Co % 64 == 0 && kConvs[r.slot].Ci >= 64);      // (Co = 64: the kernel's 64-channel form)
   return h->winograd && !(r.needs & ~on) && shape && !(h->split_gemm_skip & r.skip_bit);
 }
@@ -782,7 +790,9 @@ const DerivedRow kDerived[] = {      // (a conv's U in front of the plane image 
     {C1_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C2_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C3_28B, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
     {C1_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C2_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN}, {C3_28C, DK_PLANES, &Derived::planes, ON_SPLIT_CHAIN},
     // the 1x1 convs inside wino_mid
-    {C1_14A, DK_PLANES, &Derived::planes, ON_SPLIT_MID}, {C1_7, DK_PLANES, &Derived::planes, ON_SPLIT_MID}};
+    {C1_14A, DK_PLANES, &Derived::planes, ON_SPLIT_MID}, {C1_7, DK_PLANES, &Derived::planes, ON_SPLIT_MID},
+    // the 7-head behind the pooled sums of xv_7 (both arithmetic modes: the FC launch is fp32)
+    {merged_slot(2), DK_HEAD_COMPOSED, &Derived::head, ON_POOL_FIRST7}};
 
 // the [Co][K] weights behind a slot: a conv's (library K order, K = Ci k k) or a merged conv's ([Co][Ci_main | Ci_branch])
 struct Matrix { const float* w; int Co, K; };
@@ -797,6 +807,7 @@ size_t derived_floats(const offk_handle* h, const DerivedRow& r) {
     case DK_CHAIN_U2: return (size_t)16 * 64 * 64;
     case DK_PLANES: { const Matrix m = slot_matrix(h, r.slot); return plane_floats((size_t)m.Co * (r.alloc_K ? r.alloc_K : m.K)); }
     case DK_U_PLANES: return plane_floats(u_elems(kConvs[r.slot]));
+    case DK_HEAD_COMPOSED: return (size_t)h->cfg.num_classes * (slot_matrix(h, r.slot).K + 1);
   }
   return 0;
 }
@@ -821,6 +832,12 @@ int pack_derived(offk_handle* h, const DerivedRow& r, hipStream_t st) {
         HIP_TRY(h, wino_pack_split_launch(d.u + grp[g].u_off, reinterpret_cast<char*>(d.u_planes) + grp[g].u_off * 6, c.Co, grp[g].kmul * c.Ci, grp[g].batch, st));
       break;
     }
+    case DK_HEAD_COMPOSED: {
+      const Matrix m = slot_matrix(h, r.slot);
+      HIP_TRY(h, head_compose_launch(h->fc_w[0], h->fc_b[0], h->cfg.num_classes, m.w, h->merged_b[r.slot - kNumConvs], m.Co, m.K, d.head,
+                                     d.head + (size_t)h->cfg.num_classes * m.K, st));
+      break;
+    }
   }
   return OFFK_OK;
 }
@@ -839,7 +856,7 @@ int finalize_merged(offk_handle* h, hipStream_t st) {
   h->merged_dirty = false;
   return OFFK_OK;
 }
-// (re)pack every derived image after any conv weight changed (behind finalize_merged: the merged matrices are sources too)
+// (re)pack every derived image after any of its sources changed (behind finalize_merged: the merged matrices and biases are sources too)
 int finalize_derived(offk_handle* h, hipStream_t st) {
   if (!h->derived_dirty) return OFFK_OK;
   for (const DerivedRow& r : kDerived)
@@ -888,13 +905,14 @@ struct Fwd {
   float *out7, *out14, *out28;     // the caller's (out28 nullptr: no 28-head)
   float *l7, *l14, *l28;           // where the heads write: those, or the per-pair regions consensus averages afterwards
   FcPooledJobs fcj{};              // the folded-pool FCs of the heads, launched together behind the last stage (fc_pooled_multi_kernel)
-  bool wino, w7, mid, w5, chained, fold, fold14t;      // the paths of this call (init)
+  bool wino, w7, mid, w5, chained, fold, fold14t, pool7;      // the paths of this call (init)
 
   float* reg(const char* name) const { return region(h, ws, name); }
 
-  int init(offk_handle* handle, hipStream_t st, void* workspace, float* o7, float* o14, float* o28) {
+  // stage_only (offk_stage_tensors): a launch outside a forward -- it takes no stage events
+  int init(offk_handle* handle, hipStream_t st, void* workspace, float* o7, float* o14, float* o28, bool stage_only = false) {
     h = handle; s = st; ws = workspace; n = h->P; out7 = o7; out14 = o14; out28 = o28;
-    if (h->profiling == 1) {
+    if (h->profiling == 1 && !stage_only) {
       const size_t per = OFFK_NUM_STAGES + 1;
       if ((h->ev_used + 1) * per > h->events.size() && h->events.size() < 4096 * per) {
         for (size_t i = 0; i < per; ++i) {
@@ -920,6 +938,7 @@ struct Fwd {
     auto generic = [](int cfg) { return cfg != 6 && cfg != 7 && cfg != 10; };      // the LDS-patch kernels have no pooling epilogue
     fold = h->fold_pool && generic(h->conv_cfg[C3_14B]) && generic(h->merged_cfg[2]);
     fold14t = wino && h->fold_pool;      // (the Winograd output transform of sum_14b leaves per-tile sums)
+    pool7 = h->pool_first7 && mid && fold14t && h->derived[merged_slot(2)].head;      // (the 7-head from the per-tile sums of xv_7)
     F14 = reg("fusion_14"); F7 = reg("fusion_7"); splitk = reg("splitk");
     wino_V = wino ? reg("wino_v") : nullptr;
     wino_M = wino ? reg("wino_m") : nullptr;
@@ -995,11 +1014,11 @@ struct Fwd {
     if (e != hipSuccess) return fail(h, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(c.key) + " (winograd): " + (why ? why : hipGetErrorString(e)));
     return OFFK_OK;
   }
-  int wino_out(ConvId id, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t) {
+  int wino_out(ConvId id, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t, int pool_cs = 0) {
     const ConvSpec& c = kConvs[id];
     TRY(trace_mark(h, s, c.key, " [winograd: output transform]"));
     if (u_kind(c) == DK_U_F54) HIP_TRY(h, wino7_output_launch(wino_M, n, c.Co, h->conv_b[id], flags, y, y_cs, y_coff, s));
-    else HIP_TRY(h, wino_output_launch(wino_M, n, c.Co, wino_phases(c), h->conv_b[id], res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t, s));
+    else HIP_TRY(h, wino_output_launch(wino_M, n, c.Co, wino_phases(c), h->conv_b[id], res, res_cs, res_coff, flags, y, y_cs, y_coff, pool_t, s, pool_cs, 0));
     return OFFK_OK;
   }
   int wino_conv(ConvId id, View x, const float* res, int res_cs, int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_t) {
@@ -1009,25 +1028,29 @@ struct Fwd {
   }
   // What sits between two convs on that path, in ONE launch (wino_mid.hip): the output transform (+ bias, ReLU) of conv `a` from
   // wino_M, optionally the 1x1 conv `c1` (+ bias, ReLU; kNumConvs: none), the input transform of the conv behind into wino_V.  xa: where
-  // the activation of conv `a` is ALSO stored (the merged convs read x1 / x2 from there later); nullptr: nowhere.
-  int wino_between(ConvId a, ConvId c1, float* xa, int xa_cs, int xa_coff, const char* name) {
+  // the activation of conv `a` is ALSO stored (the merged convs read x1 / x2 from there later); nullptr: nowhere.  pool_t: the per-tile sums
+  // of that activation go to rows of xa_cs floats there, at xa_coff as well.
+  int wino_between(ConvId a, ConvId c1, float* xa, int xa_cs, int xa_coff, const char* name, float* pool_t = nullptr) {
     const bool has = c1 != kNumConvs;
-    const WinoMidArgs m = wino_mid_args(wino_M, h->conv_b[a], wino_phases(kConvs[a]), n, kConvs[a].Co, xa, xa_cs, xa_coff, has ? h->conv_w[c1] : nullptr,
+    WinoMidArgs m = wino_mid_args(wino_M, h->conv_b[a], wino_phases(kConvs[a]), n, kConvs[a].Co, xa, xa_cs, xa_coff, has ? h->conv_w[c1] : nullptr,
                                         has ? h->conv_b[c1] : nullptr, kConvs[has ? c1 : a].Co, wino_V, has ? h->derived[c1].planes : nullptr);
+    m.pool_part = pool_t; m.pool_cs = xa_cs; m.pool_coff = xa_coff;
     TRY(trace_mark(h, s, name));
     HIP_TRY(h, wino_mid_launch(m, s));
     return OFFK_OK;
   }
   // x = relu(conv k x k (F)) -> c1 (1x1) -> c2 (3x3), the head of fusion@14 and fusion@7: xx = [c2's output | x] per pixel, t: c1's output.
   // wino_t: `ct` on its Winograd path; with wino_mid the 1x1 conv then sits between the two Winograd GEMM launches.
-  int conv_t_c1_c2(ConvId ct, bool wino_t, int H, View F, ConvId c1, ConvId c2, float* xx, int cs, float* t, const char* between) {
+  // pool_t (that form only): the per-tile sums of xx, [4 n][cs], from the two launches that store xx.
+  int conv_t_c1_c2(ConvId ct, bool wino_t, int H, View F, ConvId c1, ConvId c2, float* xx, int cs, float* t, const char* between,
+                   float* pool_t = nullptr) {
     const int half = cs / 2;
     if (wino_t && mid) {
       TRY(wino_in(ct, F));
       TRY(wino_mm(ct));
-      TRY(wino_between(ct, c1, xx, cs, half, between));
+      TRY(wino_between(ct, c1, xx, cs, half, between, pool_t));
       TRY(wino_mm(c2));
-      return wino_out(c2, nullptr, 0, 0, RP, xx, cs, 0, nullptr);
+      return wino_out(c2, nullptr, 0, 0, RP, xx, cs, 0, pool_t, pool_t ? cs : 0);
     }
     if (wino_t) TRY(wino_conv(ct, F, nullptr, 0, 0, RP, xx, cs, half, nullptr));
     else TRY(conv(ct, H, F, nullptr, 0, 0, RP, xx, cs, half));
@@ -1141,13 +1164,25 @@ struct Fwd {
   // ---- fusion @7 (RGB_OFF.py:831-841) and the 7-head (:843-847) ----
   int fusion7() {
     float *xv = reg("xv_7"), *v1 = reg("v1_7"), *s7 = reg("sum_7");                              // xv = [v2 | x2]
+    float* pp7t = pool7 ? reg("poolpart_7t") : nullptr;
     TRY(conv_t_c1_c2(C_T7, wino, 7, View{F7, 832, 0}, C1_7, C2_7, xv, 512, v1,                      // :833-838
-                     "motion_conv_trans out + motion_conv1_trans + motion_conv2_trans in [winograd: between]"));
+                     "motion_conv_trans out + motion_conv1_trans + motion_conv2_trans in [winograd: between]", pp7t));
+    if (pool7) {
+      // :839-847 is linear from xv to the logits (no ReLU on motion_sum, which feeds nothing else): the average pool first, then ONE FC
+      // with the composed weights in the heads' launch; sum_7 itself is left to offk_stage_tensors
+      const float* wc = h->derived[merged_slot(2)].head;
+      fcj.job[fcj.njobs++] = FcPooledJob{pp7t, 49, 1, 512, wc, wc + (size_t)h->cfg.num_classes * 512, l7};
+      h->sum7_pending = true;
+      if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
+      return OFFK_OK;
+    }
     float* pp7 = fold ? reg("poolpart_7") : nullptr;      // the 7-head's average pool in the merged conv's epilogue
-    TRY(conv_merged(2, 7, View{xv, 512, 0}, 0, s7, 1024, 0, pp7));                               // :839-841 (no ReLU)
+    TRY(merged7());
     if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
     return head(0, l7, pp7, 0, s7, 1024, 0, 7, 0, "pooled_7");
   }
+  // :839-841 (no ReLU): sum_7 from xv_7, and with `fold` the pooled sums of the 7-head in its epilogue (fusion7; offk_stage_tensors)
+  int merged7() { return conv_merged(2, 7, View{reg("xv_7"), 512, 0}, 0, reg("sum_7"), 1024, 0, fold ? reg("poolpart_7") : nullptr); }
 
   // ---- the folded-pool FCs of all heads in one launch, segment consensus (Flow_OFF.py:874-876) ----
   int heads() {
@@ -1265,6 +1300,8 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
   //   OFFK_WINO_MID      what sits between two Winograd convs on 7x7 maps (output transform, 1x1 conv, input transform) in one launch
   //                      (wino_mid.hip); 0: three launches
   //   OFFK_CHAIN_WINO    the 3x3 conv inside a bottleneck chain in Winograd F(2x2, 3x3) form (chain_fused.hip); 0: direct (also with OFFK_WINOGRAD=0)
+  //   OFFK_POOL_FIRST_7  the 7-head from pooled sums of xv_7 and composed weights, merged_7 only on demand (offk_stage_tensors; from P = 96;
+  //                      needs OFFK_WINOGRAD, OFFK_WINO_MID and OFFK_FOLD_POOL on)
   //   OFFK_WINO_GEMM     the batched GEMMs of a Winograd conv as one persistent launch (wino_gemm.hip); 0: one block of the generic 1x1 kernel per
   //                      tile (bit-identical).  The handle-less stage entry points read it once per process.
   h->fused_units = path_switch("OFFK_FUSED_UNITS");
@@ -1289,6 +1326,13 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
   { const char* e = getenv("OFFK_SPLIT_GEMM_SKIP"); if (e) h->split_gemm_skip = atoi(e); }
 #endif
   h->chain_wino = h->winograd && h->chain && path_switch("OFFK_CHAIN_WINO");
+  {
+    // (from P = 96 pairs, B = 16 x L = 7: below, the recorded launch plans and the head tests read the device's own sum_7 after every
+    //  forward, and whether the path pays there is not measured; OFFK_POOL_FIRST_7=<pairs> moves the gate)
+    int gate = 96;
+    const bool on = path_switch("OFFK_POOL_FIRST_7", &gate);
+    h->pool_first7 = on && h->winograd && h->wino_mid && h->fold_pool && h->P >= gate;
+  }
   for (const DerivedRow& r : kDerived)
     if (rc == OFFK_OK && derived_exists(h, r)) rc = dev_alloc(h, &(h->derived[r.slot].*r.image), derived_floats(h, r));
   if (rc != OFFK_OK) {
@@ -1388,6 +1432,9 @@ int offk_set_weight(offk_handle* h, const char* key, const float* data, const in
   }
   if (s.kind == SK_CONV_W || s.kind == SK_CONV_B) h->merged_dirty = true;
   if (s.kind == SK_CONV_W) h->derived_dirty = true;
+  // the composed 7-head also follows the two biases of merged_7 and the head's own weight and bias
+  if (h->derived[merged_slot(2)].head && ((s.kind == SK_CONV_B && (i == C3_7 || i == CB_7)) || ((s.kind == SK_FC_W || s.kind == SK_FC_B) && i == 0)))
+    h->derived_dirty = true;
   if (s.kind == SK_GEN_W || s.kind == SK_DOWN_W) h->pw_dirty = true;
   return rc;
 }
@@ -1674,6 +1721,23 @@ static int forward_parts(offk_handle* h, void* stream, const offk_feat_parts fea
   TRY(f.fusion14());
   TRY(f.fusion7());
   return f.heads();
+}
+
+int offk_stage_tensors(offk_handle* h, void* stream, void* workspace) {
+  if (!h || !workspace) return fail(h, OFFK_ERR_INVALID, "offk_stage_tensors: null argument");
+  if (!h->sum7_pending) return OFFK_OK;
+  DeviceGuard guard(h->cfg.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Fwd f;
+  TRY(f.init(h, st, workspace, nullptr, nullptr, nullptr, true));
+  TRY(finalize_merged(h, st));
+  TRY(finalize_derived(h, st));
+  const int prof = h->profiling;      // not a launch of a forward: it leaves no mark in the per-launch trace
+  h->profiling = 0;
+  const int rc = f.merged7();
+  h->profiling = prof;
+  if (rc == OFFK_OK) h->sum7_pending = false;
+  return rc;
 }
 
 // ---- training side of the OFF units -----------------------------------

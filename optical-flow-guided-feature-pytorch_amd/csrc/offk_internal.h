@@ -78,7 +78,8 @@ constexpr int kWinoPoints = 121, kWinoUnits4 = 400;
 hipError_t wino_weight_launch(const float* w_packed, int Co, int Ci, int phases, float* U, hipStream_t st);           // U [121][Co][Ci] / 400 Co Ci floats
 hipError_t wino_input_launch(const float* x, int x_cs, int x_coff, int n_img, int Ci, int phases, float* V, hipStream_t st);   // V [121][n_img][Ci] / 400 n_img Ci floats
 hipError_t wino_output_launch(const float* M, int n_img, int Co, int phases, const float* bias, const float* res, int res_cs,
-                              int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_part, hipStream_t st);
+                              int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_part, hipStream_t st, int pool_cs = 0,
+                              int pool_coff = 0);      // pool_cs > 0: pool_part rows of pool_cs floats, the conv's channels at pool_coff
 // the GEMM launches of a conv on the Winograd path: phases == 1: one group of 121 points with K = Ci; phases == 4: four groups
 // (81 points K = 4 Ci, 18 + 18 points K = 2 Ci, 4 points K = Ci; winograd.hip).  Offsets in floats for `rows` images / Co output channels.
 struct WinoGroup { int batch, kmul; long long v_off, u_off, m_off; };
@@ -118,6 +119,8 @@ struct WinoMidArgs {
   float* V;                // GEMM input of the conv behind: [121][n_img][Cmid] (3x3 / stride 1 point order)
   int nsplit = 0;          // blocks per image the 1x1 conv's output channels are split over (0: the default of the shape; tools)
   const void* w1p = nullptr;   // != nullptr: the plane image of w1 (wino_pack_split_launch(w1, img, Cmid, Cin, 1)): stage B in split-fp32 arithmetic
+  float* pool_part = nullptr;  // != nullptr (needs x): per-tile sums of the stored x, [n_img * 4][pool_cs] with the Cin channels at pool_coff --
+  int pool_cs = 0, pool_coff = 0;   //   wino_output_launch's pool_part layout (row = img * 4 + tile), summed in the same fixed order
 };
 bool wino_mid_supported(int Cin, int Cmid, bool gemm, int phases_in);
 hipError_t wino_mid_launch(const WinoMidArgs& a, hipStream_t st);
@@ -337,6 +340,10 @@ hipError_t fc_pooled_multi_launch(const FcPooledJobs& j, hipStream_t st);      /
 hipError_t fc_pooled_launch(const float* part, int hw, int tiles, int n_img, int C, const float* fw, const float* fb, int ncls, float* out,
                             hipStream_t st);
 hipError_t vec_add_launch(const float* a, const float* b, float* o, int n, hipStream_t st);
+// A head whose average pool moves in front of the linear 1x1 conv that feeds it: w_out [ncls][K] = fw [ncls][Cm] . wm [Cm][K],
+// b_out [ncls] = fw . bm + fb; sums in fp64, rounded once (a load-time kernel)
+hipError_t head_compose_launch(const float* fw, const float* fb, int ncls, const float* wm, const float* bm, int Cm, int K, float* w_out,
+                               float* b_out, hipStream_t st);
 hipError_t score_fusion_launch(const float* const* scores, const float* weights, int n, int videos, int crops, int classes,
                                float* fused, int* pred, hipStream_t st);
 hipError_t consensus_launch(const float* x, int B, int T, int C, float* out, hipStream_t st);

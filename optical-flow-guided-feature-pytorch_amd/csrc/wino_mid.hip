@@ -7,7 +7,9 @@
 // (profiles/r03/bench_b64_final.json, roofline_in_path).  Here a block owns ONE image and does all of it on chip:
 //   stage A  x = relu(A^T M A + bias)      the output transform of the conv in front, from its GEMM output M [121][P][CIN];
 //                                          x goes to LDS ([64 pixel slots][CIN], 16-byte chunks XOR-swizzled by the slot) and,
-//                                          where a later conv reads it, to its channel slice in HBM (x1 / x2 of the merged convs)
+//                                          where a later conv reads it, to its channel slice in HBM (x1 / x2 of the merged convs);
+//                                          pool_part: also the sum of each of the image's four tiles, per channel (a wave owns one
+//                                          tile: fixed order, no atomics) -- the 7-head's pool in front of merged_7 (offk_api.hip)
 //   stage B  t = relu(W1 x + b1)           the 1x1 conv: v_mfma_f32_16x16x4_f32, weights = A operand straight from L2 (a lane ends
 //                                          with four consecutive channels of one pixel), pixels = B operand from LDS; t -> LDS
 //   stage C  V = B^T t B                   the input transform of the conv behind, to its GEMM input V [121][P][CMID]
@@ -91,6 +93,7 @@ __device__ __forceinline__ void mid_out_class(const WinoMidArgs& a, int img, int
         for (int i = 0; i < OY; ++i) s[i][j] = sc[i];
       }
       const float bv = a.bias_in ? a.bias_in[c] : 0.f;
+      float psum = 0.f;      // the tile's sum of what is stored, in wino_output_tile's order
 #pragma unroll
       for (int i = 0; i < OY; ++i) {
         float yv[OX];
@@ -102,8 +105,10 @@ __device__ __forceinline__ void mid_out_class(const WinoMidArgs& a, int img, int
           if constexpr (SPL) store_planes<LC>(xt, px, c - 64 * G0, v);
           else *reinterpret_cast<float*>(xt + tile_off<LC>(px, c - 64 * G0)) = v;
           if (xg) xg[((size_t)img * 49 + px) * a.x_cs + a.x_coff + c] = v;
+          psum += v;
         }
       }
+      if (xg && a.pool_part) a.pool_part[((size_t)img * 4 + 2 * CY + CX) * a.pool_cs + a.pool_coff + c] = psum;
     }
   }
 }
@@ -347,7 +352,7 @@ bool wino_mid_supported(int Cin, int Cmid, bool gemm, int phases_in) {
 hipError_t wino_mid_launch(const WinoMidArgs& a, hipStream_t st) {
   const bool gemm = a.w1 != nullptr;
   if (!wino_mid_supported(a.Cin, a.Cmid, gemm, a.phases_in) || a.n_img < 1 || !a.M || !a.V || (gemm && !a.b1) ||
-      (a.x && (a.x_cs % 4 || a.x_coff % 4)))
+      (a.x && (a.x_cs % 4 || a.x_coff % 4)) || (a.pool_part && (!a.x || a.pool_coff < 0 || a.pool_coff + a.Cin > a.pool_cs)))
     return hipErrorInvalidValue;
 #define OFFK_MID_LAUNCH_KH(CI, CM, G, PH, NSP, KHV)                                                                \
   {                                                                                                                \

@@ -105,7 +105,8 @@ struct WinoOutArgs {
   const float* bias;             // [Co]
   const float* res; int res_cs, res_coff;
   float* y; int y_cs, y_coff;
-  float* pool_part;              // != nullptr: [n_img * 4][Co] sums of the stored values of each tile (row = img * 4 + cls)
+  float* pool_part;              // != nullptr: [n_img * 4][pool_cs] sums of the stored values of each tile (row = img * 4 + cls), the Co
+  int pool_cs, pool_coff;        //   channels at pool_coff of a row
   int n_img, Co, flags;
 };
 namespace {
@@ -142,7 +143,7 @@ __device__ __forceinline__ void wino_output_tile(const WinoOutArgs& a, int img, 
       psum += v;
     }
   }
-  if (a.pool_part) a.pool_part[((size_t)img * 4 + 2 * CY + CX) * a.Co + c] = psum;
+  if (a.pool_part) a.pool_part[((size_t)img * 4 + 2 * CY + CX) * a.pool_cs + a.pool_coff + c] = psum;
 }
 }  // namespace
 template <int NPH>
@@ -244,10 +245,12 @@ hipError_t wino_input_launch(const float* x, int x_cs, int x_coff, int n_img, in
 }
 
 hipError_t wino_output_launch(const float* M, int n_img, int Co, int phases, const float* bias, const float* res, int res_cs,
-                              int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_part, hipStream_t st) {
+                              int res_coff, int flags, float* y, int y_cs, int y_coff, float* pool_part, hipStream_t st, int pool_cs, int pool_coff) {
+  if (pool_part && pool_cs > 0 && (pool_coff < 0 || pool_coff + Co > pool_cs)) return hipErrorInvalidValue;
   WinoOutArgs a;
   a.M = M; a.bias = bias; a.res = res; a.res_cs = res_cs; a.res_coff = res_coff;
   a.y = y; a.y_cs = y_cs; a.y_coff = y_coff; a.pool_part = pool_part;
+  a.pool_cs = pool_cs > 0 ? pool_cs : Co; a.pool_coff = pool_cs > 0 ? pool_coff : 0;
   a.n_img = n_img; a.Co = Co; a.flags = flags;
   const long long waves = (long long)4 * n_img * ((Co + 63) / 64);
   if (phases == 4) hipLaunchKernelGGL(wino_output_kernel<4>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);

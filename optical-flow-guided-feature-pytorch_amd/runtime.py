@@ -277,8 +277,11 @@ class OffForward:
         self._ws = t
 
     def region(self, name, channels):
-        """View of a named workspace region as [rows, channels] fp32 (channels-last)."""
+        """View of a named workspace region as [rows, channels] fp32 (channels-last).  sum_7: filled first where the last forward left
+        it out (offk_stage_tensors; handles that take the 7-head pool-first)."""
         off, nb = ctypes.c_size_t(), ctypes.c_size_t()
+        if name == "sum_7":
+            _lib.check(self.lib.offk_stage_tensors(self._h, _stream(self.device), _ptr(self.workspace)), self._h)
         _lib.check(self.lib.offk_workspace_region(self._h, name.encode(), ctypes.byref(off), ctypes.byref(nb)), self._h)
         flat = self.workspace[off.value:off.value + nb.value].view(torch.float32)
         return flat.view(-1, channels)
