@@ -126,8 +126,9 @@ int offk_destroy(offk_handle* h);
  * The library keeps its own packed device copy.  Blocking, load-time call: it first waits for all work on the device
  * (so no kernel still reads the copy being replaced and a device-side `data` is complete whatever stream produced it). */
 int offk_set_weight(offk_handle* h, const char* key, const float* data, const int64_t* shape, int ndim);
-/* Training-side alternative for the parameters that change every optimizer step (train_off.py:39-45 leaves exactly the
- * OFF units' tensors trainable: motion_conv_gen_<s>, motion_spatial_down_<s>, motion_spatial_grad_<s>, weight and bias):
+/* Training-side alternative for the parameters that change every optimizer step.  (train_off.py:39-45 un-freezes every tensor
+ * whose name contains "motion" or "fc_action_motion" -- the units, the fusion stages and the heads; the OFF UNITS' share of
+ * those, which this library trains, is motion_conv_gen_<s>, motion_spatial_down_<s>, motion_spatial_grad_<s>, weight and bias):
  * bind the caller's own parameter storage instead of copying it.  `device_data` is the tensor in the reference layout of
  * the key ([128,C,1,1], [128], [32,C,1,1], [32], [32,1,3,3], [32]; contiguous, 16-byte aligned, on the handle's device);
  * every later launch reads it in place, so an in-place optimizer update needs NO call at all -- it only has to be ordered
@@ -418,8 +419,8 @@ int offk_score_fusion(void* stream, const float* const* scores, const float* wei
 /* ---- Training side of the OFF units ------------------------------
  * What train_off.py:126-151 needs from the path: the units' forward in training mode (nn.Dropout(p=0.8),
  * RGB_OFF.py:356, on every spatial gradient, :612 ...), and the gradients of the units' parameters --
- * the only unit-side tensors train_off.py:39-45 leaves trainable; the feature maps come from the frozen
- * backbone and get no gradient.  The fusion stages / heads between the units and the loss are ordinary
+ * the unit-side tensors among those train_off.py:39-45 leaves trainable; the feature maps come from a backbone
+ * the reference's scripts freeze (their gradient, for callers that un-freeze it: offk_off_units_backward_feats).  The fusion stages / heads between the units and the loss are ordinary
  * convolutions and stay with the caller's autograd; the cut is the gradient w.r.t. each unit output
  * motion_<site> = cat(S 32, T 128) (:616), i.e. the leading channels of the gradients of the three cat
  * results (:656, :760, :832).
@@ -530,6 +531,34 @@ int offk_off_units_train_cl(offk_handle* h, void* stream, int feat_dtype, const 
 int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, const void* const feats[OFFK_NUM_SITES],
                                const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed,
                                double drop_p, float* grads, int accumulate);
+
+/* ---- gradient w.r.t. the nine feature maps (additive; ABI version unchanged) -----------
+ * The reference's training scripts freeze the backbone (train_off.py:39-56), so the entries above give parameter gradients
+ * only.  A caller that un-freezes inception_5a / 5b (the usual TSN partial fine-tune) or the whole backbone for a joint last
+ * stage needs dX as well, and it is linear in what the backward already left behind:
+ *   dX[frame n, pixel, c] = sum_o dGpre[n, pixel, o] Wg[o, c]                     (all B*L frames)
+ *                         + sum_j dD[r(n), pixel, j] Wd[j, c]                     (frames inside the spatial slice only)
+ *   r(n): OFFK_SLICE_REFERENCE_FLAT: r = n for n < B*(L-1), none above; OFFK_SLICE_PER_CLIP: frame (b, t), t < L-1 ->
+ *   r = b*(L-1) + t, none for t = L-1.
+ * It needs neither the maps, the dropout seed nor the maps' dtype, so there is one entry for all three backward forms.
+ *
+ * Gradient w.r.t. the feature maps, from the dG_<site> / dD_<site> regions the LAST offk_off_units_backward
+ * (any of its three forms) on `h` left in `workspace`, and the gen / down weights as they are at launch time
+ * (bound: read in place -> enqueue before the optimizer step).  dfeats[i] == NULL: site i is skipped.
+ * layout: OFFK_FEAT_NCHW ([B*L, C_i, H_i, H_i]) or OFFK_FEAT_NHWC ([B*L*H_i*H_i][C_i]), fp32, 16-byte aligned,
+ * not overlapping `workspace`.  accumulate != 0 adds (out = old + new, new being the bits the overwrite form stores).
+ * One launch on `stream` (csrc/units_dx.hip), no sync, no allocation, capturable.
+ * Exact fp32 on the fp32 matrix pipe whatever the handle's precision (a split-fp32 handle runs its training side on the
+ * fp32 kernels), a fixed k order, no atomics: bit-reproducible, and the two layouts hold the same sums bit for bit.
+ * Refused with OFFK_ERR_INVALID, nothing enqueued: a null h, workspace or dfeats; an unknown layout; a pointer that is not
+ * 16-byte aligned; a buffer that overlaps the offk_train_workspace_bytes of `workspace`; a handle on which no
+ * offk_off_units_backward* has run since offk_create.  That last check is a flag the backward entries set on the handle: a
+ * backward replayed from a captured graph does not pass through the library and sets none (as for offk_stage_tensors) -- run
+ * one backward through the library first.  The library cannot see how large `workspace` is: it must be the train workspace
+ * (offk_train_workspace_bytes), the one the backward wrote.  All nine pointers NULL: OFFK_OK, nothing enqueued.
+ * Per-launch trace: "units:feature-map gradient (dX, NCHW)" / "... (dX, NHWC)". */
+int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
+                                  float* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
 
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);

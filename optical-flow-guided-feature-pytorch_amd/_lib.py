@@ -12,6 +12,7 @@ STAGE_NAMES = ("pw_reduce", "sobel_tdiff", "fusion_28", "fusion_14", "fusion_7",
 CONV_RELU_IN, CONV_RELU_PRE, CONV_RELU_POST = 1, 2, 4
 PRECISION_FP32, PRECISION_F32SPLIT = 0, 2
 PRECISIONS = {"fp32": 0, "f32split": 2}      # (1 was "bf16x3", retired in ABI v9)
+FEAT_NCHW, FEAT_NHWC = 0, 1                  # enum offk_feat_layout (offk_off_units_backward_feats)
 FEAT_F32, FEAT_BF16, FEAT_F16 = 0, 1, 2      # enum offk_feat_dtype (offk_forward_typed, offk_off_units_typed, ...)
 
 
@@ -96,6 +97,7 @@ SIGNATURES = {
     "offk_off_units_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _P]),
     "offk_off_units_train_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _P, _c.c_uint64, _c.c_double]),
     "offk_off_units_backward_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _c.POINTER(OffkGradView), _P, _c.c_uint64, _c.c_double, _F, _I]),
+    "offk_off_units_backward_feats": (_I, [_P, _P, _P, _c.POINTER(_F), _I, _I]),
     "offk_segment_consensus_backward": (_I, [_P, _F, _I, _I, _I, _F]),
     "offk_nchw_to_nhwc": (_I, [_P, _F, _I, _I, _I, _F]),
     "offk_nhwc_to_nchw": (_I, [_P, _F, _I, _I, _I, _I, _I, _F]),

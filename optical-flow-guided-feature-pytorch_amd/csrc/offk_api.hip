@@ -220,6 +220,7 @@ struct offk_handle {
   bool chain = true;             // fp32: one launch per bottleneck chain of fusion@28 (chain_fused.hip); OFFK_CHAIN=0 at offk_create: three convs
   int chain_min_p = 72;          // ... from this many pairs (OFFK_CHAIN=<n> with n > 1 at offk_create: tests / tools)
   size_t train_ws_bytes = 0;
+  bool units_bwd_done = false;   // an offk_off_units_backward* call has been enqueued since offk_create: dG_<site> / dD_<site> hold a backward's output
   int wg_kpb = 0;                // 32-pixel K-tiles one pw_wgrad block walks
   std::map<std::string, std::pair<size_t, size_t>> grad_slots;   // key -> (offset, count) in floats
   size_t grad_floats = 0;
@@ -1841,6 +1842,7 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
   wp.total_blocks = blk;
   TRY(launch_k1b(h, st, wp, feat_dtype, nhwc));
   HIP_TRY(h, wgrad_reduce_launch(rp, st));
+  h->units_bwd_done = true;   // what offk_off_units_backward_feats asks for
   return OFFK_OK;
 }
 
@@ -1907,6 +1909,54 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
                                float* grads, int accumulate) {
   return off_units_backward_kind(h, stream, &kKindCl, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate,
                                  "offk_off_units_backward_cl");
+}
+
+// ---- gradient w.r.t. the feature maps (units_dx.hip) ----
+int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace, float* const dfeats[OFFK_NUM_SITES], int layout,
+                                  int accumulate) {
+  const char* fn = "offk_off_units_backward_feats";
+  if (!h || !workspace || !dfeats) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  if (layout != OFFK_FEAT_NCHW && layout != OFFK_FEAT_NHWC)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": layout must be OFFK_FEAT_NCHW or OFFK_FEAT_NHWC");
+  if (!h->units_bwd_done)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": no offk_off_units_backward has run on this handle: dG_<site> / dD_<site> hold nothing yet");
+  const char* ws_lo = static_cast<const char*>(workspace);
+  const char* ws_hi = ws_lo + h->train_ws_bytes;
+  int nreq = 0;
+  for (int s = 0; s < kNumSites; ++s) {
+    if (!dfeats[s]) continue;
+    ++nreq;
+    if (reinterpret_cast<uintptr_t>(dfeats[s]) & 15) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": gradient pointers must be 16-byte aligned");
+    const char* lo = reinterpret_cast<const char*>(dfeats[s]);
+    const char* hi = lo + (size_t)h->N * kSites[s].C * kSites[s].H * kSites[s].H * sizeof(float);
+    if (lo < ws_hi && ws_lo < hi) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": a gradient buffer overlaps the workspace");
+    TRY(site_weights_ready(h, s, true, false));
+  }
+  if (!nreq) return OFFK_OK;
+  DeviceGuard guard(h->cfg.device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  DxParams dp;
+  memset(&dp, 0, sizeof(dp));
+  dp.L = h->cfg.length; dp.P = h->P; dp.slice_mode = h->cfg.slice_mode;
+  dp.nchw = layout == OFFK_FEAT_NCHW; dp.accumulate = accumulate ? 1 : 0; dp.zeros = h->zero_page;
+  int blk = 0, n = 0;
+  for (int i = 0; i < kNumSites; ++i) {      // the widest sites first, as K1 / K1b order theirs
+    const int s = kPwOrder[i];
+    if (!dfeats[s]) continue;
+    DxSite& d = dp.s[n++];
+    const float *b, *bd;
+    pw_weight_ptrs(h, s, &d.wg, &d.wd, &b, &bd);
+    d.dG = region(h, workspace, (std::string("dG_") + kSites[s].name).c_str());
+    d.dD = region(h, workspace, (std::string("dD_") + kSites[s].name).c_str());
+    d.out = dfeats[s];
+    d.C = kSites[s].C; d.HW = kSites[s].H * kSites[s].H; d.M = h->N * d.HW;
+    d.blk_begin = blk;
+    blk += (d.M + units_dx_rows_per_block() - 1) / units_dx_rows_per_block();
+  }
+  dp.nsites = n; dp.total_blocks = blk;
+  TRY(trace_mark(h, st, dp.nchw ? "units:feature-map gradient (dX, NCHW)" : "units:feature-map gradient (dX, NHWC)"));
+  HIP_TRY(h, units_dx_launch(dp, st));
+  return trace_mark(h, st, nullptr);
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

@@ -325,6 +325,25 @@ struct WrParams {
 hipError_t wgrad_reduce_launch(const WrParams& p, hipStream_t st);
 hipError_t consensus_bwd_launch(const float* go, int B, int T, int C, float* gi, hipStream_t st);
 
+// ---- gradient w.r.t. the feature maps (units_dx.hip): dX = [dGpre | dD] . [Wg ; Wd], one grouped launch ----
+struct DxSite {
+  const float* dG;      // [N*HW][128] as K2b left it
+  const float* dD;      // [P*HW][32]
+  const float* wg;      // gen rows [128][C] fp32 (PwSite::w)
+  const float* wd;      // down rows [32][C] (PwSite::w_down)
+  float* out;           // nchw: [N][C][HW], else [N*HW][C]
+  int C, HW, M;         // M = N*HW rows
+  int blk_begin;
+};
+struct DxParams {
+  DxSite s[kNumSites];
+  int nsites, total_blocks, L, P, slice_mode;
+  int nchw, accumulate;
+  const float* zeros;   // >= 16 bytes of zeros in device memory: what a masked-out load reads
+};
+int units_dx_rows_per_block();
+hipError_t units_dx_launch(const DxParams& p, hipStream_t st);
+
 // ---- K5 / K6 / layout helpers ----------------------------------------------------
 hipError_t head_launch(const float* x, int x_cs, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fw,
                        const float* fb, int ncls, float* out, hipStream_t st, const char** why);

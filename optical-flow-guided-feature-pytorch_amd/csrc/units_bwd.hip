@@ -2,8 +2,8 @@
 //   G = relu(motion_conv_gen_s(X)); T = G[t+1] - G[t]            RGB_OFF.py:597-604
 //   D = motion_spatial_down_s(X[:P]); S = dropout(dw3x3(D))       :609-612
 //   motion_s = cat(S, T)                                          :616
-// for the parameters train_off.py:39-45 leaves trainable (every `*motion*` tensor).  The feature
-// maps come from the frozen backbone and get no gradient, so the backward is
+// for the units' parameters (train_off.py:39-45 leaves every `*motion*` / `fc_action_motion*` tensor trainable; the units' share
+// is what this file differentiates).  The reference's scripts freeze the backbone, so the parameter backward is
 //   K2b  units_bwd_kernel   dM -> dGpre [N*HW][128] (temporal-difference transpose, ReLU mask from the
 //                           saved G) and dD [P*HW][32] (transposed depthwise 3x3 of dS = dM_S * dropout
 //                           multiplier), plus per-block partial sums of the depthwise weight / bias
@@ -13,6 +13,7 @@
 //   reduce kernels          slabs / partials summed in a fixed order into the caller's gradient buffer
 //                           in the reference's parameter layouts ([128,C,1,1], [32,C,1,1], [32,1,3,3]).
 // Every sum has a fixed order: the gradients are bit-reproducible run to run.
+// The gradient w.r.t. the feature maps themselves (an un-frozen backbone) is linear in dGpre / dD: units_dx.hip.
 //
 // This file is compiled twice: as it is, and through units_bwd_cl.hip with OFFK_UNITS_BWD_CL defined (the channels-last X loader
 // forms of pw_wgrad_kernel and pw_wgrad_cl_launch alone), so that the forms of this object keep the code they have.

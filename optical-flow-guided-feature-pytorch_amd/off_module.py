@@ -177,6 +177,31 @@ class _OFFUnitsFn(torch.autograd.Function):
         return (None, None, None) + tuple(grads[k] for k in mod.param_keys)
 
 
+class _OFFUnitsFeatFn(torch.autograd.Function):
+    """_OFFUnitsFn for ``OFFUnits(feat_grad=True)``: the nine maps are tensor inputs of the node (after ``mod`` and ``drop``), so
+    autograd sees them, and the backward returns their gradients too -- offk_off_units_backward_feats, one launch behind the
+    parameter backward, for the sites in ``ctx.needs_input_grad`` only (none required: no launch).  Forward, the stale-generation
+    recompute and the parameter-version check are _OFFUnitsFn's own code."""
+
+    @staticmethod
+    def forward(ctx, mod, drop, *maps_and_params):
+        feats, params = tuple(maps_and_params[:spec.NUM_SITES]), maps_and_params[spec.NUM_SITES:]
+        return _OFFUnitsFn.forward(ctx, mod, feats, drop, *params)
+
+    @staticmethod
+    def backward(ctx, g28, g14, g7):
+        pgrads = _OFFUnitsFn.backward(ctx, g28, g14, g7)[3:]
+        sites = runtime.feat_grad_sites(ctx.needs_input_grad, first=2)
+        dx = [None] * spec.NUM_SITES
+        if sites:
+            # the layout the maps came in: all nine channels_last (the route the forward took) -> channels_last gradients
+            layout = "cl" if ctx.mod._as_handed_over(ctx.feats) else "nchw"
+            dx = ctx.mod._rt.off_units_backward_feats(sites, layout)
+            # torch wants a gradient in its input's dtype: a 16-bit map gets the fp32 result cast to it (one rounding of the fp32 sum)
+            dx = [g if g is None or g.dtype == f.dtype else g.to(f.dtype) for g, f in zip(dx, ctx.feats)]
+        return (None, None) + tuple(dx) + tuple(pgrads)
+
+
 class OFFUnits(nn.Module):
     """The nine OFF units as a trainable module on liboffk: parameters under the
     reference's state_dict keys (``motion_conv_gen_*``, ``motion_spatial_down_*``, ``motion_spatial_grad_*``;
@@ -195,10 +220,18 @@ class OFFUnits(nn.Module):
     Nine ``torch.channels_last`` maps (logical shape as ever, any of the three dtypes) -- what a backbone run in channels_last
     emits -- are not made contiguous either: offk_off_units_train_cl / offk_off_units_backward_cl read them as they are, the
     autograd node keeps those very tensors, and outputs and gradients equal those from the contiguous copies.  Any other
-    layout, a mix included, is made contiguous as ever."""
+    layout, a mix included, is made contiguous as ever.
 
-    def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8):
+    ``feat_grad=False`` (the default) is the reference's training setup: the backbone is frozen (train_off.py:39-56), the maps are
+    no inputs of the autograd node and get no gradient, whatever their ``requires_grad``.  ``feat_grad=True`` is for an un-frozen
+    backbone (inception_5a / 5b of a TSN partial fine-tune, or all of it): the maps become inputs of the node and every map that
+    requires grad gets its gradient from offk_off_units_backward_feats -- one more launch per backward, for those sites only, in
+    the maps' layout (contiguous, or channels_last where all nine came so).  The gradient is computed in fp32; a bf16 / fp16 map
+    receives it CAST to its dtype, as torch requires.  Parameter gradients are the same bits either way."""
+
+    def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False):
         super().__init__()
+        self.feat_grad = bool(feat_grad)
         if variant not in _VARIANTS:
             raise ValueError("variant must be one of %s" % sorted(_VARIANTS))
         self.variant = _VARIANTS[variant]
@@ -280,7 +313,10 @@ class OFFUnits(nn.Module):
             drop = (int(drop_seed), self.drop_p)
         else:
             drop = (0, 0.0)
-        return _OFFUnitsFn.apply(self, feats, drop, *[self._param(k) for k in self.param_keys])
+        params = [self._param(k) for k in self.param_keys]
+        if self.feat_grad:
+            return _OFFUnitsFeatFn.apply(self, drop, *(feats + tuple(params)))
+        return _OFFUnitsFn.apply(self, feats, drop, *params)
 
 
 class BNInception_OFF(nn.Module):

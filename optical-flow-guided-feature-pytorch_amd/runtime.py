@@ -172,6 +172,25 @@ def train_feat_layout(feats, batch, length):
     return "cl" if _all_channels_last(feats, batch, length, "train", True) else "nchw"
 
 
+def feat_grad_sites(needs_input_grad, first=0):
+    """The sites whose map wants a gradient, from an autograd node's ``ctx.needs_input_grad``: the nine maps are its inputs
+    ``first .. first + 8``.  A pure function of the flags (CPU)."""
+    flags = tuple(needs_input_grad)[first:first + spec.NUM_SITES]
+    if len(flags) != spec.NUM_SITES:
+        raise ValueError("need the flags of nine feature maps, got %d" % len(flags))
+    return [i for i, f in enumerate(flags) if f]
+
+
+def feat_grad_sites_mask(sites):
+    """sites (None: all nine, else site indices 0..8, each once) -> nine booleans."""
+    if sites is None:
+        return [True] * spec.NUM_SITES
+    sites = [int(i) for i in sites]
+    if any(not 0 <= i < spec.NUM_SITES for i in sites) or len(set(sites)) != len(sites):
+        raise ValueError("sites must be distinct indices in 0..8, got %s" % (sites,))
+    return [i in sites for i in range(spec.NUM_SITES)]
+
+
 class OffForward:
     """One liboffk handle for a fixed (batch, length, variant).
 
@@ -441,6 +460,44 @@ class OffForward:
                    int(bool(accumulate)))
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
+
+    def off_units_backward_feats(self, sites=None, layout="nchw", out=None, accumulate=False):
+        """Gradient w.r.t. the feature maps (offk_off_units_backward_feats): one launch, from what the LAST off_units_backward on this
+        handle left in the workspace and the gen / down weights as they are now (bound weights: call it before the optimizer step).
+        sites: the site indices wanted (None: all nine).  layout "nchw": contiguous [B*L, C, H, H] tensors; "cl": the same logical
+        shape with torch.channels_last strides.  out: nine entries (None where a site is skipped) to write -- or, accumulate=True,
+        add -- into instead of fresh tensors.  Returns a list of nine, None for the skipped sites; fp32 always."""
+        if not self.training:
+            raise _lib.OffkError("create the handle with training=True for the units' backward")
+        if layout not in ("nchw", "cl"):
+            raise ValueError("layout must be \"nchw\" or \"cl\", got %r" % (layout,))
+        want = feat_grad_sites_mask(sites)
+        if out is not None and len(out) != spec.NUM_SITES:
+            raise ValueError("out must have nine entries (None for a skipped site)")
+        if accumulate and out is None:
+            raise ValueError("accumulate=True needs the tensors to add to (out)")
+        res = [None] * spec.NUM_SITES
+        for i, (n, c, h, _w) in enumerate(spec.feature_shapes(self.batch, self.length)):
+            if not want[i]:
+                continue
+            t = out[i] if out is not None else None
+            if t is None:
+                if accumulate:
+                    raise ValueError("accumulate=True: out[%d] is None but site %d is asked for" % (i, i))
+                t = torch.empty((n, c, h, h) if layout == "nchw" else (n, h, h, c), dtype=torch.float32, device=self.device)
+                t = t if layout == "nchw" else t.permute(0, 3, 1, 2)
+            dense = t.is_contiguous() if layout == "nchw" else _is_channels_last(t)
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and dense):
+                raise ValueError("out[%d] must be an fp32 CUDA/HIP tensor, %s" % (i, "contiguous" if layout == "nchw" else "torch.channels_last"))
+            if t.device != self.device:
+                raise ValueError("out[%d] lives on %s, handle on %s" % (i, t.device, self.device))
+            if tuple(t.shape) != (n, c, h, h):
+                raise ValueError("out[%d] has shape %s, expected %s" % (i, tuple(t.shape), (n, c, h, h)))
+            res[i] = t
+        arr = (ctypes.c_void_p * spec.NUM_SITES)(*[t.data_ptr() if t is not None else None for t in res])
+        _lib.check(self.lib.offk_off_units_backward_feats(self._h, _stream(self.device), _ptr(self.workspace), arr,
+                                                          _lib.FEAT_NCHW if layout == "nchw" else _lib.FEAT_NHWC, int(bool(accumulate))), self._h)
+        return res
 
     # ---- stage entry points -----------------------------------------------------------
     def pw_reduce(self, site, feat, G=None, D=None):

@@ -1,11 +1,14 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
-    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy]
+    python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy] [--feat-grad]
 --feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
 .float() casts that path makes unnecessary are timed beside it.
 --feat-layout cl: the maps are torch.channels_last tensors and go in as they are (offk_off_units_train_cl / offk_off_units_backward_cl);
 copy: the same channels_last maps made contiguous inside the timed region of the forward (nine .contiguous() calls, what a caller
 without the _cl entries does; the backward then reads the copies); nchw (default): contiguous maps.  units_step_ms is forward + backward.
+--feat-grad: the gradient w.r.t. the nine maps (offk_off_units_backward_feats, in the maps' layout) joins the timed backward, so
+units_backward_ms / units_step_ms are those of a step that trains through the maps; the call alone and the same gradient composed
+from torch ops (torch.nn.grad.conv2d_input for the two 1x1 convs, the add into the frames of the slice) are timed beside it.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--variant", type=int, default=spec.VARIANT_RGB)
     ap.add_argument("--feat-dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--feat-layout", default="nchw", choices=["nchw", "cl", "copy"])
+    ap.add_argument("--feat-grad", action="store_true")
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
@@ -54,6 +58,17 @@ def main():
     bufs = [torch.randn(P, H, H, C, device="cuda", generator=gen) for H, C in ((28, 320), (14, 1056), (7, 832))]
     views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
     grads = h.new_unit_grads()
+    dx_layout = "nchw" if a.feat_layout == "nchw" else "cl"      # (copy: the maps the model holds are the channels_last ones)
+    dx = None
+    if a.feat_grad:
+        h.off_units_train(feats, 21, 0.8)
+        h.off_units_backward(feats, views, 21, 0.8, grads=grads)
+        dx = h.off_units_backward_feats(layout=dx_layout)
+
+    def bwd(x):
+        h.off_units_backward(x, views, 21, 0.8, grads=grads)
+        if a.feat_grad:
+            h.off_units_backward_feats(layout=dx_layout, out=dx)
     if a.feat_layout != "nchw":
         feats = [f.contiguous(memory_format=torch.channels_last) for f in feats]
     if a.feat_layout == "copy":
@@ -64,12 +79,36 @@ def main():
             h.off_units_train(held[0], 21, 0.8)
         t_fwd = timed(fwd, a.iters)
         t_copy = timed(lambda: [f.contiguous() for f in feats], a.iters)
-        t_bwd = timed(lambda: h.off_units_backward(held[0], views, 21, 0.8, grads=grads), a.iters)
+        t_bwd = timed(lambda: bwd(held[0]), a.iters)
     else:
         t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8), a.iters)
         t_copy = 0.0
-        t_bwd = timed(lambda: h.off_units_backward(feats, views, 21, 0.8, grads=grads), a.iters)
+        t_bwd = timed(lambda: bwd(feats), a.iters)
     t_cast = timed(lambda: [f.float() for f in feats], a.iters) if fdt != torch.float32 else 0.0
+    extra = {}
+    if a.feat_grad:
+        w = {k: torch.from_numpy(v).cuda() for k, v in synth.make_weights(a.variant).items()}
+
+        def composed():
+            out = []
+            for site, C, H in spec.SITES:
+                dG = h.region("dG_" + site, 128).view(N, H, H, 128).permute(0, 3, 1, 2)
+                dD = h.region("dD_" + site, 32).view(P, H, H, 32).permute(0, 3, 1, 2)
+                g = torch.nn.grad.conv2d_input((N, C, H, H), w["motion_conv_gen_%s.weight" % site], dG)
+                g[:P].add_(torch.nn.grad.conv2d_input((P, C, H, H), w["motion_spatial_down_%s.weight" % site], dD))   # flat slice
+                out.append(g)
+            return out
+        t_dx = timed(lambda: h.off_units_backward_feats(layout=dx_layout, out=dx), a.iters)
+        t_torch = timed(composed, a.iters)
+        ref = composed()
+        err = max(float((a_ - b_).abs().max() / b_.abs().max()) for a_, b_ in zip(dx, ref))
+        dx_write = sum(N * C * H * H * 4 for _n, C, H in spec.SITES)
+        dx_read = sum((N * 128 + P * 32) * H * H * 4 for _n, _c, H in spec.SITES)
+        dx_flops = sum(2 * N * H * H * C * 160 for _n, C, H in spec.SITES)
+        extra = {"feat_grad_layout": dx_layout, "feat_grad_ms": round(t_dx, 4), "feat_grad_torch_composed_ms": round(t_torch, 4),
+                 "feat_grad_vs_torch_max_rel": float("%.3g" % err), "feat_grad_bytes_read": dx_read, "feat_grad_bytes_written": dx_write,
+                 "feat_grad_flops": dx_flops, "feat_grad_floor_ms_hbm_6TBs": round((dx_read + dx_write) / 6e12 * 1e3, 4),
+                 "feat_grad_floor_ms_fp32_mfma_157TF": round(dx_flops / 157e12 * 1e3, 4)}
     esz = 4 if fdt == torch.float32 else 2
     hw = sum(H * H for _n, _c, H in spec.SITES)
     # K2b: read dM (160 ch, P rows) + G (128, N) + D (32, P), write dG (128, N) + dD (32, P)
@@ -78,7 +117,7 @@ def main():
     x_bytes = sum(N * C * H * H * esz for _n, C, H in spec.SITES)
     k1b = x_bytes + B * hw * 4 * (128 * L + 32 * (L - 1))
     flops = sum(2 * N * H * H * C * 128 + 2 * P * H * H * C * 32 for _n, C, H in spec.SITES)
-    print(json.dumps({"batch": B, "length": L, "precision_fwd": a.precision, "feat_dtype": a.feat_dtype,
+    print(json.dumps({**extra, "feat_grad": bool(a.feat_grad), "batch": B, "length": L, "precision_fwd": a.precision, "feat_dtype": a.feat_dtype,
                       "feat_layout": a.feat_layout, "nine_contiguous_copies_ms": round(t_copy, 4),
                       "nine_float_casts_ms": round(t_cast, 4),
                       "units_train_forward_ms": round(t_fwd, 4), "units_backward_ms": round(t_bwd, 4),
