@@ -560,6 +560,29 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
 int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
                                   float* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
 
+/* ---- the same gradient in the maps' own 16-bit dtype (additive; ABI version unchanged) -----------
+ * An un-frozen backbone under autocast hands over bf16 / fp16 maps and wants their gradients in that dtype.  The kernel holds
+ * every finished fp32 sum in a register in front of its store, so it rounds there: no fp32 dX buffer, no cast kernels.
+ * grad_dtype: enum offk_feat_dtype, one per call.  OFFK_FEAT_F32 forwards to offk_off_units_backward_feats (dfeats cast to
+ * float* const*): same launch, same bits.  OFFK_FEAT_BF16 / OFFK_FEAT_F16: dfeats[i] is [B*L, C_i, H_i, H_i] (OFFK_FEAT_NCHW) or
+ * [B*L*H_i*H_i][C_i] (OFFK_FEAT_NHWC) in that element type.
+ * Rounding: every fp32 sum is rounded ONCE, to nearest-even, to grad_dtype.  For finite sums every element is the fp32 entry's
+ * element rounded to nearest-even: the result is bit-equal to dx32.to(dtype), dx32 being what the overwrite form of
+ * offk_off_units_backward_feats stores.  fp16 overflow gives +-Inf (so does a bf16 sum above the largest finite bf16); fp16
+ * subnormal results are kept, not flushed.
+ * accumulate != 0: out = rne16(widen(old) + new) -- the old 16-bit element widened exactly to fp32, ONE fp32 add of the finished
+ * sum, ONE rounding; the partial sums never pass through 16 bits: bit-equal to (old.float() + dx32).to(dtype).
+ * Equal bits across the two layouts, across runs and under graph replay follow from that.  A NaN, or the sign of a zero sum, is
+ * outside the equality.
+ * Everything else is offk_off_units_backward_feats': a NULL site is skipped, all nine NULL is OFFK_OK with nothing enqueued;
+ * pointers 16-byte aligned; no buffer may overlap the offk_train_workspace_bytes of `workspace` (tested with the buffer's real
+ * byte size, 2 bytes per element here); the handle's backward-has-run flag; weights read as they are at launch; one launch on
+ * `stream` (csrc/units_dx_f16.hip: the fp32 kernel's body with a 16-bit epilogue), no sync, no allocation, capturable.
+ * Refused with OFFK_ERR_INVALID, nothing enqueued: the fp32 entry's refusals, plus an unknown grad_dtype.
+ * Per-launch trace: "units:feature-map gradient (dX, NCHW, bf16)" / "(dX, NHWC, bf16)" / "(dX, NCHW, fp16)" / "(dX, NHWC, fp16)". */
+int offk_off_units_backward_feats_typed(offk_handle* h, void* stream, void* workspace, int grad_dtype,
+                                        void* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
+
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);
 

@@ -1912,10 +1912,13 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
 }
 
 // ---- gradient w.r.t. the feature maps (units_dx.hip) ----
-int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace, float* const dfeats[OFFK_NUM_SITES], int layout,
-                                  int accumulate) {
-  const char* fn = "offk_off_units_backward_feats";
+// the body of both entries: out_dtype kFeatF32 (fn the untyped entry's name: its launch, its bits) / kFeatBf16 / kFeatF16
+static int off_units_backward_feats(offk_handle* h, void* stream, void* workspace, int out_dtype, void* const dfeats[OFFK_NUM_SITES], int layout,
+                                    int accumulate, const char* fn) {
   if (!h || !workspace || !dfeats) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  if (out_dtype != kFeatF32 && out_dtype != kFeatBf16 && out_dtype != kFeatF16)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": grad_dtype must be OFFK_FEAT_F32, OFFK_FEAT_BF16 or OFFK_FEAT_F16");
+  const size_t esize = out_dtype == kFeatF32 ? sizeof(float) : 2;
   if (layout != OFFK_FEAT_NCHW && layout != OFFK_FEAT_NHWC)
     return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": layout must be OFFK_FEAT_NCHW or OFFK_FEAT_NHWC");
   if (!h->units_bwd_done)
@@ -1928,7 +1931,7 @@ int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
     ++nreq;
     if (reinterpret_cast<uintptr_t>(dfeats[s]) & 15) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": gradient pointers must be 16-byte aligned");
     const char* lo = reinterpret_cast<const char*>(dfeats[s]);
-    const char* hi = lo + (size_t)h->N * kSites[s].C * kSites[s].H * kSites[s].H * sizeof(float);
+    const char* hi = lo + (size_t)h->N * kSites[s].C * kSites[s].H * kSites[s].H * esize;
     if (lo < ws_hi && ws_lo < hi) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": a gradient buffer overlaps the workspace");
     TRY(site_weights_ready(h, s, true, false));
   }
@@ -1938,7 +1941,7 @@ int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
   DxParams dp;
   memset(&dp, 0, sizeof(dp));
   dp.L = h->cfg.length; dp.P = h->P; dp.slice_mode = h->cfg.slice_mode;
-  dp.nchw = layout == OFFK_FEAT_NCHW; dp.accumulate = accumulate ? 1 : 0; dp.zeros = h->zero_page;
+  dp.nchw = layout == OFFK_FEAT_NCHW; dp.accumulate = accumulate ? 1 : 0; dp.zeros = h->zero_page; dp.out_dtype = out_dtype;
   int blk = 0, n = 0;
   for (int i = 0; i < kNumSites; ++i) {      // the widest sites first, as K1 / K1b order theirs
     const int s = kPwOrder[i];
@@ -1954,9 +1957,26 @@ int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
     blk += (d.M + units_dx_rows_per_block() - 1) / units_dx_rows_per_block();
   }
   dp.nsites = n; dp.total_blocks = blk;
-  TRY(trace_mark(h, st, dp.nchw ? "units:feature-map gradient (dX, NCHW)" : "units:feature-map gradient (dX, NHWC)"));
-  HIP_TRY(h, units_dx_launch(dp, st));
+  static const char* const kDxTrace[3][2] = {
+      {"units:feature-map gradient (dX, NHWC)", "units:feature-map gradient (dX, NCHW)"},
+      {"units:feature-map gradient (dX, NHWC, bf16)", "units:feature-map gradient (dX, NCHW, bf16)"},
+      {"units:feature-map gradient (dX, NHWC, fp16)", "units:feature-map gradient (dX, NCHW, fp16)"}};
+  TRY(trace_mark(h, st, kDxTrace[out_dtype][dp.nchw]));
+  HIP_TRY(h, out_dtype == kFeatF32 ? units_dx_launch(dp, st) : units_dx16_launch(dp, st));
   return trace_mark(h, st, nullptr);
+}
+
+int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace, float* const dfeats[OFFK_NUM_SITES], int layout,
+                                  int accumulate) {
+  return off_units_backward_feats(h, stream, workspace, kFeatF32, reinterpret_cast<void* const*>(dfeats), layout, accumulate,
+                                  "offk_off_units_backward_feats");
+}
+
+int offk_off_units_backward_feats_typed(offk_handle* h, void* stream, void* workspace, int grad_dtype, void* const dfeats[OFFK_NUM_SITES],
+                                        int layout, int accumulate) {
+  if (grad_dtype == OFFK_FEAT_F32)
+    return offk_off_units_backward_feats(h, stream, workspace, reinterpret_cast<float* const*>(dfeats), layout, accumulate);
+  return off_units_backward_feats(h, stream, workspace, grad_dtype, dfeats, layout, accumulate, "offk_off_units_backward_feats_typed");
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

@@ -331,7 +331,7 @@ struct DxSite {
   const float* dD;      // [P*HW][32]
   const float* wg;      // gen rows [128][C] fp32 (PwSite::w)
   const float* wd;      // down rows [32][C] (PwSite::w_down)
-  float* out;           // nchw: [N][C][HW], else [N*HW][C]
+  void* out;            // nchw: [N][C][HW], else [N*HW][C]; elements of DxParams::out_dtype
   int C, HW, M;         // M = N*HW rows
   int blk_begin;
 };
@@ -340,9 +340,12 @@ struct DxParams {
   int nsites, total_blocks, L, P, slice_mode;
   int nchw, accumulate;
   const float* zeros;   // >= 16 bytes of zeros in device memory: what a masked-out load reads
+  int out_dtype;        // kFeatF32 (units_dx_launch) / kFeatBf16 / kFeatF16 (units_dx16_launch): the element type of DxSite::out
 };
 int units_dx_rows_per_block();
 hipError_t units_dx_launch(const DxParams& p, hipStream_t st);
+// dX in 16-bit elements (units_dx_f16.hip): the same blocks and sums, each rounded once to nearest-even to out_dtype
+hipError_t units_dx16_launch(const DxParams& p, hipStream_t st);
 
 // ---- K5 / K6 / layout helpers ----------------------------------------------------
 hipError_t head_launch(const float* x, int x_cs, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fw,

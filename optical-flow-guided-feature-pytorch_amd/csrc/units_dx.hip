@@ -19,6 +19,17 @@
 // stores them as they lie (lanes along c), NCHW turns the wave's 64 x 32 tile through a wave-private LDS image so that the
 // stores run along the pixel axis (scalar stores: the 49-float rows of the 7x7 sites are only 4-byte aligned and a tile crosses
 // image boundaries there).  accumulate adds the finished sum to what is there: out = old + new, new the overwrite form's bits.
+//
+// 16-bit dX (offk_off_units_backward_feats_typed, OUT = kFeatBf16 / kFeatF16): the same body up to the accumulators; the epilogue
+// rounds each finished fp32 sum ONCE, to nearest-even, and stores 16-bit elements (accumulate: rne16(widen(old) + new), one fp32
+// add of the exactly widened old element, one rounding).  NHWC: lane pairs (2 j, 2 j + 1) exchange one register of two (DPP
+// quad_perm [1, 0, 3, 2]) -- the even lane ends with channels (c, c + 1) of the first register's row, the odd lane with
+// (c - 1, c) of the second's -- and every lane issues ONE aligned 4-byte store per register pair: 16 stores per wave tile, not 32.
+// NCHW: the turn through Ts carries the fp32 sums, the lanes round what they read back and store 2-byte elements along the pixel
+// axis (the 98-byte rows of the 7x7 sites are only 2-byte aligned).
+//
+// This file is compiled twice: as it is (the two fp32 kernels and units_dx_launch), and through units_dx_f16.hip with
+// OFFK_UNITS_DX_F16 defined (the four 16-bit kernels and units_dx16_launch alone), so that the fp32 kernels keep the code they have.
 #include "offk_common.h"
 #include "offk_internal.h"
 
@@ -41,10 +52,40 @@ __device__ __forceinline__ int dx_down_row(int f, int L, int P, int slice_mode) 
   return t < L - 1 ? b * (L - 1) + t : -1;
 }
 
+// ---- 16-bit output elements: one rounding to nearest-even, exact widening ----
+template <int OUT>
+__device__ __forceinline__ unsigned dx_pack16(float lo, float hi) {     // element lo in bits 0..15 (the lower address)
+  if constexpr (OUT == kFeatBf16) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+  } else {
+    const _Float16 l = (_Float16)lo, u = (_Float16)hi;                   // v_cvt_f16_f32 under the default (nearest-even) mode
+    return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, u) << 16);
+  }
+}
+template <int OUT>
+__device__ __forceinline__ unsigned short dx_round16(float v) {
+  if constexpr (OUT == kFeatBf16) return (unsigned short)(dx_pack16<OUT>(v, 0.f) & 0xFFFFu);
+  else return __builtin_bit_cast(unsigned short, (_Float16)v);
+}
+template <int OUT>
+__device__ __forceinline__ float dx_widen16(unsigned short b) {
+  if constexpr (OUT == kFeatBf16) return __builtin_bit_cast(float, (unsigned)b << 16);
+  else return (float)__builtin_bit_cast(_Float16, b);
+}
+
 }  // namespace
 
+// one kernel text under two names: the fp32 kernels of this object, the 16-bit kernels (OUT a template parameter) of units_dx_f16.o
+#ifndef OFFK_UNITS_DX_F16
 template <bool NCHW>
 __global__ __launch_bounds__(DX_THREADS, 1) void units_dx_kernel(DxParams p) {
+  constexpr int OUT = kFeatF32;
+#else
+template <bool NCHW, int OUT>
+__global__ __launch_bounds__(DX_THREADS, 1) void units_dx16_kernel(DxParams p) {
+#endif
   extern __shared__ __attribute__((aligned(16))) float dx_lds[];
   float* As = dx_lds;                            // [128][DX_AS]
   float* Bs = dx_lds + DX_BM * DX_AS;            // [160][64]
@@ -141,15 +182,39 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx_kernel(DxParams p) {
     }
 
     // ---- epilogue: acc[t][reg] = row wr * 64 + t * 32 + acc_row(reg, h), channel cbase + r32 ----
-    if constexpr (!NCHW) {
+    if constexpr (!NCHW && OUT == kFeatF32) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
           const int row = row0 + wr * 64 + t * 32 + acc_row(reg, h);
           if (row < M) {
-            float* o = S.out + (size_t)row * C + cbase + r32;
+            float* o = static_cast<float*>(S.out) + (size_t)row * C + cbase + r32;
             *o = p.accumulate ? *o + acc[t][reg] : acc[t][reg];
+          }
+        }
+    } else if constexpr (!NCHW) {
+      // registers (2 i, 2 i + 1) are two adjacent rows: the even lane keeps the first and takes its neighbour's first (channel + 1),
+      // the odd lane keeps the second and takes its neighbour's second (channel - 1).  The exchange runs in every lane (a DPP read
+      // of a lane that sat out a branch is undefined); only the store is masked by the row.
+      const bool odd = lane & 1;
+      unsigned short* const o16 = static_cast<unsigned short*>(S.out);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float a = acc[t][2 * i], b = acc[t][2 * i + 1];
+          const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? a : b), 0xB1, 0xF, 0xF, false));
+          float lo = odd ? got : a, hi = odd ? b : got;
+          const int row = row0 + wr * 64 + t * 32 + acc_row(2 * i, h) + (odd ? 1 : 0);
+          if (row < M) {       // channels cbase + (r32 & ~1), + 1: both below C (C and cbase are even), 4-byte aligned (row * C is even)
+            unsigned* o = reinterpret_cast<unsigned*>(o16 + (size_t)row * C + cbase + (r32 & ~1));
+            if (p.accumulate) {
+              const unsigned old = *o;
+              lo += dx_widen16<OUT>((unsigned short)(old & 0xFFFFu));
+              hi += dx_widen16<OUT>((unsigned short)(old >> 16));
+            }
+            *o = dx_pack16<OUT>(lo, hi);
           }
         }
     } else {
@@ -162,13 +227,25 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx_kernel(DxParams p) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (erow < M) {
-        float* o = S.out + ((size_t)ef * C + cbase) * HW + epx;
+      if constexpr (OUT == kFeatF32) {
+        if (erow < M) {
+          float* o = static_cast<float*>(S.out) + ((size_t)ef * C + cbase) * HW + epx;
 #pragma unroll 8
-        for (int ch = 0; ch < 32; ++ch) {
-          const float v = T[ch * DX_TS + lane];
-          float* oc = o + (size_t)ch * HW;
-          *oc = p.accumulate ? *oc + v : v;
+          for (int ch = 0; ch < 32; ++ch) {
+            const float v = T[ch * DX_TS + lane];
+            float* oc = o + (size_t)ch * HW;
+            *oc = p.accumulate ? *oc + v : v;
+          }
+        }
+      } else {
+        if (erow < M) {
+          unsigned short* o = static_cast<unsigned short*>(S.out) + ((size_t)ef * C + cbase) * HW + epx;
+#pragma unroll 8
+          for (int ch = 0; ch < 32; ++ch) {
+            const float v = T[ch * DX_TS + lane];
+            unsigned short* oc = o + (size_t)ch * HW;
+            *oc = dx_round16<OUT>(p.accumulate ? dx_widen16<OUT>(*oc) + v : v);
+          }
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -180,6 +257,7 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx_kernel(DxParams p) {
 
 #undef OFFK_DX_LOAD_W
 
+#ifndef OFFK_UNITS_DX_F16
 hipError_t units_dx_launch(const DxParams& p, hipStream_t st) {
   if (p.total_blocks <= 0) return hipSuccess;
   constexpr int lds = DX_LDS_FLOATS * (int)sizeof(float);
@@ -192,5 +270,23 @@ hipError_t units_dx_launch(const DxParams& p, hipStream_t st) {
 }
 
 int units_dx_rows_per_block() { return DX_BM; }
+
+#else   // OFFK_UNITS_DX_F16
+template <bool NCHW, int OUT>
+static hipError_t dx16_launch(const DxParams& p, hipStream_t st) {
+  constexpr int lds = DX_LDS_FLOATS * (int)sizeof(float);
+  hipError_t e = lds_attr_once(reinterpret_cast<const void*>(units_dx16_kernel<NCHW, OUT>), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((units_dx16_kernel<NCHW, OUT>), dim3(p.total_blocks), dim3(DX_THREADS), lds, st, p);
+  return hipGetLastError();
+}
+
+hipError_t units_dx16_launch(const DxParams& p, hipStream_t st) {
+  if (p.total_blocks <= 0) return hipSuccess;
+  if (p.out_dtype == kFeatBf16) return p.nchw ? dx16_launch<true, kFeatBf16>(p, st) : dx16_launch<false, kFeatBf16>(p, st);
+  if (p.out_dtype == kFeatF16) return p.nchw ? dx16_launch<true, kFeatF16>(p, st) : dx16_launch<false, kFeatF16>(p, st);
+  return hipErrorInvalidValue;
+}
+#endif  // OFFK_UNITS_DX_F16
 
 }  // namespace offk

@@ -196,9 +196,14 @@ class _OFFUnitsFeatFn(torch.autograd.Function):
         if sites:
             # the layout the maps came in: all nine channels_last (the route the forward took) -> channels_last gradients
             layout = "cl" if ctx.mod._as_handed_over(ctx.feats) else "nchw"
-            dx = ctx.mod._rt.off_units_backward_feats(sites, layout)
-            # torch wants a gradient in its input's dtype: a 16-bit map gets the fp32 result cast to it (one rounding of the fp32 sum)
-            dx = [g if g is None or g.dtype == f.dtype else g.to(f.dtype) for g, f in zip(dx, ctx.feats)]
+            # torch wants a gradient in its input's dtype.  Nine maps of one dtype (always so on the typed / cl routes): the kernel
+            # stores that dtype itself, each fp32 sum rounded once.  A mix of dtypes (the plain route): fp32 dX, cast per map
+            dts = set(f.dtype for f in ctx.feats)
+            dtype = dts.pop() if len(dts) == 1 else torch.float32
+            dtype = dtype if dtype in (torch.bfloat16, torch.float16) else torch.float32
+            dx = ctx.mod._rt.off_units_backward_feats(sites, layout, dtype=dtype)
+            if dtype == torch.float32:
+                dx = [g if g is None or g.dtype == f.dtype else g.to(f.dtype) for g, f in zip(dx, ctx.feats)]
         return (None, None) + tuple(dx) + tuple(pgrads)
 
 
@@ -227,7 +232,7 @@ class OFFUnits(nn.Module):
     backbone (inception_5a / 5b of a TSN partial fine-tune, or all of it): the maps become inputs of the node and every map that
     requires grad gets its gradient from offk_off_units_backward_feats -- one more launch per backward, for those sites only, in
     the maps' layout (contiguous, or channels_last where all nine came so).  The gradient is computed in fp32; a bf16 / fp16 map
-    receives it CAST to its dtype, as torch requires.  Parameter gradients are the same bits either way."""
+    receives it rounded once in the kernel to its dtype (nearest-even, offk_off_units_backward_feats_typed: no fp32 buffer, no cast).  Parameter gradients are the same bits either way."""
 
     def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False):
         super().__init__()

@@ -461,16 +461,22 @@ class OffForward:
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
 
-    def off_units_backward_feats(self, sites=None, layout="nchw", out=None, accumulate=False):
+    def off_units_backward_feats(self, sites=None, layout="nchw", out=None, accumulate=False, dtype=torch.float32):
         """Gradient w.r.t. the feature maps (offk_off_units_backward_feats): one launch, from what the LAST off_units_backward on this
         handle left in the workspace and the gen / down weights as they are now (bound weights: call it before the optimizer step).
         sites: the site indices wanted (None: all nine).  layout "nchw": contiguous [B*L, C, H, H] tensors; "cl": the same logical
         shape with torch.channels_last strides.  out: nine entries (None where a site is skipped) to write -- or, accumulate=True,
-        add -- into instead of fresh tensors.  Returns a list of nine, None for the skipped sites; fp32 always."""
+        add -- into instead of fresh tensors.  dtype: torch.float32 (offk_off_units_backward_feats), or torch.bfloat16 / torch.float16
+        (offk_off_units_backward_feats_typed: the kernel rounds each fp32 sum once, to nearest-even -- bit-equal to the fp32 result's
+        .to(dtype); accumulate: (old.float() + dx32).to(dtype)); fresh tensors and `out` tensors are of that dtype.  Returns a list of
+        nine, None for the skipped sites."""
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
         if layout not in ("nchw", "cl"):
             raise ValueError("layout must be \"nchw\" or \"cl\", got %r" % (layout,))
+        if dtype not in _CL_DTYPES:
+            raise ValueError("dtype must be torch.float32, torch.bfloat16 or torch.float16, got %r" % (dtype,))
+        dname = {torch.float32: "an fp32", torch.bfloat16: "a bf16", torch.float16: "an fp16"}[dtype]
         want = feat_grad_sites_mask(sites)
         if out is not None and len(out) != spec.NUM_SITES:
             raise ValueError("out must have nine entries (None for a skipped site)")
@@ -484,19 +490,24 @@ class OffForward:
             if t is None:
                 if accumulate:
                     raise ValueError("accumulate=True: out[%d] is None but site %d is asked for" % (i, i))
-                t = torch.empty((n, c, h, h) if layout == "nchw" else (n, h, h, c), dtype=torch.float32, device=self.device)
+                t = torch.empty((n, c, h, h) if layout == "nchw" else (n, h, h, c), dtype=dtype, device=self.device)
                 t = t if layout == "nchw" else t.permute(0, 3, 1, 2)
             dense = t.is_contiguous() if layout == "nchw" else _is_channels_last(t)
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and dense):
-                raise ValueError("out[%d] must be an fp32 CUDA/HIP tensor, %s" % (i, "contiguous" if layout == "nchw" else "torch.channels_last"))
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 4 and dense):
+                raise ValueError("out[%d] must be %s CUDA/HIP tensor, %s" % (i, dname, "contiguous" if layout == "nchw" else "torch.channels_last"))
             if t.device != self.device:
                 raise ValueError("out[%d] lives on %s, handle on %s" % (i, t.device, self.device))
             if tuple(t.shape) != (n, c, h, h):
                 raise ValueError("out[%d] has shape %s, expected %s" % (i, tuple(t.shape), (n, c, h, h)))
             res[i] = t
         arr = (ctypes.c_void_p * spec.NUM_SITES)(*[t.data_ptr() if t is not None else None for t in res])
-        _lib.check(self.lib.offk_off_units_backward_feats(self._h, _stream(self.device), _ptr(self.workspace), arr,
-                                                          _lib.FEAT_NCHW if layout == "nchw" else _lib.FEAT_NHWC, int(bool(accumulate))), self._h)
+        lay = _lib.FEAT_NCHW if layout == "nchw" else _lib.FEAT_NHWC
+        if dtype == torch.float32:
+            _lib.check(self.lib.offk_off_units_backward_feats(self._h, _stream(self.device), _ptr(self.workspace), arr, lay,
+                                                              int(bool(accumulate))), self._h)
+        else:
+            _lib.check(self.lib.offk_off_units_backward_feats_typed(self._h, _stream(self.device), _ptr(self.workspace), _CL_DTYPES[dtype], arr,
+                                                                    lay, int(bool(accumulate))), self._h)
         return res
 
     # ---- stage entry points -----------------------------------------------------------
