@@ -583,6 +583,36 @@ int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
 int offk_off_units_backward_feats_typed(offk_handle* h, void* stream, void* workspace, int grad_dtype,
                                         void* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
 
+/* ---- the same gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, opt-in; ABI version unchanged) -----------
+ * The first piece of the training side in the arithmetic of OFFK_PRECISION_F32SPLIT; it works on ANY handle, whatever its
+ * precision, and the entries above stay the default with their contract (exact fp32 on the fp32 matrix pipe).
+ * Arithmetic: dX[n, q, c] = sum_{k < 160} a[n, q, k] w[c, k], a = [dGpre | dD at row r(n), zeros for a frame outside the slice],
+ * w[c] = [Wg[:, c] ; Wd[:, c]].  Both fp32 operands are cut into THREE bf16 planes by truncation (exactly: h + m + l == value);
+ * per 32-k step six of the nine plane products run on v_mfma_f32_16x16x32_bf16, w_h a_h into one fp32 accumulator and the five
+ * small ones (w_l a_h, w_h a_l, w_m a_m, w_m a_h, w_h a_m, in that order) into a second, five steps in increasing k (gen
+ * channels, then down), out = A1 + A2 once in the epilogue.  The three dropped products are below (2^-21 + 2^-30) sum|a w| per
+ * element; to that come the fp32 accumulation of the two accumulators and the one epilogue add.  +-Inf in an operand gives NaN
+ * (Inf - Inf in the cut), and tiny operands behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT says (below 2^-109 an
+ * operand's last plane falls under the last bf16 subnormal).  No split-K, no atomics, one fixed order.
+ * Equal bits: across the two layouts, across runs and under graph replay.  It is NOT bit-equal to offk_off_units_backward_feats.
+ * grad_dtype: enum offk_feat_dtype, OFFK_FEAT_F32 included (dfeats[i] then points at fp32).  The 16-bit forms round each
+ * finished fp32 sum ONCE, to nearest-even: for finite sums they are dx32s.to(dtype), and with accumulate != 0
+ * (old.float() + dx32s).to(dtype), bit for bit, dx32s being what the fp32 overwrite form of THIS entry stores (a NaN, or the
+ * sign of a zero sum, is outside the equality).  fp32 with accumulate: out = old + dx32s.  fp16 overflow gives +-Inf, fp16
+ * subnormal results are kept.
+ * TWO launches on `stream` (csrc/units_dx_split.hip): a pre-pass that cuts [Wg ; Wd] of the requested sites, as they are at
+ * launch time (bound weights: read in place -> enqueue before the optimizer step), into a plane image the handle owns (5.3 MB,
+ * allocated at offk_create), then the GEMM.  No sync, no allocation, capturable.  The image is per handle: two calls on one
+ * handle must be ordered (one stream, or an event), like every other use of the handle's buffers.
+ * Everything else is offk_off_units_backward_feats_typed's: a NULL site is skipped, all nine NULL is OFFK_OK with nothing
+ * enqueued; pointers 16-byte aligned; no buffer may overlap the offk_train_workspace_bytes of `workspace` (tested with the
+ * buffer's real byte size); the handle's backward-has-run flag.  Refused with OFFK_ERR_INVALID, nothing enqueued: a null h,
+ * workspace or dfeats, an unknown layout or grad_dtype, a misaligned pointer, an overlap, no backward run yet.
+ * Per-launch trace: "units:feature-map gradient (dX, NCHW, split)" / "(dX, NHWC, split)", with ", bf16" / ", fp16" behind
+ * "split" for the 16-bit forms. */
+int offk_off_units_backward_feats_split(offk_handle* h, void* stream, void* workspace, int grad_dtype,
+                                        void* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
+
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);
 

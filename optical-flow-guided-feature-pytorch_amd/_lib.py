@@ -99,6 +99,7 @@ SIGNATURES = {
     "offk_off_units_backward_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _c.POINTER(OffkGradView), _P, _c.c_uint64, _c.c_double, _F, _I]),
     "offk_off_units_backward_feats": (_I, [_P, _P, _P, _c.POINTER(_F), _I, _I]),
     "offk_off_units_backward_feats_typed": (_I, [_P, _P, _P, _I, _c.POINTER(_P), _I, _I]),
+    "offk_off_units_backward_feats_split": (_I, [_P, _P, _P, _I, _c.POINTER(_P), _I, _I]),
     "offk_segment_consensus_backward": (_I, [_P, _F, _I, _I, _I, _F]),
     "offk_nchw_to_nhwc": (_I, [_P, _F, _I, _I, _I, _F]),
     "offk_nhwc_to_nchw": (_I, [_P, _F, _I, _I, _I, _I, _I, _F]),

@@ -205,6 +205,7 @@ struct offk_handle {
 
   // training side (offk_off_units_backward): workspace superset, K1b chunking, gradient-buffer layout
   float* zero_page = nullptr;    // 256 B of zeros (target of masked-out loads)
+  float* dx_split_w[kNumSites] = {};   // offk_off_units_backward_feats_split: plane image of [Wg ; Wd] per site, rewritten by every call (960 B per channel)
   bool fused_units = true;       // forward: K1 fused with the temporal difference (OFFK_FUSED_UNITS=0 at offk_create: K1 + K2)
   bool winograd = true;          // fp32: Winograd F(4x4, 3x3) for the three 3x3 / stride 1 convs on 7x7 maps (winograd.hip); OFFK_WINOGRAD=0: direct
   bool wino_7x7 = true;          // the 7x7 / stride 2 conv of fusion@28 in polyphase Winograd form F(5x5, 4x4) (OFFK_WINOGRAD_7X7=0: direct)
@@ -1291,6 +1292,7 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
 
   }
   if (rc == OFFK_OK) rc = dev_alloc(h, &h->zero_page, 64);
+  for (int s = 0; s < kNumSites && rc == OFFK_OK; ++s) rc = dev_alloc(h, &h->dx_split_w[s], units_dx_split_image_bytes(kSites[s].C) / sizeof(float));
   // The path switches of the product library, all read HERE and nowhere else (INTEGRATION.md lists them): each names one
   // algorithm choice of the exact-fp32 forward; "0" = off, a number > 1 = use it from that many frame pairs P = B (L - 1).
   //   OFFK_FUSED_UNITS   K1 fused with the temporal difference (pw_tdiff.hip); 0: K1 + K2 (what training always runs)
@@ -1912,9 +1914,42 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
 }
 
 // ---- gradient w.r.t. the feature maps (units_dx.hip) ----
+// the launches of offk_off_units_backward_feats_split (units_dx_split.hip) behind the checks all dX entries share
+static int off_units_backward_feats_split(offk_handle* h, hipStream_t st, void* workspace, int out_dtype, void* const dfeats[OFFK_NUM_SITES], int layout,
+                                          int accumulate) {
+  DxsParams dp;
+  memset(&dp, 0, sizeof(dp));
+  dp.L = h->cfg.length; dp.P = h->P; dp.slice_mode = h->cfg.slice_mode;
+  dp.nchw = layout == OFFK_FEAT_NCHW; dp.accumulate = accumulate ? 1 : 0; dp.zeros = h->zero_page; dp.out_dtype = out_dtype;
+  int blk = 0, pblk = 0, n = 0;
+  for (int i = 0; i < kNumSites; ++i) {      // the widest sites first, as the fp32 entry orders them
+    const int s = kPwOrder[i];
+    if (!dfeats[s]) continue;
+    DxsSite& d = dp.s[n++];
+    const float *b, *bd;
+    pw_weight_ptrs(h, s, &d.wg, &d.wd, &b, &bd);
+    d.dG = region(h, workspace, (std::string("dG_") + kSites[s].name).c_str());
+    d.dD = region(h, workspace, (std::string("dD_") + kSites[s].name).c_str());
+    d.wimg = h->dx_split_w[s];
+    d.out = dfeats[s];
+    d.C = kSites[s].C; d.HW = kSites[s].H * kSites[s].H; d.M = h->N * d.HW;
+    d.blk_begin = blk; d.pack_begin = pblk;
+    blk += (d.M + units_dx_split_rows_per_block() - 1) / units_dx_split_rows_per_block();
+    pblk += units_dx_split_pack_blocks(d.C);
+  }
+  dp.nsites = n; dp.total_blocks = blk; dp.pack_blocks = pblk;
+  static const char* const kDxsTrace[3][2] = {
+      {"units:feature-map gradient (dX, NHWC, split)", "units:feature-map gradient (dX, NCHW, split)"},
+      {"units:feature-map gradient (dX, NHWC, split, bf16)", "units:feature-map gradient (dX, NCHW, split, bf16)"},
+      {"units:feature-map gradient (dX, NHWC, split, fp16)", "units:feature-map gradient (dX, NCHW, split, fp16)"}};
+  TRY(trace_mark(h, st, kDxsTrace[out_dtype][dp.nchw]));
+  HIP_TRY(h, units_dx_split_launch(dp, st));
+  return trace_mark(h, st, nullptr);
+}
+
 // the body of both entries: out_dtype kFeatF32 (fn the untyped entry's name: its launch, its bits) / kFeatBf16 / kFeatF16
 static int off_units_backward_feats(offk_handle* h, void* stream, void* workspace, int out_dtype, void* const dfeats[OFFK_NUM_SITES], int layout,
-                                    int accumulate, const char* fn) {
+                                    int accumulate, const char* fn, bool split = false) {
   if (!h || !workspace || !dfeats) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
   if (out_dtype != kFeatF32 && out_dtype != kFeatBf16 && out_dtype != kFeatF16)
     return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": grad_dtype must be OFFK_FEAT_F32, OFFK_FEAT_BF16 or OFFK_FEAT_F16");
@@ -1938,6 +1973,7 @@ static int off_units_backward_feats(offk_handle* h, void* stream, void* workspac
   if (!nreq) return OFFK_OK;
   DeviceGuard guard(h->cfg.device);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (split) return off_units_backward_feats_split(h, st, workspace, out_dtype, dfeats, layout, accumulate);
   DxParams dp;
   memset(&dp, 0, sizeof(dp));
   dp.L = h->cfg.length; dp.P = h->P; dp.slice_mode = h->cfg.slice_mode;
@@ -1977,6 +2013,11 @@ int offk_off_units_backward_feats_typed(offk_handle* h, void* stream, void* work
   if (grad_dtype == OFFK_FEAT_F32)
     return offk_off_units_backward_feats(h, stream, workspace, reinterpret_cast<float* const*>(dfeats), layout, accumulate);
   return off_units_backward_feats(h, stream, workspace, grad_dtype, dfeats, layout, accumulate, "offk_off_units_backward_feats_typed");
+}
+
+int offk_off_units_backward_feats_split(offk_handle* h, void* stream, void* workspace, int grad_dtype, void* const dfeats[OFFK_NUM_SITES],
+                                        int layout, int accumulate) {
+  return off_units_backward_feats(h, stream, workspace, grad_dtype, dfeats, layout, accumulate, "offk_off_units_backward_feats_split", true);
 }
 
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in) {

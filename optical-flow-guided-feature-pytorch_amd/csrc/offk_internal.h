@@ -347,6 +347,30 @@ hipError_t units_dx_launch(const DxParams& p, hipStream_t st);
 // dX in 16-bit elements (units_dx_f16.hip): the same blocks and sums, each rounded once to nearest-even to out_dtype
 hipError_t units_dx16_launch(const DxParams& p, hipStream_t st);
 
+// ---- the same gradient in split-fp32 arithmetic on the bf16 matrix pipe (units_dx_split.hip): TWO launches, the weight pre-pass and the GEMM ----
+struct DxsSite {
+  const float* dG;      // [N*HW][128] as K2b left it
+  const float* dD;      // [P*HW][32]
+  const float* wg;      // gen rows [128][C] fp32
+  const float* wd;      // down rows [32][C]
+  void* wimg;           // units_dx_split_image_bytes(C) of the handle: the plane image of [Wg ; Wd], written by the pre-pass of THIS call
+  void* out;            // nchw: [N][C][HW], else [N*HW][C]; elements of DxsParams::out_dtype
+  int C, HW, M;         // M = N*HW rows
+  int blk_begin;        // first block of the site in the GEMM launch
+  int pack_begin;       // ... in the pre-pass launch
+};
+struct DxsParams {
+  DxsSite s[kNumSites];
+  int nsites, total_blocks, pack_blocks, L, P, slice_mode;
+  int nchw, accumulate;
+  const float* zeros;   // >= 16 bytes of zeros in device memory: what a masked-out load reads
+  int out_dtype;        // kFeatF32 / kFeatBf16 / kFeatF16
+};
+int units_dx_split_rows_per_block();
+int units_dx_split_pack_blocks(int C);
+size_t units_dx_split_image_bytes(int C);
+hipError_t units_dx_split_launch(const DxsParams& p, hipStream_t st);
+
 // ---- K5 / K6 / layout helpers ----------------------------------------------------
 hipError_t head_launch(const float* x, int x_cs, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fw,
                        const float* fb, int ncls, float* out, hipStream_t st, const char** why);

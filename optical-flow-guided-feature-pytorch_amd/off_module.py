@@ -201,7 +201,9 @@ class _OFFUnitsFeatFn(torch.autograd.Function):
             dts = set(f.dtype for f in ctx.feats)
             dtype = dts.pop() if len(dts) == 1 else torch.float32
             dtype = dtype if dtype in (torch.bfloat16, torch.float16) else torch.float32
-            dx = ctx.mod._rt.off_units_backward_feats(sites, layout, dtype=dtype)
+            # (the default arithmetic makes today's call, argument for argument)
+            arith = {} if ctx.mod.feat_grad_arith == "fp32" else {"arith": ctx.mod.feat_grad_arith}
+            dx = ctx.mod._rt.off_units_backward_feats(sites, layout, dtype=dtype, **arith)
             if dtype == torch.float32:
                 dx = [g if g is None or g.dtype == f.dtype else g.to(f.dtype) for g, f in zip(dx, ctx.feats)]
         return (None, None) + tuple(dx) + tuple(pgrads)
@@ -232,11 +234,17 @@ class OFFUnits(nn.Module):
     backbone (inception_5a / 5b of a TSN partial fine-tune, or all of it): the maps become inputs of the node and every map that
     requires grad gets its gradient from offk_off_units_backward_feats -- one more launch per backward, for those sites only, in
     the maps' layout (contiguous, or channels_last where all nine came so).  The gradient is computed in fp32; a bf16 / fp16 map
-    receives it rounded once in the kernel to its dtype (nearest-even, offk_off_units_backward_feats_typed: no fp32 buffer, no cast).  Parameter gradients are the same bits either way."""
+    receives it rounded once in the kernel to its dtype (nearest-even, offk_off_units_backward_feats_typed: no fp32 buffer, no cast).  Parameter gradients are the same bits either way.
+    ``feat_grad_arith="f32split"`` (default ``"fp32"``) computes that gradient in split-fp32 arithmetic on the bf16 matrix pipe instead
+    (offk_off_units_backward_feats_split: dropped part below (2^-21 + 2^-30) sum|a w| per element, reproducible, its own bits); it
+    changes nothing else -- the parameter gradients are the same bits."""
 
-    def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False):
+    def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False,
+                 feat_grad_arith="fp32"):
         super().__init__()
-        self.feat_grad = bool(feat_grad)
+        if feat_grad_arith not in runtime.FEAT_GRAD_ARITHS:
+            raise ValueError("feat_grad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.FEAT_GRAD_ARITHS), feat_grad_arith))
+        self.feat_grad, self.feat_grad_arith = bool(feat_grad), feat_grad_arith
         if variant not in _VARIANTS:
             raise ValueError("variant must be one of %s" % sorted(_VARIANTS))
         self.variant = _VARIANTS[variant]

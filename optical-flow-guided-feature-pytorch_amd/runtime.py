@@ -172,6 +172,10 @@ def train_feat_layout(feats, batch, length):
     return "cl" if _all_channels_last(feats, batch, length, "train", True) else "nchw"
 
 
+# the arithmetic of the feature-map gradient: "fp32" = offk_off_units_backward_feats[_typed], "f32split" = offk_off_units_backward_feats_split
+FEAT_GRAD_ARITHS = ("fp32", "f32split")
+
+
 def feat_grad_sites(needs_input_grad, first=0):
     """The sites whose map wants a gradient, from an autograd node's ``ctx.needs_input_grad``: the nine maps are its inputs
     ``first .. first + 8``.  A pure function of the flags (CPU)."""
@@ -461,7 +465,7 @@ class OffForward:
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
 
-    def off_units_backward_feats(self, sites=None, layout="nchw", out=None, accumulate=False, dtype=torch.float32):
+    def off_units_backward_feats(self, sites=None, layout="nchw", out=None, accumulate=False, dtype=torch.float32, arith="fp32"):
         """Gradient w.r.t. the feature maps (offk_off_units_backward_feats): one launch, from what the LAST off_units_backward on this
         handle left in the workspace and the gen / down weights as they are now (bound weights: call it before the optimizer step).
         sites: the site indices wanted (None: all nine).  layout "nchw": contiguous [B*L, C, H, H] tensors; "cl": the same logical
@@ -469,7 +473,12 @@ class OffForward:
         add -- into instead of fresh tensors.  dtype: torch.float32 (offk_off_units_backward_feats), or torch.bfloat16 / torch.float16
         (offk_off_units_backward_feats_typed: the kernel rounds each fp32 sum once, to nearest-even -- bit-equal to the fp32 result's
         .to(dtype); accumulate: (old.float() + dx32).to(dtype)); fresh tensors and `out` tensors are of that dtype.  Returns a list of
-        nine, None for the skipped sites."""
+        nine, None for the skipped sites.
+        arith: "fp32" (the default: the entries above, exact fp32 on the fp32 matrix pipe) or "f32split"
+        (offk_off_units_backward_feats_split: split-fp32 arithmetic on the bf16 matrix pipe for every dtype, a weight pre-pass plus
+        the GEMM; its own bits, reproducible, the 16-bit forms bit-equal to ITS fp32 result's .to(dtype))."""
+        if arith not in FEAT_GRAD_ARITHS:
+            raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in FEAT_GRAD_ARITHS), arith))
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
         if layout not in ("nchw", "cl"):
@@ -502,7 +511,10 @@ class OffForward:
             res[i] = t
         arr = (ctypes.c_void_p * spec.NUM_SITES)(*[t.data_ptr() if t is not None else None for t in res])
         lay = _lib.FEAT_NCHW if layout == "nchw" else _lib.FEAT_NHWC
-        if dtype == torch.float32:
+        if arith == "f32split":
+            _lib.check(self.lib.offk_off_units_backward_feats_split(self._h, _stream(self.device), _ptr(self.workspace), _CL_DTYPES[dtype], arr,
+                                                                    lay, int(bool(accumulate))), self._h)
+        elif dtype == torch.float32:
             _lib.check(self.lib.offk_off_units_backward_feats(self._h, _stream(self.device), _ptr(self.workspace), arr, lay,
                                                               int(bool(accumulate))), self._h)
         else:

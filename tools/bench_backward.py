@@ -1,7 +1,7 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
     python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy] [--feat-grad]
-                                     [--feat-grad-dtype map|fp32]
+                                     [--feat-grad-dtype map|fp32] [--feat-grad-arith fp32|f32split]
 --feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
 .float() casts that path makes unnecessary are timed beside it.
 --feat-layout cl: the maps are torch.channels_last tensors and go in as they are (offk_off_units_train_cl / offk_off_units_backward_cl);
@@ -14,6 +14,8 @@ from torch ops (torch.nn.grad.conv2d_input for the two 1x1 convs, the add into t
 rounded in the kernel; fp32: the route without that entry -- the fp32 launch plus nine .to(dtype) casts of its result (what
 OFFUnits(feat_grad=True) did on 16-bit maps before), for the A/B.  feat_grad_ms is the whole route, feat_grad_launch_ms the launch
 alone, feat_grad_casts_ms the nine casts alone.
+--feat-grad-arith f32split: dX from offk_off_units_backward_feats_split (split-fp32 on the bf16 matrix pipe; feat_grad_launch_ms then
+covers its two launches, the weight pre-pass included); fp32 (default): the fp32 matrix pipe's entries.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -53,6 +55,7 @@ def main():
     ap.add_argument("--feat-layout", default="nchw", choices=["nchw", "cl", "copy"])
     ap.add_argument("--feat-grad", action="store_true")
     ap.add_argument("--feat-grad-dtype", default="map", choices=["map", "fp32"])
+    ap.add_argument("--feat-grad-arith", default="fp32", choices=list(runtime.FEAT_GRAD_ARITHS))
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
@@ -70,13 +73,13 @@ def main():
     if a.feat_grad:
         h.off_units_train(feats, 21, 0.8)
         h.off_units_backward(feats, views, 21, 0.8, grads=grads)
-        dx = h.off_units_backward_feats(layout=dx_layout, dtype=dx_dt)
+        dx = h.off_units_backward_feats(layout=dx_layout, dtype=dx_dt, arith=a.feat_grad_arith)
 
     def dx_casts():
         return [g.to(fdt) for g in dx] if dx_dt != fdt else dx
 
     def dx_route():
-        h.off_units_backward_feats(layout=dx_layout, out=dx, dtype=dx_dt)
+        h.off_units_backward_feats(layout=dx_layout, out=dx, dtype=dx_dt, arith=a.feat_grad_arith)
         return dx_casts()
 
     def bwd(x):
@@ -113,7 +116,7 @@ def main():
                 out.append(g)
             return out
         t_dx = timed(dx_route, a.iters)
-        t_launch = timed(lambda: h.off_units_backward_feats(layout=dx_layout, out=dx, dtype=dx_dt), a.iters)
+        t_launch = timed(lambda: h.off_units_backward_feats(layout=dx_layout, out=dx, dtype=dx_dt, arith=a.feat_grad_arith), a.iters)
         t_casts = timed(dx_casts, a.iters) if dx_dt != fdt else 0.0
         t_torch = timed(composed, a.iters)
         ref = composed()
@@ -121,7 +124,7 @@ def main():
         dx_write = sum(N * C * H * H * dx[0].element_size() for _n, C, H in spec.SITES)
         dx_read = sum((N * 128 + P * 32) * H * H * 4 for _n, _c, H in spec.SITES)
         dx_flops = sum(2 * N * H * H * C * 160 for _n, C, H in spec.SITES)
-        extra = {"feat_grad_layout": dx_layout, "feat_grad_dtype": str(dx_dt).replace("torch.", ""), "feat_grad_ms": round(t_dx, 4),
+        extra = {"feat_grad_arith": a.feat_grad_arith, "feat_grad_layout": dx_layout, "feat_grad_dtype": str(dx_dt).replace("torch.", ""), "feat_grad_ms": round(t_dx, 4),
                  "feat_grad_launch_ms": round(t_launch, 4), "feat_grad_casts_ms": round(t_casts, 4), "feat_grad_torch_composed_ms": round(t_torch, 4),
                  "feat_grad_vs_torch_max_rel": float("%.3g" % err), "feat_grad_bytes_read": dx_read, "feat_grad_bytes_written": dx_write,
                  "feat_grad_flops": dx_flops, "feat_grad_floor_ms_hbm_6TBs": round((dx_read + dx_write) / 6e12 * 1e3, 4),
