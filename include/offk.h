@@ -613,6 +613,45 @@ int offk_off_units_backward_feats_typed(offk_handle* h, void* stream, void* work
 int offk_off_units_backward_feats_split(offk_handle* h, void* stream, void* workspace, int grad_dtype,
                                         void* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
 
+/* ---- the units' backward with the weight gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, opt-in; ABI version unchanged) -----------
+ * The second piece of the training side in the arithmetic of OFFK_PRECISION_F32SPLIT: offk_off_units_backward, _typed and _cl in one
+ * entry whose largest kernel, the weight-gradient GEMM K1b (dW[160][C] = [dGpre | dD]^T X), runs on v_mfma_f32_16x16x32_bf16.  It works
+ * on ANY handle -- either precision, bound or set weights, any OFFK_FUSED_UNITS setting -- and is opt-in: the three entries above keep
+ * their kernels and their contracts, and a split-fp32 handle does not switch it on by itself.
+ * feat_dtype: enum offk_feat_dtype, OFFK_FEAT_F32 included.  layout: OFFK_FEAT_NCHW (feats[i] = [B*L, C_i, H_i, H_i], what
+ * offk_off_units_backward / _typed take) or OFFK_FEAT_NHWC (the channels-last image [B*L*H_i*H_i][C_i], what offk_off_units_backward_cl
+ * takes); the layout belongs to the call, as in the _cl entries.  Every other argument is offk_off_units_backward's.
+ * Arithmetic: for site s, dW[m][c] = sum over (frame f, pixel q) a[(f, q)][m] X[f][c][q], a = [dGpre (128) | dD at row r(f) (32), zeros
+ * for a frame outside the spatial slice].  Both operands are cut into THREE bf16 planes by truncation (exactly: h + m + l == value).  A
+ * k step is K1b's K-tile: 32 pixels of one frame, ceil(HW / 32) per frame, pad pixels zeros.  Per step six of the nine plane products
+ * are issued, a_h x_h into one fp32 accumulator and the five small ones (a_l x_h, a_h x_l, a_m x_m, a_m x_h, a_h x_m, in that order)
+ * into a second; steps in increasing K-tile order over K1b's chunk of K-tiles, partial tile = A1 + A2 once, and the unchanged reduce
+ * sums the per-chunk slabs in chunk order and then adds `accumulate`.  The three dropped products are below (2^-21 + 2^-30) sum|a x|
+ * per element; to that come the fp32 accumulation of the two accumulators, the one A1 + A2 add and the slab sums.
+ * bf16 maps: a bf16 value IS its leading plane, so only the three products with x_h exist and NOTHING is dropped.  fp16 maps: an fp16
+ * value is exactly two planes, the five products without x_l are issued and only a_l x_m is dropped (below 2^-22 sum|a x|).  Both are
+ * compile-time forms that leave out MFMAs which would have added +-0.
+ * Equal bits: the result on bf16 / fp16 maps equals this entry's result on x.float() element for element (only the sign of a zero may
+ * differ); NCHW and channels-last maps of the same logical tensor give the same bits; so do two runs, and a captured graph's replay.
+ * Every bias gradient, every depthwise weight / bias gradient and the dG_<site> / dD_<site> regions are bit-equal to what
+ * offk_off_units_backward* writes (the same launches, respectively the same sums in the same order), so every
+ * offk_off_units_backward_feats* entry works behind this one exactly as behind those (it sets the same backward-has-run flag).
+ * It is NOT bit-equal to offk_off_units_backward* for the two weight matrices (motion_conv_gen_*.weight, motion_spatial_down_*.weight).
+ * +-Inf in an operand gives NaN (Inf - Inf in the cut), and tiny operands behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT
+ * says (below 2^-109 an operand's last plane falls under the last bf16 subnormal).
+ * The launch plan and the workspace are K1b's: the same blocks, chunks, slabs ("wgs_<site>") and bias partials ("wgb_<site>"), no split-K
+ * beyond those chunks, no atomics, one fixed order: bit-reproducible.  offk_train_workspace_bytes is unchanged.
+ * THREE launches on `stream`: K2b and the reduce as offk_off_units_backward enqueues them, between them the GEMM of
+ * csrc/units_wgrad_split.hip.  No sync, no allocation, capturable.
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: a null h, feats, gm, workspace or grads; an unknown layout or feat_dtype;
+ * for OFFK_FEAT_NCHW what offk_off_units_backward_typed refuses (an NHWC handle, a null map, a 16-bit map pointer that is not 8-byte
+ * aligned, a single 16-bit map of 2 GiB or more); for OFFK_FEAT_NHWC what offk_off_units_backward_cl refuses (a null map, a map
+ * pointer that is not 16-byte aligned, a single 16-bit map of 2 GiB or more); and the untyped entry's own checks (dropout probability
+ * outside [0, 1), a gradient view without 16-byte aligned 160 channels inside its cstride). */
+int offk_off_units_backward_split(offk_handle* h, void* stream, int feat_dtype, int layout,
+                                  const void* const feats[OFFK_NUM_SITES], const offk_grad_view gm[OFFK_NUM_SITES],
+                                  void* workspace, uint64_t drop_seed, double drop_p, float* grads, int accumulate);
+
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);
 

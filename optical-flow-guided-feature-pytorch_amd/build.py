@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "liboffk.so")
-SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "units_bwd_cl.hip", "units_dx.hip", "units_dx_f16.hip", "units_dx_split.hip", "pw_tdiff.hip",
+SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "units_bwd_cl.hip", "units_dx.hip", "units_dx_f16.hip", "units_dx_split.hip", "units_wgrad_split.hip", "pw_tdiff.hip",
            "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip")
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",), "pw_reduce_cl.hip": ("pw_reduce.hip",), "units_bwd_cl.hip": ("units_bwd.hip",),
@@ -30,7 +30,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # kernels in that file are latency-bound anyway.
 # conv_igemm.hip: its LDS-DMA inline asm writes m0 and says so in the clobber list (the compiler must not assume an m0 value
 # of its own survives the statement); clang answers every such statement with "clobber list contains reserved registers".
-EXTRA_FLAGS = {"heads.hip": ["-fno-slp-vectorize"], "units_bwd.hip": ["-fno-slp-vectorize"], "units_bwd_cl.hip": ["-fno-slp-vectorize"], "units_dx.hip": ["-fno-slp-vectorize"], "units_dx_f16.hip": ["-fno-slp-vectorize"], "units_dx_split.hip": ["-fno-slp-vectorize"],
+EXTRA_FLAGS = {"heads.hip": ["-fno-slp-vectorize"], "units_bwd.hip": ["-fno-slp-vectorize"], "units_bwd_cl.hip": ["-fno-slp-vectorize"], "units_dx.hip": ["-fno-slp-vectorize"], "units_dx_f16.hip": ["-fno-slp-vectorize"], "units_dx_split.hip": ["-fno-slp-vectorize"], "units_wgrad_split.hip": ["-fno-slp-vectorize"],
                "conv_igemm.hip": ["-Wno-inline-asm"], "pw_tdiff.hip": ["-Wno-inline-asm"], "pw_tdiff_split.hip": ["-Wno-inline-asm", "-fno-slp-vectorize"],
                "pw_tdiff_f16.hip": ["-fno-slp-vectorize"], "pw_tdiff_cl.hip": ["-fno-slp-vectorize"],
                "chain_fused.hip": ["-Wno-inline-asm"], "wino_gemm_split.hip": ["-fno-slp-vectorize"], "chain_split.hip": ["-fno-slp-vectorize"]}
@@ -343,6 +343,34 @@ def check_resources(src_name, kernels):
     return rows
 
 
+# ---- kernels whose plan rests on staying in registers, with no asm and no counted waits of their own --------------------------------------
+# pw_wgrad_split_kernel keeps three K-tiles of prefetched operands, 80 accumulator registers and the MFMA operands in registers at one block
+# of eight waves per CU (two waves per SIMD: 256 registers each).  One of its six forms once came out of hipcc with its prefetch sets in
+# scratch memory (a load, a wait for it and a scratch store per piece: the prefetch gone); the build refuses that instead of timing it.
+# (source file, regex on the demangled kernel name, how many kernels must match, max vgpr_count, what the bound stands for)
+REGISTER_RESIDENT_KERNELS = (
+    ("units_wgrad_split.hip", r"^void offk::pw_wgrad_split_kernel<", 6, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+)
+
+
+def check_register_resident(src_name, kernels):
+    """Applies REGISTER_RESIDENT_KERNELS to the kernels of one translation unit; returns the rows it checked."""
+    rows = []
+    for src, pat, count, max_vgpr, why in REGISTER_RESIDENT_KERNELS:
+        if src != src_name:
+            continue
+        found = [k for k in kernels if re.search(pat, k["name"])]
+        if len(found) != count:
+            raise RuntimeError("register guard: %d kernels of %s match %r, expected %d (renamed? update REGISTER_RESIDENT_KERNELS)" % (len(found), src_name, pat, count))
+        for k in found:
+            if k["vgpr_spill_count"] or k["sgpr_spill_count"] or k["private_segment_fixed_size"] or k["vgpr_count"] > max_vgpr:
+                raise RuntimeError("register guard failed for %s in %s: vgpr_spill_count %d, sgpr_spill_count %d, private_segment_fixed_size %d "
+                                   "(all must be 0), vgpr_count %d (at most %d: %s)" % (k["name"], src_name, k["vgpr_spill_count"], k["sgpr_spill_count"],
+                                                                                      k["private_segment_fixed_size"], k["vgpr_count"], max_vgpr, why))
+        rows += found
+    return rows
+
+
 def check_object(obj):
     """ISA check + resource guard of one freshly compiled object."""
     if _llvm_objdump() is None or _llvm_readelf() is None or _cxxfilt() is None:
@@ -358,6 +386,7 @@ def check_object(obj):
         src = os.path.basename(obj).replace(".o", ".hip")
         kernels = [k for co in cos for k in kernel_resources(co)]
         check_resources(src, kernels)
+        check_register_resident(src, kernels)
         check_counted_store_waits(src, cos)
         check_counted_load_steps(src, cos)
     finally:

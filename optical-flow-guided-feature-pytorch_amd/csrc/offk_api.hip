@@ -1766,9 +1766,11 @@ int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[
 
 // feat_dtype != OFFK_FEAT_F32: feats[] address 16-bit elements; nhwc: the maps of this call are channels-last (offk_off_units_backward_cl).
 // Either way check_feat_train has passed, and only K1b reads the maps.
+// split (offk_off_units_backward_split): K1b's GEMM runs in split-fp32 arithmetic (units_wgrad_split.hip) on K1b's launch plan; K2b and the
+// reduce are the same launches either way.
 static int off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                               const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
-                              float* grads, int accumulate, int feat_dtype, bool nhwc) {
+                              float* grads, int accumulate, int feat_dtype, bool nhwc, bool split = false) {
   if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, "offk_off_units_backward: null argument");
   DropCfg drop;
   TRY(make_drop(h, drop_seed, drop_p, &drop));
@@ -1842,7 +1844,8 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
     r.C = w.C; r.cpad = w.ntiles * 128; r.nchunks = w.nchunks; r.nsblocks = nsblocks[s];
   }
   wp.total_blocks = blk;
-  TRY(launch_k1b(h, st, wp, feat_dtype, nhwc));
+  if (split) HIP_TRY(h, pw_wgrad_split_launch(wp, feat_dtype, nhwc, st));
+  else TRY(launch_k1b(h, st, wp, feat_dtype, nhwc));
   HIP_TRY(h, wgrad_reduce_launch(rp, st));
   h->units_bwd_done = true;   // what offk_off_units_backward_feats asks for
   return OFFK_OK;
@@ -1850,12 +1853,13 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
 
 // the common prologue of the three offk_off_units_backward* entries (k == nullptr: the plain one, NCHW handles only)
 static int off_units_backward_kind(offk_handle* h, void* stream, const FeatKind* k, int feat_dtype, MapPtrs feats, const offk_grad_view gm[OFFK_NUM_SITES],
-                                   void* workspace, uint64_t drop_seed, double drop_p, float* grads, int accumulate, const char* fn) {
+                                   void* workspace, uint64_t drop_seed, double drop_p, float* grads, int accumulate, const char* fn,
+                                   bool split = false) {
   if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
   if (!k && h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": NCHW feature maps only");
   if (k) TRY(check_feat_train(h, *k, feat_dtype, feats, 0, kNumSites, fn));
   return off_units_backward(h, stream, reinterpret_cast<const float* const*>(feats), gm, workspace, drop_seed, drop_p, grads, accumulate, feat_dtype,
-                            k && k->cl);
+                            k && k->cl, split);
 }
 
 int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
@@ -1911,6 +1915,22 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
                                float* grads, int accumulate) {
   return off_units_backward_kind(h, stream, &kKindCl, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate,
                                  "offk_off_units_backward_cl");
+}
+
+// ---- the units' backward with the weight-gradient GEMM in split-fp32 arithmetic (units_wgrad_split.hip) ----
+// The kind of the maps follows from (layout, feat_dtype) as it follows from the entry's name elsewhere: NHWC -> the _cl entry's checks, NCHW
+// 16-bit -> the _typed entry's, NCHW fp32 -> the plain entry's.
+int offk_off_units_backward_split(offk_handle* h, void* stream, int feat_dtype, int layout, const void* const feats[OFFK_NUM_SITES],
+                                  const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
+                                  float* grads, int accumulate) {
+  const char* fn = "offk_off_units_backward_split";
+  if (!h || !feats || !gm || !workspace || !grads) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  if (layout != OFFK_FEAT_NCHW && layout != OFFK_FEAT_NHWC)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": layout must be OFFK_FEAT_NCHW or OFFK_FEAT_NHWC");
+  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  const FeatKind* k = layout == OFFK_FEAT_NHWC ? &kKindCl : (feat_dtype == OFFK_FEAT_F32 ? nullptr : &kKind16);
+  return off_units_backward_kind(h, stream, k, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, fn, true);
 }
 
 // ---- gradient w.r.t. the feature maps (units_dx.hip) ----

@@ -312,6 +312,9 @@ hipError_t pw_wgrad_feat16_launch(const WgParams& p, int feat_dtype, hipStream_t
 // K1b on channels-last maps (units_bwd_cl.hip): xp[] point at [N*HW][cp] images of feat_dtype kFeatF32 / kFeatBf16 / kFeatF16
 // elements, 16-byte aligned; same blocks, same slabs, bit-equal to the NCHW forms
 hipError_t pw_wgrad_cl_launch(const WgParams& p, int feat_dtype, hipStream_t st);
+// K1b's GEMM in split-fp32 arithmetic on the bf16 matrix pipe (units_wgrad_split.hip, offk_off_units_backward_split): the same blocks, slabs
+// and bias partials (those bit-equal to K1b's); xp[] as the launcher above that serves the same (feat_dtype, cl) wants them
+hipError_t pw_wgrad_split_launch(const WgParams& p, int feat_dtype, bool cl, hipStream_t st);
 
 struct WrSite {
   const float* slab; const float* bpart; const float* dw_part;

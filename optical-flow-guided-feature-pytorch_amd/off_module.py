@@ -173,7 +173,9 @@ class _OFFUnitsFn(torch.autograd.Function):
             mod._run_units(rt, feats, ctx.drop)
         bufs = [g.permute(0, 2, 3, 1).contiguous() for g in (g28, g14, g7)]      # channels-last rows
         views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
-        _flat, grads = rt.off_units_backward(feats, views, seed, p)
+        # (the default arithmetic makes today's call, argument for argument)
+        arith = {} if mod.wgrad_arith == "fp32" else {"arith": mod.wgrad_arith}
+        _flat, grads = rt.off_units_backward(feats, views, seed, p, **arith)
         return (None, None, None) + tuple(grads[k] for k in mod.param_keys)
 
 
@@ -237,11 +239,19 @@ class OFFUnits(nn.Module):
     receives it rounded once in the kernel to its dtype (nearest-even, offk_off_units_backward_feats_typed: no fp32 buffer, no cast).  Parameter gradients are the same bits either way.
     ``feat_grad_arith="f32split"`` (default ``"fp32"``) computes that gradient in split-fp32 arithmetic on the bf16 matrix pipe instead
     (offk_off_units_backward_feats_split: dropped part below (2^-21 + 2^-30) sum|a w| per element, reproducible, its own bits); it
-    changes nothing else -- the parameter gradients are the same bits."""
+    changes nothing else -- the parameter gradients are the same bits.
+    ``wgrad_arith="f32split"`` (default ``"fp32"``) runs the backward's largest kernel, the weight-gradient GEMM of the stacked 1x1
+    reduces, in the same split-fp32 arithmetic (offk_off_units_backward_split, for every dtype and layout of the maps): the
+    ``motion_conv_gen_*.weight`` / ``motion_spatial_down_*.weight`` gradients get bits of their own (dropped part below
+    (2^-21 + 2^-30) sum|a x| per element, nothing dropped on bf16 maps), every other gradient keeps the default's bits.  It is
+    independent of ``feat_grad_arith``."""
 
     def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False,
-                 feat_grad_arith="fp32"):
+                 feat_grad_arith="fp32", wgrad_arith="fp32"):
         super().__init__()
+        if wgrad_arith not in runtime.WGRAD_ARITHS:
+            raise ValueError("wgrad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.WGRAD_ARITHS), wgrad_arith))
+        self.wgrad_arith = wgrad_arith
         if feat_grad_arith not in runtime.FEAT_GRAD_ARITHS:
             raise ValueError("feat_grad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.FEAT_GRAD_ARITHS), feat_grad_arith))
         self.feat_grad, self.feat_grad_arith = bool(feat_grad), feat_grad_arith

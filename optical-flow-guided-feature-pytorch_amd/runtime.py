@@ -174,6 +174,9 @@ def train_feat_layout(feats, batch, length):
 
 # the arithmetic of the feature-map gradient: "fp32" = offk_off_units_backward_feats[_typed], "f32split" = offk_off_units_backward_feats_split
 FEAT_GRAD_ARITHS = ("fp32", "f32split")
+# the arithmetic of the weight-gradient GEMM of the units' backward: "fp32" = offk_off_units_backward[_typed / _cl], "f32split" =
+# offk_off_units_backward_split
+WGRAD_ARITHS = ("fp32", "f32split")
 
 
 def feat_grad_sites(needs_input_grad, first=0):
@@ -439,14 +442,19 @@ class OffForward:
     def new_unit_grads(self):
         return torch.zeros(int(self.lib.offk_unit_grad_floats(self._h)), dtype=torch.float32, device=self.device)
 
-    def off_units_backward(self, feats, grad_views, drop_seed=0, drop_p=0.0, grads=None, accumulate=False):
+    def off_units_backward(self, feats, grad_views, drop_seed=0, drop_p=0.0, grads=None, accumulate=False, arith="fp32"):
         """Gradients of the units' parameters.  grad_views: nine (tensor, coff) pairs -- a channels-last
         gradient buffer [P, H, W, Cs] (or [P*H*W, Cs]) and the first of the unit's 160 channels in it.
         Needs training=True (workspace superset) and the G/D state of the matching forward call.
         feats: the maps of the matching forward call, fp32 or bf16 / fp16 of one dtype (offk_off_units_backward_typed; gradients
         are fp32 and equal those from the upcast maps), contiguous or all nine torch.channels_last (offk_off_units_backward_cl;
         equal to the gradients from the contiguous copies).
+        arith: "fp32" (the default: the entries above, the weight-gradient GEMM on the fp32 matrix pipe) or "f32split"
+        (offk_off_units_backward_split: that GEMM in split-fp32 arithmetic on the bf16 matrix pipe, for every dtype and layout of
+        the maps; the two weight matrices get bits of their own, every other gradient and dG / dD keep the default's).
         Returns (flat grads tensor, dict key -> view in the reference's parameter shape)."""
+        if arith not in WGRAD_ARITHS:
+            raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in WGRAD_ARITHS), arith))
         if not self.training:
             raise _lib.OffkError("create the handle with training=True for the units' backward")
         r = self._route(feats, "train")
@@ -460,8 +468,12 @@ class OffForward:
         if grads is None:
             grads = self.new_unit_grads()
         _check_dev(grads, "grads", self.device)
-        self._call("off_units_backward", r, arr, gv, _ptr(self.workspace), ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads),
-                   int(bool(accumulate)))
+        tail = (arr, gv, _ptr(self.workspace), ctypes.c_uint64(int(drop_seed)), float(drop_p), _ptr(grads), int(bool(accumulate)))
+        if arith == "f32split":    # layout and dtype of the call: what the route found (plain: contiguous fp32 -> NCHW)
+            _lib.check(self.lib.offk_off_units_backward_split(self._h, _stream(self.device), r.fdt, _lib.FEAT_NHWC if r.route == "cl" else _lib.FEAT_NCHW,
+                                                              *tail), self._h)
+        else:
+            self._call("off_units_backward", r, *tail)
         views = dict((k, grads[off:off + int(np.prod(shape))].view(shape)) for k, (off, shape) in self.unit_grad_slots().items())
         return grads, views
 

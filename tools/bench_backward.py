@@ -1,7 +1,7 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
     python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy] [--feat-grad]
-                                     [--feat-grad-dtype map|fp32] [--feat-grad-arith fp32|f32split]
+                                     [--feat-grad-dtype map|fp32] [--feat-grad-arith fp32|f32split] [--wgrad-arith fp32|f32split]
 --feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
 .float() casts that path makes unnecessary are timed beside it.
 --feat-layout cl: the maps are torch.channels_last tensors and go in as they are (offk_off_units_train_cl / offk_off_units_backward_cl);
@@ -16,6 +16,10 @@ OFFUnits(feat_grad=True) did on 16-bit maps before), for the A/B.  feat_grad_ms 
 alone, feat_grad_casts_ms the nine casts alone.
 --feat-grad-arith f32split: dX from offk_off_units_backward_feats_split (split-fp32 on the bf16 matrix pipe; feat_grad_launch_ms then
 covers its two launches, the weight pre-pass included); fp32 (default): the fp32 matrix pipe's entries.
+--wgrad-arith f32split: the parameter backward from offk_off_units_backward_split (K1b's GEMM in split-fp32 arithmetic on the bf16
+matrix pipe, for every --feat-dtype / --feat-layout; with copy the backward reads the contiguous copies); fp32 (default): the
+fp32 matrix pipe's entries.  The matrix floors printed beside it count the plane products that form issues: 6 (fp32 maps), 5
+(fp16), 3 (bf16) bf16 MFMA passes over K1b's FLOPs at 2.5 PFLOP/s.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--feat-grad", action="store_true")
     ap.add_argument("--feat-grad-dtype", default="map", choices=["map", "fp32"])
     ap.add_argument("--feat-grad-arith", default="fp32", choices=list(runtime.FEAT_GRAD_ARITHS))
+    ap.add_argument("--wgrad-arith", default="fp32", choices=list(runtime.WGRAD_ARITHS))
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
@@ -72,7 +77,7 @@ def main():
     dx_dt = fdt if a.feat_grad_dtype == "map" else torch.float32
     if a.feat_grad:
         h.off_units_train(feats, 21, 0.8)
-        h.off_units_backward(feats, views, 21, 0.8, grads=grads)
+        h.off_units_backward(feats, views, 21, 0.8, grads=grads, arith=a.wgrad_arith)
         dx = h.off_units_backward_feats(layout=dx_layout, dtype=dx_dt, arith=a.feat_grad_arith)
 
     def dx_casts():
@@ -83,7 +88,7 @@ def main():
         return dx_casts()
 
     def bwd(x):
-        h.off_units_backward(x, views, 21, 0.8, grads=grads)
+        h.off_units_backward(x, views, 21, 0.8, grads=grads, arith=a.wgrad_arith)
         if a.feat_grad:
             dx_route()
     if a.feat_layout != "nchw":
@@ -137,6 +142,11 @@ def main():
     x_bytes = sum(N * C * H * H * esz for _n, C, H in spec.SITES)
     k1b = x_bytes + B * hw * 4 * (128 * L + 32 * (L - 1))
     flops = sum(2 * N * H * H * C * 128 + 2 * P * H * H * C * 32 for _n, C, H in spec.SITES)
+    products = {"fp32": 6, "fp16": 5, "bf16": 3}[a.feat_dtype]
+    extra["wgrad_arith"] = a.wgrad_arith
+    if a.wgrad_arith == "f32split":
+        extra["k1b_split_products"] = products
+        extra["k1b_floor_ms_bf16_mfma_2500TF"] = round(products * flops / 2.5e15 * 1e3, 4)
     print(json.dumps({**extra, "feat_grad": bool(a.feat_grad), "batch": B, "length": L, "precision_fwd": a.precision, "feat_dtype": a.feat_dtype,
                       "feat_layout": a.feat_layout, "nine_contiguous_copies_ms": round(t_copy, 4),
                       "nine_float_casts_ms": round(t_cast, 4),
