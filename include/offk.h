@@ -467,8 +467,8 @@ int offk_off_units_backward(offk_handle* h, void* stream, const float* const fea
  * OFFK_FEAT_F32 forwards to the untyped entry.  Outputs, gradients and the workspace stay fp32, and
  * offk_train_workspace_bytes is unchanged.
  *
- * Unlike offk_forward_typed they make no condition on the handle: both precisions (a split-fp32 handle runs its training
- * side on the fp32 kernels anyway), weights bound through offk_bind_weight, any OFFK_FUSED_UNITS setting (they run the
+ * Unlike offk_forward_typed they make no condition on the handle: both precisions (a handle's precision does not choose the
+ * training side's kernels: these entries run the fp32 kernels, the _split entries below are the opt-in), weights bound through offk_bind_weight, any OFFK_FUSED_UNITS setting (they run the
  * two-kernel form K1 + K2, never the fused kernel).  Only the two kernels that read the maps have 16-bit forms: K1
  * (the stacked 1x1 reduces) and K1b (the weight-gradient GEMM dW = A^T X); K2, K2b and the reductions are the untyped
  * entries' own launches.
@@ -548,8 +548,8 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
  * layout: OFFK_FEAT_NCHW ([B*L, C_i, H_i, H_i]) or OFFK_FEAT_NHWC ([B*L*H_i*H_i][C_i]), fp32, 16-byte aligned,
  * not overlapping `workspace`.  accumulate != 0 adds (out = old + new, new being the bits the overwrite form stores).
  * One launch on `stream` (csrc/units_dx.hip), no sync, no allocation, capturable.
- * Exact fp32 on the fp32 matrix pipe whatever the handle's precision (a split-fp32 handle runs its training side on the
- * fp32 kernels), a fixed k order, no atomics: bit-reproducible, and the two layouts hold the same sums bit for bit.
+ * Exact fp32 on the fp32 matrix pipe whatever the handle's precision (the training side's three GEMMs run in split-fp32
+ * arithmetic only through the opt-in _split entries below, on any handle), a fixed k order, no atomics: bit-reproducible, and the two layouts hold the same sums bit for bit.
  * Refused with OFFK_ERR_INVALID, nothing enqueued: a null h, workspace or dfeats; an unknown layout; a pointer that is not
  * 16-byte aligned; a buffer that overlaps the offk_train_workspace_bytes of `workspace`; a handle on which no
  * offk_off_units_backward* has run since offk_create.  That last check is a flag the backward entries set on the handle: a
@@ -651,6 +651,48 @@ int offk_off_units_backward_feats_split(offk_handle* h, void* stream, void* work
 int offk_off_units_backward_split(offk_handle* h, void* stream, int feat_dtype, int layout,
                                   const void* const feats[OFFK_NUM_SITES], const offk_grad_view gm[OFFK_NUM_SITES],
                                   void* workspace, uint64_t drop_seed, double drop_p, float* grads, int accumulate);
+
+/* ---- the units' train forward with the 1x1 reduces in split-fp32 arithmetic on the bf16 matrix pipe (additive, opt-in; ABI version unchanged) -----------
+ * The third and last piece of the training side in the arithmetic of OFFK_PRECISION_F32SPLIT: offk_off_units_train, _typed and _cl in one
+ * entry whose largest kernel, K1 (the stacked 1x1 reduces G = relu(Wg X + bg) on all frames, D = Wd X + bd on the frames of the spatial
+ * slice), runs on v_mfma_f32_16x16x32_bf16.  It works on ANY handle -- either precision, bound or set weights, any OFFK_FUSED_UNITS
+ * setting -- and is opt-in: the entries above keep their kernels and their contracts, and a split-fp32 handle does not switch it on by
+ * itself.  drop_p = 0 is eval mode: the entry then stands for offk_off_units / _typed / _cl as well.
+ * feat_dtype: enum offk_feat_dtype, OFFK_FEAT_F32 included.  layout: OFFK_FEAT_NCHW (feats[i] = [B*L, C_i, H_i, H_i]) or OFFK_FEAT_NHWC
+ * (the channels-last image [B*L*H_i*H_i][C_i]); the layout belongs to the call.  Every other argument is offk_off_units_train's.
+ * Arithmetic: both operands are cut into THREE bf16 planes by truncation (exactly: h + m + l == value).  A k step is 32 consecutive
+ * channels; the steps run in increasing channel order over the whole C_i; channel 32 kt + 8 g + e sits in lane group g, element e of
+ * step kt.  Per step six of the nine plane products are issued, w_h x_h into one fp32 accumulator A1 and the five small ones (w_l x_h,
+ * w_h x_l, w_m x_m, w_m x_h, w_h x_m, in that order) into a second, A2; no split-K, no atomics; v = (A1 + A2) + bias, G = max(v, 0),
+ * D = v.  The three dropped products are below (2^-21 + 2^-30) sum|w x| per element; to that come the fp32 accumulation of the two
+ * accumulators, the one A1 + A2 add and the bias add.
+ * bf16 maps: a bf16 value IS its leading plane, so only the three products with x_h exist and NOTHING is dropped.  fp16 maps: an fp16
+ * value is exactly two planes, the five products without x_l are issued and only w_l x_m is dropped.  Both are compile-time forms that
+ * leave out MFMAs which would have added +-0.
+ * +-Inf in an operand gives NaN (Inf - Inf in the cut), and tiny operands behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT
+ * says (below 2^-109 an operand's last plane falls under the last bf16 subnormal).
+ * Equal bits: D_<site> and the temporal channels of fusion_28 / _14 / _7 equal what offk_off_units_fused writes on a split-fp32 handle
+ * for the same fp32 NCHW maps and weights (the same arithmetic in front of the temporal difference; only the sign of a zero may
+ * differ); the result on bf16 / fp16 maps equals this entry's result on x.float(); NCHW and channels-last maps of the same logical
+ * tensor give the same bits; so do two runs, a captured graph's replay, and bound against set weights.  G_<site> / D_<site> are NOT
+ * bit-equal to what offk_off_units_train* / offk_off_units* write.  They lie in the same workspace regions in the same layout, so K2 and
+ * every offk_off_units_backward* / _feats* entry run behind this one unchanged.
+ * THREE launches on `stream`: a pre-pass that cuts [Wg ; Wd] of the nine sites, as they are at launch time (bound weights: read in
+ * place, an in-place update is picked up by the next call), into a plane image the handle owns (5,345,280 bytes, allocated at
+ * offk_create; a buffer of its own, neither the dX image nor the fused kernel's), the GEMM of csrc/units_fwd_split.hip, and K2 exactly
+ * as offk_off_units_train enqueues it.  No sync, no allocation, capturable; offk_train_workspace_bytes and offk_workspace_bytes are
+ * unchanged.  The image is per handle: two calls on one handle must be ordered (one stream, or an event), like every other use of the
+ * handle's buffers.
+ * Refused with OFFK_ERR_INVALID before anything is enqueued: a null h, feats or workspace ("offk_off_units_train_split: null
+ * argument"); an unknown layout or feat_dtype; a dropout probability outside [0, 1); for OFFK_FEAT_NCHW what
+ * offk_off_units_train_typed refuses (an NHWC handle, a null map, a 16-bit map pointer that is not 8-byte aligned, a single 16-bit map
+ * of 2 GiB or more); for OFFK_FEAT_NHWC what offk_off_units_train_cl refuses (a null map, a map pointer that is not 16-byte aligned, a
+ * single 16-bit map of 2 GiB or more).
+ * Per-launch trace: "units:pw_reduce weight cut (K1, split)", then "units:pw_reduce (K1, NCHW, split)" / "(K1, NHWC, split)", with
+ * ", bf16" / ", fp16" behind "split" for 16-bit maps, then "units:sobel_tdiff (K2)". */
+int offk_off_units_train_split(offk_handle* h, void* stream, int feat_dtype, int layout,
+                               const void* const feats[OFFK_NUM_SITES], void* workspace,
+                               uint64_t drop_seed, double drop_p);
 
 /* Backward of offk_segment_consensus, basic_ops.py:29-33: grad_in[b*T + t][c] = grad_out[b][c] / T. */
 int offk_segment_consensus_backward(void* stream, const float* grad_out, int B, int T, int C, float* grad_in);

@@ -98,6 +98,7 @@ SIGNATURES = {
     "offk_off_units_train_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _P, _c.c_uint64, _c.c_double]),
     "offk_off_units_backward_cl": (_I, [_P, _P, _I, _c.POINTER(_P), _c.POINTER(OffkGradView), _P, _c.c_uint64, _c.c_double, _F, _I]),
     "offk_off_units_backward_split": (_I, [_P, _P, _I, _I, _c.POINTER(_P), _c.POINTER(OffkGradView), _P, _c.c_uint64, _c.c_double, _F, _I]),
+    "offk_off_units_train_split": (_I, [_P, _P, _I, _I, _c.POINTER(_P), _P, _c.c_uint64, _c.c_double]),
     "offk_off_units_backward_feats": (_I, [_P, _P, _P, _c.POINTER(_F), _I, _I]),
     "offk_off_units_backward_feats_typed": (_I, [_P, _P, _P, _I, _c.POINTER(_P), _I, _I]),
     "offk_off_units_backward_feats_split": (_I, [_P, _P, _P, _I, _c.POINTER(_P), _I, _I]),

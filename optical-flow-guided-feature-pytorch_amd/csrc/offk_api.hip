@@ -206,6 +206,7 @@ struct offk_handle {
   // training side (offk_off_units_backward): workspace superset, K1b chunking, gradient-buffer layout
   float* zero_page = nullptr;    // 256 B of zeros (target of masked-out loads)
   float* dx_split_w[kNumSites] = {};   // offk_off_units_backward_feats_split: plane image of [Wg ; Wd] per site, rewritten by every call (960 B per channel)
+  float* fwd_split_w[kNumSites] = {};  // offk_off_units_train_split: plane image of [Wg ; Wd] per site in K1's operand order, rewritten by every call (960 B per channel)
   bool fused_units = true;       // forward: K1 fused with the temporal difference (OFFK_FUSED_UNITS=0 at offk_create: K1 + K2)
   bool winograd = true;          // fp32: Winograd F(4x4, 3x3) for the three 3x3 / stride 1 convs on 7x7 maps (winograd.hip); OFFK_WINOGRAD=0: direct
   bool wino_7x7 = true;          // the 7x7 / stride 2 conv of fusion@28 in polyphase Winograd form F(5x5, 4x4) (OFFK_WINOGRAD_7X7=0: direct)
@@ -635,6 +636,43 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
   { int rc = run_sobel_tdiff_all(h, st, ws, 0, drop); if (rc != OFFK_OK) return rc; }
   if (ev) HIP_TRY(h, hipEventRecord(ev[2], st));
   return OFFK_OK;
+}
+
+// offk_off_units_train_split: run_off_units with K1 in split-fp32 arithmetic (units_fwd_split.hip) -- the weight pre-pass, the GEMM on K1's
+// grid into the same G_<site> / D_<site> regions, then K2 as above.  cl: the maps of THIS call are channels-last.
+const char* const kK1SplitPack = "units:pw_reduce weight cut (K1, split)";
+const char* const kK1SplitName[2][3] = {
+    {"units:pw_reduce (K1, NCHW, split)", "units:pw_reduce (K1, NCHW, split, bf16)", "units:pw_reduce (K1, NCHW, split, fp16)"},
+    {"units:pw_reduce (K1, NHWC, split)", "units:pw_reduce (K1, NHWC, split, bf16)", "units:pw_reduce (K1, NHWC, split, fp16)"}};
+int run_off_units_split(offk_handle* h, hipStream_t st, const offk_feat_parts feats[], void* ws, bool cl, const DropCfg& drop, int feat_dtype) {
+  TRY(finalize_pw(h, st));
+  UfsParams up;
+  memset(&up, 0, sizeof(up));
+  up.nsites = kNumSites; up.L = h->cfg.length; up.P = h->P; up.slice_mode = h->cfg.slice_mode;
+  int blk = 0, pblk = 0;
+  for (int i = 0; i < kNumSites; ++i) {
+    const int s = kPwOrder[i];
+    UfsSite& o = up.s[i];
+    const offk_feat_parts& fp = feats[s];
+    for (int q = 0; q < 4; ++q) { o.xp[q] = q < fp.n_parts ? fp.data[q] : nullptr; o.cp[q] = q < fp.n_parts ? fp.channels[q] : 0; }
+    o.nparts = fp.n_parts;
+    pw_weight_ptrs(h, s, &o.wg, &o.wd, &o.bias, &o.bias_down);
+    o.wimg = h->fwd_split_w[s];
+    o.G = region(h, ws, (std::string("G_") + kSites[s].name).c_str());
+    o.D = region(h, ws, (std::string("D_") + kSites[s].name).c_str());
+    o.C = kSites[s].C; o.HW = kSites[s].H * kSites[s].H; o.M = h->N * o.HW;
+    o.blk_begin = blk; o.pack_begin = pblk;
+    blk += pw_blocks_for(o.M);
+    pblk += units_fwd_split_pack_blocks(o.C);
+  }
+  up.total_blocks = blk; up.pack_blocks = pblk;
+  TRY(trace_mark(h, st, kK1SplitPack));
+  HIP_TRY(h, units_fwd_split_pack_launch(up, st));
+  TRY(trace_mark(h, st, kK1SplitName[cl ? 1 : 0][feat_dtype]));
+  HIP_TRY(h, units_fwd_split_launch(up, feat_dtype, cl, st));
+  TRY(trace_mark(h, st, "units:sobel_tdiff (K2)"));
+  TRY(run_sobel_tdiff_all(h, st, ws, 0, drop));
+  return trace_mark(h, st, nullptr);
 }
 
 // Inference path of the units: K1 fused with the temporal difference (pw_tdiff.hip), then the S-blocks of K2 alone.
@@ -1293,6 +1331,7 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
   }
   if (rc == OFFK_OK) rc = dev_alloc(h, &h->zero_page, 64);
   for (int s = 0; s < kNumSites && rc == OFFK_OK; ++s) rc = dev_alloc(h, &h->dx_split_w[s], units_dx_split_image_bytes(kSites[s].C) / sizeof(float));
+  for (int s = 0; s < kNumSites && rc == OFFK_OK; ++s) rc = dev_alloc(h, &h->fwd_split_w[s], units_fwd_split_image_bytes(kSites[s].C) / sizeof(float));
   // The path switches of the product library, all read HERE and nowhere else (INTEGRATION.md lists them): each names one
   // algorithm choice of the exact-fp32 forward; "0" = off, a number > 1 = use it from that many frame pairs P = B (L - 1).
   //   OFFK_FUSED_UNITS   K1 fused with the temporal difference (pw_tdiff.hip); 0: K1 + K2 (what training always runs)
@@ -1931,6 +1970,27 @@ int offk_off_units_backward_split(offk_handle* h, void* stream, int feat_dtype, 
     return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
   const FeatKind* k = layout == OFFK_FEAT_NHWC ? &kKindCl : (feat_dtype == OFFK_FEAT_F32 ? nullptr : &kKind16);
   return off_units_backward_kind(h, stream, k, feat_dtype, feats, gm, workspace, drop_seed, drop_p, grads, accumulate, fn, true);
+}
+
+// ---- the units' train forward with K1 in split-fp32 arithmetic (units_fwd_split.hip): offk_off_units_train / _typed / _cl in one entry ----
+int offk_off_units_train_split(offk_handle* h, void* stream, int feat_dtype, int layout, const void* const feats[OFFK_NUM_SITES], void* workspace,
+                               uint64_t drop_seed, double drop_p) {
+  const char* fn = "offk_off_units_train_split";
+  if (!h || !feats || !workspace) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": null argument");
+  if (layout != OFFK_FEAT_NCHW && layout != OFFK_FEAT_NHWC)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": layout must be OFFK_FEAT_NCHW or OFFK_FEAT_NHWC");
+  if (feat_dtype != OFFK_FEAT_F32 && feat_dtype != OFFK_FEAT_BF16 && feat_dtype != OFFK_FEAT_F16)
+    return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": unknown feat_dtype " + std::to_string(feat_dtype) + " (OFFK_FEAT_F32 / _BF16 / _F16)");
+  DropCfg drop;
+  TRY(make_drop(h, drop_seed, drop_p, &drop));
+  const bool cl = layout == OFFK_FEAT_NHWC;
+  if (cl || feat_dtype != OFFK_FEAT_F32) TRY(check_feat_train(h, cl ? kKindCl : kKind16, feat_dtype, feats, 0, kNumSites, fn));
+  else if (h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, std::string(fn) + ": NCHW feature maps on an NHWC handle (pass OFFK_FEAT_NHWC)");
+  offk_feat_parts parts[kNumSites];
+  TRY(whole_maps(h, feats, parts, fn));
+  for (int s = 0; s < kNumSites; ++s) TRY(site_weights_ready(h, s, true, true));
+  DeviceGuard guard(h->cfg.device);
+  return run_off_units_split(h, static_cast<hipStream_t>(stream), parts, workspace, cl, drop, feat_dtype);
 }
 
 // ---- gradient w.r.t. the feature maps (units_dx.hip) ----

@@ -171,6 +171,33 @@ bool pw_reduce_feat16_supported(const PwParams& p);
 hipError_t pw_reduce_feat16_launch(const PwParams& p, int feat_dtype, hipStream_t st);
 hipError_t pw_reduce_cl16_launch(const PwParams& p, int feat_dtype, hipStream_t st);
 
+// ---- K1 in split-fp32 arithmetic on the bf16 matrix pipe (units_fwd_split.hip, offk_off_units_train_split): TWO launches, the weight
+//      pre-pass and the GEMM; K1's grid (pw_blocks_for), row map and G / D layout ----
+struct UfsSite {
+  const float* xp[4];   // feature map parts as PwSite's (16-bit maps: pointers to 16-bit elements)
+  int cp[4];
+  int nparts;
+  const float* wg;      // gen rows [128][C] fp32 (PwSite::w)
+  const float* wd;      // down rows [32][C] (PwSite::w_down)
+  void* wimg;           // units_fwd_split_image_bytes(C) of the handle: the plane image of [Wg ; Wd], written by the pre-pass of THIS call
+  const float* bias;    // [128]
+  const float* bias_down;   // [32]
+  float* G;             // [N*HW][128]
+  float* D;             // [P*HW][32]
+  int C, HW, M;         // M = N*HW rows
+  int blk_begin;        // first block of the site in the GEMM launch
+  int pack_begin;       // ... in the pre-pass launch
+};
+struct UfsParams {
+  UfsSite s[kNumSites];
+  int nsites, total_blocks, pack_blocks, L, P, slice_mode;
+};
+int units_fwd_split_pack_blocks(int C);
+size_t units_fwd_split_image_bytes(int C);
+hipError_t units_fwd_split_pack_launch(const UfsParams& p, hipStream_t st);
+// feat_dtype kFeatF32 / kFeatBf16 / kFeatF16; cl: channels-last parts
+hipError_t units_fwd_split_launch(const UfsParams& p, int feat_dtype, bool cl, hipStream_t st);
+
 // ---- K1T: K1 fused with the temporal difference (pw_tdiff.hip) -------------------------
 struct PtSite {
   const float* xp[4];   // feature map parts, NCHW (as PwSite)

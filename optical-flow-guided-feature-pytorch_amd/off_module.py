@@ -244,11 +244,19 @@ class OFFUnits(nn.Module):
     reduces, in the same split-fp32 arithmetic (offk_off_units_backward_split, for every dtype and layout of the maps): the
     ``motion_conv_gen_*.weight`` / ``motion_spatial_down_*.weight`` gradients get bits of their own (dropped part below
     (2^-21 + 2^-30) sum|a x| per element, nothing dropped on bf16 maps), every other gradient keeps the default's bits.  It is
-    independent of ``feat_grad_arith``."""
+    independent of ``feat_grad_arith``.
+    ``fwd_arith="f32split"`` (default ``"fp32"``) runs the forward's largest kernel, the stacked 1x1 reduces K1, in the same split-fp32
+    arithmetic (offk_off_units_train_split, for every dtype and layout of the maps; dropped part below (2^-21 + 2^-30) sum|w x| per
+    element, nothing dropped on bf16 maps): the outputs and the saved G / D get bits of their own, the backward runs behind it
+    unchanged, and the recompute of a stale generation inside the backward uses the same arithmetic.  It is independent of the other
+    two switches."""
 
     def __init__(self, batch=16, length=7, variant="rgb", slice_mode=spec.SLICE_FLAT, precision="fp32", drop_p=0.8, feat_grad=False,
-                 feat_grad_arith="fp32", wgrad_arith="fp32"):
+                 feat_grad_arith="fp32", wgrad_arith="fp32", fwd_arith="fp32"):
         super().__init__()
+        if fwd_arith not in runtime.FWD_ARITHS:
+            raise ValueError("fwd_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.FWD_ARITHS), fwd_arith))
+        self.fwd_arith = fwd_arith
         if wgrad_arith not in runtime.WGRAD_ARITHS:
             raise ValueError("wgrad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.WGRAD_ARITHS), wgrad_arith))
         self.wgrad_arith = wgrad_arith
@@ -273,10 +281,12 @@ class OFFUnits(nn.Module):
 
     def _run_units(self, rt, feats, drop):
         seed, p = drop
+        # (the default arithmetic makes today's calls, argument for argument)
+        arith = {} if self.fwd_arith == "fp32" else {"arith": self.fwd_arith}
         if p > 0.0:
-            rt.off_units_train(feats, seed, p)
+            rt.off_units_train(feats, seed, p, **arith)
         else:
-            rt.off_units(feats)
+            rt.off_units(feats, **arith)
         self._generation += 1
 
     def _param(self, key):

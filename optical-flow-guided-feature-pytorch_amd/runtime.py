@@ -177,6 +177,8 @@ FEAT_GRAD_ARITHS = ("fp32", "f32split")
 # the arithmetic of the weight-gradient GEMM of the units' backward: "fp32" = offk_off_units_backward[_typed / _cl], "f32split" =
 # offk_off_units_backward_split
 WGRAD_ARITHS = ("fp32", "f32split")
+# the arithmetic of the units' forward (off_units, off_units_train): "fp32" = K1 on the fp32 matrix pipe, "f32split" = offk_off_units_train_split
+FWD_ARITHS = ("fp32", "f32split")
 
 
 def feat_grad_sites(needs_input_grad, first=0):
@@ -196,6 +198,11 @@ def feat_grad_sites_mask(sites):
     if any(not 0 <= i < spec.NUM_SITES for i in sites) or len(set(sites)) != len(sites):
         raise ValueError("sites must be distinct indices in 0..8, got %s" % (sites,))
     return [i in sites for i in range(spec.NUM_SITES)]
+
+
+def _check_fwd_arith(arith):
+    if arith not in FWD_ARITHS:
+        raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in FWD_ARITHS), arith))
 
 
 class OffForward:
@@ -407,10 +414,15 @@ class OffForward:
         _lib.check(self.lib.offk_forward(self._h, _stream(self.device), feat_array, _ptr(out7), _ptr(out14), _ptr(out28),
                                          _ptr(self.workspace)), self._h)
 
-    def off_units(self, feats):
+    def off_units(self, feats, arith="fp32"):
         """K1 + K2 into the workspace.  feats: nine fp32 maps, or nine bf16 / fp16 maps of one dtype (offk_off_units_typed: the values
         of the same maps upcast, on any handle).  Nine torch.channels_last maps of any of the three dtypes are taken as they are
-        (offk_off_units_cl, any handle) and give the values of their contiguous copies."""
+        (offk_off_units_cl, any handle) and give the values of their contiguous copies.
+        arith: "fp32" (the default: the entries above) or "f32split" (offk_off_units_train_split with drop_p = 0: K1 in split-fp32
+        arithmetic on the bf16 matrix pipe, for every dtype and layout of the maps; G / D get bits of their own)."""
+        _check_fwd_arith(arith)
+        if arith == "f32split":
+            return self._units_split(feats, 0, 0.0)
         self._units_call("off_units", feats)
 
     def off_units_fused(self, feats):
@@ -419,12 +431,24 @@ class OffForward:
         self._units_call("off_units_fused", feats)
 
     # ---- training side of the units ----------------------------
-    def off_units_train(self, feats, drop_seed=0, drop_p=0.8):
+    def off_units_train(self, feats, drop_seed=0, drop_p=0.8, arith="fp32"):
         """K1+K2 in training mode: nn.Dropout(p) (RGB_OFF.py:356, :612) on the spatial gradients with the
         reproducible mask of synth.dropout_keep; leaves G/D in the workspace for off_units_backward.
         bf16 / fp16 maps of one dtype are taken as they are (offk_off_units_train_typed), and so are nine torch.channels_last maps
-        of any of the three dtypes (offk_off_units_train_cl)."""
+        of any of the three dtypes (offk_off_units_train_cl).
+        arith: "fp32" (the default: the entries above) or "f32split" (offk_off_units_train_split: K1 in split-fp32 arithmetic on the
+        bf16 matrix pipe, for every dtype and layout of the maps; G / D get bits of their own, K2 and the backward run unchanged)."""
+        _check_fwd_arith(arith)
+        if arith == "f32split":
+            return self._units_split(feats, drop_seed, drop_p)
         self._units_call("off_units_train", feats, ctypes.c_uint64(int(drop_seed)), float(drop_p))
+
+    def _units_split(self, feats, drop_seed, drop_p):
+        """offk_off_units_train_split with the dtype and layout the route found (plain: contiguous fp32 -> NCHW)"""
+        r = self._route(feats, "train")
+        arr = self._feat_array(feats, _ENTRIES["off_units_train"][r.route][1])
+        _lib.check(self.lib.offk_off_units_train_split(self._h, _stream(self.device), r.fdt, _lib.FEAT_NHWC if r.route == "cl" else _lib.FEAT_NCHW,
+                                                       arr, _ptr(self.workspace), ctypes.c_uint64(int(drop_seed)), float(drop_p)), self._h)
 
     def unit_grad_slots(self):
         """OrderedDict key -> (offset, shape) of every unit parameter in the flat gradient buffer."""

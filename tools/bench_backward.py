@@ -1,7 +1,7 @@
 """Training side of the OFF units on MI355X: train-mode forward (K1 + K2 with dropout) and the units'
 backward (K2b + K1b + reductions) at BASELINE config 2 size, with algorithmic bytes / FLOPs.
     python tools/bench_backward.py [--batch 64] [--length 7] [--iters 20] [--feat-dtype fp32|bf16|fp16] [--feat-layout nchw|cl|copy] [--feat-grad]
-                                     [--feat-grad-dtype map|fp32] [--feat-grad-arith fp32|f32split] [--wgrad-arith fp32|f32split]
+                                     [--feat-grad-dtype map|fp32] [--feat-grad-arith fp32|f32split] [--wgrad-arith fp32|f32split] [--fwd-arith fp32|f32split]
 --feat-dtype bf16 / fp16: the maps go in as 16-bit tensors (offk_off_units_train_typed / offk_off_units_backward_typed), and the nine
 .float() casts that path makes unnecessary are timed beside it.
 --feat-layout cl: the maps are torch.channels_last tensors and go in as they are (offk_off_units_train_cl / offk_off_units_backward_cl);
@@ -20,6 +20,9 @@ covers its two launches, the weight pre-pass included); fp32 (default): the fp32
 matrix pipe, for every --feat-dtype / --feat-layout; with copy the backward reads the contiguous copies); fp32 (default): the
 fp32 matrix pipe's entries.  The matrix floors printed beside it count the plane products that form issues: 6 (fp32 maps), 5
 (fp16), 3 (bf16) bf16 MFMA passes over K1b's FLOPs at 2.5 PFLOP/s.
+--fwd-arith f32split: the train forward from offk_off_units_train_split (K1 in split-fp32 arithmetic on the bf16 matrix pipe, for every
+--feat-dtype / --feat-layout; units_train_forward_ms then covers its three launches, the weight pre-pass included); fp32 (default):
+the fp32 matrix pipe's entries.  The train-forward time is reported separately either way.
 Under rocprofv3 --kernel-trace --stats the per-kernel split is in the stats CSV."""
 import argparse
 import json
@@ -61,6 +64,7 @@ def main():
     ap.add_argument("--feat-grad-dtype", default="map", choices=["map", "fp32"])
     ap.add_argument("--feat-grad-arith", default="fp32", choices=list(runtime.FEAT_GRAD_ARITHS))
     ap.add_argument("--wgrad-arith", default="fp32", choices=list(runtime.WGRAD_ARITHS))
+    ap.add_argument("--fwd-arith", default="fp32", choices=list(runtime.FWD_ARITHS))
     a = ap.parse_args()
     B, L = a.batch, a.length
     N, P = B * L, B * (L - 1)
@@ -72,11 +76,12 @@ def main():
     bufs = [torch.randn(P, H, H, C, device="cuda", generator=gen) for H, C in ((28, 320), (14, 1056), (7, 832))]
     views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
     grads = h.new_unit_grads()
+    fwd_kw = {} if a.fwd_arith == "fp32" else {"arith": a.fwd_arith}      # (the default makes today's call)
     dx_layout = "nchw" if a.feat_layout == "nchw" else "cl"      # (copy: the maps the model holds are the channels_last ones)
     dx = None
     dx_dt = fdt if a.feat_grad_dtype == "map" else torch.float32
     if a.feat_grad:
-        h.off_units_train(feats, 21, 0.8)
+        h.off_units_train(feats, 21, 0.8, **fwd_kw)
         h.off_units_backward(feats, views, 21, 0.8, grads=grads, arith=a.wgrad_arith)
         dx = h.off_units_backward_feats(layout=dx_layout, dtype=dx_dt, arith=a.feat_grad_arith)
 
@@ -98,12 +103,12 @@ def main():
 
         def fwd():
             held[0] = [f.contiguous() for f in feats]        # the copies live until the backward has run, as in an autograd node
-            h.off_units_train(held[0], 21, 0.8)
+            h.off_units_train(held[0], 21, 0.8, **fwd_kw)
         t_fwd = timed(fwd, a.iters)
         t_copy = timed(lambda: [f.contiguous() for f in feats], a.iters)
         t_bwd = timed(lambda: bwd(held[0]), a.iters)
     else:
-        t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8), a.iters)
+        t_fwd = timed(lambda: h.off_units_train(feats, 21, 0.8, **fwd_kw), a.iters)
         t_copy = 0.0
         t_bwd = timed(lambda: bwd(feats), a.iters)
     t_cast = timed(lambda: [f.float() for f in feats], a.iters) if fdt != torch.float32 else 0.0
@@ -144,6 +149,11 @@ def main():
     flops = sum(2 * N * H * H * C * 128 + 2 * P * H * H * C * 32 for _n, C, H in spec.SITES)
     products = {"fp32": 6, "fp16": 5, "bf16": 3}[a.feat_dtype]
     extra["wgrad_arith"] = a.wgrad_arith
+    extra["fwd_arith"] = a.fwd_arith
+    if a.fwd_arith == "f32split":
+        extra["k1_split_products"] = products
+        extra["k1_floor_ms_bf16_mfma_2500TF"] = round(products * flops / 2.5e15 * 1e3, 4)
+        extra["k1_floor_ms_hbm_8TBs"] = round((x_bytes + B * hw * 4 * (128 * L + 32 * (L - 1))) / 8e12 * 1e3, 4)
     if a.wgrad_arith == "f32split":
         extra["k1b_split_products"] = products
         extra["k1b_floor_ms_bf16_mfma_2500TF"] = round(products * flops / 2.5e15 * 1e3, 4)
