@@ -310,6 +310,40 @@ int offk_conv2d_ex(void* stream, const float* x, int x_cstride, int x_coff, int 
                    int precision);
 /* [Co][Ci][KH][KW] (PyTorch) -> [Co][Ci/32][KH*KW][32]; both device pointers. */
 int offk_pack_conv_weight(void* stream, const float* w_oihw, int Co, int Ci, int KH, int KW, float* w_packed);
+/* K4b (additive, ABI v10). Backward of ONE stride-1 fusion convolution (22 of the reference's 24: RGB_OFF.py:657-685, 766-780, 833-841), exact
+ * fp32, as stage entry points with the view conventions above: activations and gradients are channels-last rows [n_img * H * W][cstride]
+ * addressed as (ptr, cstride, coff); weights and weight gradients are PyTorch's [Co][Ci][KH][KW], contiguous (a bound nn.Conv2d.weight and
+ * its .grad).  Shapes: KH = KW in {1, 3}, stride 1, pad = (KH - 1) / 2, Ci % 64 == 0, Co % 64 == 0, any H, W >= 1, strides and offsets
+ * % 4 == 0.  Every entry enqueues on `stream` in order, does not synchronise and does not allocate (capturable).  Refused with
+ * OFFK_ERR_INVALID before any HIP call, the entry's name in offk_last_error(NULL): a null pointer (db excepted), another shape, a negative
+ * offset, cstride < coff + C, a scratch smaller than offk_conv2d_backward_plan says, and the overlaps named below.
+ *
+ * offk_relu_backward: g = dy where y > 0, else exactly 0 (y <= 0, y = -0.0, y = NaN: torch's rule); accumulate != 0: g += that.  C % 4 == 0.
+ * g may be dy itself (same pointer, stride and offset: in place); any other overlap of g's bytes [g, g + rows * g_cstride * 4) with dy's
+ * or y's is refused.  Serves the ReLU behind a conv (y = the conv's stored output), behind a residual add, and in front of a conv
+ * (OFFK_CONV_RELU_IN: y = the conv's input, applied to its dx).
+ *
+ * offk_conv2d_backward_data: dx[n,h,w,ci] (+)= sum_{co,kh,kw} g[n, h - kh + pad, w - kw + pad, co] * w[co,ci,kh,kw], terms outside the map 0:
+ * the library's direct conv (never a Winograd form) on the transposed, 180-degree rotated weight, which a device kernel cuts into `scratch`
+ * on every call.  accumulate != 0 adds the (completely summed, once rounded) result to dx.  dx's bytes may not overlap g's.
+ *
+ * offk_conv2d_backward_weight: dw[co,ci,kh,kw] (+)= sum_{n,h,w} g[n,h,w,co] * in(x)[n, h + kh - pad, w + kw - pad, ci], in(x) = max(x, 0) if
+ * relu_in else x; db[co] (+)= sum_{n,h,w} g[n,h,w,co] (db may be NULL).  A TN GEMM over K = the pixels on the fp32 matrix pipe, K split into
+ * weight_chunks chunks of ceil(n_img / weight_chunks) whole images (the last one may be shorter); the partial slabs [chunk][Co][Ci * KH * KW]
+ * (+ [chunk][Co] for db) live in `scratch` and a second launch adds them in chunk order: bit-reproducible.
+ *
+ * offk_conv2d_backward_plan: pure host code (no GPU needed): the scratch bytes of the two entries above and the number of K chunks.  A function
+ * of these seven integers only -- not of the device, the stream or the environment.  Output pointers may be NULL. */
+int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_coff, const float* y, int y_cstride, int y_coff, int rows, int C,
+                       float* g, int g_cstride, int g_coff, int accumulate);
+int offk_conv2d_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
+                              int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
+                              size_t scratch_bytes);
+int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
+                                int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db, int accumulate,
+                                void* scratch, size_t scratch_bytes);
+int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
+                              size_t* weight_scratch_bytes, int* weight_chunks);
 /* Override the plan offk_forward uses for one fusion conv (key = its state_dict name without
  * ".weight", e.g. "motion_conv_trans_28"); tile_cfg < 0 / splitk < 1 restore the automatic choice. */
 int offk_set_conv_plan(offk_handle* h, const char* conv_key, int tile_cfg, int splitk);

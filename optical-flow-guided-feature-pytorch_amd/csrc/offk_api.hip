@@ -2128,6 +2128,99 @@ int offk_conv2d_ex(void* stream, const float* x, int x_cstride, int x_coff, int 
   return OFFK_OK;
 }
 
+// ---- K4b: backward of one stride-1 fusion conv (conv_bwd.hip) ----
+namespace {
+// a channels-last view [rows][cstride] that holds C channels at coff; nullptr = fine, else what is wrong with it
+const char* view_problem(const void* ptr, int cstride, int coff, int C) {
+  if (!ptr) return "null pointer";
+  if (coff < 0) return "negative channel offset";
+  if (cstride % 4 || coff % 4) return "strides and offsets must be multiples of 4";
+  if (cstride < coff + C) return "cstride < coff + C";
+  return nullptr;
+}
+bool views_overlap(const void* a, int a_cs, const void* b, int b_cs, long long rows) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), a1 = a0 + (size_t)rows * (size_t)a_cs * sizeof(float);
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(b), b1 = b0 + (size_t)rows * (size_t)b_cs * sizeof(float);
+  return a0 < b1 && b0 < a1;
+}
+int conv_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {
+  if (n_img < 1 || H < 1 || W < 1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (n_img, H, W >= 1)");
+  if (KH != KW || (KH != 1 && KH != 3)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": the kernel must be 1x1 or 3x3");
+  if (pad != (KH - 1) / 2) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": pad must be (KH - 1) / 2 (stride 1, same-size output)");
+  if (Ci < 64 || Co < 64 || Ci % 64 || Co % 64) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need Ci % 64 == 0 and Co % 64 == 0");
+  if (!conv_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  return OFFK_OK;
+}
+}  // namespace
+
+int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
+                              size_t* weight_scratch_bytes, int* weight_chunks) {
+  const char* who = "offk_conv2d_backward_plan";
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t df = 0, wf = 0;
+  int chunks = 0;
+  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, &wf, &chunks, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (data_scratch_bytes) *data_scratch_bytes = df * sizeof(float);
+  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
+  if (weight_chunks) *weight_chunks = chunks;
+  return OFFK_OK;
+}
+
+int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_coff, const float* y, int y_cstride, int y_coff, int rows, int C,
+                       float* g, int g_cstride, int g_coff, int accumulate) {
+  const char* who = "offk_relu_backward";
+  if (rows < 1 || C < 4 || C % 4) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (rows >= 1, C % 4 == 0)");
+  if (const char* w = view_problem(dy, dy_cstride, dy_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dy: " + w);
+  if (const char* w = view_problem(y, y_cstride, y_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": y: " + w);
+  if (const char* w = view_problem(g, g_cstride, g_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  const bool in_place = g == dy && g_cstride == dy_cstride && g_coff == dy_coff;
+  if (!in_place && views_overlap(g, g_cstride, dy, dy_cstride, rows))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g overlaps dy without being dy itself (same pointer, stride and offset)");
+  if (views_overlap(g, g_cstride, y, y_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g overlaps y");
+  hipError_t e = relu_backward_launch(dy, dy_cstride, dy_coff, y, y_cstride, y_coff, rows, C, g, g_cstride, g_coff, accumulate != 0,
+                                      static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
+int offk_conv2d_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
+                              int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
+                              size_t scratch_bytes) {
+  const char* who = "offk_conv2d_backward_data";
+  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+  const long long rows = (long long)n_img * H * W;
+  if (views_overlap(dx, dx_cstride, g, g_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  size_t df = 0;
+  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, nullptr, nullptr, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (scratch_bytes < df * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_plan)");
+  const char* why = nullptr;
+  hipError_t e = conv_bwd_data_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, dx, dx_cstride, dx_coff, accumulate != 0,
+                                      static_cast<float*>(scratch), df, static_cast<hipStream_t>(stream), &why);
+  if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(who) + ": " + (why ? why : hipGetErrorString(e)));
+  return OFFK_OK;
+}
+
+int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
+                                int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db, int accumulate,
+                                void* scratch, size_t scratch_bytes) {
+  const char* who = "offk_conv2d_backward_weight";
+  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  size_t wf = 0;
+  int chunks = 0;
+  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, &wf, &chunks, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (scratch_bytes < wf * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_plan)");
+  hipError_t e = conv_bwd_weight_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
+                                        accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
 int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Cin, int relu_in,
                             const float* w1, const float* b1, const float* w2_packed, const float* b2, const float* w3,
                             const float* b3, int K3, const float* res, int res_cstride, int res_coff, float* y, int y_cstride,

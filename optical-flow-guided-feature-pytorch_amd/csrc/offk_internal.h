@@ -41,6 +41,20 @@ void conv2d_auto_plan(long long M, int Co, int nkt, int* cfg_out, int* splitk_ou
 hipError_t conv2d_launch(const ConvDesc& d, hipStream_t st, const char** why);
 hipError_t pack_conv_weight_launch(const float* src, int Co, int Ci, int KH, int KW, float* dst, hipStream_t st);
 
+// ---- K4b: backward of one stride-1 fusion conv, k = 1 or 3 (conv_bwd.hip, exact fp32) ----
+bool conv_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int KW);
+// scratch floats of the data / weight gradient, K chunks of the weight gradient, K slices of the data gradient's conv; pure host code
+bool conv_bwd_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_floats, size_t* weight_floats, int* chunks,
+                   int* dgrad_splitk);
+hipError_t relu_backward_launch(const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs, int y_coff, long long rows, int C, float* g,
+                                int g_cs, int g_coff, int accumulate, hipStream_t st);
+hipError_t conv_bwd_data_launch(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS,
+                                float* dx, int dx_cs, int dx_coff, int accumulate, float* scratch, size_t scratch_floats, hipStream_t st,
+                                const char** why);
+hipError_t conv_bwd_weight_launch(const float* x, int x_cs, int x_coff, const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Ci,
+                                  int Co, int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch, int chunks,
+                                  hipStream_t st);
+
 // ---- K4c: one 1x1 -> 3x3 -> 1x1 (+ residual) bottleneck chain at 14x14 per launch (chain_fused.hip, exact fp32) ----
 struct ChainArgs {
   const float* x; int x_cs, x_coff;       // chain input, channels-last [n_img * 196][x_cs], Cin channels at x_coff

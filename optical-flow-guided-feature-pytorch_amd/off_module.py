@@ -218,8 +218,9 @@ class OFFUnits(nn.Module):
     nn.Dropout(p=0.8) on the spatial gradients, RGB_OFF.py:356/:612, reproducible from ``drop_seed``), backward
     = offk_off_units_backward.  Returns the three motion maps the fusion stages start from
     (cat(motion_3a, motion_3b) [P,320,28,28], cat(motion_3c..4d) [P,800,14,14], cat(motion_5a, motion_5b)
-    [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The reference's fusion convolutions
-    and heads stay ordinary PyTorch modules in training.
+    [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The stride-1 fusion convolutions that
+    follow can be built from ``FusionConv2d`` (below: forward and backward on liboffk, one conv per module); the two
+    stride-2 convolutions and the heads are ordinary PyTorch modules in training.
 
     The nine maps may be fp32, or bf16 / fp16 of one dtype -- what a frozen backbone under ``torch.autocast`` emits.
     16-bit maps are neither cast nor copied: the kernels read them as they are (offk_off_units_train_typed,
@@ -350,6 +351,83 @@ class OFFUnits(nn.Module):
         if self.feat_grad:
             return _OFFUnitsFeatFn.apply(self, drop, *(feats + tuple(params)))
         return _OFFUnitsFn.apply(self, feats, drop, *params)
+
+
+class _FusionConvFn(torch.autograd.Function):
+    """autograd node of one ``FusionConv2d``: forward = offk_conv2d (direct fp32), backward = offk_relu_backward, then
+    offk_conv2d_backward_weight (weight and bias) and offk_conv2d_backward_data, each only where ``ctx.needs_input_grad`` asks.
+    Tensors cross the node as logical NCHW in channels-last memory; inside they are the [n, H, W, C] rows the library reads."""
+
+    @staticmethod
+    def forward(ctx, mod, x, res, weight, bias):
+        xr = x.permute(0, 2, 3, 1).contiguous()                    # no copy where x is channels-last already
+        rr = res.permute(0, 2, 3, 1).contiguous() if res is not None else None
+        flags = (runtime._lib.CONV_RELU_IN if mod.relu_in else 0) | (runtime._lib.CONV_RELU_POST if mod.relu else 0)
+        y = runtime.conv2d_nhwc(xr, weight, bias, 1, mod.padding[0], res=rr, flags=flags)
+        out = y.permute(0, 3, 1, 2)
+        ctx.mod = mod
+        ctx.save_for_backward(xr, weight, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        mod = ctx.mod
+        xr, weight, out = ctx.saved_tensors
+        need_x, need_res, need_w, need_b = ctx.needs_input_grad[1:5]
+        g = gy.permute(0, 2, 3, 1).contiguous()
+        if mod.relu:
+            g = runtime.relu_backward(g, out.permute(0, 2, 3, 1))
+        dx = dw = db = None
+        if need_w or need_b:
+            FusionConv2d.weight_grad_launches += 1
+            dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+        if need_x:
+            dx = runtime.conv2d_backward_data(g, weight, mod.padding[0])
+            if mod.relu_in:
+                runtime.relu_backward(dx, xr, out=dx)
+            dx = dx.permute(0, 3, 1, 2)
+        return None, dx, (g.permute(0, 3, 1, 2) if need_res else None), (dw if need_w else None), db
+
+
+class FusionConv2d(nn.Conv2d):
+    """One stride-1 fusion convolution of the OFF sub-network as a trainable module on liboffk: ``nn.Conv2d``'s constructor
+    arguments, parameters and state_dict keys (reference checkpoints load into a stage built from these under the
+    reference's names), plus ``relu`` (a ReLU behind the conv and its residual add) and ``relu_in`` (the conv reads
+    ``max(x, 0)``: RGB_OFF.py:658, conv1 of chain 28a).  ``forward(x, res=None)`` returns
+    ``post(conv(in(x)) + bias + res)``; x (and res) are fp32, logical NCHW in channels-last memory -- what ``OFFUnits``
+    returns; any other layout is made so once -- and so is the result.  Exact fp32, direct sums in a fixed order: forward
+    and every gradient are the same bits on every run.  The parameters are read in place on each call, nothing is
+    cached across optimizer steps.  Covers what offk_conv2d_backward_* cover: kernel 1 or 3, stride 1, padding
+    (k - 1) / 2, channels in multiples of 64; anything else raises ValueError at construction."""
+
+    weight_grad_launches = 0      # calls of offk_conv2d_backward_weight made by all modules (a frozen layer makes none)
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
+                 padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode,
+                         device=device, dtype=dtype)
+        k = self.kernel_size
+        if self.stride != (1, 1) or self.dilation != (1, 1) or self.groups != 1:
+            raise ValueError("FusionConv2d: stride, dilation and groups must be 1 (the stride-2 fusion convs are nn.Conv2d)")
+        if k not in ((1, 1), (3, 3)):
+            raise ValueError("FusionConv2d: kernel_size must be 1 or 3")
+        if isinstance(self.padding, str) or self.padding != ((k[0] - 1) // 2,) * 2 or self.padding_mode != "zeros":
+            raise ValueError("FusionConv2d: padding must be (kernel_size - 1) / 2 zeros")
+        if in_channels % 64 or out_channels % 64:
+            raise ValueError("FusionConv2d: in_channels and out_channels must be multiples of 64")
+        if self.weight.dtype != torch.float32:
+            raise ValueError("FusionConv2d: fp32 parameters only")
+        self.relu, self.relu_in = bool(relu), bool(relu_in)
+
+    def forward(self, x, res=None):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+            raise ValueError("FusionConv2d: x must be an fp32 CUDA/HIP tensor [n, C, H, W]")
+        if res is not None and (res.dtype != torch.float32 or res.shape != (x.shape[0], self.out_channels) + tuple(x.shape[2:])):
+            raise ValueError("FusionConv2d: res must be an fp32 tensor of the output's shape")
+        return _FusionConvFn.apply(self, x, res, self.weight, self.bias)
+
+    def extra_repr(self):
+        return super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
 
 
 class BNInception_OFF(nn.Module):

@@ -656,6 +656,95 @@ def pack_conv_weight(w_oihw, out=None):
     return wp
 
 
+# ---- backward of one stride-1 fusion conv (offk_relu_backward / offk_conv2d_backward_*; csrc/conv_bwd.hip) ----
+def _nhwc(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4):
+        raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor [n, H, W, Cs]" % name)
+    return t
+
+
+def conv2d_backward_plan(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_backward_plan: (data_scratch_bytes, weight_scratch_bytes, weight_chunks) of one conv's backward -- host code, a function
+    of these integers only.  The weight gradient's K chunks hold ceil(n_img / weight_chunks) images each, the last one what is left."""
+    lib = _lib.load()
+    d, w, c = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
+    _lib.check(lib.offk_conv2d_backward_plan(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d),
+                                             ctypes.byref(w), ctypes.byref(c)))
+    return d.value, w.value, c.value
+
+
+def relu_backward(dy, y, out=None, accumulate=False, dy_coff=0, y_coff=0, out_coff=0, c=None):
+    """out = dy * [y > 0] (exactly 0 where y <= 0, -0.0 or NaN), or out += that.  dy, y, out: [n, H, W, Cs] fp32 CUDA, channels
+    [coff, coff + c) of each (c: what dy holds behind dy_coff); out=None: a new dense tensor; out may be dy itself (in place)."""
+    lib = _lib.load()
+    _nhwc(dy, "dy"), _nhwc(y, "y")
+    n, H, W, cs = dy.shape
+    C = cs - dy_coff if c is None else int(c)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs the tensor to add to (out)")
+        out = torch.empty(n, H, W, C, dtype=torch.float32, device=dy.device)
+    _nhwc(out, "out")
+    if y.shape[:3] != dy.shape[:3] or out.shape[:3] != dy.shape[:3]:
+        raise ValueError("dy, y and out must agree in [n, H, W]")
+    _lib.check(lib.offk_relu_backward(_stream(dy.device), _ptr(dy), cs, dy_coff, _ptr(y), y.shape[-1], y_coff, n * H * W, C, _ptr(out),
+                                      out.shape[-1], out_coff, int(bool(accumulate))))
+    return out
+
+
+def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0):
+    """dx (+)= the gradient of a stride-1 conv's input.  g: [n, H, W, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
+    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx).  scratch: the caller's uint8
+    buffer of exactly conv2d_backward_plan's data_scratch_bytes."""
+    lib = _lib.load()
+    _nhwc(g, "g")
+    n, H, W, gs = g.shape
+    Co, Ci, KH, KW = w_oihw.shape
+    if not (w_oihw.is_cuda and w_oihw.dtype == torch.float32 and w_oihw.is_contiguous()):
+        raise ValueError("w_oihw must be a contiguous fp32 CUDA/HIP tensor")
+    if dx is None:
+        if accumulate:
+            raise ValueError("accumulate needs the tensor to add to (dx)")
+        dx = torch.empty(n, H, W, Ci, dtype=torch.float32, device=g.device)
+    _nhwc(dx, "dx")
+    nbytes = conv2d_backward_plan(n, H, W, Ci, Co, KH)[0] if KH == KW else 0
+    scratch = _given(scratch, (nbytes,), "scratch", g.device, torch.uint8)
+    _lib.check(lib.offk_conv2d_backward_data(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad), _ptr(dx),
+                                             dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
+    return dx
+
+
+def conv2d_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
+                           scratch=None, want_db=True):
+    """(dw, db) (+)= the weight and bias gradient of a stride-1 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
+    read max(x, 0)); g: [n, H, W, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co]: e.g. the parameters' .grad, written in
+    place (None: new tensors; want_db=False: no bias gradient, db comes back None).  scratch: the caller's uint8 buffer of exactly
+    conv2d_backward_plan's weight_scratch_bytes."""
+    lib = _lib.load()
+    _nhwc(x, "x"), _nhwc(g, "g")
+    n, H, W, xs = x.shape
+    if g.shape[:3] != x.shape[:3]:
+        raise ValueError("x and g must agree in [n, H, W]")
+    Ci = xs - x_coff if ci is None else int(ci)
+    Co = g.shape[-1] - g_coff if co is None else int(co)
+    k = int(ksize)
+    if accumulate and (dw is None or (want_db and db is None)):
+        raise ValueError("accumulate needs the tensors to add to (dw, db)")
+    if dw is None:
+        dw = torch.empty(Co, Ci, k, k, dtype=torch.float32, device=x.device)
+    if db is None and want_db:
+        db = torch.empty(Co, dtype=torch.float32, device=x.device)
+    for t, name, numel in ((dw, "dw", Co * Ci * k * k), (db, "db", Co)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+            raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
+    nbytes = conv2d_backward_plan(n, H, W, Ci, Co, k)[1]
+    scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
+    _lib.check(lib.offk_conv2d_backward_weight(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
+                                               int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch),
+                                               scratch.numel()))
+    return dw, db
+
+
 def bottleneck_chain14(x, w1, b1, w2_oihw, b2, w3, b3, res=None, relu_in=False, x_coff=0, y=None, y_coff=0, w2_packed=None):
     """One 1x1 -> 3x3 -> 1x1 (+ residual) chain of fusion@28 in one launch (offk_bottleneck_chain14).  x: [n, 14, 14, Cs] fp32 CUDA,
     the chain reads channels [x_coff, x_coff + Cin); w1 [64, Cin], w2_oihw [64, 64, 3, 3], w3 [256, K3] (K3 = 128: contracts

@@ -1,0 +1,112 @@
+"""Times the backward of the stride-1 fusion convs (offk_relu_backward, offk_conv2d_backward_data, offk_conv2d_backward_weight) against
+torch's own backward of F.conv2d on the same channels-last fp32 tensors, in one process and one session.
+
+    python tools/bench_fusion_bwd.py [--n-img 384] [--iters 30] [--warmup 5] [--out profiles/fusion_bwd/README.md]
+
+For each of the 13 distinct shapes of the 22 stride-1 fusion convs (spec.FUSION_CONVS): device-event time over --iters iterations after
+--warmup warm-ups of the three entries separately, torch.autograd.grad of F.conv2d (input, weight and bias gradients in one call; its
+forward runs outside the timed region), and the achieved TFLOP/s against the 157 TF fp32-matrix peak.  Prints a markdown table and the
+sums over the 22 convs; --out writes the same text to a file.  Nothing here gates anything: the numbers are reported.
+"""
+import argparse
+import collections
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import offk_amd  # noqa: E402,F401
+from offk_amd import runtime, spec  # noqa: E402
+
+PEAK_TF = 157.3
+
+
+def shapes():
+    """[(H, ci, co, k, how many of the 22 convs have this shape, their names)] in spec order"""
+    seen = collections.OrderedDict()
+    for key, co, ci, k, stride, _pad in spec.FUSION_CONVS:
+        if stride != 1:
+            continue
+        H = 14 if "28" in key else 7
+        seen.setdefault((H, ci, co, k), []).append(key)
+    return [(H, ci, co, k, len(v), v) for (H, ci, co, k), v in seen.items()]
+
+
+def timed(fn, iters, warmup, setup=None):
+    """mean ms of fn() by device events, one pair per iteration (setup() runs outside the timed region)"""
+    for _ in range(warmup):
+        arg = setup() if setup else None
+        fn(arg) if setup else fn()
+    total = 0.0
+    for _ in range(iters):
+        arg = setup() if setup else None
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn(arg) if setup else fn()
+        b.record()
+        b.synchronize()
+        total += a.elapsed_time(b)
+    return total / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-img", type=int, default=384)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    n = a.n_img
+    rows, tot = [], collections.Counter()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for H, ci, co, k, mult, names in shapes():
+        pad = (k - 1) // 2
+        x = torch.randn(n, H, H, ci, device="cuda", generator=gen)
+        g = torch.randn(n, H, H, co, device="cuda", generator=gen)
+        y = torch.randn(n, H, H, co, device="cuda", generator=gen)
+        w = torch.randn(co, ci, k, k, device="cuda", generator=gen) * 0.05
+        dbytes, wbytes, chunks = runtime.conv2d_backward_plan(n, H, H, ci, co, k)
+        sd, sw = torch.empty(dbytes, dtype=torch.uint8, device="cuda"), torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+        gm, dx = torch.empty_like(g), torch.empty_like(x)
+        dw, db = torch.empty_like(w), torch.empty(co, device="cuda")
+        t_relu = timed(lambda: runtime.relu_backward(g, y, out=gm), a.iters, a.warmup)
+        t_data = timed(lambda: runtime.conv2d_backward_data(g, w, pad, dx=dx, scratch=sd), a.iters, a.warmup)
+        t_wgt = timed(lambda: runtime.conv2d_backward_weight(x, g, k, pad, dw=dw, db=db, scratch=sw), a.iters, a.warmup)
+        # torch: the same tensors as logical NCHW views of the channels-last memory
+        xt = x.permute(0, 3, 1, 2).requires_grad_(True)
+        wt = w.contiguous(memory_format=torch.channels_last).requires_grad_(True)
+        bt = torch.zeros(co, device="cuda", requires_grad=True)
+        gt = g.permute(0, 3, 1, 2)
+        t_torch = timed(lambda yy: torch.autograd.grad(yy, (xt, wt, bt), gt), a.iters, a.warmup, setup=lambda: F.conv2d(xt, wt, bt, padding=pad))
+        flop = 2.0 * n * H * H * ci * co * k * k
+        rows.append((H, ci, co, k, mult, chunks, t_relu, t_data, t_wgt, t_torch, flop / t_data / 1e9, flop / t_wgt / 1e9))
+        tot["relu"] += mult * t_relu
+        tot["data"] += mult * t_data
+        tot["weight"] += mult * t_wgt
+        tot["torch"] += mult * t_torch
+        del x, g, y, w, sd, sw, gm, dx, dw, db, xt, wt, bt, gt
+    lines = ["Backward of the 22 stride-1 fusion convs at n_img = %d (%s), %d iterations after %d warm-ups, device events, one process." % (
+                 n, torch.cuda.get_device_name(0), a.iters, a.warmup), "",
+             "| map | Ci -> Co, k | convs | K chunks | relu_backward ms | data grad ms | TF/s (%% of %.0f) | weight grad ms | TF/s (%% of %.0f) | "
+             "liboffk data + weight ms | torch backward ms |" % (PEAK_TF, PEAK_TF),
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for H, ci, co, k, mult, chunks, tr, td, tw, tt, fd, fw in rows:
+        lines.append("| %dx%d | %d -> %d, %dx%d | %d | %d | %.3f | %.3f | %.1f (%.0f %%) | %.3f | %.1f (%.0f %%) | %.3f | %.3f |" % (
+            H, H, ci, co, k, k, mult, chunks, tr, td, fd, 100 * fd / PEAK_TF, tw, fw, 100 * fw / PEAK_TF, td + tw, tt))
+    lines += ["", "Sum over the 22 convs: data gradient %.3f ms, weight gradient %.3f ms, together %.3f ms (+ %.3f ms if every conv had a ReLU "
+              "to undo); torch's backward of the same convs %.3f ms." % (tot["data"], tot["weight"], tot["data"] + tot["weight"], tot["relu"],
+                                                                          tot["torch"])]
+    slower = ["%dx%d %d -> %d %dx%d (%.3f vs %.3f ms)" % (r[0], r[0], r[1], r[2], r[3], r[3], r[7] + r[8], r[9]) for r in rows if r[7] + r[8] > r[9]]
+    lines.append("Shapes slower than torch: %s." % ("; ".join(slower) if slower else "none"))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
