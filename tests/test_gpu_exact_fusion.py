@@ -17,7 +17,8 @@ of a wider buffer is written.
      reaches it) in an fp32 handle, chain_split.hip on the handle's pre-cut plane images in a split-fp32 handle.
   d. offk_winograd_between / _ex in the eight forms of test_winograd_between_vs_fp64.
 
-Not covered: the whole Winograd convs and the heads (their 1/6, 1/12, 1/24, 1/3 and 1/49 factors are not exact in binary).
+Not covered here: the whole Winograd convs (tests/test_gpu_exact_wino.py: single scaled taps make their 1/6, 1/12, 1/24 and 1/3 exact) and
+the heads (1/49 is not exact in binary).
 """
 import pytest
 import torch
