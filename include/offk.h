@@ -124,7 +124,15 @@ int offk_destroy(offk_handle* h);
  * state_dict key (an optional "module." prefix is ignored, test_flow_off.py:52-58);
  * `data` may be a host or a device pointer; shape is checked against the reference's.
  * The library keeps its own packed device copy.  Blocking, load-time call: it first waits for all work on the device
- * (so no kernel still reads the copy being replaced and a device-side `data` is complete whatever stream produced it). */
+ * (so no kernel still reads the copy being replaced and a device-side `data` is complete whatever stream produced it).
+ * The copy and every image derived from it (the operand-order images of the units kernels, the merged matrices, the Winograd,
+ * chain, plane and composed-head images) are handle-owned and made again IN PLACE: the copy by this call, the images by the
+ * first forward enqueued after it.  A captured forward (HIP graph) therefore sees a later offk_set_weight once one forward has
+ * passed through the library after it, and not before: until then a replay reads the new copy beside images of the old weight.
+ * Two updates change the launches themselves, which a graph fixes at capture, and need a re-capture: a sobel_edge_diagonal weight
+ * that leaves or enters the four-tap form of util.py:61 (the host picks the four-tap or the nine-tap kernel from its values at
+ * every launch; a graph captured on the four-tap kernel goes on ignoring the other five taps), and offk_set_weight on a key bound
+ * with offk_bind_weight (the bound pointer, and for a gen / down weight the register-staged units kernel, stay in the graph). */
 int offk_set_weight(offk_handle* h, const char* key, const float* data, const int64_t* shape, int ndim);
 /* Training-side alternative for the parameters that change every optimizer step.  (train_off.py:39-45 un-freezes every tensor
  * whose name contains "motion" or "fc_action_motion" -- the units, the fusion stages and the heads; the OFF UNITS' share of

@@ -277,7 +277,7 @@ class OFFUnits(nn.Module):
         if self.variant == spec.VARIANT_FLOW:
             self.sobel_edge_diagonal = _SobelHolder()
         self.param_keys = [k for k in spec.weight_shapes(self.variant) if k.startswith(spec.UNIT_PARAM_PREFIXES)]
-        self._rt, self._bound, self.drop_seed = None, {}, 0
+        self._rt, self._bound, self._sobel_pushed, self.drop_seed = None, {}, None, 0
         self._generation = 0    # bumped by every units forward: tells a backward whether G / D in the workspace are its own
 
     def _run_units(self, rt, feats, drop):
@@ -313,8 +313,16 @@ class OFFUnits(nn.Module):
             self._rt = runtime.OffForward(self.batch, self.length, self.variant, self.slice_mode, False,
                                           device=device, precision=self.precision, training=True)
             self._bound = {}
-            if self.variant == spec.VARIANT_FLOW:
-                self._rt.set_weight(spec.SOBEL_KEY, self.sobel_edge_diagonal.conv.weight)
+            self._sobel_pushed = None
+        if self.variant == spec.VARIANT_FLOW:
+            # frozen (util.py:72) and therefore copied, not bound -- but it travels in checkpoints: one loaded after the first forward
+            # moves its (data_ptr, _version) tag, like the parameters OFFSubNetwork pushes.  The tag has that class's blind spot too: an
+            # in-place write through .data (sobel.data.copy_(w)) moves neither half of it; OFFK_ALWAYS_PUSH=1 copies on every forward.
+            sobel = self.sobel_edge_diagonal.conv.weight
+            tag = (sobel.data_ptr(), sobel._version)
+            if self._sobel_pushed != tag or os.environ.get("OFFK_ALWAYS_PUSH") == "1":
+                self._rt.set_weight(spec.SOBEL_KEY, sobel)
+                self._sobel_pushed = tag
         # The trainable tensors are BOUND, not copied (offk_bind_weight): liboffk reads the parameters' own storage at
         # launch time, so an optimizer step costs the library nothing -- no 54 blocking copies per step, no staging, no
         # re-packing -- and is ordered like any other kernel on the stream.  Only a re-allocated parameter is re-bound.

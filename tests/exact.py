@@ -35,6 +35,9 @@ SHAPES = [(1, 2, spec.VARIANT_RGB, spec.SLICE_FLAT), (2, 3, spec.VARIANT_RGB, sp
 IDS = ["b1l2_rgb_flat", "b2l3_rgb_flat", "b3l4_rgb_clip", "b2l8_flow_flat", "b2l13_rgb_clip", "b2l14_flow_flat", "b1l15_rgb_flat",
        "b5l9_flow_clip"]
 FULL_SIZE = (64, 7, spec.VARIANT_RGB, spec.SLICE_FLAT)
+# the Flow shapes run again with a dense Sobel weight (dense_sobel): both slice modes, one and several strips per map at every site
+SOBEL_SHAPES = [(2, 3, spec.VARIANT_FLOW, spec.SLICE_FLAT), (3, 4, spec.VARIANT_FLOW, spec.SLICE_PER_CLIP), (2, 8, spec.VARIANT_FLOW, spec.SLICE_FLAT)]
+SOBEL_IDS = ["b2l3_flow_flat", "b3l4_flow_clip", "b2l8_flow_flat"]
 
 
 # ---- the project's counter-based generator (synth.raw_u64: splitmix64 finaliser on seed, index) on torch int64 ----------------
@@ -100,6 +103,15 @@ def stream(seed, kind, site=0):
 
 
 _X, _WG, _BG, _WD, _BD, _TAP, _TB, _DM = range(8)
+_SOBEL = 16          # (8 .. 15: the conv and GEMM inputs of tests/test_gpu_exact.py)
+
+
+def dense_sobel(seed=1, device="cpu"):
+    """A Sobel weight [32, 1, 3, 3] of integers in -1..1 with every tap in use, corners and centre included: what a checkpoint whose
+    sobel_edge_diagonal.conv.weight is not the fixed kernel of util.py:61 sends down K2's nine-tap, no-bias path."""
+    w = ints(stream(seed, _SOBEL), (DOWN, 1, 3, 3), -1, 1, device)
+    assert bool((w != 0).reshape(DOWN, 9).any(0).all())
+    return w
 
 
 def keep_mask(seed, site_index, pairs, H, device="cpu"):
@@ -122,9 +134,11 @@ def keep_mask_torch(seed, site_index, pairs, H, device):
 class SiteInputs:
     """Integer inputs of one site: x [N, C, H, H] in -2..2, wg [128, C, 1, 1] in -1..1, bg [128] in -3..3, wd [32, C, 1, 1] in -1..1 with
     a quarter nonzero, bd [32] in -3..3, tap [32, 1, 3, 3] in -1..1 and tb [32] in -1..1 (RGB; Flow: the fixed diagonal Sobel, tb None),
-    dm [P, 160, H, H] in -2..2, keep [P, 32, H, H] bool (p = 0.5, drop_seed); all fp32."""
+    dm [P, 160, H, H] in -2..2, keep [P, 32, H, H] bool (p = 0.5, drop_seed); all fp32.
+    sobel (Flow only): the weight that stands in for the fixed kernel, the same tensor at all nine sites as in the reference
+    (dense_sobel)."""
 
-    def __init__(self, si, B, L, variant, seed=1, drop_seed=21, device="cpu"):
+    def __init__(self, si, B, L, variant, seed=1, drop_seed=21, device="cpu", sobel=None):
         name, C, H = spec.SITES[si]
         N, P = B * L, B * (L - 1)
         self.si, self.name, self.C, self.H, self.variant = si, name, C, H, variant
@@ -136,9 +150,13 @@ class SiteInputs:
         if variant == spec.VARIANT_RGB:
             self.tap = ints(stream(seed, _TAP, si), (DOWN, 1, 3, 3), -1, 1, device)
             self.tb = ints(stream(seed, _TB, si), (DOWN,), -1, 1, device)
+        elif sobel is not None:
+            assert tuple(sobel.shape) == (DOWN, 1, 3, 3)
+            self.tap, self.tb = sobel.to(device=device, dtype=torch.float32).contiguous(), None
         else:
             k = torch.tensor(spec.DIAG_SOBEL, dtype=torch.float32, device=device)
             self.tap, self.tb = k.expand(DOWN, 1, 3, 3).contiguous(), None
+        assert sobel is None or variant == spec.VARIANT_FLOW
         self.dm = ints(stream(seed, _DM, si), (P, UNIT, H, H), -2, 2, device)
         self.keep = keep_mask(drop_seed, si, P, H, device)
 
@@ -154,8 +172,11 @@ class SiteInputs:
 
 def weights(variant, sites):
     """A full state_dict (numpy fp32): the integer unit parameters of `sites` (nine SiteInputs), the fusion convs and heads as
-    synth.make_weights leaves them -- nothing here reads those."""
+    synth.make_weights leaves them -- nothing here reads those.  Flow: the Sobel weight the sites hold (the fixed kernel, or theirs)."""
     w = synth.make_weights(variant)
+    if variant == spec.VARIANT_FLOW:
+        assert all(torch.equal(s.tap, sites[0].tap) for s in sites)
+        w[spec.SOBEL_KEY] = sites[0].tap.cpu().numpy()
     for s in sites:
         for k, v in s.params().items():
             assert w[k].shape == tuple(v.shape), k

@@ -81,6 +81,30 @@ def test_condition_holds(case):
     print("B = %d, L = %d: largest sum of |terms| %.0f (%s at %s), %.4f of its limit" % (B, L, worst["sum"], worst["output"], worst["site"], worst["share"]))
 
 
+@pytest.mark.parametrize("shape", exact.SOBEL_SHAPES, ids=exact.SOBEL_IDS)
+def test_condition_holds_with_a_dense_sobel_weight(shape):
+    """Flow shapes (exact.SOBEL_SHAPES) with exact.dense_sobel in place of the fixed four-tap kernel (K2's nine-tap path, tests/test_gpu_sobel_taps.py):
+    nine terms per S element instead of four, the same 2^24 / 2^23 limits; and the reference is still the oracle's."""
+    B, L, variant, slice_mode = shape
+    sob = exact.dense_sobel()
+    assert set(sob.unique().tolist()) == {-1.0, 0.0, 1.0}
+    assert torch.equal(sob, exact.dense_sobel()) and not torch.equal(sob, exact.dense_sobel(seed=2))
+    sites = [exact.SiteInputs(si, B, L, variant, sobel=sob) for si in range(spec.NUM_SITES)]
+    w = exact.weights(variant, sites)
+    assert np.array_equal(w[spec.SOBEL_KEY], sob.numpy())
+    wt = dict((k, torch.from_numpy(v).double()) for k, v in w.items())
+    for s in sites:
+        out, cap = exact.unit_reference(s, B, L, variant, slice_mode)
+        assert len(out) == 11
+        exact.check_caps(cap, s.name)
+        assert cap["M"] <= 4e3 and cap["M_train"] <= 4e3
+        for k, t in out.items():
+            assert bool((t == t.round()).all()) and bool((t != 0).any()), (s.name, k)
+        with torch.no_grad():
+            m_eval = orc.off_unit(s.x.double(), wt, s.name, B, L, variant, slice_mode)
+        exact.assert_exact(m_eval.permute(0, 2, 3, 1).reshape(-1, 160), out["M"], s.name + " M")
+
+
 def test_reference_is_the_oracles(case):
     (B, L, variant, slice_mode), sites, refs = case
     P = B * (L - 1)
