@@ -352,6 +352,32 @@ int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int
                                 void* scratch, size_t scratch_bytes);
 int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
                               size_t* weight_scratch_bytes, int* weight_chunks);
+/* K4b, stride 2 (additive, ABI v10). Backward of the two stage-opening fusion convolutions (motion_conv_trans_28: 7x7 / 2 / 3, RGB_OFF.py:657;
+ * motion_conv_trans_14: 5x5 / 2 / 2, RGB_OFF.py:762), exact fp32 -- with the entries above all 24 fusion convs.  The conventions are K4b's,
+ * word for word (views, enqueue only, no synchronisation, no allocation, refusals with OFFK_ERR_INVALID and the entry's name before any HIP
+ * call: a null pointer (db excepted), another form, an odd H or W, bad channel counts, a negative offset, cstride < coff + C, a scratch
+ * smaller than the plan's, dx overlapping g).  H and W are the INPUT map's size, even and >= 2; g is [n_img * (H/2) * (W/2)][g_cstride].
+ * Forms: (KH = KW, pad) in {(7, 3), (5, 2)}; Ci % 32 == 0, Co % 64 == 0; strides and offsets % 4 == 0.  The stride-1 entries above keep
+ * refusing k = 5 and k = 7.
+ *
+ * offk_conv2d_s2_backward_data: dx[n, 2a+r, 2b+s, ci] (+)= sum_co sum_{kh = r+pad (mod 2)} sum_{kw = s+pad (mod 2)}
+ * g[n, a + (r+pad-kh)/2, b + (s+pad-kw)/2, co] * w[co,ci,kh,kw], terms outside the map 0: one implicit GEMM per phase (r, s) of the input
+ * pixel on the fp32 matrix pipe, all four in one launch, only the taps that exist, stored straight to the dx pixels.  A device kernel cuts the
+ * phase weights into `scratch` on every call.  K is not split; accumulate != 0 adds the completely summed, once rounded result to dx.
+ *
+ * offk_conv2d_s2_backward_weight: dw[co,ci,kh,kw] (+)= sum_{n,oh,ow} g[n,oh,ow,co] * in(x)[n, 2 oh + kh - pad, 2 ow + kw - pad, ci];
+ * db[co] (+)= sum g (db may be NULL).  Split over K into weight_chunks chunks of ceil(n_img / weight_chunks) whole images; partial slabs
+ * [chunk][Co][Ci * KH * KW] (+ [chunk][Co]) in `scratch`, added in chunk order by the stride-1 entry's reduce: bit-reproducible.
+ *
+ * offk_conv2d_s2_backward_plan: pure host code, a function of these seven integers only.  Output pointers may be NULL. */
+int offk_conv2d_s2_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
+                                 int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
+                                 size_t scratch_bytes);
+int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
+                                   int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
+                                   int accumulate, void* scratch, size_t scratch_bytes);
+int offk_conv2d_s2_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
+                                 size_t* weight_scratch_bytes, int* weight_chunks);
 /* Override the plan offk_forward uses for one fusion conv (key = its state_dict name without
  * ".weight", e.g. "motion_conv_trans_28"); tile_cfg < 0 / splitk < 1 restore the automatic choice. */
 int offk_set_conv_plan(offk_handle* h, const char* conv_key, int tile_cfg, int splitk);

@@ -343,4 +343,16 @@ hipError_t conv_bwd_weight_launch(const float* x, int x_cs, int x_coff, const fl
   return hipGetLastError();
 }
 
+// the same reduce for the slabs of another weight-gradient kernel (conv_bwd_s2.hip): one kernel, one summation order
+hipError_t conv_wgrad_reduce_launch(float* slab, float* dbslab, int Co, int Ci, int KK, int chunks, float* dw, float* db, int accumulate,
+                                    hipStream_t st) {
+  WgradArgs a = {};
+  a.Ci = Ci; a.Co = Co; a.want_db = db != nullptr; a.chunks = chunks;
+  a.slab = slab; a.dbslab = dbslab; a.dw = dw; a.db = db; a.accumulate = accumulate;
+  const size_t n = (size_t)Co * Ci * KK + Co;
+  int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+  hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, a, KK);
+  return hipGetLastError();
+}
+
 }  // namespace offk

@@ -2221,6 +2221,71 @@ int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int
   return OFFK_OK;
 }
 
+// ---- K4b, stride 2: backward of the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip) ----
+namespace {
+int conv_s2_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {
+  if (n_img < 1 || H < 2 || W < 2) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (n_img >= 1, H, W >= 2)");
+  if (!(KH == KW && ((KH == 7 && pad == 3) || (KH == 5 && pad == 2))))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": the form must be 7x7 with pad 3 or 5x5 with pad 2 (stride 2)");
+  if ((H & 1) || (W & 1)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": H and W (the input map) must be even");
+  if (Ci < 32 || Co < 64 || Ci % 32 || Co % 64) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need Ci % 32 == 0 and Co % 64 == 0");
+  if (!conv_s2_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  return OFFK_OK;
+}
+}  // namespace
+
+int offk_conv2d_s2_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
+                                 size_t* weight_scratch_bytes, int* weight_chunks) {
+  const char* who = "offk_conv2d_s2_backward_plan";
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t df = 0, wf = 0;
+  int chunks = 0;
+  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (data_scratch_bytes) *data_scratch_bytes = df * sizeof(float);
+  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
+  if (weight_chunks) *weight_chunks = chunks;
+  return OFFK_OK;
+}
+
+int offk_conv2d_s2_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
+                                 int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
+                                 size_t scratch_bytes) {
+  const char* who = "offk_conv2d_s2_backward_data";
+  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+  const long long g_rows = (long long)n_img * (H / 2) * (W / 2), dx_rows = (long long)n_img * H * W;
+  const uintptr_t g0 = reinterpret_cast<uintptr_t>(g), g1 = g0 + (size_t)g_rows * (size_t)g_cstride * sizeof(float);
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dx), d1 = d0 + (size_t)dx_rows * (size_t)dx_cstride * sizeof(float);
+  if (g0 < d1 && d0 < g1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  size_t df = 0;
+  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, nullptr, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (scratch_bytes < df * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan)");
+  hipError_t e = conv_s2_bwd_data_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0,
+                                         static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
+int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
+                                   int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
+                                   int accumulate, void* scratch, size_t scratch_bytes) {
+  const char* who = "offk_conv2d_s2_backward_weight";
+  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  size_t wf = 0;
+  int chunks = 0;
+  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
+  if (scratch_bytes < wf * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan)");
+  hipError_t e = conv_s2_bwd_weight_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
+                                           accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
 int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Cin, int relu_in,
                             const float* w1, const float* b1, const float* w2_packed, const float* b2, const float* w3,
                             const float* b3, int K3, const float* res, int res_cstride, int res_coff, float* y, int y_cstride,

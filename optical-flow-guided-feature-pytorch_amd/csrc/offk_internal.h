@@ -55,6 +55,20 @@ hipError_t conv_bwd_weight_launch(const float* x, int x_cs, int x_coff, const fl
                                   int Co, int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch, int chunks,
                                   hipStream_t st);
 
+// slabs [chunks][Co][Ci * KK] (+ [chunks][Co]) -> dw, db (+)= their sum in chunk order; db may be nullptr
+hipError_t conv_wgrad_reduce_launch(float* slab, float* dbslab, int Co, int Ci, int KK, int chunks, float* dw, float* db, int accumulate,
+                                    hipStream_t st);
+
+// ---- K4b, stride 2: backward of the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip, exact fp32); H, W = the INPUT map ----
+bool conv_s2_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int KW);
+// scratch floats of the data / weight gradient and the K chunks of the weight gradient; pure host code
+bool conv_s2_bwd_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_floats, size_t* weight_floats, int* chunks);
+hipError_t conv_s2_bwd_data_launch(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS,
+                                   int pad, float* dx, int dx_cs, int dx_coff, int accumulate, float* scratch, hipStream_t st);
+hipError_t conv_s2_bwd_weight_launch(const float* x, int x_cs, int x_coff, const float* g, int g_cs, int g_coff, int n_img, int H, int W,
+                                     int Ci, int Co, int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch,
+                                     int chunks, hipStream_t st);
+
 // ---- K4c: one 1x1 -> 3x3 -> 1x1 (+ residual) bottleneck chain at 14x14 per launch (chain_fused.hip, exact fp32) ----
 struct ChainArgs {
   const float* x; int x_cs, x_coff;       // chain input, channels-last [n_img * 196][x_cs], Cin channels at x_coff

@@ -218,9 +218,9 @@ class OFFUnits(nn.Module):
     nn.Dropout(p=0.8) on the spatial gradients, RGB_OFF.py:356/:612, reproducible from ``drop_seed``), backward
     = offk_off_units_backward.  Returns the three motion maps the fusion stages start from
     (cat(motion_3a, motion_3b) [P,320,28,28], cat(motion_3c..4d) [P,800,14,14], cat(motion_5a, motion_5b)
-    [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The stride-1 fusion convolutions that
-    follow can be built from ``FusionConv2d`` (below: forward and backward on liboffk, one conv per module); the two
-    stride-2 convolutions and the heads are ordinary PyTorch modules in training.
+    [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The fusion convolutions that
+    follow -- the two stride-2 stage openers included -- can be built from ``FusionConv2d`` (below: forward and backward on
+    liboffk, one conv per module); the heads are ordinary PyTorch modules in training.
 
     The nine maps may be fp32, or bf16 / fp16 of one dtype -- what a frozen backbone under ``torch.autocast`` emits.
     16-bit maps are neither cast nor copied: the kernels read them as they are (offk_off_units_train_typed,
@@ -363,7 +363,8 @@ class OFFUnits(nn.Module):
 
 class _FusionConvFn(torch.autograd.Function):
     """autograd node of one ``FusionConv2d``: forward = offk_conv2d (direct fp32), backward = offk_relu_backward, then
-    offk_conv2d_backward_weight (weight and bias) and offk_conv2d_backward_data, each only where ``ctx.needs_input_grad`` asks.
+    offk_conv2d_backward_weight (weight and bias) and offk_conv2d_backward_data -- the offk_conv2d_s2_backward_* entries for a stride-2
+    module --, each only where ``ctx.needs_input_grad`` asks.
     Tensors cross the node as logical NCHW in channels-last memory; inside they are the [n, H, W, C] rows the library reads."""
 
     @staticmethod
@@ -371,7 +372,7 @@ class _FusionConvFn(torch.autograd.Function):
         xr = x.permute(0, 2, 3, 1).contiguous()                    # no copy where x is channels-last already
         rr = res.permute(0, 2, 3, 1).contiguous() if res is not None else None
         flags = (runtime._lib.CONV_RELU_IN if mod.relu_in else 0) | (runtime._lib.CONV_RELU_POST if mod.relu else 0)
-        y = runtime.conv2d_nhwc(xr, weight, bias, 1, mod.padding[0], res=rr, flags=flags)
+        y = runtime.conv2d_nhwc(xr, weight, bias, mod.stride[0], mod.padding[0], res=rr, flags=flags)
         out = y.permute(0, 3, 1, 2)
         ctx.mod = mod
         ctx.save_for_backward(xr, weight, out)
@@ -383,14 +384,16 @@ class _FusionConvFn(torch.autograd.Function):
         xr, weight, out = ctx.saved_tensors
         need_x, need_res, need_w, need_b = ctx.needs_input_grad[1:5]
         g = gy.permute(0, 2, 3, 1).contiguous()
+        s2 = mod.stride[0] == 2
         if mod.relu:
             g = runtime.relu_backward(g, out.permute(0, 2, 3, 1))
         dx = dw = db = None
         if need_w or need_b:
             FusionConv2d.weight_grad_launches += 1
-            dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+            wgrad = runtime.conv2d_s2_backward_weight if s2 else runtime.conv2d_backward_weight
+            dw, db = wgrad(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
         if need_x:
-            dx = runtime.conv2d_backward_data(g, weight, mod.padding[0])
+            dx = (runtime.conv2d_s2_backward_data if s2 else runtime.conv2d_backward_data)(g, weight, mod.padding[0])
             if mod.relu_in:
                 runtime.relu_backward(dx, xr, out=dx)
             dx = dx.permute(0, 3, 1, 2)
@@ -398,7 +401,7 @@ class _FusionConvFn(torch.autograd.Function):
 
 
 class FusionConv2d(nn.Conv2d):
-    """One stride-1 fusion convolution of the OFF sub-network as a trainable module on liboffk: ``nn.Conv2d``'s constructor
+    """One fusion convolution of the OFF sub-network as a trainable module on liboffk: ``nn.Conv2d``'s constructor
     arguments, parameters and state_dict keys (reference checkpoints load into a stage built from these under the
     reference's names), plus ``relu`` (a ReLU behind the conv and its residual add) and ``relu_in`` (the conv reads
     ``max(x, 0)``: RGB_OFF.py:658, conv1 of chain 28a).  ``forward(x, res=None)`` returns
@@ -406,23 +409,27 @@ class FusionConv2d(nn.Conv2d):
     returns; any other layout is made so once -- and so is the result.  Exact fp32, direct sums in a fixed order: forward
     and every gradient are the same bits on every run.  The parameters are read in place on each call, nothing is
     cached across optimizer steps.  Covers what offk_conv2d_backward_* cover: kernel 1 or 3, stride 1, padding
-    (k - 1) / 2, channels in multiples of 64; anything else raises ValueError at construction."""
+    (k - 1) / 2, channels in multiples of 64; and what offk_conv2d_s2_backward_* cover, the two stage openers: exactly
+    (kernel 7, stride 2, padding 3) and (kernel 5, stride 2, padding 2) on even maps, in_channels a multiple of 32,
+    out_channels of 64.  Anything else raises ValueError at construction."""
 
-    weight_grad_launches = 0      # calls of offk_conv2d_backward_weight made by all modules (a frozen layer makes none)
+    weight_grad_launches = 0      # calls of offk_conv2d[_s2]_backward_weight made by all modules (a frozen layer makes none)
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode,
                          device=device, dtype=dtype)
         k = self.kernel_size
-        if self.stride != (1, 1) or self.dilation != (1, 1) or self.groups != 1:
-            raise ValueError("FusionConv2d: stride, dilation and groups must be 1 (the stride-2 fusion convs are nn.Conv2d)")
-        if k not in ((1, 1), (3, 3)):
-            raise ValueError("FusionConv2d: kernel_size must be 1 or 3")
+        if self.stride not in ((1, 1), (2, 2)) or self.dilation != (1, 1) or self.groups != 1:
+            raise ValueError("FusionConv2d: dilation and groups must be 1, stride 1 (kernel 1 or 3) or 2 (kernel 7 with padding 3, "
+                             "kernel 5 with padding 2)")
+        s2 = self.stride == (2, 2)
+        if k not in (((7, 7), (5, 5)) if s2 else ((1, 1), (3, 3))):
+            raise ValueError("FusionConv2d: kernel_size must be 1 or 3 at stride 1, 7 or 5 at stride 2")
         if isinstance(self.padding, str) or self.padding != ((k[0] - 1) // 2,) * 2 or self.padding_mode != "zeros":
             raise ValueError("FusionConv2d: padding must be (kernel_size - 1) / 2 zeros")
-        if in_channels % 64 or out_channels % 64:
-            raise ValueError("FusionConv2d: in_channels and out_channels must be multiples of 64")
+        if in_channels % (32 if s2 else 64) or out_channels % 64:
+            raise ValueError("FusionConv2d: out_channels must be a multiple of 64, in_channels of 64 (stride 1) or 32 (stride 2)")
         if self.weight.dtype != torch.float32:
             raise ValueError("FusionConv2d: fp32 parameters only")
         self.relu, self.relu_in = bool(relu), bool(relu_in)
@@ -430,7 +437,9 @@ class FusionConv2d(nn.Conv2d):
     def forward(self, x, res=None):
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
             raise ValueError("FusionConv2d: x must be an fp32 CUDA/HIP tensor [n, C, H, W]")
-        if res is not None and (res.dtype != torch.float32 or res.shape != (x.shape[0], self.out_channels) + tuple(x.shape[2:])):
+        if self.stride == (2, 2) and (x.shape[2] % 2 or x.shape[3] % 2):
+            raise ValueError("FusionConv2d: a stride-2 module needs an even map")
+        if res is not None and (res.dtype != torch.float32 or res.shape != (x.shape[0], self.out_channels) + tuple(d // self.stride[0] for d in x.shape[2:])):
             raise ValueError("FusionConv2d: res must be an fp32 tensor of the output's shape")
         return _FusionConvFn.apply(self, x, res, self.weight, self.bias)
 

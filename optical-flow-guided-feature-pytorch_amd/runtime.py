@@ -745,6 +745,72 @@ def conv2d_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g
     return dw, db
 
 
+# ---- backward of the two stride-2 fusion convs, 7x7 / 2 / 3 and 5x5 / 2 / 2 (offk_conv2d_s2_backward_*; csrc/conv_bwd_s2.hip) ----
+def conv2d_s2_backward_plan(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_s2_backward_plan: (data_scratch_bytes, weight_scratch_bytes, weight_chunks) of one stride-2 conv's backward -- host code, a
+    function of these integers only.  H, W: the INPUT map.  The weight gradient's K chunks hold ceil(n_img / weight_chunks) images each."""
+    lib = _lib.load()
+    d, w, c = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
+    _lib.check(lib.offk_conv2d_s2_backward_plan(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d),
+                                                ctypes.byref(w), ctypes.byref(c)))
+    return d.value, w.value, c.value
+
+
+def conv2d_s2_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0):
+    """dx (+)= the gradient of a stride-2 conv's input.  g: [n, H/2, W/2, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
+    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx, whose map is twice g's).
+    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's data_scratch_bytes."""
+    lib = _lib.load()
+    _nhwc(g, "g")
+    n, OH, OW, gs = g.shape
+    H, W = 2 * OH, 2 * OW
+    Co, Ci, KH, KW = w_oihw.shape
+    if not (w_oihw.is_cuda and w_oihw.dtype == torch.float32 and w_oihw.is_contiguous()):
+        raise ValueError("w_oihw must be a contiguous fp32 CUDA/HIP tensor")
+    if dx is None:
+        if accumulate:
+            raise ValueError("accumulate needs the tensor to add to (dx)")
+        dx = torch.empty(n, H, W, Ci, dtype=torch.float32, device=g.device)
+    _nhwc(dx, "dx")
+    if tuple(dx.shape[:3]) != (n, H, W):
+        raise ValueError("dx must be [n, 2 * g's H, 2 * g's W, Cs]")
+    nbytes = conv2d_s2_backward_plan(n, H, W, Ci, Co, KH)[0] if KH == KW else 0
+    scratch = _given(scratch, (nbytes,), "scratch", g.device, torch.uint8)
+    _lib.check(lib.offk_conv2d_s2_backward_data(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad),
+                                                _ptr(dx), dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
+    return dx
+
+
+def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
+                              scratch=None, want_db=True):
+    """(dw, db) (+)= the weight and bias gradient of a stride-2 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
+    read max(x, 0)); g: [n, H/2, W/2, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co] as in conv2d_backward_weight.
+    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's weight_scratch_bytes."""
+    lib = _lib.load()
+    _nhwc(x, "x"), _nhwc(g, "g")
+    n, H, W, xs = x.shape
+    if tuple(g.shape[:3]) != (n, H // 2, W // 2) or H % 2 or W % 2:
+        raise ValueError("x must be [n, H, W, Xs] with even H and W, g [n, H / 2, W / 2, Gs]")
+    Ci = xs - x_coff if ci is None else int(ci)
+    Co = g.shape[-1] - g_coff if co is None else int(co)
+    k = int(ksize)
+    if accumulate and (dw is None or (want_db and db is None)):
+        raise ValueError("accumulate needs the tensors to add to (dw, db)")
+    if dw is None:
+        dw = torch.empty(Co, Ci, k, k, dtype=torch.float32, device=x.device)
+    if db is None and want_db:
+        db = torch.empty(Co, dtype=torch.float32, device=x.device)
+    for t, name, numel in ((dw, "dw", Co * Ci * k * k), (db, "db", Co)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+            raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
+    nbytes = conv2d_s2_backward_plan(n, H, W, Ci, Co, k)[1]
+    scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
+    _lib.check(lib.offk_conv2d_s2_backward_weight(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
+                                                  int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch),
+                                                  scratch.numel()))
+    return dw, db
+
+
 def bottleneck_chain14(x, w1, b1, w2_oihw, b2, w3, b3, res=None, relu_in=False, x_coff=0, y=None, y_coff=0, w2_packed=None):
     """One 1x1 -> 3x3 -> 1x1 (+ residual) chain of fusion@28 in one launch (offk_bottleneck_chain14).  x: [n, 14, 14, Cs] fp32 CUDA,
     the chain reads channels [x_coff, x_coff + Cin); w1 [64, Cin], w2_oihw [64, 64, 3, 3], w3 [256, K3] (K3 = 128: contracts

@@ -6,7 +6,8 @@ torch's own backward of F.conv2d on the same channels-last fp32 tensors, in one 
 For each of the 13 distinct shapes of the 22 stride-1 fusion convs (spec.FUSION_CONVS): device-event time over --iters iterations after
 --warmup warm-ups of the three entries separately, torch.autograd.grad of F.conv2d (input, weight and bias gradients in one call; its
 forward runs outside the timed region), and the achieved TFLOP/s against the 157 TF fp32-matrix peak.  Prints a markdown table and the
-sums over the 22 convs; --out writes the same text to a file.  Nothing here gates anything: the numbers are reported.
+sums over the 22 convs, then the table of the two stride-2 convs (tools/bench_fusion_bwd_s2.py); --out
+writes the same text to a file.  Nothing here gates anything: the numbers are reported.
 """
 import argparse
 import collections
@@ -19,6 +20,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import offk_amd  # noqa: E402,F401
 from offk_amd import runtime, spec  # noqa: E402
+import bench_fusion_bwd_s2  # noqa: E402  (the sibling tool: the two stride-2 convs)
 
 PEAK_TF = 157.3
 
@@ -101,6 +103,7 @@ def main():
     slower = ["%dx%d %d -> %d %dx%d (%.3f vs %.3f ms)" % (r[0], r[0], r[1], r[2], r[3], r[3], r[7] + r[8], r[9]) for r in rows if r[7] + r[8] > r[9]]
     lines.append("Shapes slower than torch: %s." % ("; ".join(slower) if slower else "none"))
     text = "\n".join(lines) + "\n"
+    text += "\n" + bench_fusion_bwd_s2.table(n, a.iters, a.warmup)
     print(text)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

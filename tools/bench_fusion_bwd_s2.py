@@ -1,0 +1,100 @@
+"""Times the backward of the two stride-2 fusion convs (offk_relu_backward, offk_conv2d_s2_backward_data, offk_conv2d_s2_backward_weight)
+against torch's own backward of F.conv2d(stride=2) on the same channels-last fp32 tensors, in one process and one session.
+
+    python tools/bench_fusion_bwd_s2.py [--n-img 384] [--iters 30] [--warmup 5] [--out FILE]
+
+tools/bench_fusion_bwd.py calls table() and prints it behind its stride-1 table.  Device-event times; TF/s counts
+2 n OH OW Ci Co k^2 per gradient against the fp32-matrix peak.  Nothing here gates anything: the numbers are reported.
+"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import offk_amd  # noqa: E402,F401
+from offk_amd import runtime, spec  # noqa: E402
+
+PEAK_TF = 157.3
+
+
+def shapes():
+    """[(key, H of the input map, ci, co, k, pad)] of the stride-2 fusion convs in spec order"""
+    return [(key, 28 if "28" in key else 14, ci, co, k, pad) for key, co, ci, k, stride, pad in spec.FUSION_CONVS if stride == 2]
+
+
+def timed(fn, iters, warmup, setup=None):
+    """mean ms of fn() by device events, one pair per iteration (setup() runs outside the timed region)"""
+    for _ in range(warmup):
+        arg = setup() if setup else None
+        fn(arg) if setup else fn()
+    total = 0.0
+    for _ in range(iters):
+        arg = setup() if setup else None
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn(arg) if setup else fn()
+        b.record()
+        b.synchronize()
+        total += a.elapsed_time(b)
+    return total / iters
+
+
+def table(n, iters, warmup):
+    rows = []
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    for key, H, ci, co, k, pad in shapes():
+        OH = H // 2
+        x = torch.randn(n, H, H, ci, device="cuda", generator=gen)
+        g = torch.randn(n, OH, OH, co, device="cuda", generator=gen)
+        y = torch.randn(n, OH, OH, co, device="cuda", generator=gen)
+        w = torch.randn(co, ci, k, k, device="cuda", generator=gen) * 0.05
+        dbytes, wbytes, chunks = runtime.conv2d_s2_backward_plan(n, H, H, ci, co, k)
+        sd, sw = torch.empty(dbytes, dtype=torch.uint8, device="cuda"), torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+        gm, dx = torch.empty_like(g), torch.empty_like(x)
+        dw, db = torch.empty_like(w), torch.empty(co, device="cuda")
+        t_relu = timed(lambda: runtime.relu_backward(g, y, out=gm), iters, warmup)
+        t_data = timed(lambda: runtime.conv2d_s2_backward_data(g, w, pad, dx=dx, scratch=sd), iters, warmup)
+        t_wgt = timed(lambda: runtime.conv2d_s2_backward_weight(x, g, k, pad, dw=dw, db=db, scratch=sw), iters, warmup)
+        # torch: the same tensors as logical NCHW views of the channels-last memory
+        xt = x.permute(0, 3, 1, 2).requires_grad_(True)
+        wt = w.contiguous(memory_format=torch.channels_last).requires_grad_(True)
+        bt = torch.zeros(co, device="cuda", requires_grad=True)
+        gt = g.permute(0, 3, 1, 2)
+        t_torch = timed(lambda yy: torch.autograd.grad(yy, (xt, wt, bt), gt), iters, warmup,
+                        setup=lambda: F.conv2d(xt, wt, bt, stride=2, padding=pad))
+        flop = 2.0 * n * OH * OH * ci * co * k * k
+        rows.append((key, H, ci, co, k, chunks, t_relu, t_data, t_wgt, t_torch, flop / t_data / 1e9, flop / t_wgt / 1e9))
+        del x, g, y, w, sd, sw, gm, dx, dw, db, xt, wt, bt, gt
+    lines = ["Backward of the two stride-2 fusion convs at n_img = %d (%s), %d iterations after %d warm-ups, device events, one process." % (
+                 n, torch.cuda.get_device_name(0), iters, warmup), "",
+             "| conv | input map | Ci -> Co, k / 2 | K chunks | relu_backward ms | data grad ms | TF/s (%% of %.0f) | weight grad ms | TF/s (%% of %.0f) | "
+             "liboffk data + weight ms | torch backward ms |" % (PEAK_TF, PEAK_TF),
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for key, H, ci, co, k, chunks, tr, td, tw, tt, fd, fw in rows:
+        lines.append("| %s | %dx%d | %d -> %d, %dx%d | %d | %.3f | %.3f | %.1f (%.0f %%) | %.3f | %.1f (%.0f %%) | %.3f | %.3f |" % (
+            key, H, H, ci, co, k, k, chunks, tr, td, fd, 100 * fd / PEAK_TF, tw, fw, 100 * fw / PEAK_TF, td + tw, tt))
+    slower = ["%s (%.3f vs %.3f ms)" % (r[0], r[7] + r[8], r[9]) for r in rows if r[7] + r[8] > r[9]]
+    lines += ["", "Slower than torch: %s." % ("; ".join(slower) if slower else "none")]
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-img", type=int, default=384)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    text = table(a.n_img, a.iters, a.warmup)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
