@@ -470,6 +470,45 @@ int offk_batched_gemm_nt(void* stream, const float* x, const float* w, float* y,
 int offk_head(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C,
               int maxpool, const float* fc_w, const float* fc_b, int num_classes, float* out);
 
+/* K5t / K5b (additive, ABI v10). Training side of ONE classifier head (fc_action_motion_28 / _14 / fc_action_motion, un-frozen by
+ * train_off.py:39-45): K5's pooling, the training-mode nn.Dropout(p = 0.8) on the pooled vector (RGB_OFF.py:785, 791, 845), the Linear, and
+ * their backward -- exact fp32, as stage entry points in K4b's conventions: x and dx are the channel slice [coff, coff + C) of channels-last
+ * rows [n_img * H * W][cstride]; fc_w is PyTorch's [num_classes][C] and dw has the same layout (a bound nn.Linear.weight and its .grad);
+ * g, out are [n_img][num_classes], z is [n_img][C], all contiguous.  Every entry enqueues on `stream` in order, does not synchronise and
+ * does not allocate (capturable).  Domain (K5's): 4 <= C <= 1024, C % 4 == 0, strides and offsets % 4 == 0, H, W >= 1 (>= 3 with maxpool),
+ * any num_classes >= 1, 0 <= drop_p < 1, 0 <= head_index <= 239.  Refused with OFFK_ERR_INVALID before any HIP call, the entry's name in
+ * offk_last_error(NULL): a null pointer that the call needs, anything outside the domain, a negative offset, cstride < coff + C, a scratch
+ * smaller than offk_head_backward_plan says, dx's bytes [dx, dx + n_img * H * W * dx_cstride * 4) overlapping x's or g's.
+ *
+ * offk_head_train: pooled[n][c] = the mean over the map (maxpool = 0) or over the MaxPool2d(3, 2, ceil_mode) windows, clipped at the border
+ * (maxpool = 1), as K5 defines it; z[n][c] = pooled * keep * scale, scale = (float)(1.0 / (1.0 - drop_p)); out = z . fc_w^T + fc_b.  z is
+ * caller-owned and is what the backward reads.  keep is the library's reproducible dropout, not the framework's generator: stream
+ * (drop_seed, 16 + head_index) -- head_index 0 / 1 / 2 for the 28 / 14 / 7 head, beside the units' streams 0 .. 8 --, draw
+ * n * (C / 4) + c / 4 serves a channel quad, 16 bits each, kept iff the field >= round(drop_p * 65536) (the units' rule;
+ * offk_amd.synth.head_dropout_keep is the same integer function).  drop_p = 0 is eval arithmetic: every keep * scale is exactly 1.0f.
+ *
+ * offk_head_backward: g = d loss / d out.  Any of dx, dw, db may be NULL and then that work is not launched (x and fc_w are needed for dx only,
+ * z for dw only, scratch for dw and db only).
+ *   dz[n][c] = sum_o g[n][o] fc_w[o][c];  dpooled = dz * keep * scale, the mask recomputed from the seed, never stored;
+ *   v = dpooled * (1.f / nwin), nwin = H * W (maxpool = 0) or Ho * Wo windows (maxpool = 1)
+ *   maxpool = 0: dx[n,h,w,c] (+)= v[n][c] for every pixel
+ *   maxpool = 1: dx[n,y,x,c] (+)= the sum of v[n][c] over the windows whose maximum sits at (y, x); the maximum of a window is the FIRST one
+ *   in row-major window order (torch's rule, CPU and GPU): an all-zero window sends its gradient to its top-left pixel.  A gather -- no
+ *   atomics, every dx element of the slice is written, zeros included; accumulate_dx != 0 adds to what dx holds (a head's input also feeds
+ *   the next stage).  NaN in x on this path is outside the contract: K5's forward drops a NaN where torch propagates it.
+ *   dw[o][c] (+)= sum_n g[n][o] z[n][c], db[o] (+)= sum_n g[n][o]  (accumulate_w), split over n_img into `chunks` chunks of
+ *   ceil(n_img / chunks) whole images (the last one may be shorter); the partial slabs [chunk][num_classes][C] + [chunk][num_classes] live
+ *   in `scratch` and a second launch adds them in chunk order: bit-reproducible whatever the scratch held.
+ *
+ * offk_head_backward_plan: pure host code (no GPU needed), a function of these three integers only.  Output pointers may be NULL. */
+int offk_head_train(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fc_w,
+                    const float* fc_b, int num_classes, int head_index, uint64_t drop_seed, double drop_p, float* z, float* out);
+int offk_head_backward(void* stream, const float* g, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C, int maxpool,
+                       const float* fc_w, int num_classes, const float* z, int head_index, uint64_t drop_seed, double drop_p, float* dx,
+                       int dx_cstride, int dx_coff, int accumulate_dx, float* dw, float* db, int accumulate_w, void* scratch,
+                       size_t scratch_bytes);
+int offk_head_backward_plan(int n_img, int C, int num_classes, size_t* scratch_bytes, int* chunks);
+
 /* K6. Replaces ConsensusModule('avg') (basic_ops.py:12-46) as applied in
  * Flow_OFF.py:867-876: x [B, T, C] -> mean over T -> [B, C]. */
 int offk_segment_consensus(void* stream, const float* x, int B, int T, int C, float* out);

@@ -89,6 +89,10 @@ SIGNATURES = {
     "offk_conv2d_s2_backward_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t), _c.POINTER(_I)]),
     "offk_set_conv_plan": (_I, [_P, _c.c_char_p, _I, _I]),
     "offk_head": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _F]),
+    "offk_head_train": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _c.c_uint64, _c.c_double, _F, _F]),
+    "offk_head_backward": (_I, [_P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _F, _I, _F, _I, _c.c_uint64, _c.c_double, _F, _I, _I, _I, _F, _F, _I, _P,
+                                _c.c_size_t]),
+    "offk_head_backward_plan": (_I, [_I, _I, _I, _c.POINTER(_c.c_size_t), _c.POINTER(_I)]),
     "offk_segment_consensus": (_I, [_P, _F, _I, _I, _I, _F]),
     "offk_score_fusion": (_I, [_P, _c.POINTER(_F), _c.POINTER(_c.c_float), _I, _I, _I, _I, _F, _F]),
     "offk_train_workspace_bytes": (_c.c_size_t, [_P]),

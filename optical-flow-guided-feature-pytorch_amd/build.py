@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "liboffk.so")
 SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "units_bwd_cl.hip", "units_dx.hip", "units_dx_f16.hip", "units_dx_split.hip", "units_wgrad_split.hip", "units_fwd_split.hip", "pw_tdiff.hip",
-           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip")
+           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip", "head_bwd.hip")
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",), "pw_reduce_cl.hip": ("pw_reduce.hip",), "units_bwd_cl.hip": ("units_bwd.hip",),
                     "units_dx_f16.hip": ("units_dx.hip",)}
@@ -33,7 +33,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 EXTRA_FLAGS = {"heads.hip": ["-fno-slp-vectorize"], "units_bwd.hip": ["-fno-slp-vectorize"], "units_bwd_cl.hip": ["-fno-slp-vectorize"], "units_dx.hip": ["-fno-slp-vectorize"], "units_dx_f16.hip": ["-fno-slp-vectorize"], "units_dx_split.hip": ["-fno-slp-vectorize"], "units_wgrad_split.hip": ["-fno-slp-vectorize"], "units_fwd_split.hip": ["-fno-slp-vectorize"],
                "conv_igemm.hip": ["-Wno-inline-asm"], "pw_tdiff.hip": ["-Wno-inline-asm"], "pw_tdiff_split.hip": ["-Wno-inline-asm", "-fno-slp-vectorize"],
                "pw_tdiff_f16.hip": ["-fno-slp-vectorize"], "pw_tdiff_cl.hip": ["-fno-slp-vectorize"],
-               "chain_fused.hip": ["-Wno-inline-asm"], "wino_gemm_split.hip": ["-fno-slp-vectorize"], "chain_split.hip": ["-fno-slp-vectorize"], "conv_bwd.hip": ["-fno-slp-vectorize"], "conv_bwd_s2.hip": ["-fno-slp-vectorize"]}
+               "chain_fused.hip": ["-Wno-inline-asm"], "wino_gemm_split.hip": ["-fno-slp-vectorize"], "chain_split.hip": ["-fno-slp-vectorize"], "conv_bwd.hip": ["-fno-slp-vectorize"], "conv_bwd_s2.hip": ["-fno-slp-vectorize"],
+               "head_bwd.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():

@@ -2490,6 +2490,83 @@ int offk_head(void* stream, const float* x, int x_cstride, int x_coff, int n_img
   return OFFK_OK;
 }
 
+// ---- K5t / K5b: training side of one classifier head (head_bwd.hip) ----
+namespace {
+// what offk_head_train and offk_head_backward share: the domain of K5 plus the dropout arguments
+int head_train_shape(const char* who, int n_img, int H, int W, int C, int maxpool, int num_classes, int head_index, double drop_p) {
+  if (n_img < 1 || H < 1 || W < 1 || num_classes < 1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (n_img, H, W, num_classes >= 1)");
+  if (C < 4 || C > 1024 || C % 4) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need 4 <= C <= 1024 and C % 4 == 0");
+  if (maxpool && (H < 3 || W < 3)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": maxpool needs H, W >= 3");
+  if (head_index < 0 || head_index > 239) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": head_index must be in [0, 239] (0 / 1 / 2: the 28 / 14 / 7 head)");
+  if (!(drop_p >= 0.0) || drop_p >= 1.0) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dropout probability must be in [0, 1)");
+  if ((long long)n_img * H * W > 0x7fffffffLL || (long long)n_img * num_classes > 0x7fffffffLL)
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  return OFFK_OK;
+}
+bool bytes_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+}  // namespace
+
+int offk_head_backward_plan(int n_img, int C, int num_classes, size_t* scratch_bytes, int* chunks) {
+  const char* who = "offk_head_backward_plan";
+  size_t sf = 0;
+  int ch = 0;
+  if (!head_bwd_plan(n_img, C, num_classes, &sf, &ch))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need n_img >= 1, 4 <= C <= 1024, C % 4 == 0, num_classes >= 1");
+  if (scratch_bytes) *scratch_bytes = sf * sizeof(float);
+  if (chunks) *chunks = ch;
+  return OFFK_OK;
+}
+
+int offk_head_train(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fc_w,
+                    const float* fc_b, int num_classes, int head_index, uint64_t drop_seed, double drop_p, float* z, float* out) {
+  const char* who = "offk_head_train";
+  if (!fc_w || !fc_b || !z || !out) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = head_train_shape(who, n_img, H, W, C, maxpool, num_classes, head_index, drop_p)) return rc;
+  if (const char* w = view_problem(x, x_cstride, x_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+  hipError_t e = head_train_launch(x, x_cstride, x_coff, n_img, H, W, C, maxpool != 0, fc_w, fc_b, num_classes, head_index, drop_seed, drop_p, z,
+                                   out, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
+int offk_head_backward(void* stream, const float* g, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C, int maxpool,
+                       const float* fc_w, int num_classes, const float* z, int head_index, uint64_t drop_seed, double drop_p, float* dx,
+                       int dx_cstride, int dx_coff, int accumulate_dx, float* dw, float* db, int accumulate_w, void* scratch,
+                       size_t scratch_bytes) {
+  const char* who = "offk_head_backward";
+  if (!g) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer (g)");
+  if (dx && !fc_w) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer (fc_w, needed for dx)");
+  if (dw && !z) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer (z, needed for dw)");
+  if ((dw || db) && !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer (scratch, needed for dw and db)");
+  if (int rc = head_train_shape(who, n_img, H, W, C, maxpool, num_classes, head_index, drop_p)) return rc;
+  if (dx) {
+    if (const char* w = view_problem(x, x_cstride, x_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+    if (const char* w = view_problem(dx, dx_cstride, dx_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+    const size_t rows = (size_t)n_img * H * W, dx_bytes = rows * (size_t)dx_cstride * sizeof(float);
+    if (bytes_overlap(dx, dx_bytes, x, rows * (size_t)x_cstride * sizeof(float))) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps x");
+    if (bytes_overlap(dx, dx_bytes, g, (size_t)n_img * num_classes * sizeof(float))) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  }
+  size_t sf = 0;
+  int chunks = 0;
+  head_bwd_plan(n_img, C, num_classes, &sf, &chunks);
+  if ((dw || db) && scratch_bytes < sf * sizeof(float))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_head_backward_plan)");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dx) {
+    hipError_t e = head_bwd_data_launch(g, x, x_cstride, x_coff, n_img, H, W, C, maxpool != 0, fc_w, num_classes, head_index, drop_seed, drop_p, dx,
+                                        dx_cstride, dx_coff, accumulate_dx != 0, st);
+    if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  }
+  if (dw || db) {
+    hipError_t e = head_bwd_weight_launch(g, z, n_img, C, num_classes, dw, db, accumulate_w != 0, static_cast<float*>(scratch), chunks, st);
+    if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  }
+  return OFFK_OK;
+}
+
 int offk_segment_consensus(void* stream, const float* x, int B, int T, int C, float* out) {
   if (!x || !out || B < 1 || T < 1 || C < 1) return fail(nullptr, OFFK_ERR_INVALID, "offk_segment_consensus: bad argument");
   hipError_t e = consensus_launch(x, B, T, C, out, static_cast<hipStream_t>(stream));

@@ -443,6 +443,16 @@ struct FcPooledJobs { FcPooledJob job[3]; int njobs, n_img, ncls; };
 hipError_t fc_pooled_multi_launch(const FcPooledJobs& j, hipStream_t st);      // the folded-pool FCs of up to three heads in one launch
 hipError_t fc_pooled_launch(const float* part, int hw, int tiles, int n_img, int C, const float* fw, const float* fb, int ncls, float* out,
                             hipStream_t st);
+// ---- K5t / K5b: training side of a head (head_bwd.hip): pooled -> dropout -> z -> FC, and its three gradients ----
+bool head_bwd_plan(int n_img, int C, int ncls, size_t* scratch_floats, int* chunks);
+hipError_t head_train_launch(const float* x, int x_cs, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fw, const float* fb,
+                             int ncls, int head_index, unsigned long long seed, double drop_p, float* z, float* out, hipStream_t st);
+hipError_t head_bwd_data_launch(const float* g, const float* x, int x_cs, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fw,
+                                int ncls, int head_index, unsigned long long seed, double drop_p, float* dx, int dx_cs, int dx_coff,
+                                int accumulate, hipStream_t st);
+// slabs [chunks][ncls][C] + [chunks][ncls] in scratch -> dw, db (+)= their sum in chunk order; either of dw, db may be nullptr
+hipError_t head_bwd_weight_launch(const float* g, const float* z, int n_img, int C, int ncls, float* dw, float* db, int accumulate, float* scratch,
+                                  int chunks, hipStream_t st);
 hipError_t vec_add_launch(const float* a, const float* b, float* o, int n, hipStream_t st);
 // A head whose average pool moves in front of the linear 1x1 conv that feeds it: w_out [ncls][K] = fw [ncls][Cm] . wm [Cm][K],
 // b_out [ncls] = fw . bm + fb; sums in fp64, rounded once (a load-time kernel)

@@ -447,6 +447,81 @@ class FusionConv2d(nn.Conv2d):
         return super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
 
 
+class _MotionHeadFn(torch.autograd.Function):
+    """autograd node of one ``MotionHead``: forward = offk_head_train, backward = offk_head_backward with each of dx, dw, db only where
+    ``ctx.needs_input_grad`` asks.  Saved: the [n, H, W, C] rows of x, z (the pooled vector behind the dropout) and the seed -- the mask is
+    recomputed from it, never stored."""
+
+    @staticmethod
+    def forward(ctx, mod, x, drop, weight, bias):
+        xr = x.permute(0, 2, 3, 1).contiguous()                    # no copy where x is channels-last already
+        out, z = runtime.head_train(xr, weight, bias, mod.maxpool, mod.head_index, drop)
+        ctx.mod, ctx.drop = mod, drop
+        ctx.save_for_backward(xr, weight, z)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        xr, weight, z = ctx.saved_tensors
+        need_x, _, need_w, need_b = ctx.needs_input_grad[1:5]
+        if need_w or need_b:
+            MotionHead.weight_grad_launches += 1
+        dx, dw, db = runtime.head_backward(g.contiguous(), xr, weight, z, mod.maxpool, mod.head_index, ctx.drop, want_dx=bool(need_x),
+                                           want_dw=bool(need_w), want_db=bool(need_b))
+        return None, (dx.permute(0, 3, 1, 2) if need_x else None), None, dw, db
+
+
+class MotionHead(nn.Linear):
+    """One classifier head of the OFF sub-network (fc_action_motion_28 / fc_action_motion_14 / fc_action_motion, RGB_OFF.py:782-793,
+    843-847) as a trainable module on liboffk: ``nn.Linear``'s parameters and state_dict keys (the reference's ``fc_action_motion*`` keys
+    load), in front of it the head's pooling -- ``maxpool``: MaxPool2d(3, 2, ceil_mode) first, the 28-head -- the mean over the map and
+    nn.Dropout(``drop_p``) on the pooled vector.  ``head_index`` 0 / 1 / 2 (the 28 / 14 / 7 head) picks the dropout stream.
+    ``forward(x, drop_seed=None)``: x is fp32, logical [n, C, H, W] in channels-last memory -- what ``FusionConv2d`` returns; any other
+    layout is made so once; returns the logits [n, out_features].  In training mode with drop_p > 0 the mask is the library's
+    reproducible dropout (``synth.head_dropout_keep``) of ``drop_seed``, or of an own counter that advances per call (as ``OFFUnits``);
+    eval mode and drop_p = 0 run without a mask, and where no gradient is asked for that is K5 itself (``runtime.head``).  Exact fp32,
+    sums in a fixed order: forward and every gradient are the same bits on every run.  The parameters are read in place on each call,
+    nothing is cached across optimizer steps.  in_features: a multiple of 4 in [4, 1024]; fp32 parameters; drop_p in [0, 1) --
+    anything else raises ValueError at construction."""
+
+    weight_grad_launches = 0      # offk_head_backward calls with a weight or bias gradient made by all modules (a frozen head makes none)
+
+    def __init__(self, in_features, out_features=101, maxpool=False, head_index=0, drop_p=0.8, bias=True, device=None, dtype=None):
+        if not (isinstance(in_features, int) and 4 <= in_features <= 1024 and in_features % 4 == 0):
+            raise ValueError("MotionHead: in_features must be a multiple of 4 in [4, 1024]")
+        if not bias:
+            raise ValueError("MotionHead: the head has a bias (bias=True)")
+        if not (0.0 <= float(drop_p) < 1.0):
+            raise ValueError("MotionHead: drop_p must be in [0, 1)")
+        if not (isinstance(head_index, int) and 0 <= head_index <= 239):
+            raise ValueError("MotionHead: head_index must be an int in [0, 239] (0 / 1 / 2: the 28 / 14 / 7 head)")
+        super().__init__(in_features, out_features, bias=True, device=device, dtype=dtype)
+        if self.weight.dtype != torch.float32:
+            raise ValueError("MotionHead: fp32 parameters only")
+        self.maxpool, self.head_index, self.drop_p, self.drop_seed = bool(maxpool), head_index, float(drop_p), 0
+
+    def forward(self, x, drop_seed=None):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.in_features):
+            raise ValueError("MotionHead: x must be an fp32 CUDA/HIP tensor [n, %d, H, W]" % self.in_features)
+        if self.maxpool and (x.shape[2] < 3 or x.shape[3] < 3):
+            raise ValueError("MotionHead: maxpool needs a map of 3 x 3 or more")
+        if self.training and self.drop_p > 0.0:
+            if drop_seed is None:
+                self.drop_seed += 1
+                drop_seed = self.drop_seed
+            drop = (int(drop_seed), self.drop_p)
+        else:
+            drop = (0, 0.0)
+        wants_grad = torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad or self.bias.requires_grad)
+        if drop == (0, 0.0) and not wants_grad:
+            return runtime.head(x.permute(0, 2, 3, 1).contiguous(), self.weight.detach(), self.bias.detach(), self.maxpool)
+        return _MotionHeadFn.apply(self, x, drop, self.weight, self.bias)
+
+    def extra_repr(self):
+        return super().extra_repr() + ", maxpool=%s, head_index=%d, drop_p=%g" % (self.maxpool, self.head_index, self.drop_p)
+
+
 class BNInception_OFF(nn.Module):
     """Drop-in for the reference class of the same name, OFF part on liboffk.
 

@@ -956,6 +956,74 @@ def head(x, fc_w, fc_b, maxpool, x_coff=0, c=None, out=None):
     return out
 
 
+# ---- training side of one classifier head (offk_head_train / offk_head_backward; csrc/head_bwd.hip) ----
+def _fc_param(t, name, numel):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+        raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
+    return t
+
+
+def head_backward_plan(n_img, c, num_classes):
+    """offk_head_backward_plan: (scratch_bytes, chunks) of one head's weight and bias gradient -- host code, a function of these integers
+    only.  The chunks hold ceil(n_img / chunks) images each, the last one what is left."""
+    lib = _lib.load()
+    s, ch = ctypes.c_size_t(0), ctypes.c_int(0)
+    _lib.check(lib.offk_head_backward_plan(int(n_img), int(c), int(num_classes), ctypes.byref(s), ctypes.byref(ch)))
+    return s.value, ch.value
+
+
+def head_train(x, fc_w, fc_b, maxpool, head_index, drop=(0, 0.0), x_coff=0, c=None, z=None, out=None):
+    """(out, z) of one head in training arithmetic: z = pooled * keep * scale [n, c], out = z . fc_w^T + fc_b [n, classes].  x: [n, H, W, Xs]
+    fp32 CUDA, channels [x_coff, x_coff + c); fc_w [classes, c] and fc_b [classes] are read in place; drop = (seed, p), the mask is
+    synth.head_dropout_keep(seed, head_index, n, c, p); (0, 0.0) is eval arithmetic.  z is what head_backward reads."""
+    lib = _lib.load()
+    _nhwc(x, "x")
+    n, H, W, xs = x.shape
+    C = xs - x_coff if c is None else int(c)
+    ncls = fc_w.shape[0]
+    _fc_param(fc_w, "fc_w", ncls * C), _fc_param(fc_b, "fc_b", ncls)
+    z = _given(z, (n, C), "z", x.device)
+    out = _given(out, (n, ncls), "out", x.device)
+    seed, p = drop
+    _lib.check(lib.offk_head_train(_stream(x.device), _ptr(x), xs, x_coff, n, H, W, C, int(bool(maxpool)), _ptr(fc_w), _ptr(fc_b), ncls,
+                                   int(head_index), int(seed), float(p), _ptr(z), _ptr(out)))
+    return out, z
+
+
+def head_backward(g, x, fc_w, z, maxpool, head_index, drop=(0, 0.0), x_coff=0, c=None, dx=None, dx_coff=0, accumulate_dx=False, dw=None,
+                  db=None, accumulate_w=False, scratch=None, want_dx=True, want_dw=True, want_db=True):
+    """(dx, dw, db) of one head; g: [n, classes] = d loss / d out, x / fc_w / z / drop as in head_train (z: what it returned).  dx comes back
+    as [n, H, W, c] (or channels [dx_coff, dx_coff + c) of the given dx are written, added to with accumulate_dx); dw [classes, c] and
+    db [classes]: e.g. the parameters' .grad, written in place (accumulate_w: added to).  want_* = False: that gradient is not launched
+    and comes back None.  scratch: the caller's uint8 buffer of exactly head_backward_plan's scratch_bytes."""
+    lib = _lib.load()
+    _nhwc(x, "x")
+    n, H, W, xs = x.shape
+    C = xs - x_coff if c is None else int(c)
+    ncls = fc_w.shape[0]
+    _fc_param(fc_w, "fc_w", ncls * C), _fc_param(g, "g", n * ncls), _fc_param(z, "z", n * C)
+    if (accumulate_dx and want_dx and dx is None) or (accumulate_w and ((want_dw and dw is None) or (want_db and db is None))):
+        raise ValueError("accumulate needs the tensors to add to")
+    if want_dx:
+        if dx is None:
+            dx = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device)
+        _nhwc(dx, "dx")
+        if tuple(dx.shape[:3]) != (n, H, W):
+            raise ValueError("dx must agree with x in [n, H, W]")
+    else:
+        dx = None
+    dw = (torch.empty(ncls, C, dtype=torch.float32, device=x.device) if dw is None else _fc_param(dw, "dw", ncls * C)) if want_dw else None
+    db = (torch.empty(ncls, dtype=torch.float32, device=x.device) if db is None else _fc_param(db, "db", ncls)) if want_db else None
+    nbytes = head_backward_plan(n, C, ncls)[0] if (want_dw or want_db) else 0
+    scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
+    seed, p = drop
+    _lib.check(lib.offk_head_backward(_stream(x.device), _ptr(g), _ptr(x), xs, x_coff, n, H, W, C, int(bool(maxpool)), _ptr(fc_w), ncls, _ptr(z),
+                                      int(head_index), int(seed), float(p), _ptr(dx), dx.shape[-1] if dx is not None else 0, dx_coff,
+                                      int(bool(accumulate_dx)), _ptr(dw), _ptr(db), int(bool(accumulate_w)),
+                                      _ptr(scratch) if nbytes else ctypes.c_void_p(0), scratch.numel()))
+    return dx, dw, db
+
+
 def segment_consensus(x, batch, out=None):
     lib = _lib.load()
     T = x.shape[0] // batch

@@ -143,6 +143,24 @@ def dropout_keep(seed, site_index, pairs, H, p):
     return np.ascontiguousarray(keep.reshape(pairs, H, H, spec.DOWN_CH).transpose(0, 3, 1, 2))
 
 
+HEAD_DROP_STREAM0 = 16                 # the heads' dropout streams sit behind the units' nine: stream index 16 + head_index
+
+
+def head_dropout_keep(seed, head_index, n_img, C, p):
+    """Keep-mask [n_img, C] (bool) of the training-mode nn.Dropout on a head's pooled vector (RGB_OFF.py:785, 791, 845): head_index
+    0 / 1 / 2 = the 28 / 14 / 7 head.  Stream (seed, 16 + head_index); draw n * (C / 4) + c / 4 serves a channel quad, channel c of the
+    quad uses bits [16 (c % 4), 16 (c % 4) + 16), kept iff the field >= dropout_threshold(p).  csrc/head_bwd.hip evaluates the same
+    integer function."""
+    if C % 4:
+        raise ValueError("C must be a multiple of 4")
+    x = raw_u64(dropout_stream(seed, HEAD_DROP_STREAM0 + int(head_index)), 0, n_img * (C // 4)).reshape(n_img, C // 4)
+    thr = np.uint64(dropout_threshold(p))
+    keep = np.empty((n_img, C // 4, 4), dtype=bool)
+    for c in range(4):
+        keep[..., c] = ((x >> np.uint64(16 * c)) & np.uint64(0xFFFF)) >= thr
+    return keep.reshape(n_img, C)
+
+
 # ---- a CPU model of the split-fp32 arithmetic and its worst-case operands (tests/test_split_contract.py, tests/test_gpu_split.py) ----
 # The kernels cut every fp32 operand into three bf16 planes by TRUNCATION (h = the upper 16 bits of the word, the remainder is exact in fp32,
 # cut again; csrc/chain_split.hip cut4, pw_tdiff_split.hip, wino_gemm_split.hip, wino_mid.hip) and form six of the nine plane products.  For
