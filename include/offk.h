@@ -352,6 +352,39 @@ int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int
                                 void* scratch, size_t scratch_bytes);
 int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
                               size_t* weight_scratch_bytes, int* weight_chunks);
+/* K4b's weight / bias gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, ABI v10; csrc/conv_wgrad_split.hip).
+ * offk_conv2d_backward_weight_split has offk_conv2d_backward_weight's argument list, shapes, conventions and refusals word for word (its own
+ * name in offk_last_error(NULL); the scratch is sized by offk_conv2d_backward_plan_split) and computes the same dw and db.  An opt-in entry:
+ * nothing in the library calls it on its own.
+ *
+ * Arithmetic: g and in(x) (the ReLU comes before the cut) are cut by truncation into three bf16 planes h, m, l (the upper 16 bits of the
+ * word, of the exact remainder, and of its remainder).  K runs over POSITIONS q in steps of 32:
+ *   k = 1: the pixels, q = (img * H + h) * W + w, PP = H * W positions per image, images back to back.
+ *   k = 3: pitch = 8 * ceil((W + 1) / 8) positions per row (the W pixels, then pitch - W >= 1 zeros), PP = (H + 1) * pitch positions per image
+ *          (its H rows, then one row of zeros), q = img * PP + h * pitch + w; every position outside [0, n_img * PP) is a zero.  Tap (kh, kw)
+ *          multiplies g at q with x at q + (kh - 1) * pitch + (kw - 1).
+ * Chunk c holds the positions [img_b * PP, img_e * PP) of its whole images img_b = c * ceil(n_img / weight_chunks) .. img_e (the last chunk may
+ * be shorter); its step t is the 32 positions from img_b * PP + 32 t on, g counting as zero from img_e * PP on.  Per step and tap the six
+ * products g_l x_h, g_h x_l, g_m x_m, g_m x_h, g_h x_m (into accumulator A2) and g_h x_h (into A1) are issued on v_mfma_f32_16x16x32_bf16 in
+ * this order, steps in increasing order; a chunk's partial is A1 + A2, added once; the partial slabs [chunk][Co][Ci * KH * KW] live in
+ * `scratch` and the second launch of offk_conv2d_backward_weight (the same kernel) adds them in chunk order.  No atomics, every slab element
+ * is written by exactly one thread: bit-reproducible from run to run and under graph capture.  db is an fp32 sum of g itself in a fixed
+ * order (per chunk: a thread's position quads q % 32 in {4 j .. 4 j + 3} in step order, each quad as (g0 + g1) + (g2 + g3); then j = 0 .. 7 in
+ * order; then the chunks in order): nothing is split.
+ * Contract: the three dropped products g_m x_l + g_l x_m + g_l x_l are at most (2^-21 + 2^-30) sum |g x| per element of dw, beside an fp32
+ * accumulation error: |dw - exact| <= |dropped| + A * 2^-24 * sum |g x| + 2^-24 |exact| with A = max(1, 2 c_acc), c_acc the accumulation
+ * constant of the CPU emulation of exactly this order (tests/conv_wgrad_split.py); integer operands whose planes and sums fit are exact.
+ * Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT says (+-Inf in an operand gives NaN: Inf - Inf
+ * in the cut; below 2^-109 an operand's last plane is lost).  One difference under relu_in, shared with offk_conv2d_backward_weight: the
+ * ReLU is max(x, 0) in hardware, so a NaN in x counts as 0 there, where torch's relu would keep it.
+ *
+ * offk_conv2d_backward_plan_split: pure host code, a function of the seven integers only; output pointers may be NULL.  weight_scratch_bytes
+ * = weight_chunks * (Co * Ci * KH * KW + Co) * 4.  The chunks are the split kernel's own (its tile, occupancy and minimum chunk length
+ * differ from the fp32 kernel's) under the same rules: whole images per chunk, ceil(n_img / weight_chunks) each, no empty chunk. */
+int offk_conv2d_backward_weight_split(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff,
+                                      int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
+                                      int accumulate, void* scratch, size_t scratch_bytes);
+int offk_conv2d_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes, int* weight_chunks);
 /* K4b, stride 2 (additive, ABI v10). Backward of the two stage-opening fusion convolutions (motion_conv_trans_28: 7x7 / 2 / 3, RGB_OFF.py:657;
  * motion_conv_trans_14: 5x5 / 2 / 2, RGB_OFF.py:762), exact fp32 -- with the entries above all 24 fusion convs.  The conventions are K4b's,
  * word for word (views, enqueue only, no synchronisation, no allocation, refusals with OFFK_ERR_INVALID and the entry's name before any HIP

@@ -59,6 +59,12 @@ hipError_t conv_bwd_weight_launch(const float* x, int x_cs, int x_coff, const fl
 hipError_t conv_wgrad_reduce_launch(float* slab, float* dbslab, int Co, int Ci, int KK, int chunks, float* dw, float* db, int accumulate,
                                     hipStream_t st);
 
+// ---- K4b's weight / bias gradient in split-fp32 arithmetic on the bf16 matrix pipe (conv_wgrad_split.hip): its own plan, the same slabs and reduce ----
+bool conv_wgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_floats, int* chunks);
+hipError_t conv_wgrad_split_launch(const float* x, int x_cs, int x_coff, const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Ci,
+                                   int Co, int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch, int chunks,
+                                   hipStream_t st);
+
 // ---- K4b, stride 2: backward of the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip, exact fp32); H, W = the INPUT map ----
 bool conv_s2_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int KW);
 // scratch floats of the data / weight gradient and the K chunks of the weight gradient; pure host code

@@ -390,8 +390,13 @@ class _FusionConvFn(torch.autograd.Function):
         dx = dw = db = None
         if need_w or need_b:
             FusionConv2d.weight_grad_launches += 1
-            wgrad = runtime.conv2d_s2_backward_weight if s2 else runtime.conv2d_backward_weight
-            dw, db = wgrad(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+            if s2:
+                dw, db = runtime.conv2d_s2_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+            elif mod.wgrad_arith == "fp32":
+                dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+            else:
+                dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b),
+                                                        arith=mod.wgrad_arith)
         if need_x:
             dx = (runtime.conv2d_s2_backward_data if s2 else runtime.conv2d_backward_data)(g, weight, mod.padding[0])
             if mod.relu_in:
@@ -411,15 +416,29 @@ class FusionConv2d(nn.Conv2d):
     cached across optimizer steps.  Covers what offk_conv2d_backward_* cover: kernel 1 or 3, stride 1, padding
     (k - 1) / 2, channels in multiples of 64; and what offk_conv2d_s2_backward_* cover, the two stage openers: exactly
     (kernel 7, stride 2, padding 3) and (kernel 5, stride 2, padding 2) on even maps, in_channels a multiple of 32,
-    out_channels of 64.  Anything else raises ValueError at construction."""
+    out_channels of 64.  Anything else raises ValueError at construction.
+
+    ``wgrad_arith`` ("fp32", the default: nothing changes) or "f32split": the module's weight and bias gradient run on
+    offk_conv2d_backward_weight_split -- both operands cut into three bf16 planes, six of the nine plane products on the
+    bf16 matrix pipe (include/offk.h has the bound: the dropped products are at most (2^-21 + 2^-30) sum |g x| per element,
+    beside an fp32 accumulation error; integer data stays exact), still bit-reproducible; the forward, the ReLU masks
+    and the data gradient are untouched.  Stride-1 modules only (the two stride-2 forms have no split entry: ValueError).
+    At n_img = 384 it takes the weight gradient of the 22 stride-1 convs from 3.76 to 2.66 ms (3x3 shapes 0.55 - 0.73 x the
+    fp32 entry's time, 1x1 shapes 0.79 - 1.0 x; one shape is NOT faster: 128 -> 128 1x1 on 7x7 maps, 0.036 ms in both;
+    DESIGN.md 8.4)."""
 
     weight_grad_launches = 0      # calls of offk_conv2d[_s2]_backward_weight made by all modules (a frozen layer makes none)
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
-                 padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False):
+                 padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False, wgrad_arith="fp32"):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode,
                          device=device, dtype=dtype)
         k = self.kernel_size
+        if wgrad_arith not in runtime.WGRAD_ARITHS:
+            raise ValueError("FusionConv2d: wgrad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.WGRAD_ARITHS), wgrad_arith))
+        if wgrad_arith == "f32split" and self.stride == (2, 2):
+            raise ValueError("FusionConv2d: wgrad_arith='f32split' needs stride 1 (the two stride-2 forms have no split entry)")
+        self.wgrad_arith = wgrad_arith
         if self.stride not in ((1, 1), (2, 2)) or self.dilation != (1, 1) or self.groups != 1:
             raise ValueError("FusionConv2d: dilation and groups must be 1, stride 1 (kernel 1 or 3) or 2 (kernel 7 with padding 3, "
                              "kernel 5 with padding 2)")
@@ -444,7 +463,8 @@ class FusionConv2d(nn.Conv2d):
         return _FusionConvFn.apply(self, x, res, self.weight, self.bias)
 
     def extra_repr(self):
-        return super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
+        s = super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
+        return s if self.wgrad_arith == "fp32" else s + ", wgrad_arith=%s" % self.wgrad_arith
 
 
 class _MotionHeadFn(torch.autograd.Function):

@@ -2,12 +2,15 @@
 torch's own backward of F.conv2d on the same channels-last fp32 tensors, in one process and one session.
 
     python tools/bench_fusion_bwd.py [--n-img 384] [--iters 30] [--warmup 5] [--out profiles/fusion_bwd/README.md]
+    python tools/bench_fusion_bwd.py --wgrad-arith f32split      # the split-fp32 weight gradient beside the fp32 entry and torch
 
 For each of the 13 distinct shapes of the 22 stride-1 fusion convs (spec.FUSION_CONVS): device-event time over --iters iterations after
 --warmup warm-ups of the three entries separately, torch.autograd.grad of F.conv2d (input, weight and bias gradients in one call; its
 forward runs outside the timed region), and the achieved TFLOP/s against the 157 TF fp32-matrix peak.  Prints a markdown table and the
 sums over the 22 convs, then the table of the two stride-2 convs (tools/bench_fusion_bwd_s2.py); --out
-writes the same text to a file.  Nothing here gates anything: the numbers are reported.
+writes the same text to a file.  --wgrad-arith f32split prints another table instead: per shape the fp32 entry's weight gradient, the
+split entry's (offk_conv2d_backward_weight_split, with its own plan's chunks), the unchanged data gradient and torch's backward, same
+method, same session.  Nothing here gates anything: the numbers are reported.
 """
 import argparse
 import collections
@@ -53,14 +56,63 @@ def timed(fn, iters, warmup, setup=None):
     return total / iters
 
 
+def split_table(n, iters, warmup):
+    """the weight gradient in both arithmetics beside the data gradient and torch's backward, one session"""
+    rows, tot = [], collections.Counter()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for H, ci, co, k, mult, _names in shapes():
+        pad = (k - 1) // 2
+        x = torch.randn(n, H, H, ci, device="cuda", generator=gen)
+        g = torch.randn(n, H, H, co, device="cuda", generator=gen)
+        w = torch.randn(co, ci, k, k, device="cuda", generator=gen) * 0.05
+        dbytes, wbytes, chunks = runtime.conv2d_backward_plan(n, H, H, ci, co, k)
+        sbytes, schunks = runtime.conv2d_backward_plan_split(n, H, H, ci, co, k)
+        sd, sw, ss = (torch.empty(b, dtype=torch.uint8, device="cuda") for b in (dbytes, wbytes, sbytes))
+        dx, dw, db = torch.empty_like(x), torch.empty_like(w), torch.empty(co, device="cuda")
+        t_data = timed(lambda: runtime.conv2d_backward_data(g, w, pad, dx=dx, scratch=sd), iters, warmup)
+        t_f32 = timed(lambda: runtime.conv2d_backward_weight(x, g, k, pad, dw=dw, db=db, scratch=sw), iters, warmup)
+        t_spl = timed(lambda: runtime.conv2d_backward_weight(x, g, k, pad, dw=dw, db=db, scratch=ss, arith="f32split"), iters, warmup)
+        xt = x.permute(0, 3, 1, 2).requires_grad_(True)
+        wt = w.contiguous(memory_format=torch.channels_last).requires_grad_(True)
+        bt = torch.zeros(co, device="cuda", requires_grad=True)
+        gt = g.permute(0, 3, 1, 2)
+        t_torch = timed(lambda yy: torch.autograd.grad(yy, (xt, wt, bt), gt), iters, warmup, setup=lambda: F.conv2d(xt, wt, bt, padding=pad))
+        rows.append((H, ci, co, k, mult, chunks, schunks, t_f32, t_spl, t_data, t_torch))
+        for key, t in (("f32", t_f32), ("split", t_spl), ("data", t_data), ("torch", t_torch)):
+            tot[key] += mult * t
+        del x, g, w, sd, sw, ss, dx, dw, db, xt, wt, bt, gt
+    lines = ["Weight gradient of the 22 stride-1 fusion convs in both arithmetics at n_img = %d (%s), %d iterations after %d warm-ups, device "
+             "events, one process." % (n, torch.cuda.get_device_name(0), iters, warmup), "",
+             "| map | Ci -> Co, k | convs | chunks fp32 / split | weight grad fp32 ms | weight grad f32split ms | split / fp32 | data grad ms | "
+             "data + split weight ms | torch backward ms |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for H, ci, co, k, mult, chunks, schunks, tf, ts, td, tt in rows:
+        lines.append("| %dx%d | %d -> %d, %dx%d | %d | %d / %d | %.3f | %.3f | %.2f | %.3f | %.3f | %.3f |" % (
+            H, H, ci, co, k, k, mult, chunks, schunks, tf, ts, ts / tf, td, td + ts, tt))
+    lines += ["", "Sum over the 22 convs: weight gradient fp32 %.3f ms, f32split %.3f ms; data gradient %.3f ms; backward with the fp32 weight "
+              "gradient %.3f ms, with the split one %.3f ms; torch's backward of the same convs %.3f ms." % (
+                  tot["f32"], tot["split"], tot["data"], tot["data"] + tot["f32"], tot["data"] + tot["split"], tot["torch"])]
+    slower = ["%dx%d %d -> %d %dx%d (%.3f vs %.3f ms)" % (r[0], r[0], r[1], r[2], r[3], r[3], r[8], r[7]) for r in rows if r[8] > r[7]]
+    lines.append("Shapes whose split weight gradient is slower than the fp32 entry's: %s." % ("; ".join(slower) if slower else "none"))
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-img", type=int, default=384)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--wgrad-arith", choices=runtime.WGRAD_ARITHS, default="fp32")
     a = ap.parse_args()
     n = a.n_img
+    if a.wgrad_arith == "f32split":
+        text = split_table(n, a.iters, a.warmup)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     rows, tot = [], collections.Counter()
     gen = torch.Generator(device="cuda").manual_seed(1)
     for H, ci, co, k, mult, names in shapes():
