@@ -411,6 +411,35 @@ int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, 
                                    int accumulate, void* scratch, size_t scratch_bytes);
 int offk_conv2d_s2_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
                                  size_t* weight_scratch_bytes, int* weight_chunks);
+/* K4b, stride 2: the data gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, ABI v10; csrc/conv_dgrad_s2_split.hip).
+ * offk_conv2d_s2_backward_data_split has offk_conv2d_s2_backward_data's argument list, shapes, views, forms and refusals word for word (its
+ * own name in offk_last_error(NULL); the scratch is sized by offk_conv2d_s2_backward_plan_split and must be 16-byte aligned) and computes
+ * the same dx (at n_img = 384 in 0.99 against 1.36 ms (7x7 / 2, 320 -> 64) and 0.91 against 1.18 ms (5x5 / 2, 1056 -> 128)
+ * on the fp32 entry).  An opt-in entry: nothing in the library calls it on its own.  Enqueue only: three launches on `stream` (two pre-passes and
+ * the GEMM), no allocation, no library-owned stream, capturable; a refused call makes no HIP call and writes nothing.
+ *
+ * Arithmetic (DESIGN.md 5.1's): per phase (r, s) of the input pixel the sum above is a contraction over K = (tap, co) with the conv weight
+ * in the role of `w` and g in the role of `x`.  Both are cut by truncation into three bf16 planes h, m, l (the upper 16 bits of the word,
+ * of the exact remainder, and of its remainder).  K order of phase (r, s): the taps in the fp32 entry's packing order (th major, then tw;
+ * tap (th, tw) is kernel element (kh0 + 2 th, kw0 + 2 tw), kh0 = (r + pad) & 1, and reads g at (a + (r + pad - kh0) / 2 - th, b + ... - tw)),
+ * inside a tap co in steps of 32 (Co % 64 == 0: a step never straddles a tap); a tap that leaves the map at a pixel contributes zeros.
+ * Per 32-k step the six products w_l g_h, w_h g_l, w_m g_m, w_m g_h, w_h g_m (into accumulator A2) and w_h g_h (into A1) are issued on
+ * v_mfma_f32_16x16x32_bf16 in this order, steps in increasing order; the result is A1 + A2, added once; accumulate != 0 then adds that
+ * once-rounded value to dx.  K is not split, there are no atomics and every dx element is written by exactly one thread: bit-reproducible
+ * from run to run, whatever `scratch` held before, and under graph capture.
+ * Contract: the three dropped products w_m g_l + w_l g_m + w_l g_l are at most (2^-21 + 2^-30) sum |g w| per element of dx, beside an fp32
+ * accumulation error: |dx - exact| <= |dropped| + A * 2^-24 * sum |g w| + 2^-24 |exact| with A = max(1, 2 c_acc), c_acc the accumulation
+ * constant of the CPU emulation of exactly this order (tests/conv_s2_dgrad_split.py), and one more 2^-24 |result| when accumulating; integer
+ * operands whose planes and sums fit are exact.  Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT
+ * says (+-Inf in an operand gives NaN: Inf - Inf in the cut; below 2^-109 an operand's last plane is lost).
+ *
+ * offk_conv2d_s2_backward_plan_split: pure host code, a function of the seven integers only; the output pointer may be NULL.
+ * data_scratch_bytes = round256(Co * Ci * KH * KW * 6) + round256(n_img * (H/2) * (W/2) * Co * 6): the three bf16 planes of the packed
+ * weight, then the three channels-last bf16 plane images of g, each region rounded up to 256 bytes. */
+int offk_conv2d_s2_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
+                                       const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
+                                       int accumulate, void* scratch, size_t scratch_bytes);
+int offk_conv2d_s2_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes);
 /* Override the plan offk_forward uses for one fusion conv (key = its state_dict name without
  * ".weight", e.g. "motion_conv_trans_28"); tile_cfg < 0 / splitk < 1 restore the automatic choice. */
 int offk_set_conv_plan(offk_handle* h, const char* conv_key, int tile_cfg, int splitk);

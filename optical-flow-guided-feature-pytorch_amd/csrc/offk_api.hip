@@ -2298,6 +2298,38 @@ int offk_conv2d_s2_backward_data(void* stream, const float* g, int g_cstride, in
   return OFFK_OK;
 }
 
+// ---- K4b, stride 2: the data gradient in split-fp32 arithmetic (conv_dgrad_s2_split.hip) ----
+int offk_conv2d_s2_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes) {
+  const char* who = "offk_conv2d_s2_backward_plan_split";
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t wb = 0, gb = 0;
+  if (!conv_s2_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (data_scratch_bytes) *data_scratch_bytes = wb + gb;
+  return OFFK_OK;
+}
+
+int offk_conv2d_s2_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
+                                       const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
+                                       int accumulate, void* scratch, size_t scratch_bytes) {
+  const char* who = "offk_conv2d_s2_backward_data_split";
+  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+  const long long g_rows = (long long)n_img * (H / 2) * (W / 2), dx_rows = (long long)n_img * H * W;
+  const uintptr_t g0 = reinterpret_cast<uintptr_t>(g), g1 = g0 + (size_t)g_rows * (size_t)g_cstride * sizeof(float);
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dx), d1 = d0 + (size_t)dx_rows * (size_t)dx_cstride * sizeof(float);
+  if (g0 < d1 && d0 < g1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  size_t wb = 0, gb = 0;
+  if (!conv_s2_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (scratch_bytes < wb + gb) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan_split)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch must be 16-byte aligned");
+  hipError_t e = conv_s2_dgrad_split_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0,
+                                            scratch, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
 int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
                                    int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
                                    int accumulate, void* scratch, size_t scratch_bytes) {

@@ -364,7 +364,7 @@ class OFFUnits(nn.Module):
 class _FusionConvFn(torch.autograd.Function):
     """autograd node of one ``FusionConv2d``: forward = offk_conv2d (direct fp32), backward = offk_relu_backward, then
     offk_conv2d_backward_weight (weight and bias) and offk_conv2d_backward_data -- the offk_conv2d_s2_backward_* entries for a stride-2
-    module --, each only where ``ctx.needs_input_grad`` asks.
+    module, the *_split entries where the module's wgrad_arith / dgrad_arith ask --, each only where ``ctx.needs_input_grad`` asks.
     Tensors cross the node as logical NCHW in channels-last memory; inside they are the [n, H, W, C] rows the library reads."""
 
     @staticmethod
@@ -398,7 +398,12 @@ class _FusionConvFn(torch.autograd.Function):
                 dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b),
                                                         arith=mod.wgrad_arith)
         if need_x:
-            dx = (runtime.conv2d_s2_backward_data if s2 else runtime.conv2d_backward_data)(g, weight, mod.padding[0])
+            if not s2:
+                dx = runtime.conv2d_backward_data(g, weight, mod.padding[0])
+            elif mod.dgrad_arith == "fp32":
+                dx = runtime.conv2d_s2_backward_data(g, weight, mod.padding[0])
+            else:
+                dx = runtime.conv2d_s2_backward_data(g, weight, mod.padding[0], arith=mod.dgrad_arith)
             if mod.relu_in:
                 runtime.relu_backward(dx, xr, out=dx)
             dx = dx.permute(0, 3, 1, 2)
@@ -425,12 +430,22 @@ class FusionConv2d(nn.Conv2d):
     and the data gradient are untouched.  Stride-1 modules only (the two stride-2 forms have no split entry: ValueError).
     At n_img = 384 it takes the weight gradient of the 22 stride-1 convs from 3.76 to 2.66 ms (3x3 shapes 0.55 - 0.73 x the
     fp32 entry's time, 1x1 shapes 0.79 - 1.0 x; one shape is NOT faster: 128 -> 128 1x1 on 7x7 maps, 0.036 ms in both;
-    DESIGN.md 8.4)."""
+    DESIGN.md 8.4).
+
+    ``dgrad_arith`` ("fp32", the default: nothing changes) or "f32split": the data gradient of a STRIDE-2 module runs on
+    offk_conv2d_s2_backward_data_split -- the conv weight and g cut into three bf16 planes in two pre-pass launches, six of
+    the nine plane products on the bf16 matrix pipe (include/offk.h has the K order and the bound: the dropped products are
+    at most (2^-21 + 2^-30) sum |g w| per element of dx, beside an fp32 accumulation error; integer data stays exact), still
+    bit-reproducible; the forward, the ReLU masks, dW and db are untouched.  Stride-2 modules only (the stride-1 forms
+    have no split entry: ValueError).  At n_img = 384 the entry (two pre-passes and the GEMM) takes
+    0.99 against 1.36 ms (7x7, 320 -> 64) and 0.91 against 1.18 ms (5x5, 1056 -> 128) on the fp32 entry, same session, interleaved:
+    both faster by more than the spread of three repeats."""
 
     weight_grad_launches = 0      # calls of offk_conv2d[_s2]_backward_weight made by all modules (a frozen layer makes none)
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
-                 padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False, wgrad_arith="fp32"):
+                 padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False, wgrad_arith="fp32",
+                 dgrad_arith="fp32"):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode,
                          device=device, dtype=dtype)
         k = self.kernel_size
@@ -439,6 +454,11 @@ class FusionConv2d(nn.Conv2d):
         if wgrad_arith == "f32split" and self.stride == (2, 2):
             raise ValueError("FusionConv2d: wgrad_arith='f32split' needs stride 1 (the two stride-2 forms have no split entry)")
         self.wgrad_arith = wgrad_arith
+        if dgrad_arith not in runtime.DGRAD_ARITHS:
+            raise ValueError("FusionConv2d: dgrad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.DGRAD_ARITHS), dgrad_arith))
+        if dgrad_arith == "f32split" and self.stride != (2, 2):
+            raise ValueError("FusionConv2d: dgrad_arith='f32split' needs stride 2 (the stride-1 forms have no split entry)")
+        self.dgrad_arith = dgrad_arith
         if self.stride not in ((1, 1), (2, 2)) or self.dilation != (1, 1) or self.groups != 1:
             raise ValueError("FusionConv2d: dilation and groups must be 1, stride 1 (kernel 1 or 3) or 2 (kernel 7 with padding 3, "
                              "kernel 5 with padding 2)")
@@ -464,7 +484,8 @@ class FusionConv2d(nn.Conv2d):
 
     def extra_repr(self):
         s = super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
-        return s if self.wgrad_arith == "fp32" else s + ", wgrad_arith=%s" % self.wgrad_arith
+        s = s if self.wgrad_arith == "fp32" else s + ", wgrad_arith=%s" % self.wgrad_arith
+        return s if self.dgrad_arith == "fp32" else s + ", dgrad_arith=%s" % self.dgrad_arith
 
 
 class _MotionHeadFn(torch.autograd.Function):
