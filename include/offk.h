@@ -296,7 +296,10 @@ int offk_off_units_fused_cl(offk_handle* h, void* stream, int feat_dtype, const 
  * 833-841): y = post( pre(conv(in(x)) + bias) + res ).  x,y,res are channel-sliced views
  * (ptr, channels-per-pixel stride, first channel).  w is in the library's K order
  * [Co][Ci/32][KH*KW][32] (see offk_pack_conv_weight).  Requires Ci % 32 == 0, Co % 64 == 0,
- * strides/offsets % 4 == 0.  Tile shape and K-split are chosen automatically. */
+ * strides/offsets % 4 == 0.  Tile shape and K-split are chosen automatically.
+ * Non-finite values (tests/test_gpu_train_ranges.py): a +-Inf or NaN in x reaches its footprint in its own image, all output channels,
+ * and nothing else; in w[co, ci, kh, kw] at most every pixel of y[.., co] (a tap that leaves the map is a zero times it), in bias[co]
+ * every pixel of y[.., co]; other images / other output channels are bit-equal. */
 enum offk_conv_flags { OFFK_CONV_RELU_IN = 1, OFFK_CONV_RELU_PRE = 2, OFFK_CONV_RELU_POST = 4,
                        /* (256 was OFFK_CONV_WINO7_FUSED in ABI v8: an experiment that lost, out of the library since ABI v9) */ };
 int offk_conv2d(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int Ci,
@@ -341,7 +344,21 @@ int offk_pack_conv_weight(void* stream, const float* w_oihw, int Co, int Ci, int
  * (+ [chunk][Co] for db) live in `scratch` and a second launch adds them in chunk order: bit-reproducible.
  *
  * offk_conv2d_backward_plan: pure host code (no GPU needed): the scratch bytes of the two entries above and the number of K chunks.  A function
- * of these seven integers only -- not of the device, the stream or the environment.  Output pointers may be NULL. */
+ * of these seven integers only -- not of the device, the stream or the environment.  Output pointers may be NULL.
+ *
+ * Range and non-finite values (these entries, the stride-2 ones and the heads' below; tests/test_gpu_scale_equivariance.py,
+ * tests/test_gpu_train_ranges.py).  The sums are fp32 +, x and fma in a fixed order with no constant that is not an operand, so multiplying an
+ * operand by 2^a multiplies the result by exactly 2^a, bit for bit, as long as no term or sum leaves fp32's normal range.  fp32 subnormal
+ * operands are kept, not flushed (hipcc's default keeps fp32 denormals and v_mfma_f32_16x16x4_f32 honours them).  A +-Inf or NaN in an
+ * operand comes out non-finite in every output element whose sum it enters (0 * Inf = NaN) and leaves every other image (dx), every other
+ * input channel (dw under a value in x) and every other output channel (a value in g) finite and bit-equal.  INSIDE those limits a kernel
+ * that removes a term by zeroing one operand turns 0 * Inf into NaN where the value does not belong:
+ *   offk_relu_backward selects: dy reaches its own element where y > 0, nothing else; y = NaN or -Inf gives exactly 0, y = +Inf passes dy.
+ *   offk_conv2d_backward_data: a value in g reaches exactly the pixels of its footprint; a value in w[co,ci,kh,kw] makes EVERY pixel of
+ *   dx[.., ci] non-finite, in every image (k = 3: the taps that leave the map multiply it by a zero).
+ *   offk_conv2d_backward_weight (and _split): k = 3: a value in x[.., ci] makes ALL NINE taps of dw[:, ci] non-finite (g is zero on the ring
+ *   around the pixel), a value in g[.., co] all nine taps of dw[co, :] (x is zero on the ring) and db[co]; k = 1: exactly the elements reached.
+ *   relu_in: max(x, 0) in hardware -- x = NaN and x = -Inf count as 0, x = +Inf as above. */
 int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_coff, const float* y, int y_cstride, int y_coff, int rows, int C,
                        float* g, int g_cstride, int g_coff, int accumulate);
 int offk_conv2d_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
@@ -376,7 +393,10 @@ int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, i
  * constant of the CPU emulation of exactly this order (tests/conv_wgrad_split.py); integer operands whose planes and sums fit are exact.
  * Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT says (+-Inf in an operand gives NaN: Inf - Inf
  * in the cut; below 2^-109 an operand's last plane is lost).  One difference under relu_in, shared with offk_conv2d_backward_weight: the
- * ReLU is max(x, 0) in hardware, so a NaN in x counts as 0 there, where torch's relu would keep it.
+ * ReLU is max(x, 0) in hardware, so a NaN in x counts as 0 there, where torch's relu would keep it.  Which elements a non-finite value
+ * reaches is offk_conv2d_backward_weight's paragraph above, word for word (the zero columns and the zero row of the K layout play the
+ * ring's part: all nine taps of dw[:, ci] or dw[co, :]); dw holds NaN there, db -- an fp32 sum of g itself -- +-Inf or NaN.  Scaling
+ * an operand by 2^a scales dw and db by exactly 2^a (the cut masks significand bits), operands and planes in the normal range.
  *
  * offk_conv2d_backward_plan_split: pure host code, a function of the seven integers only; output pointers may be NULL.  weight_scratch_bytes
  * = weight_chunks * (Co * Ci * KH * KW + Co) * 4.  The chunks are the split kernel's own (its tile, occupancy and minimum chunk length
@@ -401,6 +421,18 @@ int offk_conv2d_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int
  * offk_conv2d_s2_backward_weight: dw[co,ci,kh,kw] (+)= sum_{n,oh,ow} g[n,oh,ow,co] * in(x)[n, 2 oh + kh - pad, 2 ow + kw - pad, ci];
  * db[co] (+)= sum g (db may be NULL).  Split over K into weight_chunks chunks of ceil(n_img / weight_chunks) whole images; partial slabs
  * [chunk][Co][Ci * KH * KW] (+ [chunk][Co]) in `scratch`, added in chunk order by the stride-1 entry's reduce: bit-reproducible.
+ *
+ * Range and non-finite values: the paragraph at the stride-1 entries holds (exact power-of-two scaling, subnormals kept, a non-finite
+ * value reaches every sum it enters and no other image / input channel / output channel).  Inside those limits:
+ *   offk_conv2d_s2_backward_data (and _split, which gives NaN): a value in g reaches exactly the pixels of its footprint; a value in
+ *   w[co,ci,kh,kw] makes every pixel of ITS PHASE of dx[.., ci] non-finite -- rows of parity (kh + pad) & 1, columns of parity (kw + pad) & 1,
+ *   every image (a tap that leaves the map is a zero times the weight).
+ *   offk_conv2d_s2_backward_weight: a value in x[n, R, C, ci] makes dw[:, ci, kh, kw] non-finite for the kernel rows kh that read row R
+ *   (R = 2 oh + kh - pad, 0 <= oh < H / 2) and in them for EVERY kw of C's parity ((C + pad - kw) even), also where 2 ow + kw - pad = C has no
+ *   ow inside the map: the kernel removes the taps that wrap into the neighbouring row by zeroing its g operand, and 0 * Inf is NaN.  A
+ *   value in g[n, oh, ow, co] makes dw[co, :, kh, kw] non-finite for EVERY kernel row kh (a row outside the map is a row of zeros times it)
+ *   and the kw whose x column 2 ow + kw - pad lies inside the map -- the wrapped column taps are removed by a select on g and stay
+ *   clean, bit for bit -- and db[co].  relu_in: x = NaN and x = -Inf count as 0.
  *
  * offk_conv2d_s2_backward_plan: pure host code, a function of these seven integers only.  Output pointers may be NULL. */
 int offk_conv2d_s2_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
@@ -431,7 +463,9 @@ int offk_conv2d_s2_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH
  * accumulation error: |dx - exact| <= |dropped| + A * 2^-24 * sum |g w| + 2^-24 |exact| with A = max(1, 2 c_acc), c_acc the accumulation
  * constant of the CPU emulation of exactly this order (tests/conv_s2_dgrad_split.py), and one more 2^-24 |result| when accumulating; integer
  * operands whose planes and sums fit are exact.  Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT
- * says (+-Inf in an operand gives NaN: Inf - Inf in the cut; below 2^-109 an operand's last plane is lost).
+ * says (+-Inf in an operand gives NaN: Inf - Inf in the cut; below 2^-109 an operand's last plane is lost).  The elements a non-finite
+ * value reaches are offk_conv2d_s2_backward_data's (the paragraph above: the footprint for g, the whole phase of dx[.., ci] for w); the ci
+ * tiles behind Ci that a block stages are never stored.  Scaling g or w by 2^a scales dx by exactly 2^a.
  *
  * offk_conv2d_s2_backward_plan_split: pure host code, a function of the seven integers only; the output pointer may be NULL.
  * data_scratch_bytes = round256(Co * Ci * KH * KW * 6) + round256(n_img * (H/2) * (W/2) * Co * 6): the three bf16 planes of the packed
@@ -561,6 +595,12 @@ int offk_head(void* stream, const float* x, int x_cstride, int x_coff, int n_img
  *   dw[o][c] (+)= sum_n g[n][o] z[n][c], db[o] (+)= sum_n g[n][o]  (accumulate_w), split over n_img into `chunks` chunks of
  *   ceil(n_img / chunks) whole images (the last one may be shorter); the partial slabs [chunk][num_classes][C] + [chunk][num_classes] live
  *   in `scratch` and a second launch adds them in chunk order: bit-reproducible whatever the scratch held.
+ * Range and non-finite values (tests/test_gpu_scale_equivariance.py, tests/test_gpu_train_ranges.py): x and fc_b, fc_w and fc_b, or g times
+ * 2^a scale every output by exactly 2^(a degree) and the max-pool picks the same cells; fp32 subnormals are kept, and where a result
+ * is itself subnormal (z of a subnormal x) each rounded operation may add half of 2^-149 beside its relative error: the format's.  Nothing here zeroes an
+ * operand to remove a term, so a +-Inf or NaN comes out non-finite in exactly the elements IEEE arithmetic on the formulas above gives
+ * (a dropped channel's keep * scale = 0 turns an Inf into NaN), every other element bit-equal -- except under the max-pool, where a NaN
+ * or -Inf in x is not there (fmaxf drops the NaN, -Inf is never a maximum) and a +Inf in x moves the route of dx without entering it.
  *
  * offk_head_backward_plan: pure host code (no GPU needed), a function of these three integers only.  Output pointers may be NULL. */
 int offk_head_train(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int H, int W, int C, int maxpool, const float* fc_w,
@@ -609,7 +649,15 @@ typedef struct offk_grad_view {
 size_t offk_train_workspace_bytes(const offk_handle* h);
 
 /* offk_off_units in training mode: like offk_off_units, with the dropout above applied to S.  Leaves
- * G_<site> / D_<site> in the workspace for the backward. */
+ * G_<site> / D_<site> in the workspace for the backward.
+ * Non-finite values (this entry and offk_off_units_train_split; tests/test_gpu_train_ranges.py).  The ReLU of G is a hardware max: a
+ * pre-activation that is NaN or -Inf gives exactly 0, +Inf stays.  A +-Inf or NaN in x[n, c, y, x] makes D of that pixel non-finite in all
+ * 32 channels (NaN in split arithmetic) and G of that pixel +Inf or 0 in each of its 128 channels; K2 carries the D part into the 3 x 3
+ * neighbourhood of the pixel, all 32 spatial channels of the pair the frame is the spatial row of (kept or dropped: 0 * NaN is NaN), and
+ * the G part at most into the 128 temporal channels of that pixel in the pairs of its clip that hold the frame.  A value in Wg[o, c] or
+ * bg[o] makes column o of G +Inf or 0 (bg[o] = +Inf: +Inf everywhere; the bias is added in fp32 in split arithmetic too) and at most
+ * temporal channel o of the unit output non-finite; a value in Wd[j, c] or bd[j] makes column j of D non-finite everywhere (NaN for Wd in
+ * split arithmetic) and at most spatial channel j of the unit output.  Every other pixel, column and site is bit-equal. */
 int offk_off_units_train(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES], void* workspace,
                          uint64_t drop_seed, double drop_p);
 
@@ -624,7 +672,14 @@ int offk_unit_grad_slot(const offk_handle* h, const char* key, size_t* offset_fl
  * gm[s]: gradient w.r.t. motion_<site>.  grads: the flat buffer above; accumulate != 0 adds to it (the
  * reference calls backward three times per step, train_off.py:141-143), otherwise it is overwritten.
  * Every reduction has a fixed order: results are bit-reproducible.  NCHW feature maps only (channels-last maps:
- * offk_off_units_backward_cl below). */
+ * offk_off_units_backward_cl below).
+ * Non-finite values (this entry and offk_off_units_backward_split, whose two weight matrices then hold NaN; tests/test_gpu_train_ranges.py).
+ * The parameter gradients read the maps, g and the forward's G (as a mask: a select), not Wg, Wd or the biases.  A +-Inf or NaN in g at
+ * spatial channel j of a site makes exactly down.weight[j, :], down.bias[j] and the depthwise conv's weight[j] and bias[j] of that site
+ * non-finite; at temporal channel o, where the forward's G is positive in one of the pair's two frames, exactly gen.weight[o, :] and
+ * gen.bias[o]; in x[n, c, y, x] (seen by forward and backward alike) exactly gen.weight[:, c], down.weight[:, c] (a frame of the slice)
+ * and the depthwise weight of that site, whose other gradients stay finite (the pixel's ReLU mask changed).  Every other element, and
+ * every other site, is bit-equal to the run without the value. */
 int offk_off_units_backward(offk_handle* h, void* stream, const float* const feats[OFFK_NUM_SITES],
                             const offk_grad_view gm[OFFK_NUM_SITES], void* workspace, uint64_t drop_seed, double drop_p,
                             float* grads, int accumulate);
@@ -725,6 +780,10 @@ int offk_off_units_backward_cl(offk_handle* h, void* stream, int feat_dtype, con
  * backward replayed from a captured graph does not pass through the library and sets none (as for offk_stage_tensors) -- run
  * one backward through the library first.  The library cannot see how large `workspace` is: it must be the train workspace
  * (offk_train_workspace_bytes), the one the backward wrote.  All nine pointers NULL: OFFK_OK, nothing enqueued.
+ * Range and non-finite values (this entry and its _split form, which gives NaN; tests/test_gpu_train_ranges.py): g times 2^a scales dX by
+ * exactly 2^a; a +-Inf or NaN in dGpre or dD reaches all channels of its own pixel (dD: of the frame whose row it is) and no other
+ * element; in Wg[o, c] channel c of every pixel of every frame; in Wd[j, c] channel c of every frame too -- also of the frames outside
+ * the slice, whose dD part is a row of zeros times it (0 * Inf = NaN).  Every other element, every other site, is bit-equal.
  * Per-launch trace: "units:feature-map gradient (dX, NCHW)" / "... (dX, NHWC)". */
 int offk_off_units_backward_feats(offk_handle* h, void* stream, void* workspace,
                                   float* const dfeats[OFFK_NUM_SITES], int layout, int accumulate);
