@@ -171,7 +171,10 @@ class _OFFUnitsFn(torch.autograd.Function):
         if mod._generation != ctx.gen:
             # another forward has overwritten G / D since: recompute them (K1 + K2 only, same seed => same mask)
             mod._run_units(rt, feats, ctx.drop)
-        bufs = [g.permute(0, 2, 3, 1).contiguous() for g in (g28, g14, g7)]      # channels-last rows
+            # G / D are this call's again: a further backward through the same graph (train_off.py:144-146 makes three, two of them
+            # with retain_graph=True) finds them and does not recompute a second and a third time
+            ctx.gen = mod._generation
+        bufs =[g.permute(0, 2, 3, 1).contiguous() for g in (g28, g14, g7)]      # channels-last rows
         views = [(bufs[0], 0), (bufs[0], 160)] + [(bufs[1], 160 * k) for k in range(5)] + [(bufs[2], 0), (bufs[2], 160)]
         # (the default arithmetic makes today's call, argument for argument)
         arith = {} if mod.wgrad_arith == "fp32" else {"arith": mod.wgrad_arith}
@@ -220,7 +223,8 @@ class OFFUnits(nn.Module):
     (cat(motion_3a, motion_3b) [P,320,28,28], cat(motion_3c..4d) [P,800,14,14], cat(motion_5a, motion_5b)
     [P,320,7,7]; RGB_OFF.py:656, :760, :832), channels-last in memory.  The fusion convolutions that
     follow -- the two stride-2 stage openers included -- can be built from ``FusionConv2d`` (below: forward and backward on
-    liboffk, one conv per module); the heads are ordinary PyTorch modules in training.
+    liboffk, one conv per module) and the three heads from ``MotionHead`` (below: pooling, dropout and the Linear, forward and
+    backward on liboffk), so the whole branch train_off.py un-freezes trains on the library.
 
     The nine maps may be fp32, or bf16 / fp16 of one dtype -- what a frozen backbone under ``torch.autocast`` emits.
     16-bit maps are neither cast nor copied: the kernels read them as they are (offk_off_units_train_typed,

@@ -75,54 +75,100 @@ def off_unit(x, w, site, batch, length, variant, slice_mode, drop=None, gen_mask
     return torch.cat((s, t), dim=1)                                        # :616
 
 
-def fusion_28(f28, w):
-    """RGB_OFF.py:655-685.  Note the 28a branch takes the PRE-ReLU 7x7 output (:665)."""
+FUSION_RELUS = ("x0", "c1_28a", "c2_28a", "s28a", "c1_28b", "c2_28b", "s28b", "c1_28c", "c2_28c", "s28c",
+                "x1", "c1_14a", "c2_14a", "s14a", "c1_14b", "c2_14b", "c3_14b", "s14b", "x2", "c1_7", "c2_7")
+
+
+class Pattern:
+    """Gradient tests only -- the activation pattern of one forward through the fusion stages and the heads, what ``gen_mask`` is to
+    the units.  ``masks``: name -> 0/1 tensor for any of FUSION_RELUS, each named after the tensor the ReLU produces; that ReLU
+    computes ``z * mask`` instead of ``torch.relu(z)`` (a name left out keeps its own decision).  ``pool_idx``: the 28-head's
+    MaxPool2d gathers at these flat h * W + w indices ([P,256,7,7] int64, ``F.max_pool2d(..., return_indices=True)``'s) instead of
+    choosing.  ``head_drop``: key -> the multiplier nn.Dropout (:785, :791, :845) would use in training mode, keep / (1 - p) as
+    [P,C], applied to the pooled vector in front of the Linear.  ``record=True``: ``pre`` collects every pre-activation under its
+    ReLU's name, the 28-head's map as "pool_in" and the values its windows picked as "pool".  Both sides of a gradient
+    comparison then differentiate the same piecewise-linear function (off_unit's docstring has the why)."""
+
+    def __init__(self, masks=None, pool_idx=None, head_drop=None, record=False):
+        self.masks = dict(masks or {})
+        unknown = sorted(set(self.masks) - set(FUSION_RELUS))
+        if unknown:
+            raise KeyError("no such fusion ReLU: %s" % ", ".join(unknown))
+        self.pool_idx, self.head_drop = pool_idx, dict(head_drop or {})
+        self.pre = {} if record else None
+
+    def note(self, name, z):
+        if self.pre is not None:
+            self.pre[name] = z
+
+
+def _relu(pat, name, z):
+    if pat is None:
+        return torch.relu(z)
+    pat.note(name, z)
+    m = pat.masks.get(name)
+    return torch.relu(z) if m is None else z * m
+
+
+def fusion_28(f28, w, pat=None):
+    """RGB_OFF.py:655-685.  Note the 28a branch takes the PRE-ReLU 7x7 output (:665).  ``pat``: a Pattern (gradient tests)."""
     x0 = _conv(f28, w, "motion_conv_trans_28", stride=2, pad=3)            # :657
-    a = torch.relu(x0)                                                     # :658
-    a = torch.relu(_conv(a, w, "motion_conv1_trans_28a"))                  # :659-660
-    a = torch.relu(_conv(a, w, "motion_conv2_trans_28a", pad=1))           # :661-662
+    a = _relu(pat, "x0", x0)                                               # :658
+    a = _relu(pat, "c1_28a", _conv(a, w, "motion_conv1_trans_28a"))        # :659-660
+    a = _relu(pat, "c2_28a", _conv(a, w, "motion_conv2_trans_28a", pad=1))  # :661-662
     a = _conv(a, w, "motion_conv3_trans_28a")                              # :663
-    s = torch.relu(a + _conv(x0, w, "motion_conv_branch_28a"))             # :665-667
+    s = _relu(pat, "s28a", a + _conv(x0, w, "motion_conv_branch_28a"))     # :665-667
     for blk in ("28b", "28c"):                                             # :670-685
-        a = torch.relu(_conv(s, w, "motion_conv1_trans_" + blk))
-        a = torch.relu(_conv(a, w, "motion_conv2_trans_" + blk, pad=1))
+        a = _relu(pat, "c1_" + blk, _conv(s, w, "motion_conv1_trans_" + blk))
+        a = _relu(pat, "c2_" + blk, _conv(a, w, "motion_conv2_trans_" + blk, pad=1))
         a = _conv(a, w, "motion_conv3_trans_" + blk)
-        s = torch.relu(a + s)
+        s = _relu(pat, "s" + blk, a + s)
     return s                                                               # motion_sum_28c
 
 
-def fusion_14(f14, w):
-    """RGB_OFF.py:759-780."""
-    x1 = torch.relu(_conv(f14, w, "motion_conv_trans_14", stride=2, pad=2))   # :762-763
-    a = torch.relu(_conv(x1, w, "motion_conv1_trans_14a"))                    # :764-765
-    a = torch.relu(_conv(a, w, "motion_conv2_trans_14a", pad=1))              # :766-767
-    a = _conv(a, w, "motion_conv3_trans_14a")                                 # :768
-    s = torch.relu(a + _conv(x1, w, "motion_conv_expand_trans_14a"))          # :769-771
-    a = torch.relu(_conv(s, w, "motion_conv1_trans_14b"))                     # :773-774
-    a = torch.relu(_conv(a, w, "motion_conv2_trans_14b", pad=1))              # :775-776
-    a = torch.relu(_conv(a, w, "motion_conv3_trans_14b", pad=1))              # :777-778 (3x3, own ReLU)
-    return torch.relu(s + a)                                                  # :779-780  motion_sum_14b
+def fusion_14(f14, w, pat=None):
+    """RGB_OFF.py:759-780.  ``pat``: a Pattern (gradient tests)."""
+    x1 = _relu(pat, "x1", _conv(f14, w, "motion_conv_trans_14", stride=2, pad=2))   # :762-763
+    a = _relu(pat, "c1_14a", _conv(x1, w, "motion_conv1_trans_14a"))                # :764-765
+    a = _relu(pat, "c2_14a", _conv(a, w, "motion_conv2_trans_14a", pad=1))          # :766-767
+    a = _conv(a, w, "motion_conv3_trans_14a")                                       # :768
+    s = _relu(pat, "s14a", a + _conv(x1, w, "motion_conv_expand_trans_14a"))        # :769-771
+    a = _relu(pat, "c1_14b", _conv(s, w, "motion_conv1_trans_14b"))                 # :773-774
+    a = _relu(pat, "c2_14b", _conv(a, w, "motion_conv2_trans_14b", pad=1))          # :775-776
+    a = _relu(pat, "c3_14b", _conv(a, w, "motion_conv3_trans_14b", pad=1))          # :777-778 (3x3, own ReLU)
+    return _relu(pat, "s14b", s + a)                                                # :779-780  motion_sum_14b
 
 
-def fusion_7(f7, w):
-    """RGB_OFF.py:831-841 -- no ReLU after the final add."""
-    x2 = torch.relu(_conv(f7, w, "motion_conv_trans", pad=1))                 # :833-834
-    a = torch.relu(_conv(x2, w, "motion_conv1_trans"))                        # :835-836
-    a = torch.relu(_conv(a, w, "motion_conv2_trans", pad=1))                  # :837-838
+def fusion_7(f7, w, pat=None):
+    """RGB_OFF.py:831-841 -- no ReLU after the final add.  ``pat``: a Pattern (gradient tests)."""
+    x2 = _relu(pat, "x2", _conv(f7, w, "motion_conv_trans", pad=1))           # :833-834
+    a = _relu(pat, "c1_7", _conv(x2, w, "motion_conv1_trans"))                # :835-836
+    a = _relu(pat, "c2_7", _conv(a, w, "motion_conv2_trans", pad=1))          # :837-838
     a = _conv(a, w, "motion_conv3_trans")                                     # :839
     return a + _conv(x2, w, "motion_conv_branch_trans")                       # :840-841
 
 
-def head(x, w, key, maxpool):
+def head(x, w, key, maxpool, pat=None):
     """RGB_OFF.py:782-787 (28), :789-793 (14), :843-847 (7).
 
     MaxPool2d(3, 2, ceil_mode=True) (:353) then AvgPool2d(7) (:262); dropout is the
     identity in eval; torch.squeeze also drops the pair axis when P == 1 (:786).
+    ``pat``: a Pattern (gradient tests) -- a given pool route, the training-mode dropout multiplier of this head.
     """
     if maxpool:
-        x = F.max_pool2d(x, 3, stride=2, ceil_mode=True)
+        if pat is not None:
+            pat.note("pool_in", x)
+        if pat is not None and pat.pool_idx is not None:
+            idx = pat.pool_idx
+            x = x.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
+        else:
+            x = F.max_pool2d(x, 3, stride=2, ceil_mode=True)
+        if pat is not None:
+            pat.note("pool", x)
     x = F.avg_pool2d(x, 7, stride=1, padding=0, ceil_mode=True, count_include_pad=True)
     x = torch.squeeze(x)
+    if pat is not None and key in pat.head_drop:
+        x = x * torch.squeeze(pat.head_drop[key])                             # :785 / :791 / :845 in train()
     return F.linear(x, w[key + ".weight"], w[key + ".bias"])
 
 
@@ -133,7 +179,7 @@ def segment_consensus(x, batch):
 
 
 def off_forward(feats, w, batch, length, variant=VARIANT_RGB, slice_mode=SLICE_FLAT,
-                consensus=None, return_stages=False, unit_drop=None, unit_gen_mask=None):
+                consensus=None, return_stages=False, unit_drop=None, unit_gen_mask=None, pattern=None, head_drop=None):
     """The whole OFF sub-network on nine injected feature maps.
 
     feats: list of nine [N,C,H,H] fp32 tensors (inception_{3a..5b}_output_out).
@@ -141,23 +187,30 @@ def off_forward(feats, w, batch, length, variant=VARIANT_RGB, slice_mode=SLICE_F
     Returns (fc7, fc14, fc28), each [P,101] (or [B,101] after consensus; the
     reference applies it in Flow_OFF.py / RGB_OFF_v2.py only, ``consensus=None``
     picks that default).  With return_stages also a dict of intermediates.
+    ``pattern``: a Pattern for the fusion stages and the 28-head's pool (gradient tests; the units take theirs through
+    ``unit_gen_mask``); a recording one holds the pre-activations afterwards.  ``head_drop``: training mode -- three [P,C]
+    multipliers keep / (1 - p) in (fc7, fc14, fc28) order, what ``unit_drop`` is to the units.
     """
     if consensus is None:
         consensus = (variant == VARIANT_FLOW)
+    pat = pattern
+    if head_drop is not None:
+        pat = Pattern() if pat is None else pat
+        pat.head_drop = dict(zip(("fc_action_motion", "fc_action_motion_14", "fc_action_motion_28"), head_drop))
     m = {}
     for si, ((site, _c, _h), x) in enumerate(zip(SITES, feats)):
         m[site] = off_unit(x, w, site, batch, length, variant, slice_mode,
                            None if unit_drop is None else unit_drop[si],
                            None if unit_gen_mask is None else unit_gen_mask[si])
     f28 = torch.cat((m["3a"], m["3b"]), dim=1)                                      # :656
-    sum_28c = fusion_28(f28, w)
+    sum_28c = fusion_28(f28, w, pat)
     f14 = torch.cat((m["3c"], m["4a"], m["4b"], m["4c"], m["4d"], sum_28c), dim=1)  # :760
-    sum_14b = fusion_14(f14, w)
-    fc28 = head(sum_28c, w, "fc_action_motion_28", True)                            # :782-787
-    fc14 = head(sum_14b, w, "fc_action_motion_14", False)                           # :789-793
+    sum_14b = fusion_14(f14, w, pat)
+    fc28 = head(sum_28c, w, "fc_action_motion_28", True, pat)                       # :782-787
+    fc14 = head(sum_14b, w, "fc_action_motion_14", False, pat)                      # :789-793
     f7 = torch.cat((m["5a"], m["5b"], sum_14b), dim=1)                              # :832
-    s7 = fusion_7(f7, w)
-    fc7 = head(s7, w, "fc_action_motion", False)                                    # :843-847
+    s7 = fusion_7(f7, w, pat)
+    fc7 = head(s7, w, "fc_action_motion", False, pat)                               # :843-847
     if consensus:
         fc7, fc14, fc28 = (segment_consensus(v, batch) for v in (fc7, fc14, fc28))
     if return_stages:
