@@ -258,6 +258,49 @@ int offk_launch_times(offk_handle* h, char* names, size_t names_len, double* ms,
 
 /* ---- stage entry points (the same kernels offk_forward launches) ------------------ */
 
+/* Size limits of the entries below ("Size limits"; tests/test_gpu_big_slabs.py runs every strided view with its last
+ * rows past 2 GiB and past 4 GiB, tests/test_gpu_big_batch.py the units at N = 2142).  A view is (pointer, cstride, coff, rows);
+ * its byte extent is rows * cstride * 4.  "any extent": every row index times a stride is a 64-bit product in the kernels.
+ *   offk_conv2d / offk_conv2d_ex       x, y, res: any extent (x below 2^31 - 1 bytes: buffer-descriptor loader, else the pointer
+ *                                      loader; y below 0x7f000000 bytes without a residual: buffer stores, else pointer stores);
+ *                                      n_img * Ho * Wo <= 2^31 - 257 rows, else OFFK_ERR_INVALID "conv2d: bad problem size"
+ *   offk_bottleneck_chain14            x: (n_img * 196 * x_cstride - x_coff) * 4 < 2^31 - 1 bytes, else OFFK_ERR_INVALID "chain14: input
+ *                                      beyond 31-bit byte offsets"; y, res: any extent
+ *   offk_bottleneck_chain14_split      x as above and n_img * 196 * y_cstride * 4 < 0x7fffff00 bytes, else OFFK_ERR_INVALID "... input
+ *                                      and output below 2^31 bytes"; res: any extent
+ *   offk_winograd_conv3x3 / 5x5s2 / 7x7s2, offk_winograd_between / _ex     x, y, res: any extent
+ *   offk_head, offk_head_train, offk_head_backward                         x, dx: any extent; n_img * H * W and n_img * num_classes <= 2^31 - 1
+ *   offk_relu_backward                 dy, y, g: any extent
+ *   offk_conv2d_backward_data / _weight / _weight_split, offk_conv2d_s2_backward_data / _data_split / _weight
+ *                                      x, g, dx: any extent; the padded positions n_img * (H + 2) * (W + 2) (and n_img * H * W) stay
+ *                                      below 2^31 less a tile, else OFFK_ERR_INVALID "problem too large"
+ *   offk_nhwc_to_nchw                  src: any extent; n_img <= 65535
+ *   offk_sobel_tdiff                   M (m_cstride, m_coff): any extent
+ *   offk_pw_reduce, offk_off_units, offk_off_units_fused, offk_forward, offk_forward_parts (fp32 maps)
+ *                                      a map part of 0x7fffff00 bytes or more (site 3b from N = 2140 frames) moves the WHOLE launch from
+ *                                      the buffer-descriptor kernels to the pointer-loader kernels (pw_reduce_kernel<0, 0>,
+ *                                      pw_tdiff_kernel<0, 0>).  These are fp32 kernels: an OFFK_PRECISION_F32SPLIT handle computes its
+ *                                      units in exact fp32 arithmetic, not split-fp32, from that size on (same contract, other bits); handing the
+ *                                      maps over as parts below that size (offk_forward_parts) keeps the split-fp32 kernel.
+ *   offk_off_units_train, offk_off_units_backward, offk_off_units_backward_feats (fp32 maps, and their _split forms)
+ *                                      any extent: K1 / K2 as above, K2b / K1b and the dX kernel index with 64-bit products (units_bwd.hip,
+ *                                      units_dx.hip, units_wgrad_split.hip, units_fwd_split.hip, units_dx_split.hip: no buffer descriptor).
+ *                                      Run at N = 2142 (the fp32 forms).
+ *   16-bit maps, training side         offk_pw_reduce_typed, offk_off_units_typed, _train_typed, _backward_typed refuse a map of 0x7fffff00
+ *                                      bytes or more (3b from N = 4280 frames) before anything is enqueued: "16-bit feature maps of 2 GiB or
+ *                                      more are not supported (site 3b)".  Tested at B = 612.
+ *   offk_forward_typed / _cl, offk_off_units_fused_typed / _cl
+ *                                      any extent: the 16-bit and channels-last units kernels are pointer loaders with 64-bit products
+ *                                      (pw_tdiff_f16.hip, pw_tdiff_cl.hip, pw_tdiff_staged.h).  offk_forward_typed is run at B = 612 (3b as
+ *                                      bf16 / fp16 = 2.15 GB, fusion_28 3.7 GB, the Winograd V array 9.5 GB).
+ *   offk_pw_reduce_cl, offk_off_units_cl, and offk_pw_reduce / offk_off_units / offk_forward on an OFFK_FEAT_NHWC handle (fp32 maps)
+ *                                      any extent: mode 2 of pw_reduce_kernel<0, 0>, (size_t)row * cpart (pw_reduce.hip:229-234); read,
+ *                                      not run at 2 GiB by any test.
+ *   offk_create                        batch * length * 784 * 320 <= 2^31 - 1 (N <= 8559 frames), else OFFK_ERR_INVALID "offk_create:
+ *                                      batch*length too large for one call; shard the clips"
+ * offk_forward / offk_forward_parts / offk_stage_tensors are run at N = 2142 too (the Winograd V array of the 7x7 / 2 conv is 4.76 GB
+ * there: the transforms index it with 64-bit products, the batched GEMMs take one descriptor per problem). */
+
 /* K1. Replaces motion_conv_gen_<s> + motion_relu_gen_<s> on all N frames and
  * motion_spatial_down_<s> on the sliced frames (RGB_OFF.py:597-598, 609-610), stacked so
  * the map is read once.  G: [N*HW, 128] (post-ReLU), D: [P*HW, 32] channels-last. */
