@@ -448,6 +448,42 @@ int offk_conv2d_backward_weight_split(void* stream, const float* x, int x_cstrid
                                       int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
                                       int accumulate, void* scratch, size_t scratch_bytes);
 int offk_conv2d_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes, int* weight_chunks);
+/* K4b's data gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, ABI v10; csrc/conv_dgrad_split.hip).
+ * offk_conv2d_backward_data_split has offk_conv2d_backward_data's argument list, shapes, views, forms and refusals word for word (k in {1, 3}
+ * with pad (k - 1) / 2, Ci % 64 == 0 and Co % 64 == 0, strides and offsets % 4 == 0, dx may not overlap g; its own name in
+ * offk_last_error(NULL); the scratch is sized by offk_conv2d_backward_data_plan_split and must be 16-byte aligned) and computes the same dx.
+ * An opt-in entry: nothing in the library calls it on its own; DESIGN.md 8.8 has the measured times per shape and names the shapes on
+ * which it is NOT faster than the fp32 entry.  Enqueue only: three launches on `stream` (two pre-passes that cut the weight and g into
+ * planes, then the GEMM), no allocation, no library-owned stream, capturable; a refused call makes no HIP call and writes nothing.
+ *
+ * Arithmetic (DESIGN.md 5.1's): dx[n,h,w,ci] (+)= sum_{kh,kw,co} g[n, h + pad - kh, w + pad - kw, co] * w[co,ci,kh,kw] is one contraction
+ * over K = (tap, co) with the conv weight in the role of `w` and g in the role of `x`.  Both are cut by truncation into three bf16 planes
+ * h, m, l (the upper 16 bits of the word, of the exact remainder, and of its remainder).  K order: K index = tap * Co + co with
+ * tap = kh * k + kw (kh major, then kw; k = 1 is the one-tap case), inside a tap co in steps of 32 (Co % 64 == 0: a step
+ * never straddles a tap); a tap whose g pixel leaves the map -- its row or its image -- contributes zeros.  Per 32-k step the six products
+ * w_l g_h, w_h g_l, w_m g_m, w_m g_h, w_h g_m (into accumulator A2) and w_h g_h (into A1) are issued on v_mfma_f32_16x16x32_bf16 in this order,
+ * steps in increasing order; the result is A1 + A2, added once; accumulate != 0 then adds that once-rounded value to dx.  K is not split,
+ * there is no reduce launch, there are no atomics and every dx element is written by exactly one thread: bit-reproducible from run to
+ * run, whatever `scratch` held before, and under graph capture.
+ * Contract: the three dropped products w_m g_l + w_l g_m + w_l g_l are at most (2^-21 + 2^-30) sum |g w| per element of dx, beside an fp32
+ * accumulation error: |dx - exact| <= |dropped| + A * 2^-24 * sum |g w| + 2^-24 |exact| with A = max(1, 2 c_acc), c_acc the accumulation
+ * constant of the CPU emulation of exactly this order (tests/conv_dgrad_split.py), and one more 2^-24 |result| when accumulating; integer
+ * operands whose planes and sums fit are exact.  Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT
+ * says (+-Inf in an operand gives NaN: Inf - Inf in the cut; below 2^-109 an operand's last plane is lost).  The elements a non-finite
+ * value reaches are offk_conv2d_backward_data's (the footprint for g, every pixel of dx[.., ci] for w, NaN here); the ci tiles behind Ci
+ * that a block stages are never stored.  Scaling g or w by 2^a scales dx by exactly 2^a.
+ *
+ * offk_conv2d_backward_data_plan_split: pure host code, a function of the seven integers only; the output pointer may be NULL.
+ * data_scratch_bytes = round256(Co * Ci * KH * KW * 6) + round256(n_img * H * W * Co * 6): the three bf16 planes of the packed weight
+ * ([tap][32-co step][16-ci tile][plane][lane] x 16 B), then the three channels-last bf16 plane images of g, each region rounded up to 256
+ * bytes.  offk_conv2d_backward_data_form_split: the block of the GEMM the same seven integers choose -- (ci_per_block, pixels_per_block)
+ * = (64, 256) where Ci == 64, else (128, 128) where ceil(n_img H W / 256) * ceil(Ci / 128) <= 128, else (128, 256); the arithmetic and
+ * the bits of dx do not depend on it.  Output pointers may be NULL. */
+int offk_conv2d_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
+                                    const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
+                                    int accumulate, void* scratch, size_t scratch_bytes);
+int offk_conv2d_backward_data_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes);
+int offk_conv2d_backward_data_form_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, int* ci_per_block, int* pixels_per_block);
 /* K4b, stride 2 (additive, ABI v10). Backward of the two stage-opening fusion convolutions (motion_conv_trans_28: 7x7 / 2 / 3, RGB_OFF.py:657;
  * motion_conv_trans_14: 5x5 / 2 / 2, RGB_OFF.py:762), exact fp32 -- with the entries above all 24 fusion convs.  The conventions are K4b's,
  * word for word (views, enqueue only, no synchronisation, no allocation, refusals with OFFK_ERR_INVALID and the entry's name before any HIP

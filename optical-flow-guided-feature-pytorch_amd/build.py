@@ -17,11 +17,11 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "liboffk.so")
 SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "units_bwd_cl.hip", "units_dx.hip", "units_dx_f16.hip", "units_dx_split.hip", "units_wgrad_split.hip", "units_fwd_split.hip", "pw_tdiff.hip",
-           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip", "head_bwd.hip", "conv_wgrad_split.hip", "conv_dgrad_s2_split.hip")
+           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip", "head_bwd.hip", "conv_wgrad_split.hip", "conv_dgrad_s2_split.hip", "conv_dgrad_split.hip")
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",), "pw_reduce_cl.hip": ("pw_reduce.hip",), "units_bwd_cl.hip": ("units_bwd.hip",),
                     "units_dx_f16.hip": ("units_dx.hip",)}
-HEADERS = ("offk_common.h", "offk_internal.h", "pw_tdiff_staged.h", "winograd_common.h", os.path.join("..", "..", "include", "offk.h"))
+HEADERS = ("offk_common.h", "offk_internal.h", "pw_tdiff_staged.h", "winograd_common.h", "conv_dgrad_split_common.h", os.path.join("..", "..", "include", "offk.h"))
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=fast"]
 # heads.hip: no SLP vectoriser.  It pairs the FC accumulators of neighbouring classes into v_pk_fma_f32 with
@@ -35,7 +35,7 @@ EXTRA_FLAGS = {"heads.hip": ["-fno-slp-vectorize"], "units_bwd.hip": ["-fno-slp-
                "pw_tdiff_f16.hip": ["-fno-slp-vectorize"], "pw_tdiff_cl.hip": ["-fno-slp-vectorize"],
                "chain_fused.hip": ["-Wno-inline-asm"], "wino_gemm_split.hip": ["-fno-slp-vectorize"], "chain_split.hip": ["-fno-slp-vectorize"], "conv_bwd.hip": ["-fno-slp-vectorize"], "conv_bwd_s2.hip": ["-fno-slp-vectorize"],
                "head_bwd.hip": ["-fno-slp-vectorize"], "conv_wgrad_split.hip": ["-fno-slp-vectorize"],
-               "conv_dgrad_s2_split.hip": ["-fno-slp-vectorize"]}
+               "conv_dgrad_s2_split.hip": ["-fno-slp-vectorize"], "conv_dgrad_split.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():
@@ -366,6 +366,11 @@ REGISTER_RESIDENT_KERNELS = (
     # conv_s2_dgrad_split_kernel: a wave's 64 x 64 tile in two accumulators (128 registers), the next step's nine staged pieces (36) and the MFMA
     # operands (60) stay in registers at one block of eight waves per CU (144 KB of LDS); a spill would sit in the step loop
     ("conv_dgrad_s2_split.hip", r"^void offk::\(anonymous namespace\)::conv_s2_dgrad_split_kernel<", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+    # conv_dgrad_split_kernel: the same step loop with one phase, one row per block form.  128 ci x 256 pixels: the stride-2 kernel's budget;
+    # 128 x 128 and 64 x 256: a wave's 64 x 32 tile (64 accumulator registers), at most six staged pieces (24) and the MFMA operands (48)
+    ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<2, 4, 4, 4>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+    ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<2, 4, 4, 2>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+    ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<1, 8, 4, 2>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
 )
 
 

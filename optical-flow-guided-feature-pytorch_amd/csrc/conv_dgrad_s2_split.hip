@@ -13,7 +13,7 @@
 //       order: lane (lq = lane / 16, lr = lane % 16) holds co 8 lq .. 8 lq + 7 of the step for ci = 16 tile + lr.  A block's eight ci tiles of
 //       one step are 24 KB in one piece, and consecutive steps of a phase follow each other: the staging copy is linear.  Phases and taps
 //       in conv_s2_pack_kernel's order.  (Ci % 32 == 0: there is no partial 16-row tile, nothing to zero-fill.)
-//   conv_s2_gcut_split_kernel: g (the caller's channel-sliced view) -> three channels-last bf16 plane images [plane][n OH OW][Co]: the B
+//   conv_s2_gcut_split_kernel (conv_dgrad_split_common.h, shared with the stride-1 entry): g (the caller's channel-sliced view) -> three channels-last bf16 plane images [plane][n OH OW][Co]: the B
 //       operand of (pixel, 8 co) is one aligned 16-byte read.
 // The GEMM: one block = 128 ci x 256 pixels of one phase, eight waves (2 along ci x 4 along the pixels) of 64 x 64 each: 16 tiles of 16 x 16 in
 // A1 and A2, 128 accumulator registers; one block per CU (two waves per SIMD, at most 256 registers: build.py's register guard).  Per step
@@ -24,14 +24,11 @@
 // last real piece (clamped) and are neither computed (whole waves) nor stored.  blockIdx.z walks the phases longest first (16 / 12 / 12 /
 // 9 taps for the 7x7).  The same kernel with a 128 x 128 block (eight waves of 32 x 64) took 1.25 / 1.01 ms where this one takes 1.03 /
 // 0.83 ms: per MFMA it stages and reads a third more.
-#include "offk_common.h"
+#include "conv_dgrad_split_common.h"
 #include "offk_internal.h"
 
 namespace offk {
 namespace {
-
-typedef float dsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned dsu4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDsThreads = 512;                // eight waves
 constexpr int kDsWM = 2, kDsWN = 4, kDsCT = 4, kDsPT = 4;      // 2 x 4 waves of 4 (16-ci tiles) x 4 (16-pixel tiles): a block is 128 ci x 256 pixels
@@ -58,25 +55,6 @@ __host__ __device__ __forceinline__ int ds_phase_taps(int KS, int pad, int ph) {
   ds_axis(KS, pad, ph >> 1, &nh, &k0, &d0);
   ds_axis(KS, pad, ph & 1, &nw, &k0, &d0);
   return nh * nw;
-}
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void ds_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned ds_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-__device__ __forceinline__ void ds_cut8(const float (&v)[8], dsu4& ph, dsu4& pm, dsu4& pl) {
-  unsigned h[8], m[8], l[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ds_cut(v[e], h[e], m[e], l[e]);
-  ph = dsu4{ds_pair(h[0], h[1]), ds_pair(h[2], h[3]), ds_pair(h[4], h[5]), ds_pair(h[6], h[7])};
-  pm = dsu4{ds_pair(m[0], m[1]), ds_pair(m[2], m[3]), ds_pair(m[4], m[5]), ds_pair(m[6], m[7])};
-  pl = dsu4{ds_pair(l[0], l[1]), ds_pair(l[2], l[3]), ds_pair(l[4], l[5]), ds_pair(l[6], l[7])};
 }
 
 // one thread = one lane's piece of one (phase, tap, co step, ci tile), all three planes
@@ -111,27 +89,6 @@ __global__ __launch_bounds__(256) void conv_s2_wpack_split_kernel(const float* _
     dsu4* d = dst + (size_t)(i >> 6) * 192 + lane;
     d[0] = a; d[64] = b; d[128] = c;
   }
-}
-
-// one thread = eight consecutive co of one pixel, all three planes
-__global__ __launch_bounds__(256) void conv_s2_gcut_split_kernel(const float* __restrict__ g, int g_cs, int g_coff, dsu4* __restrict__ dst, int M,
-                                                                 int Co) {
-  const int c8 = Co >> 3;
-  const size_t total = (size_t)M * c8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t m = i / c8;
-    const int o = (int)(i - m * c8);
-    const float4* s = reinterpret_cast<const float4*>(g + m * g_cs + g_coff + 8 * o);
-    const float4 u0 = s[0], u1 = s[1];
-    const float v[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
-    dsu4 a, b, c;
-    ds_cut8(v, a, b, c);
-    dst[i] = a; dst[total + i] = b; dst[2 * total + i] = c;
-  }
-}
-
-__device__ __forceinline__ void ds_mfma(dsf4& c, const dsu4& a, const dsu4& b) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // WM x WN waves of CT (16-ci tiles) x PT (16-pixel tiles) each; WM * WN = 8
@@ -295,8 +252,6 @@ hipError_t ds_launch(const DsArgs& a, int M, hipStream_t st) {
   hipLaunchKernelGGL((conv_s2_dgrad_split_kernel<WM, WN, CT, PT>), grid, dim3(kDsThreads), lds, st, a);
   return hipGetLastError();
 }
-
-size_t ds_round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 

@@ -2251,6 +2251,47 @@ int offk_conv2d_backward_weight_split(void* stream, const float* x, int x_cstrid
   return OFFK_OK;
 }
 
+// ---- K4b's data gradient in split-fp32 arithmetic (conv_dgrad_split.hip) ----
+int offk_conv2d_backward_data_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes) {
+  const char* who = "offk_conv2d_backward_data_plan_split";
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t wb = 0, gb = 0;
+  if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (data_scratch_bytes) *data_scratch_bytes = wb + gb;
+  return OFFK_OK;
+}
+
+int offk_conv2d_backward_data_form_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, int* ci_per_block, int* pixels_per_block) {
+  const char* who = "offk_conv2d_backward_data_form_split";
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  int cb = 0, pb = 0;
+  conv_dgrad_split_form(n_img, H, W, Ci, &cb, &pb);
+  if (ci_per_block) *ci_per_block = cb;
+  if (pixels_per_block) *pixels_per_block = pb;
+  return OFFK_OK;
+}
+
+int offk_conv2d_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
+                                    const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
+                                    int accumulate, void* scratch, size_t scratch_bytes) {
+  const char* who = "offk_conv2d_backward_data_split";
+  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+  const long long rows = (long long)n_img * H * W;
+  if (views_overlap(dx, dx_cstride, g, g_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  size_t wb = 0, gb = 0;
+  if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (scratch_bytes < wb + gb) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_data_plan_split)");
+  if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch must be 16-byte aligned");
+  hipError_t e = conv_dgrad_split_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0, scratch,
+                                         static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
 // ---- K4b, stride 2: backward of the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip) ----
 namespace {
 int conv_s2_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {

@@ -81,6 +81,13 @@ bool conv_s2_dgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, i
 hipError_t conv_s2_dgrad_split_launch(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS,
                                       int pad, float* dx, int dx_cs, int dx_coff, int accumulate, void* scratch, hipStream_t st);
 
+// ---- K4b, stride 1: the data gradient in split-fp32 arithmetic on the bf16 matrix pipe (conv_dgrad_split.hip) ----
+// scratch bytes of its two regions (the packed weight's planes, then g's planes; each a multiple of 256) and the GEMM's block; pure host code
+bool conv_dgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_bytes, size_t* g_bytes);
+void conv_dgrad_split_form(int n_img, int H, int W, int Ci, int* ci_per_block, int* pixels_per_block);
+hipError_t conv_dgrad_split_launch(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS,
+                                   int pad, float* dx, int dx_cs, int dx_coff, int accumulate, void* scratch, hipStream_t st);
+
 // ---- K4c: one 1x1 -> 3x3 -> 1x1 (+ residual) bottleneck chain at 14x14 per launch (chain_fused.hip, exact fp32) ----
 struct ChainArgs {
   const float* x; int x_cs, x_coff;       // chain input, channels-last [n_img * 196][x_cs], Cin channels at x_coff

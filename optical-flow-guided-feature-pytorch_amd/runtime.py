@@ -179,8 +179,10 @@ FEAT_GRAD_ARITHS = ("fp32", "f32split")
 WGRAD_ARITHS = ("fp32", "f32split")
 # the arithmetic of the units' forward (off_units, off_units_train): "fp32" = K1 on the fp32 matrix pipe, "f32split" = offk_off_units_train_split
 FWD_ARITHS = ("fp32", "f32split")
-# the arithmetic of the stride-2 fusion convs' data gradient: "fp32" = offk_conv2d_s2_backward_data, "f32split" = offk_conv2d_s2_backward_data_split
+# the arithmetic of the fusion convs' data gradient: "fp32" = offk_conv2d[_s2]_backward_data, "f32split" = offk_conv2d[_s2]_backward_data_split
 DGRAD_ARITHS = ("fp32", "f32split")
+# FusionConv2d's one switch for all its gradient GEMMs: "f32split" = every one of them that has a split entry runs on it
+BWD_ARITHS = ("fp32", "f32split")
 
 
 def feat_grad_sites(needs_input_grad, first=0):
@@ -704,10 +706,33 @@ def relu_backward(dy, y, out=None, accumulate=False, dy_coff=0, y_coff=0, out_co
     return out
 
 
-def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0):
+def conv2d_backward_data_plan_split(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_backward_data_plan_split: data_scratch_bytes of the split-fp32 data gradient (conv2d_backward_data(arith="f32split")) --
+    host code, a function of these integers only: the three bf16 planes of the packed weight, then those of g, each rounded up to 256."""
+    lib = _lib.load()
+    d = ctypes.c_size_t(0)
+    _lib.check(lib.offk_conv2d_backward_data_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d)))
+    return d.value
+
+
+def conv2d_backward_data_form_split(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_backward_data_form_split: (ci_per_block, pixels_per_block) of the split-fp32 data gradient's GEMM -- host code, a function
+    of these integers only; the result's bits do not depend on it."""
+    lib = _lib.load()
+    cb, pb = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(lib.offk_conv2d_backward_data_form_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(cb),
+                                                        ctypes.byref(pb)))
+    return cb.value, pb.value
+
+
+def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0, arith="fp32"):
     """dx (+)= the gradient of a stride-1 conv's input.  g: [n, H, W, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
     (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx).  scratch: the caller's uint8
-    buffer of exactly conv2d_backward_plan's data_scratch_bytes."""
+    buffer of exactly conv2d_backward_plan's data_scratch_bytes.  arith: "fp32" (offk_conv2d_backward_data, exact fp32 on the fp32 matrix
+    pipe) or "f32split" (offk_conv2d_backward_data_split: three bf16 planes per operand, six products on the bf16 pipe, include/offk.h has
+    the bound; its scratch is conv2d_backward_data_plan_split's bytes)."""
+    if arith not in DGRAD_ARITHS:
+        raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in DGRAD_ARITHS), arith))
     lib = _lib.load()
     _nhwc(g, "g")
     n, H, W, gs = g.shape
@@ -719,10 +744,15 @@ def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, s
             raise ValueError("accumulate needs the tensor to add to (dx)")
         dx = torch.empty(n, H, W, Ci, dtype=torch.float32, device=g.device)
     _nhwc(dx, "dx")
-    nbytes = conv2d_backward_plan(n, H, W, Ci, Co, KH)[0] if KH == KW else 0
+    split = arith == "f32split"
+    if KH != KW:
+        nbytes = 0
+    else:
+        nbytes = conv2d_backward_data_plan_split(n, H, W, Ci, Co, KH) if split else conv2d_backward_plan(n, H, W, Ci, Co, KH)[0]
     scratch = _given(scratch, (nbytes,), "scratch", g.device, torch.uint8)
-    _lib.check(lib.offk_conv2d_backward_data(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad), _ptr(dx),
-                                             dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
+    entry = lib.offk_conv2d_backward_data_split if split else lib.offk_conv2d_backward_data
+    _lib.check(entry(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad), _ptr(dx),
+                     dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
     return dx
 
 
