@@ -271,7 +271,7 @@ int offk_launch_times(offk_handle* h, char* names, size_t names_len, double* ms,
  *   offk_winograd_conv3x3 / 5x5s2 / 7x7s2, offk_winograd_between / _ex     x, y, res: any extent
  *   offk_head, offk_head_train, offk_head_backward                         x, dx: any extent; n_img * H * W and n_img * num_classes <= 2^31 - 1
  *   offk_relu_backward                 dy, y, g: any extent
- *   offk_conv2d_backward_data / _weight / _weight_split, offk_conv2d_s2_backward_data / _data_split / _weight
+ *   offk_conv2d_backward_data / _weight / _weight_split, offk_conv2d_s2_backward_data / _data_split / _weight / _weight_split
  *                                      x, g, dx: any extent; the padded positions n_img * (H + 2) * (W + 2) (and n_img * H * W) stay
  *                                      below 2^31 less a tile, else OFFK_ERR_INVALID "problem too large"
  *   offk_nhwc_to_nchw                  src: any extent; n_img <= 65535
@@ -553,6 +553,52 @@ int offk_conv2d_s2_backward_data_split(void* stream, const float* g, int g_cstri
                                        const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
                                        int accumulate, void* scratch, size_t scratch_bytes);
 int offk_conv2d_s2_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes);
+/* K4b, stride 2: the weight / bias gradient in split-fp32 arithmetic on the bf16 matrix pipe (additive, ABI v10; csrc/conv_wgrad_s2_split.hip).
+ * offk_conv2d_s2_backward_weight_split has offk_conv2d_s2_backward_weight's argument list, shapes, views, forms and refusals word for word
+ * (its own name in offk_last_error(NULL); the scratch is sized by offk_conv2d_s2_backward_weight_plan_split) and computes the same dw and
+ * db (at n_img = 384 in 1.14 against 1.55 ms (7x7 / 2, 320 -> 64) and 1.00 against 1.30 ms (5x5 / 2, 1056 -> 128) on the fp32 entry,
+ * DESIGN.md 8.9).  An opt-in entry: nothing in the library calls it on its own.  Enqueue only: two launches on `stream` (the GEMM and the reduce), no allocation, no library-owned stream, capturable; a
+ * refused call makes no HIP call and writes nothing.  db may be NULL.
+ *
+ * Arithmetic (DESIGN.md 5.1's): g and in(x) (the relu_in ReLU comes before the cut) are cut by truncation into three bf16 planes h, m, l
+ * (the upper 16 bits of the word, of the exact remainder, and of its remainder).  K layout: K runs over the OUTPUT pixels, real pixels
+ * only, q = (img * (H/2) + oh) * (W/2) + ow, PP = (H/2) * (W/2) positions per image, images back to back: no zero column, no zero row.
+ * Tap (kh, kw) multiplies g at q with X_(kh,kw)[q] = in(x)[img, 2 oh + kh - pad, 2 ow + kw - pad], which is a ZERO where that row or that
+ * column leaves the map (the tap is removed on the x side; g is staged as it lies).  Chunk c holds the positions [img_b * PP, img_e * PP) of
+ * its whole images img_b = c * ceil(n_img / weight_chunks) .. img_e (the last chunk may be shorter); its step t is the 32 positions from
+ * img_b * PP + 32 t on (steps of 32), both operands counting as zero from img_e * PP on.  Per step and tap the six products
+ * g_l x_h, g_h x_l, g_m x_m, g_m x_h, g_h x_m (into accumulator A2) and g_h x_h (into A1) are issued on v_mfma_f32_16x16x32_bf16 in this
+ * order, steps in increasing order; a chunk's partial is A1 + A2, added once; the partial slabs [chunk][Co][Ci * KH * KW] (+ [chunk][Co]) live in `scratch`
+ * and the second launch of offk_conv2d_backward_weight (the same kernel) adds them in chunk order.  No atomics, every slab element is
+ * written by exactly one thread, the scratch's old contents never show: bit-reproducible from run to run and under graph capture.  db has no
+ * products: it is an fp32 sum of g itself in a fixed order (per chunk: a thread's position quads q % 32 in {4 j .. 4 j + 3} in step order,
+ * each quad as (g0 + g1) + (g2 + g3); then j = 0 .. 7 in order; then the chunks in order): nothing is split.
+ * Contract: the three dropped products g_m x_l + g_l x_m + g_l x_l are at most (2^-21 + 2^-30) sum |g x| per element of dw, beside an fp32
+ * accumulation error: |dw - exact| <= |dropped| + A * 2^-24 * sum |g x| + 2^-24 |exact| with A = max(1, 2 c_acc), c_acc the accumulation
+ * constant of the CPU emulation of exactly this order (tests/conv_s2_wgrad_split.py); integer operands whose planes and sums fit are
+ * exact.  Scaling an operand by 2^a scales dw and db by exactly 2^a (the cut masks significand bits), operands and planes in the normal
+ * range.  Non-finite and tiny inputs behave as the split-mode paragraph at OFFK_PRECISION_F32SPLIT says (+-Inf in an operand gives NaN:
+ * Inf - Inf in the cut; below 2^-109 an operand's last plane is lost).  Which elements a non-finite value reaches DIFFERS from
+ * offk_conv2d_s2_backward_weight's paragraph, because the taps that leave the map are zeros on the x side here:
+ *   a value in x[n, R, C, ci] makes dw[:, ci, kh, kw] NaN for exactly the taps whose sum it enters -- the kernel rows kh with
+ *   R = 2 oh + kh - pad for an oh in [0, H/2) and the kernel columns kw with C = 2 ow + kw - pad for an ow in [0, W/2) -- and nothing else
+ *   (every staged x value is a pixel of the tap itself or a constant zero); relu_in: max(x, 0) in hardware, x = NaN and x = -Inf count as 0;
+ *   a value in g[n, oh, ow, co] makes ALL KH * KW taps of dw[co, :] NaN, every ci: where a tap leaves the map at (oh, ow) its x operand
+ *   is a zero and g = Inf (NaN after the cut) times a zero is NaN -- the fp32 entry's select on g keeps those taps clean, this entry does
+ *   not; db[co] is +-Inf or NaN (an fp32 sum of g itself).  Every other output channel, and every input channel under a value in x, stays
+ *   finite and bit-equal.
+ *
+ * offk_conv2d_s2_backward_weight_plan_split: pure host code, a function of the seven integers only; output pointers may be NULL; the
+ * refusals of offk_conv2d_s2_backward_plan under its own name.  weight_scratch_bytes = weight_chunks * (Co * Ci * KH * KW + Co) * 4.  The
+ * chunks are the split kernel's own (one block of eight waves per CU: tiles = (Co / 64) * ceil(Ci / 64) * KH blocks per chunk, as many
+ * chunks as fit one round of 256 blocks for the 7x7 and two rounds for the 5x5, a chunk at least 256 positions long) under the same
+ * rules: whole images per chunk, ceil(n_img / weight_chunks) each, no empty chunk.  Positions n_img * (H/2) * (W/2) above the fp32 entry's
+ * limit are refused with "problem too large". */
+int offk_conv2d_s2_backward_weight_split(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
+                                   int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
+                                   int accumulate, void* scratch, size_t scratch_bytes);
+int offk_conv2d_s2_backward_weight_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes,
+                                              int* weight_chunks);
 /* Override the plan offk_forward uses for one fusion conv (key = its state_dict name without
  * ".weight", e.g. "motion_conv_trans_28"); tile_cfg < 0 / splitk < 1 restore the automatic choice. */
 int offk_set_conv_plan(offk_handle* h, const char* conv_key, int tile_cfg, int splitk);

@@ -93,6 +93,8 @@ SIGNATURES = {
     "offk_conv2d_s2_backward_data_split": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _F, _I, _I, _I, _P, _c.c_size_t]),
     "offk_conv2d_s2_backward_plan_split": (_I, [_I, _I, _I, _I, _I, _I, _I, _c.POINTER(_c.c_size_t)]),
     "offk_conv2d_s2_backward_weight": (_I, [_P, _F, _I, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _c.c_size_t]),
+    "offk_conv2d_s2_backward_weight_split": (_I, [_P, _F, _I, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, _c.c_size_t]),
+    "offk_conv2d_s2_backward_weight_plan_split": (_I, [_I, _I, _I, _I, _I, _I, _I, _c.POINTER(_c.c_size_t), _c.POINTER(_I)]),
     "offk_conv2d_s2_backward_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t), _c.POINTER(_I)]),
     "offk_set_conv_plan": (_I, [_P, _c.c_char_p, _I, _I]),
     "offk_head": (_I, [_P, _F, _I, _I, _I, _I, _I, _I, _I, _F, _F, _I, _F]),

@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "liboffk.so")
 SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.hip", "sobel_tdiff.hip", "conv_igemm.hip", "heads.hip", "units_bwd.hip", "units_bwd_cl.hip", "units_dx.hip", "units_dx_f16.hip", "units_dx_split.hip", "units_wgrad_split.hip", "units_fwd_split.hip", "pw_tdiff.hip",
-           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip", "head_bwd.hip", "conv_wgrad_split.hip", "conv_dgrad_s2_split.hip", "conv_dgrad_split.hip")
+           "pw_tdiff_split.hip", "pw_tdiff_f16.hip", "pw_tdiff_cl.hip", "chain_fused.hip", "chain_split.hip", "winograd.hip", "winograd7.hip", "wino_mid.hip", "wino_gemm.hip", "wino_gemm_split.hip", "conv_bwd.hip", "conv_bwd_s2.hip", "head_bwd.hip", "conv_wgrad_split.hip", "conv_dgrad_s2_split.hip", "conv_dgrad_split.hip", "conv_wgrad_s2_split.hip")
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",), "pw_reduce_cl.hip": ("pw_reduce.hip",), "units_bwd_cl.hip": ("units_bwd.hip",),
                     "units_dx_f16.hip": ("units_dx.hip",)}
@@ -35,7 +35,8 @@ EXTRA_FLAGS = {"heads.hip": ["-fno-slp-vectorize"], "units_bwd.hip": ["-fno-slp-
                "pw_tdiff_f16.hip": ["-fno-slp-vectorize"], "pw_tdiff_cl.hip": ["-fno-slp-vectorize"],
                "chain_fused.hip": ["-Wno-inline-asm"], "wino_gemm_split.hip": ["-fno-slp-vectorize"], "chain_split.hip": ["-fno-slp-vectorize"], "conv_bwd.hip": ["-fno-slp-vectorize"], "conv_bwd_s2.hip": ["-fno-slp-vectorize"],
                "head_bwd.hip": ["-fno-slp-vectorize"], "conv_wgrad_split.hip": ["-fno-slp-vectorize"],
-               "conv_dgrad_s2_split.hip": ["-fno-slp-vectorize"], "conv_dgrad_split.hip": ["-fno-slp-vectorize"]}
+               "conv_dgrad_s2_split.hip": ["-fno-slp-vectorize"], "conv_dgrad_split.hip": ["-fno-slp-vectorize"],
+               "conv_wgrad_s2_split.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():
@@ -371,6 +372,11 @@ REGISTER_RESIDENT_KERNELS = (
     ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<2, 4, 4, 4>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
     ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<2, 4, 4, 2>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
     ("conv_dgrad_split.hip", r"^void offk::\(anonymous namespace\)::conv_dgrad_split_kernel<1, 8, 4, 2>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+    # conv_s2_wgrad_split_kernel<7> / <5>: one kernel row's 7 or 5 taps' two accumulators of a wave's 32 x 16 tile (112 or 80 registers), the g
+    # operands (24) and the next step's rows of the thread's two loader units (32) stay in registers at one block of eight waves per CU
+    # (96 or 72 KB of LDS)
+    ("conv_wgrad_s2_split.hip", r"^void offk::\(anonymous namespace\)::conv_s2_wgrad_split_kernel<7>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
+    ("conv_wgrad_s2_split.hip", r"^void offk::\(anonymous namespace\)::conv_s2_wgrad_split_kernel<5>", 1, 256, "one block of eight waves per CU: two waves per SIMD x 256 = 512"),
 )
 
 

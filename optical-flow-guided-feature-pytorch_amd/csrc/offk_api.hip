@@ -2389,6 +2389,38 @@ int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, 
   return OFFK_OK;
 }
 
+// ---- K4b, stride 2: the weight gradient in split-fp32 arithmetic (conv_wgrad_s2_split.hip) ----
+int offk_conv2d_s2_backward_weight_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes,
+                                              int* weight_chunks) {
+  const char* who = "offk_conv2d_s2_backward_weight_plan_split";
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t wf = 0;
+  int chunks = 0;
+  if (!conv_s2_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
+  if (weight_chunks) *weight_chunks = chunks;
+  return OFFK_OK;
+}
+
+int offk_conv2d_s2_backward_weight_split(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff,
+                                         int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw,
+                                         float* db, int accumulate, void* scratch, size_t scratch_bytes) {
+  const char* who = "offk_conv2d_s2_backward_weight_split";
+  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  size_t wf = 0;
+  int chunks = 0;
+  if (!conv_s2_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  if (scratch_bytes < wf * sizeof(float))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_weight_plan_split)");
+  hipError_t e = conv_s2_wgrad_split_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
+                                            accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
 int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Cin, int relu_in,
                             const float* w1, const float* b1, const float* w2_packed, const float* b2, const float* w3,
                             const float* b3, int K3, const float* res, int res_cstride, int res_coff, float* y, int y_cstride,

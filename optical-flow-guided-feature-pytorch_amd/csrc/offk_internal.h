@@ -81,6 +81,12 @@ bool conv_s2_dgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, i
 hipError_t conv_s2_dgrad_split_launch(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS,
                                       int pad, float* dx, int dx_cs, int dx_coff, int accumulate, void* scratch, hipStream_t st);
 
+// ---- K4b, stride 2: the weight / bias gradient in split-fp32 arithmetic on the bf16 matrix pipe (conv_wgrad_s2_split.hip): its own plan, the same slabs and reduce ----
+bool conv_s2_wgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_floats, int* chunks);
+hipError_t conv_s2_wgrad_split_launch(const float* x, int x_cs, int x_coff, const float* g, int g_cs, int g_coff, int n_img, int H, int W,
+                                      int Ci, int Co, int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch,
+                                      int chunks, hipStream_t st);
+
 // ---- K4b, stride 1: the data gradient in split-fp32 arithmetic on the bf16 matrix pipe (conv_dgrad_split.hip) ----
 // scratch bytes of its two regions (the packed weight's planes, then g's planes; each a multiple of 256) and the GEMM's block; pure host code
 bool conv_dgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_bytes, size_t* g_bytes);

@@ -368,7 +368,7 @@ class OFFUnits(nn.Module):
 class _FusionConvFn(torch.autograd.Function):
     """autograd node of one ``FusionConv2d``: forward = offk_conv2d (direct fp32), backward = offk_relu_backward, then
     offk_conv2d_backward_weight (weight and bias) and offk_conv2d_backward_data -- the offk_conv2d_s2_backward_* entries for a stride-2
-    module, the *_split entries where the module's wgrad_arith / dgrad_arith / bwd_arith ask --, each only where ``ctx.needs_input_grad`` asks.
+    module, the *_split entries where the module's wgrad_arith / s2_wgrad_arith / dgrad_arith / bwd_arith ask --, each only where ``ctx.needs_input_grad`` asks.
     Tensors cross the node as logical NCHW in channels-last memory; inside they are the [n, H, W, C] rows the library reads."""
 
     @staticmethod
@@ -395,7 +395,8 @@ class _FusionConvFn(torch.autograd.Function):
         if need_w or need_b:
             FusionConv2d.weight_grad_launches += 1
             if s2:
-                dw, db = runtime.conv2d_s2_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
+                dw, db = runtime.conv2d_s2_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b),
+                                                           arith=mod.s2_wgrad_arith)
             elif mod.wgrad_arith == "fp32" and mod.bwd_arith == "fp32":
                 dw, db = runtime.conv2d_backward_weight(xr, g, mod.kernel_size[0], mod.padding[0], relu_in=mod.relu_in, want_db=bool(need_b))
             else:
@@ -451,20 +452,33 @@ class FusionConv2d(nn.Conv2d):
     ``bwd_arith`` ("fp32", the default: nothing changes) or "f32split": ONE switch that sends every gradient GEMM of the
     module to its split entry where the library has one.  Stride 1: dX on offk_conv2d_backward_data_split (the same
     arithmetic and bound as above with K = (tap = kh k + kw, co); include/offk.h), dW / db on
-    offk_conv2d_backward_weight_split.  Stride 2: dX on offk_conv2d_s2_backward_data_split; dW / db stay fp32 (the stride-2
-    weight gradient has no split entry yet).  Together with a non-default ``wgrad_arith`` or ``dgrad_arith`` it is a
-    ValueError: there is one way to say it.  The forward and the ReLU masks are untouched.  Measured at n_img = 384
-    (same session, interleaved): the stride-1 split data gradient is NOT faster than the fp32 entry on any of
+    offk_conv2d_backward_weight_split.  Stride 2: dX on offk_conv2d_s2_backward_data_split; dW / db stay on the fp32 entry
+    under this switch, bit for bit (the stride-2 weight gradient's split entry, offk_conv2d_s2_backward_weight_split, is
+    reached by ``s2_wgrad_arith`` below, which combines with this switch).  Together with a non-default ``wgrad_arith`` or
+    ``dgrad_arith`` it is a ValueError: there is one way to say it.  The forward and the ReLU masks are untouched.  Measured
+    at n_img = 384 (same session, interleaved): the stride-1 split data gradient is NOT faster than the fp32 entry on any of
     the 13 stride-1 shapes -- 1.02 x its time on 832 -> 256 3x3 (0.547 against 0.539 ms), 1.19 - 1.70 x on the other 3x3
     shapes, 1.6 - 2.7 x on the 1x1 shapes; 2.77 against 1.86 ms over the 22 convs, 1.60 against 1.27 ms over the eight 3x3
     convs.  At stride 1 this switch therefore buys the weight gradient's gain (3.76 -> 2.66 ms) and pays 0.91 ms for the
-    data gradient; ``wgrad_arith="f32split"`` alone is the faster stride-1 setting today."""
+    data gradient; ``wgrad_arith="f32split"`` alone is the faster stride-1 setting today.
 
-    weight_grad_launches = 0      # calls of offk_conv2d[_s2]_backward_weight made by all modules (a frozen layer makes none)
+    ``s2_wgrad_arith`` ("fp32", the default: nothing changes) or "f32split": the weight and bias gradient of a STRIDE-2
+    module run on offk_conv2d_s2_backward_weight_split -- g and in(x) cut into three bf16 planes, six of the nine plane
+    products on the bf16 matrix pipe over K = the output pixels, the taps that leave the map zeros on the x side
+    (include/offk.h has the K layout and the bound: the dropped products are at most (2^-21 + 2^-30) sum |g x| per element of
+    dw, beside an fp32 accumulation error; integer data stays exact), still bit-reproducible; the forward, the ReLU masks and
+    the data gradient are untouched.  Stride-2 modules only (at stride 1 it is a ValueError: ``wgrad_arith`` is the stride-1
+    weight gradient's switch).  It is a keyword of its own because the two older ones are pinned: ``wgrad_arith="f32split"``
+    on a stride-2 module stays a ValueError, and ``bwd_arith="f32split"`` keeps a stride-2 module's dW / db on the fp32 entry.
+    It combines freely with ``dgrad_arith`` and with ``bwd_arith``.  At n_img = 384 the entry (the GEMM and the reduce) takes
+    1.14 against 1.55 ms (7x7, 320 -> 64) and 1.00 against 1.30 ms (5x5, 1056 -> 128) on the fp32 entry, same session,
+    interleaved: both faster by more than the spread of three repeats."""
+
+    weight_grad_launches = 0      # calls of offk_conv2d[_s2]_backward_weight[_split] made by all modules (a frozen layer makes none)
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
                  padding_mode="zeros", device=None, dtype=None, relu=False, relu_in=False, wgrad_arith="fp32",
-                 dgrad_arith="fp32", bwd_arith="fp32"):
+                 dgrad_arith="fp32", bwd_arith="fp32", s2_wgrad_arith="fp32"):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode,
                          device=device, dtype=dtype)
         k = self.kernel_size
@@ -484,6 +498,11 @@ class FusionConv2d(nn.Conv2d):
         if bwd_arith == "f32split" and (wgrad_arith != "fp32" or dgrad_arith != "fp32"):
             raise ValueError("FusionConv2d: bwd_arith='f32split' already covers wgrad_arith and dgrad_arith: leave them at their default")
         self.bwd_arith = bwd_arith
+        if s2_wgrad_arith not in runtime.WGRAD_ARITHS:
+            raise ValueError("FusionConv2d: s2_wgrad_arith must be one of %s, got %r" % (", ".join(repr(a) for a in runtime.WGRAD_ARITHS), s2_wgrad_arith))
+        if s2_wgrad_arith == "f32split" and self.stride != (2, 2):
+            raise ValueError("FusionConv2d: s2_wgrad_arith='f32split' needs stride 2 (wgrad_arith is the stride-1 weight gradient's switch)")
+        self.s2_wgrad_arith = s2_wgrad_arith
         if self.stride not in ((1, 1), (2, 2)) or self.dilation != (1, 1) or self.groups != 1:
             raise ValueError("FusionConv2d: dilation and groups must be 1, stride 1 (kernel 1 or 3) or 2 (kernel 7 with padding 3, "
                              "kernel 5 with padding 2)")
@@ -511,7 +530,8 @@ class FusionConv2d(nn.Conv2d):
         s = super().extra_repr() + ", relu=%s, relu_in=%s" % (self.relu, self.relu_in)
         s = s if self.wgrad_arith == "fp32" else s + ", wgrad_arith=%s" % self.wgrad_arith
         s = s if self.dgrad_arith == "fp32" else s + ", dgrad_arith=%s" % self.dgrad_arith
-        return s if self.bwd_arith == "fp32" else s + ", bwd_arith=%s" % self.bwd_arith
+        s = s if self.bwd_arith == "fp32" else s + ", bwd_arith=%s" % self.bwd_arith
+        return s if self.s2_wgrad_arith == "fp32" else s + ", s2_wgrad_arith=%s" % self.s2_wgrad_arith
 
 
 class _MotionHeadFn(torch.autograd.Function):

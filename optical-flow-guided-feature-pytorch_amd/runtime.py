@@ -846,11 +846,26 @@ def conv2d_s2_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False
     return dx
 
 
+def conv2d_s2_backward_weight_plan_split(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_s2_backward_weight_plan_split: (weight_scratch_bytes, weight_chunks) of the split-fp32 weight gradient of a stride-2 conv
+    (conv2d_s2_backward_weight(arith="f32split")) -- host code, a function of these integers only; the chunks are the split kernel's own."""
+    lib = _lib.load()
+    w, c = ctypes.c_size_t(0), ctypes.c_int(0)
+    _lib.check(lib.offk_conv2d_s2_backward_weight_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize),
+                                                             ctypes.byref(w), ctypes.byref(c)))
+    return w.value, c.value
+
+
 def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
-                              scratch=None, want_db=True):
+                              scratch=None, want_db=True, arith="fp32"):
     """(dw, db) (+)= the weight and bias gradient of a stride-2 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
     read max(x, 0)); g: [n, H/2, W/2, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co] as in conv2d_backward_weight.
-    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's weight_scratch_bytes."""
+    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's weight_scratch_bytes.  arith: "fp32"
+    (offk_conv2d_s2_backward_weight, exact fp32 on the fp32 matrix pipe) or "f32split" (offk_conv2d_s2_backward_weight_split: three bf16
+    planes per operand, six products on the bf16 pipe, include/offk.h has the K layout and the bound; its scratch is
+    conv2d_s2_backward_weight_plan_split's weight_scratch_bytes)."""
+    if arith not in WGRAD_ARITHS:
+        raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in WGRAD_ARITHS), arith))
     lib = _lib.load()
     _nhwc(x, "x"), _nhwc(g, "g")
     n, H, W, xs = x.shape
@@ -868,11 +883,12 @@ def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None
     for t, name, numel in ((dw, "dw", Co * Ci * k * k), (db, "db", Co)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
             raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
-    nbytes = conv2d_s2_backward_plan(n, H, W, Ci, Co, k)[1]
+    split = arith == "f32split"
+    nbytes = conv2d_s2_backward_weight_plan_split(n, H, W, Ci, Co, k)[0] if split else conv2d_s2_backward_plan(n, H, W, Ci, Co, k)[1]
     scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
-    _lib.check(lib.offk_conv2d_s2_backward_weight(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
-                                                  int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch),
-                                                  scratch.numel()))
+    entry = lib.offk_conv2d_s2_backward_weight_split if split else lib.offk_conv2d_s2_backward_weight
+    _lib.check(entry(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
+                     int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch), scratch.numel()))
     return dw, db
 
 
