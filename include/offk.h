@@ -294,7 +294,7 @@ int offk_launch_times(offk_handle* h, char* names, size_t names_len, double* ms,
  *                                      (pw_tdiff_f16.hip, pw_tdiff_cl.hip, pw_tdiff_staged.h).  offk_forward_typed is run at B = 612 (3b as
  *                                      bf16 / fp16 = 2.15 GB, fusion_28 3.7 GB, the Winograd V array 9.5 GB).
  *   offk_pw_reduce_cl, offk_off_units_cl, and offk_pw_reduce / offk_off_units / offk_forward on an OFFK_FEAT_NHWC handle (fp32 maps)
- *                                      any extent: mode 2 of pw_reduce_kernel<0, 0>, (size_t)row * cpart (pw_reduce.hip:229-234); read,
+ *                                      any extent: mode 2 of pw_reduce_kernel<0, 0>, (size_t)row * cpart (pw_reduce.hip:222-227); read,
  *                                      not run at 2 GiB by any test.
  *   offk_create                        batch * length * 784 * 320 <= 2^31 - 1 (N <= 8559 frames), else OFFK_ERR_INVALID "offk_create:
  *                                      batch*length too large for one call; shard the clips"

@@ -29,19 +29,16 @@
 
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 // relu on a packed-bf16 operand whose values' planes share their sign (truncating cut): per 16-bit word max(x, 0) as a signed integer.
 // (inline asm: hipcc 7.2 compiled the same thing written with __builtin_elementwise_max on the four bit-cast short2 words to ONE
 // v_pk_max_i16 of the first word, selected into all four -- found by tools/debug_chain_br.py)
-__device__ __forceinline__ u32x4 relu_planes(const u32x4& v) {
-  u32x4 o;
+__device__ __forceinline__ spu4 relu_planes(const spu4& v) {
+  spu4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     unsigned r;
@@ -59,52 +56,43 @@ constexpr int CS_T2ROW = 2 * CS_XTILE;         // phase 3: one image row of t2: 
 constexpr int CS_LDS = 2 * CS_XSTAGE;          // 49152 B = 3 * CS_T1PLANE >= 7 * CS_T2ROW: three blocks per CU
 constexpr int CS_OOB = (int)0x80000000;
 
-__device__ __forceinline__ f32x4 mfs(f32x4 c, const u32x4& a, const u32x4& b) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of one (weight planes, activation planes) pair into the tile's two accumulators; planes 0 = h, 1 = m, 2 = l
-__device__ __forceinline__ void mul6(f32x4& a1, f32x4& a2, const u32x4 (&w)[3], const u32x4 (&x)[3]) {
-  a2 = mfs(a2, w[2], x[0]);
-  a2 = mfs(a2, w[0], x[2]);
-  a1 = mfs(a1, w[0], x[0]);
-  a2 = mfs(a2, w[1], x[1]);
-  a2 = mfs(a2, w[1], x[0]);
-  a2 = mfs(a2, w[0], x[1]);
+// the six products of one (weight planes, activation planes) pair into the tile's two accumulators; planes 0 = h, 1 = m, 2 = l.  A1's
+// product is issued THIRD here: this file's own form, not sp_issue6's order
+__device__ __forceinline__ void mul6(spf4& a1, spf4& a2, const spu4 (&w)[3], const spu4 (&x)[3]) {
+  sp_mfma(a2, w[2], x[0]);
+  sp_mfma(a2, w[0], x[2]);
+  sp_mfma(a1, w[0], x[0]);
+  sp_mfma(a2, w[1], x[1]);
+  sp_mfma(a2, w[1], x[0]);
+  sp_mfma(a2, w[0], x[1]);
 }
 // two tiles that share the weight planes, their chains interleaved
-__device__ __forceinline__ void mul6x2(f32x4& a1, f32x4& a2, f32x4& b1, f32x4& b2, const u32x4 (&w)[3], const u32x4 (&x)[3], const u32x4 (&y)[3]) {
-  a2 = mfs(a2, w[2], x[0]); b2 = mfs(b2, w[2], y[0]);
-  a2 = mfs(a2, w[0], x[2]); b2 = mfs(b2, w[0], y[2]);
-  a1 = mfs(a1, w[0], x[0]); b1 = mfs(b1, w[0], y[0]);
-  a2 = mfs(a2, w[1], x[1]); b2 = mfs(b2, w[1], y[1]);
-  a2 = mfs(a2, w[1], x[0]); b2 = mfs(b2, w[1], y[0]);
-  a2 = mfs(a2, w[0], x[1]); b2 = mfs(b2, w[0], y[1]);
+__device__ __forceinline__ void mul6x2(spf4& a1, spf4& a2, spf4& b1, spf4& b2, const spu4 (&w)[3], const spu4 (&x)[3], const spu4 (&y)[3]) {
+  sp_mfma(a2, w[2], x[0]); sp_mfma(b2, w[2], y[0]);
+  sp_mfma(a2, w[0], x[2]); sp_mfma(b2, w[0], y[2]);
+  sp_mfma(a1, w[0], x[0]); sp_mfma(b1, w[0], y[0]);
+  sp_mfma(a2, w[1], x[1]); sp_mfma(b2, w[1], y[1]);
+  sp_mfma(a2, w[1], x[0]); sp_mfma(b2, w[1], y[0]);
+  sp_mfma(a2, w[0], x[1]); sp_mfma(b2, w[0], y[1]);
 }
 // two independent (weights, activations) pairs, their chains interleaved
-__device__ __forceinline__ void mul6ab(f32x4& a1, f32x4& a2, f32x4& b1, f32x4& b2, const u32x4 (&w)[3], const u32x4 (&x)[3], const u32x4 (&u)[3],
-                                       const u32x4 (&y)[3]) {
-  a2 = mfs(a2, w[2], x[0]); b2 = mfs(b2, u[2], y[0]);
-  a2 = mfs(a2, w[0], x[2]); b2 = mfs(b2, u[0], y[2]);
-  a1 = mfs(a1, w[0], x[0]); b1 = mfs(b1, u[0], y[0]);
-  a2 = mfs(a2, w[1], x[1]); b2 = mfs(b2, u[1], y[1]);
-  a2 = mfs(a2, w[1], x[0]); b2 = mfs(b2, u[1], y[0]);
-  a2 = mfs(a2, w[0], x[1]); b2 = mfs(b2, u[0], y[1]);
+__device__ __forceinline__ void mul6ab(spf4& a1, spf4& a2, spf4& b1, spf4& b2, const spu4 (&w)[3], const spu4 (&x)[3], const spu4 (&u)[3],
+                                       const spu4 (&y)[3]) {
+  sp_mfma(a2, w[2], x[0]); sp_mfma(b2, u[2], y[0]);
+  sp_mfma(a2, w[0], x[2]); sp_mfma(b2, u[0], y[2]);
+  sp_mfma(a1, w[0], x[0]); sp_mfma(b1, u[0], y[0]);
+  sp_mfma(a2, w[1], x[1]); sp_mfma(b2, u[1], y[1]);
+  sp_mfma(a2, w[1], x[0]); sp_mfma(b2, u[1], y[0]);
+  sp_mfma(a2, w[0], x[1]); sp_mfma(b2, u[0], y[1]);
 }
 // four fp32 values -> the three planes' 8 bytes each (truncating cut: h = upper 16 bits, exact remainder, again)
-__device__ __forceinline__ void cut4(const f32x4& v, u32x2& ph, u32x2& pm, u32x2& pl) {
-  unsigned h[4], m[4];
-  float l[4];
+__device__ __forceinline__ void cut4(const spf4& v, spu2& ph, spu2& pm, spu2& pl) {
+  unsigned h[4], m[4], l[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    h[e] = __float_as_uint(v[e]) & 0xffff0000u;
-    const float r = v[e] - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r) & 0xffff0000u;
-    l[e] = r - __uint_as_float(m[e]);
-  }
-  ph = u32x2{__builtin_amdgcn_perm(h[1], h[0], 0x07060302), __builtin_amdgcn_perm(h[3], h[2], 0x07060302)};
-  pm = u32x2{__builtin_amdgcn_perm(m[1], m[0], 0x07060302), __builtin_amdgcn_perm(m[3], m[2], 0x07060302)};
-  pl = u32x2{__builtin_amdgcn_perm(__float_as_uint(l[1]), __float_as_uint(l[0]), 0x07060302),
-             __builtin_amdgcn_perm(__float_as_uint(l[3]), __float_as_uint(l[2]), 0x07060302)};
+  for (int e = 0; e < 4; ++e) sp_cut(v[e], h[e], m[e], l[e]);
+  ph = spu2{sp_pair(h[0], h[1]), sp_pair(h[2], h[3])};
+  pm = spu2{sp_pair(m[0], m[1]), sp_pair(m[2], m[3])};
+  pl = spu2{sp_pair(l[0], l[1]), sp_pair(l[2], l[3])};
 }
 }  // namespace
 
@@ -125,9 +113,9 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
   const int wlane = lane * 16;
   const bool pad = li == 0 || li == 15;
 
-  f32x4 acc1[8], acc2[8];
+  spf4 acc1[8], acc2[8];
 #pragma unroll
-  for (int m = 0; m < 8; ++m) { acc1[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int m = 0; m < 8; ++m) { acc1[m] = spf4{0.f, 0.f, 0.f, 0.f}; acc2[m] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   // ---- the 1x1 conv 64 -> 256 as 28 items (channel tile n of the wave's four, row r), software-pipelined: the residual of item i + 3 and
   //      the activation tiles of item i + 1 are requested behind the MFMAs of item i, the epilogue of item i - 1 (its accumulators have
@@ -137,35 +125,35 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
   const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(a.y + a.y_coff, 0, (int)(((size_t)a.n_img * 196 * a.y_cs - a.y_coff) * 4), 0x00020000);
   auto item_loop = [&](const __amdgpu_buffer_rsrc_t wrs, auto rd, const float* bias, const float* res, const int res_cs, const int res_coff,
                        const bool res_is_y, const bool relu) {
-    u32x4 w3[2][2][3];                    // [set][K-step][plane]
+    spu4 w3[2][2][3];                    // [set][K-step][plane]
     auto load_w3 = [&](const int set, const int n) {
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
-          w3[set][s][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, ((s * 16 + 4 * wave + n) * 3 + pl) * 1024, 0));
+          w3[set][s][pl] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(wrs, wlane, ((s * 16 + 4 * wave + n) * 3 + pl) * 1024, 0));
     };
     auto res_load = [&](const int i) {
       const int n = i / 7, r = i % 7;
       const int ch = 64 * wave + 16 * n + 4 * kq;
 #if defined(OFFK_CS_EXP) && OFFK_CS_EXP == 3
-      if (res_is_y) return px_ok ? *reinterpret_cast<const volatile f32x4*>(a.y + (size_t)(pix0 + r * 14) * a.y_cs + a.y_coff + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
+      if (res_is_y) return px_ok ? *reinterpret_cast<const volatile spf4*>(a.y + (size_t)(pix0 + r * 14) * a.y_cs + a.y_coff + ch) : spf4{0.f, 0.f, 0.f, 0.f};
 #endif
       if (res_is_y)       // what this lane stored there in the branch pass (glc: past the L1)
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(yrs, px_ok ? ((pix0 + r * 14) * a.y_cs + ch) * 4 : CS_OOB, 0, 1));
-      return res ? *reinterpret_cast<const f32x4*>(res + (size_t)(pix0 + r * 14) * res_cs + res_coff + ch) : f32x4{0.f, 0.f, 0.f, 0.f};
+        return __builtin_bit_cast(spf4, __builtin_amdgcn_raw_buffer_load_b128(yrs, px_ok ? ((pix0 + r * 14) * a.y_cs + ch) * 4 : CS_OOB, 0, 1));
+      return res ? *reinterpret_cast<const spf4*>(res + (size_t)(pix0 + r * 14) * res_cs + res_coff + ch) : spf4{0.f, 0.f, 0.f, 0.f};
     };
-    u32x4 xb[2][2][3];                    // [item parity][K-step][plane]
-    f32x4 rv[4], bb[2], pc[4];
+    spu4 xb[2][2][3];                    // [item parity][K-step][plane]
+    spf4 rv[4], bb[2], pc[4];
     auto finish = [&](const int i) {      // item i: pc = its four accumulators
       const int n = i / 7, r = i % 7;
       const int ch = 64 * wave + 16 * n + 4 * kq;
-      f32x4 v = ((pc[0] + pc[2]) + (pc[1] + pc[3])) + bb[n & 1] + rv[i & 3];
-      if (relu) v = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-      if (px_ok) *reinterpret_cast<f32x4*>(a.y + (size_t)(pix0 + r * 14) * a.y_cs + a.y_coff + ch) = v;
+      spf4 v = ((pc[0] + pc[2]) + (pc[1] + pc[3])) + bb[n & 1] + rv[i & 3];
+      if (relu) v = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+      if (px_ok) *reinterpret_cast<spf4*>(a.y + (size_t)(pix0 + r * 14) * a.y_cs + a.y_coff + ch) = v;
     };
     load_w3(0, 0);
-    bb[0] = *reinterpret_cast<const f32x4*>(bias + 64 * wave + 4 * kq);
+    bb[0] = *reinterpret_cast<const spf4*>(bias + 64 * wave + 4 * kq);
     rv[0] = res_load(0); rv[1] = res_load(1); rv[2] = res_load(2);
     rd(xb[0], 0);
 #pragma unroll
@@ -173,10 +161,10 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
       const int n = i / 7, r = i % 7;
       if (r == 0 && n + 1 < 4) load_w3((n + 1) & 1, n + 1);
       // (the next tile's bias one item later: finish(i - 1) of the tile before still reads its own at r == 0)
-      if (r == 1 && n + 1 < 4) bb[(n + 1) & 1] = *reinterpret_cast<const f32x4*>(bias + 64 * wave + 16 * (n + 1) + 4 * kq);
+      if (r == 1 && n + 1 < 4) bb[(n + 1) & 1] = *reinterpret_cast<const spf4*>(bias + 64 * wave + 16 * (n + 1) + 4 * kq);
       if (i + 1 < 28) rd(xb[(i + 1) & 1], (i + 1) % 7);
       __builtin_amdgcn_sched_barrier(0);
-      f32x4 c1 = {0.f, 0.f, 0.f, 0.f}, c2 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f};
+      spf4 c1 = {0.f, 0.f, 0.f, 0.f}, c2 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f}, d2 = {0.f, 0.f, 0.f, 0.f};
       mul6ab(c1, c2, d1, d2, w3[n & 1][0], xb[i & 1][0], w3[n & 1][1], xb[i & 1][1]);      // the two K-steps as two interleaved chains
       if (i > 0) finish(i - 1);
       if (i + 3 < 28) rv[(i + 3) & 3] = res_load(i + 3);
@@ -204,29 +192,29 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
       xwr[q] = lds + lm * CS_XTILE + lkg * 256 + ((ls ^ (2 * lkg)) << 4) + (lc & 1) * 8;            // + stage, + plane * 1024
     }
     const char* const xrd = lds + kq * 256 + ((li ^ (2 * kq)) << 4);                   // + stage, + m * CS_XTILE, + plane * 1024
-    u32x4 xr2[2][4];                      // [set = K-step parity][q]: loaded two K-steps ahead of the multiply, cut one step ahead
+    spu4 xr2[2][4];                      // [set = K-step parity][q]: loaded two K-steps ahead of the multiply, cut one step ahead
     auto load_x = [&](const int kt) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) xr2[kt & 1][q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xvoff[q], kt * 128, 0));
+      for (int q = 0; q < 4; ++q) xr2[kt & 1][q] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xvoff[q], kt * 128, 0));
     };
     auto cut_x = [&](const int stage) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        f32x4 v = __builtin_bit_cast(f32x4, xr2[stage][q]);
-        if (!BR && a.relu_in) v = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};      // (BR: c1 applies it as it reads)
-        u32x2 h2, m2, l2;
+        spf4 v = __builtin_bit_cast(spf4, xr2[stage][q]);
+        if (!BR && a.relu_in) v = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};      // (BR: c1 applies it as it reads)
+        spu2 h2, m2, l2;
         cut4(v, h2, m2, l2);
         char* d = xwr[q] + stage * CS_XSTAGE;
-        *reinterpret_cast<u32x2*>(d) = h2;
-        *reinterpret_cast<u32x2*>(d + 1024) = m2;
-        *reinterpret_cast<u32x2*>(d + 2048) = l2;
+        *reinterpret_cast<spu2*>(d) = h2;
+        *reinterpret_cast<spu2*>(d + 1024) = m2;
+        *reinterpret_cast<spu2*>(d + 2048) = l2;
       }
     };
-    u32x4 w1[2][3];
+    spu4 w1[2][3];
     auto load_w1 = [&](const int set, const int kt) {
 #pragma unroll
       for (int q = 0; q < 3; ++q)
-        w1[set][q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w1rs, wlane, ((kt * 4 + wave) * 3 + q) * 1024, 0));
+        w1[set][q] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(w1rs, wlane, ((kt * 4 + wave) * 3 + q) * 1024, 0));
     };
     load_x(0);
     if (NK1 > 1) load_x(1);
@@ -239,22 +227,22 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
       // the branch 1x1 off the planes of the PRE-ReLU chain input: y = W_b x0 + b_b, to be read back as phase 3's residual
       const __amdgpu_buffer_rsrc_t wbrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wbp), 0, 256 * 64 * 6, 0x00020000);
       const char* const brd = xrd + hf * CS_XTILE;        // output row r = t1 row r + hf
-      item_loop(wbrs, [&](u32x4 (&x)[2][3], const int r) {
+      item_loop(wbrs, [&](spu4 (&x)[2][3], const int r) {
 #pragma unroll
         for (int sx = 0; sx < 2; ++sx)
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl) x[sx][pl] = *reinterpret_cast<const u32x4*>(brd + sx * CS_XSTAGE + r * CS_XTILE + pl * 1024);
+          for (int pl = 0; pl < 3; ++pl) x[sx][pl] = *reinterpret_cast<const spu4*>(brd + sx * CS_XSTAGE + r * CS_XTILE + pl * 1024);
       }, a.bbr, nullptr, 0, 0, false, false);
     }
 #pragma unroll
     for (int kt = 0; kt < NK1; ++kt) {
       const int st = kt & 1;
       if (kt + 1 < NK1) load_w1(st ^ 1, kt + 1);
-      u32x4 xb[2][3];
-      auto rdx = [&](u32x4 (&x)[3], const int m) {
+      spu4 xb[2][3];
+      auto rdx = [&](spu4 (&x)[3], const int m) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-          x[q] = *reinterpret_cast<const u32x4*>(xrd + st * CS_XSTAGE + m * CS_XTILE + q * 1024);
+          x[q] = *reinterpret_cast<const spu4*>(xrd + st * CS_XSTAGE + m * CS_XTILE + q * 1024);
           if (BR && a.relu_in) x[q] = relu_planes(x[q]);
         }
       };
@@ -273,18 +261,18 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
       __syncthreads();
     }
     // t1 -> planes: lane = (slot li, channels 16 wave + 4 kq .. + 3): k group 2 wave + (kq >> 1), its 8-byte half kq & 1
-    const f32x4 b1 = *reinterpret_cast<const f32x4*>(a.b1 + 16 * wave + 4 * kq);
+    const spf4 b1 = *reinterpret_cast<const spf4*>(a.b1 + 16 * wave + 4 * kq);
     char* const twr = lds + (2 * wave + (kq >> 1)) * CS_KG + (li + 1) * 16 + (kq & 1) * 8;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-      f32x4 v = (acc1[m] + acc2[m]) + b1;
-      v = pad ? f32x4{0.f, 0.f, 0.f, 0.f} : f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-      u32x2 h2, m2, l2;
+      spf4 v = (acc1[m] + acc2[m]) + b1;
+      v = pad ? spf4{0.f, 0.f, 0.f, 0.f} : spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+      spu2 h2, m2, l2;
       cut4(v, h2, m2, l2);
       char* d = twr + m * 240;
-      *reinterpret_cast<u32x2*>(d) = h2;
-      *reinterpret_cast<u32x2*>(d + CS_T1PLANE) = m2;
-      *reinterpret_cast<u32x2*>(d + 2 * CS_T1PLANE) = l2;
+      *reinterpret_cast<spu2*>(d) = h2;
+      *reinterpret_cast<spu2*>(d + CS_T1PLANE) = m2;
+      *reinterpret_cast<spu2*>(d + 2 * CS_T1PLANE) = l2;
     }
   }
   __syncthreads();
@@ -294,14 +282,14 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
 
   // ================= phase 2: t2 = relu(W2 * t1 + b2), seven output rows, direct 3x3 =================
 #pragma unroll
-  for (int m = 0; m < 7; ++m) { acc1[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int m = 0; m < 7; ++m) { acc1[m] = spf4{0.f, 0.f, 0.f, 0.f}; acc2[m] = spf4{0.f, 0.f, 0.f, 0.f}; }
   {
     const __amdgpu_buffer_rsrc_t w2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w2p), 0, 64 * 576 * 6, 0x00020000);
-    u32x4 w2[2][3];
+    spu4 w2[2][3];
     auto load_w2 = [&](const int set, const int q) {        // K-tile q = (channel half s = q / 9, tap q % 9): the library's packed K order
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
-        w2[set][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w2rs, wlane, ((q * 4 + wave) * 3 + pl) * 1024, 0));
+        w2[set][pl] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(w2rs, wlane, ((q * 4 + wave) * 3 + pl) * 1024, 0));
     };
     // t1 row of output row r under tap row dy: j = r + dy - 1 + hf; j = -1 (first half) and j = 8 (second half) lie outside the image
     const char* const trd = lds + kq * CS_KG + li * 16;                               // + plane, + 4 s k groups, + (15 j + dx) slots
@@ -311,11 +299,11 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
     for (int q = 0; q < 18; ++q) {
       const int s = q / 9, tap = q % 9, dy = tap / 3, dx = tap % 3;
       if (q + 1 < 18) load_w2((q + 1) & 1, q + 1);
-      u32x4 xb[4][3];
-      auto rdt = [&](u32x4 (&x)[3], const int r) {
+      spu4 xb[4][3];
+      auto rdt = [&](spu4 (&x)[3], const int r) {
         const int j = min(max(r + dy - 1 + hf, 0), 7);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) x[pl] = *reinterpret_cast<const u32x4*>(trd + pl * CS_T1PLANE + 4 * s * CS_KG + (15 * j + dx) * 16);
+        for (int pl = 0; pl < 3; ++pl) x[pl] = *reinterpret_cast<const spu4*>(trd + pl * CS_T1PLANE + 4 * s * CS_KG + (15 * j + dx) * 16);
         if (r == 0 && dy == 0) {
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) x[pl] &= keep_top;
@@ -341,18 +329,18 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
   }
   __syncthreads();                       // every wave is past its last t1 read: t2 replaces it
   {
-    const f32x4 b2 = *reinterpret_cast<const f32x4*>(a.b2 + 16 * wave + 4 * kq);
+    const spf4 b2 = *reinterpret_cast<const spf4*>(a.b2 + 16 * wave + 4 * kq);
     char* const twr = lds + (wave >> 1) * CS_XTILE + (2 * (wave & 1) + (kq >> 1)) * 256 + li * 16 + (kq & 1) * 8;
 #pragma unroll
     for (int r = 0; r < 7; ++r) {
-      f32x4 v = (acc1[r] + acc2[r]) + b2;
-      v = pad ? f32x4{0.f, 0.f, 0.f, 0.f} : f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-      u32x2 h2, m2, l2;
+      spf4 v = (acc1[r] + acc2[r]) + b2;
+      v = pad ? spf4{0.f, 0.f, 0.f, 0.f} : spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+      spu2 h2, m2, l2;
       cut4(v, h2, m2, l2);
       char* d = twr + r * CS_T2ROW;
-      *reinterpret_cast<u32x2*>(d) = h2;
-      *reinterpret_cast<u32x2*>(d + 1024) = m2;
-      *reinterpret_cast<u32x2*>(d + 2048) = l2;
+      *reinterpret_cast<spu2*>(d) = h2;
+      *reinterpret_cast<spu2*>(d + 1024) = m2;
+      *reinterpret_cast<spu2*>(d + 2048) = l2;
     }
   }
   __syncthreads();
@@ -364,11 +352,11 @@ __global__ __launch_bounds__(256, 3) void chain14_split_kernel(ChainArgs a) {
   {
     const __amdgpu_buffer_rsrc_t w3rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w3p), 0, 256 * 64 * 6, 0x00020000);
     const char* const trd = lds + kq * 256 + li * 16;                                 // + row, + K-step * CS_XTILE, + plane * 1024
-    item_loop(w3rs, [&](u32x4 (&x)[2][3], const int r) {
+    item_loop(w3rs, [&](spu4 (&x)[2][3], const int r) {
 #pragma unroll
       for (int sx = 0; sx < 2; ++sx)
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) x[sx][pl] = *reinterpret_cast<const u32x4*>(trd + r * CS_T2ROW + sx * CS_XTILE + pl * 1024);
+        for (int pl = 0; pl < 3; ++pl) x[sx][pl] = *reinterpret_cast<const spu4*>(trd + r * CS_T2ROW + sx * CS_XTILE + pl * 1024);
     }, a.b3, BR ? nullptr : a.res, a.res_cs, a.res_coff, BR, a.relu_out != 0);
   }
 }

@@ -255,6 +255,25 @@ bool conv_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int KW)
   return true;
 }
 
+// The chunk rule of every conv weight gradient (fp32 and split-fp32, stride 1 and 2): as many chunks as FIT `slots` resident blocks in one
+// round at `tiles` blocks per chunk, but a chunk no shorter than `min_positions` positions (a block's slab write and its share of the
+// reduce are paid per chunk); whole images per chunk, ceil(n_img / chunks) each, settled so that no chunk is empty
+int conv_wgrad_chunks(int n_img, long long positions_per_image, long long tiles, int slots, int min_positions) {
+  long long want = slots / tiles;
+  const long long min_imgs = (min_positions + positions_per_image - 1) / positions_per_image;
+  const long long max_chunks = (n_img + min_imgs - 1) / min_imgs;
+  if (want > max_chunks) want = max_chunks;
+  if (want < 1) want = 1;
+  int chunks = (int)want;
+  for (;;) {       // settle on chunks == ceil(n_img / ceil(n_img / chunks)): the kernels derive the images per chunk
+    const int ipc = (n_img + chunks - 1) / chunks;
+    const int c2 = (n_img + ipc - 1) / ipc;
+    if (c2 == chunks) break;
+    chunks = c2;
+  }
+  return chunks;
+}
+
 // The plan of one conv's backward: a function of these seven integers only.
 //   weight gradient: tiles = (Co / 64)(Ci / 64) blocks per chunk; as many chunks as FIT the resident slots in one round (floor: 520
 //   blocks on 512 slots ran 832 -> 256 in two rounds, 1.69 ms; 468 blocks in one), but a chunk no shorter than kWgMinPositions padded
@@ -266,18 +285,7 @@ bool conv_bwd_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size
   const int KK = KH * KW;
   const long long PP = KH == 1 ? (long long)H * W : (long long)(H + 2) * (W + 2);
   const long long tiles = (long long)(Co / 64) * (Ci / 64);
-  long long want = (KH == 1 ? kWgSlots1 : kWgSlots3) / tiles;
-  const long long min_imgs = (kWgMinPositions + PP - 1) / PP;
-  const long long max_chunks = (n_img + min_imgs - 1) / min_imgs;
-  if (want > max_chunks) want = max_chunks;
-  if (want < 1) want = 1;
-  int chunks = (int)want;
-  for (;;) {       // settle on chunks == ceil(n_img / ceil(n_img / chunks)): no empty chunk, the kernel derives the images per chunk
-    const int ipc = (n_img + chunks - 1) / chunks;
-    const int c2 = (n_img + ipc - 1) / ipc;
-    if (c2 == chunks) break;
-    chunks = c2;
-  }
+  const int chunks = conv_wgrad_chunks(n_img, PP, tiles, KH == 1 ? kWgSlots1 : kWgSlots3, kWgMinPositions);
   const long long M = (long long)n_img * H * W;
   const int nkt = KK * (Co / 32);
   int cfg = 3, sk = 1;

@@ -378,25 +378,14 @@ bool conv_s2_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int 
 
 // The plan of one stride-2 conv's backward: a function of these seven integers only.
 //   weight gradient: tiles = (Co / 64) ceil(Ci / 64) k blocks per chunk; as many chunks as fit the resident slots in one round, but a chunk
-//   no shorter than kS2MinPositions output pixels; whole images per chunk, ceil(n_img / chunks) each (conv_bwd_plan's rule)
+//   no shorter than kS2MinPositions output pixels; whole images per chunk, ceil(n_img / chunks) each (conv_wgrad_chunks, conv_bwd.hip)
 //   data gradient: the phase-major weight, nothing else (K is not split)
 bool conv_s2_bwd_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_floats, size_t* weight_floats, int* chunks_out) {
   if (!conv_s2_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return false;
   const int KK = KH * KW;
   const long long PP = (long long)(H / 2) * (W / 2);
   const long long tiles = (long long)(Co / 64) * ((Ci + 63) / 64) * KH;
-  long long want = kS2Slots / tiles;
-  const long long min_imgs = (kS2MinPositions + PP - 1) / PP;
-  const long long max_chunks = (n_img + min_imgs - 1) / min_imgs;
-  if (want > max_chunks) want = max_chunks;
-  if (want < 1) want = 1;
-  int chunks = (int)want;
-  for (;;) {       // settle on chunks == ceil(n_img / ceil(n_img / chunks)): no empty chunk
-    const int ipc = (n_img + chunks - 1) / chunks;
-    const int c2 = (n_img + ipc - 1) / ipc;
-    if (c2 == chunks) break;
-    chunks = c2;
-  }
+  const int chunks = conv_wgrad_chunks(n_img, PP, tiles, kS2Slots, kS2MinPositions);
   if (data_floats) *data_floats = (size_t)Co * Ci * KK;
   if (weight_floats) *weight_floats = (size_t)chunks * ((size_t)Co * Ci * KK + Co);
   if (chunks_out) *chunks_out = chunks;

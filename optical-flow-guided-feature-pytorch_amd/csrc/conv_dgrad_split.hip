@@ -30,14 +30,14 @@ constexpr int kDgThreads = 512;                // eight waves
 constexpr int kDgCus = 256;                    // the grid the form rule is sized for (a constant of the plan, not a device query)
 
 struct DgArgs {
-  const dsu4* wp;                  // packed weight planes
-  const dsu4* gp;                  // g planes [plane][M][Co / 8] pieces
+  const spu4* wp;                  // packed weight planes
+  const spu4* gp;                  // g planes [plane][M][Co / 8] pieces
   float* dx; int dx_cs, dx_coff;
   int n_img, H, W, Ci, Co, KS, pad, accumulate;
 };
 
 // one thread = one lane's piece of one (tap, co step, ci tile), all three planes
-__global__ __launch_bounds__(256) void conv_wpack_split_kernel(const float* __restrict__ src, dsu4* __restrict__ dst, int Co, int Ci, int KS) {
+__global__ __launch_bounds__(256) void conv_wpack_split_kernel(const float* __restrict__ src, spu4* __restrict__ dst, int Co, int Ci, int KS) {
   const int nct = Ci >> 4, ncs = Co >> 5;
   const int total = KS * KS * ncs * nct * 64;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -53,9 +53,9 @@ __global__ __launch_bounds__(256) void conv_wpack_split_kernel(const float* __re
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = s[(size_t)e * Ci * KS * KS];
-    dsu4 a, b, c;
-    ds_cut8(v, a, b, c);
-    dsu4* d = dst + (size_t)(i >> 6) * 192 + lane;
+    spu4 a, b, c;
+    sp_cut8(v, a, b, c);
+    spu4* d = dst + (size_t)(i >> 6) * 192 + lane;
     d[0] = a; d[64] = b; d[128] = c;
   }
 }
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
   constexpr bool AWhole = APieces % kDgThreads == 0;                                        // else the last A piece only for tid < the rest
   static_assert(WM * WN * 64 == kDgThreads && (Px * 4) % kDgThreads == 0 && PJ >= 1, "geometry");
   // two buffers of: A pieces [ci tile][plane][lane], then B pieces [pixel tile][plane][lane]
-  extern __shared__ __attribute__((aligned(16))) dsu4 lds[];
+  extern __shared__ __attribute__((aligned(16))) spu4 lds[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,10 +97,10 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
   }
   const int bdst = APieces + (px0 >> 4) * 192 + kg * 16 + (px0 & 15);      // pixel px0 + 128 j: eight pixel tiles further
 
-  dsu4 ar[AJ], br[PJ][3];
+  spu4 ar[AJ], br[PJ][3];
   int kh = 0, kw = 0, cs = 0, t_next = 0;                              // the step load_step loads next
   auto load_step = [&]() {
-    const dsu4* wstep = p.wp + (size_t)t_next * step_pieces;
+    const spu4* wstep = p.wp + (size_t)t_next * step_pieces;
 #pragma unroll
     for (int j = 0; j < AJ; ++j) ar[j] = wstep[min(abase + kDgThreads * j, alast)];
 #pragma unroll
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
       const size_t pix = ok ? (size_t)((gimg[j] * H + a) * W + b) : 0;
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        dsu4 v = p.gp[((size_t)q * M + pix) * c8 + cs * 4 + kg];
-        if (!ok) v = dsu4{0u, 0u, 0u, 0u};
+        spu4 v = p.gp[((size_t)q * M + pix) * c8 + cs * 4 + kg];
+        if (!ok) v = spu4{0u, 0u, 0u, 0u};
         br[j][q] = v;
       }
     }
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
     }
   };
   auto store_step = [&](int buf) {
-    dsu4* const d = lds + buf * Buf;
+    spu4* const d = lds + buf * Buf;
 #pragma unroll
     for (int j = 0; j < AJ; ++j)
       if (AWhole || j + 1 < AJ || tid + kDgThreads * j < APieces) d[tid + kDgThreads * j] = ar[j];
@@ -133,39 +133,39 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
       for (int q = 0; q < 3; ++q) d[bdst + j * (8 * 192) + q * 64] = br[j][q];
   };
 
-  dsf4 a1[CT][PT], a2[CT][PT];
+  spf4 a1[CT][PT], a2[CT][PT];
 #pragma unroll
   for (int mt = 0; mt < CT; ++mt)
 #pragma unroll
-    for (int nt = 0; nt < PT; ++nt) { a1[mt][nt] = dsf4{0.f, 0.f, 0.f, 0.f}; a2[mt][nt] = dsf4{0.f, 0.f, 0.f, 0.f}; }
+    for (int nt = 0; nt < PT; ++nt) { a1[mt][nt] = spf4{0.f, 0.f, 0.f, 0.f}; a2[mt][nt] = spf4{0.f, 0.f, 0.f, 0.f}; }
   const bool busy = ct0 + wm * CT < nct;             // a wave whose ci tiles lie behind Ci stages, waits at the barriers and computes nothing
 
   auto mma_step = [&](int buf) {
-    const dsu4* const la = lds + buf * Buf + wm * CT * 192 + lane;
-    const dsu4* const lb = lds + buf * Buf + APieces + wn * PT * 192 + lane;
-    dsu4 wa[CT][3];
+    const spu4* const la = lds + buf * Buf + wm * CT * 192 + lane;
+    const spu4* const lb = lds + buf * Buf + APieces + wn * PT * 192 + lane;
+    spu4 wa[CT][3];
 #pragma unroll
     for (int mt = 0; mt < CT; ++mt)
 #pragma unroll
       for (int q = 0; q < 3; ++q) wa[mt][q] = la[(mt * 3 + q) * 64];
 #pragma unroll
     for (int nt = 0; nt < PT; ++nt) {
-      dsu4 gx[3];
+      spu4 gx[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) gx[q] = lb[(nt * 3 + q) * 64];
       // synth.SPLIT_PRODUCTS order (w plane, g plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a2[mt][nt], wa[mt][2], gx[0]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a2[mt][nt], wa[mt][2], gx[0]);
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a2[mt][nt], wa[mt][0], gx[2]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a2[mt][nt], wa[mt][0], gx[2]);
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a2[mt][nt], wa[mt][1], gx[1]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a2[mt][nt], wa[mt][1], gx[1]);
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a2[mt][nt], wa[mt][1], gx[0]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a2[mt][nt], wa[mt][1], gx[0]);
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a2[mt][nt], wa[mt][0], gx[1]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a2[mt][nt], wa[mt][0], gx[1]);
 #pragma unroll
-      for (int mt = 0; mt < CT; ++mt) ds_mfma(a1[mt][nt], wa[mt][0], gx[0]);
+      for (int mt = 0; mt < CT; ++mt) sp_mfma(a1[mt][nt], wa[mt][0], gx[0]);
     }
   };
 
@@ -193,8 +193,8 @@ __global__ __launch_bounds__(kDgThreads, 2) void conv_dgrad_split_kernel(DgArgs 
     for (int mt = 0; mt < CT; ++mt) {
       const int ci = (ct0 + wm * CT + mt) * 16 + lq * 4;
       if (ci >= p.Ci) continue;
-      dsf4 v = a1[mt][nt] + a2[mt][nt];
-      dsf4* dst = reinterpret_cast<dsf4*>(row + ci);
+      spf4 v = a1[mt][nt] + a2[mt][nt];
+      spf4* dst = reinterpret_cast<spf4*>(row + ci);
       if (p.accumulate) v += *dst;
       *dst = v;
       __builtin_amdgcn_sched_barrier(0);
@@ -246,8 +246,8 @@ hipError_t conv_dgrad_split_launch(const float* g, int g_cs, int g_coff, int n_i
   size_t wbytes = 0;
   if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KS, KS, &wbytes, nullptr)) return hipErrorInvalidValue;
   const int M = n_img * H * W;
-  dsu4* wp = static_cast<dsu4*>(scratch);
-  dsu4* gp = reinterpret_cast<dsu4*>(static_cast<char*>(scratch) + wbytes);
+  spu4* wp = static_cast<spu4*>(scratch);
+  spu4* gp = reinterpret_cast<spu4*>(static_cast<char*>(scratch) + wbytes);
   const long long wthreads = (long long)KS * KS * (Co / 32) * (Ci / 16) * 64;
   hipLaunchKernelGGL(conv_wpack_split_kernel, dim3((unsigned)((wthreads + 255) / 256)), dim3(256), 0, st, w_oihw, wp, Co, Ci, KS);
   hipError_t e = hipGetLastError();

@@ -3,7 +3,7 @@
 // conv_wgrad_split_kernel's operand handling (conv_wgrad_split.hip):
 //     dw[co][ci][kh][kw] = sum_{n, oh, ow} g[n, oh, ow, co] * in(x)[n, 2 (oh + fh) + rph, 2 (ow + fw) + sph, ci],   db[co] = sum g
 //   with rph = (kh - pad) & 1, fh = floor((kh - pad) / 2) and sph, fw the same for kw (fw = -2 .. 1 for the 7x7, -1 .. 1 for the 5x5).
-// Both operands are cut into THREE bf16 planes by truncation (cs_cut of conv_wgrad_split.hip = synth.cut3) and per 32-position step and tap
+// Both operands are cut into THREE bf16 planes by truncation (sp_cut of split_common.h = synth.cut3) and per 32-position step and tap
 // six of the nine plane products are issued on v_mfma_f32_16x16x32_bf16 in synth.SPLIT_PRODUCTS order with g in the role of w: g_l x_h,
 // g_h x_l, g_m x_m, g_m x_h, g_h x_m into accumulator A2, g_h x_h into A1; steps in increasing order, the block's partial tile is A1 + A2,
 // added once: synth.emulate_split_dot(form="units") over the block's chunk.  The slabs [chunk][Co][Ci k k] (+ [chunk][Co]) are summed in
@@ -34,6 +34,7 @@
 // fixed order: nothing is split.  The blocks of kernel row 0 and ci tile 0 write it.
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace {
@@ -52,10 +53,6 @@ constexpr int kWsMinPositions = 256;    // a chunk is at least eight steps long 
 constexpr int kWsPlane = 4096;          // one plane of an image: 4 tiles x 4 k groups x 256 B
 constexpr int kWsImage = 3 * kWsPlane;  // x images 0 .. KS - 1, then g
 
-typedef float wsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned wsu4 __attribute__((ext_vector_type(4)));
-typedef unsigned wsu2 __attribute__((ext_vector_type(2)));
-
 struct WsArgs {
   const float* x; int x_cs, x_coff;
   const float* g; int g_cs, g_coff;
@@ -65,20 +62,6 @@ struct WsArgs {
   float* slab;                    // [chunks][Co][Ci * KS * KS]
   float* dbslab;                  // [chunks][Co]
 };
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void ws_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned ws_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-__device__ __forceinline__ void ws_mfma(wsf4& c, const wsu4& a, const wsu4& x) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 template <int KS>
 __global__ __launch_bounds__(512) void conv_s2_wgrad_split_kernel(WsArgs p) {
@@ -208,12 +191,9 @@ __global__ __launch_bounds__(512) void conv_s2_wgrad_split_kernel(WsArgs p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float v = i == 0 ? r[s][j].x : (i == 1 ? r[s][j].y : (i == 2 ? r[s][j].z : r[s][j].w));
-          ws_cut(v, h[j], m[j], l[j]);
+          sp_cut(v, h[j], m[j], l[j]);
         }
-        char* d = d0 + (((4 * (cq & 3) + i) ^ slot) << 4);
-        *reinterpret_cast<wsu2*>(d) = wsu2{ws_pair(h[0], h[1]), ws_pair(h[2], h[3])};
-        *reinterpret_cast<wsu2*>(d + kWsPlane) = wsu2{ws_pair(m[0], m[1]), ws_pair(m[2], m[3])};
-        *reinterpret_cast<wsu2*>(d + 2 * kWsPlane) = wsu2{ws_pair(l[0], l[1]), ws_pair(l[2], l[3])};
+        sp_store_quad<3>(d0 + (((4 * (cq & 3) + i) ^ slot) << 4), kWsPlane, h, m, l);
       }
     }
   };
@@ -224,37 +204,37 @@ __global__ __launch_bounds__(512) void conv_s2_wgrad_split_kernel(WsArgs p) {
   const int goff = KS * kWsImage + gt0 * 1024 + lq * 256 + ((lr ^ lq) << 4);
   const int xoff = xt0 * 1024 + lq * 256 + ((lr ^ lq) << 4);
 
-  wsf4 a1[KS][2], a2[KS][2];
+  spf4 a1[KS][2], a2[KS][2];
 #pragma unroll
   for (int t = 0; t < KS; ++t)
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) { a1[t][mt] = wsf4{0.f, 0.f, 0.f, 0.f}; a2[t][mt] = wsf4{0.f, 0.f, 0.f, 0.f}; }
+    for (int mt = 0; mt < 2; ++mt) { a1[t][mt] = spf4{0.f, 0.f, 0.f, 0.f}; a2[t][mt] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   auto mma_step = [&](int buf) {
     const char* const base = lds + buf * BUFB;
-    wsu4 ga[2][3];
+    spu4 ga[2][3];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) ga[mt][q] = *reinterpret_cast<const wsu4*>(base + goff + mt * 1024 + q * kWsPlane);
+      for (int q = 0; q < 3; ++q) ga[mt][q] = *reinterpret_cast<const spu4*>(base + goff + mt * 1024 + q * kWsPlane);
 #pragma unroll
     for (int kw = 0; kw < KS; ++kw) {
-      wsu4 xb[3];
+      spu4 xb[3];
 #pragma unroll
-      for (int q = 0; q < 3; ++q) xb[q] = *reinterpret_cast<const wsu4*>(base + xoff + kw * kWsImage + q * kWsPlane);
+      for (int q = 0; q < 3; ++q) xb[q] = *reinterpret_cast<const spu4*>(base + xoff + kw * kWsImage + q * kWsPlane);
       // synth.SPLIT_PRODUCTS order (g plane, x plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a2[kw][mt], ga[mt][2], xb[0]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a2[kw][mt], ga[mt][2], xb[0]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a2[kw][mt], ga[mt][0], xb[2]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a2[kw][mt], ga[mt][0], xb[2]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a2[kw][mt], ga[mt][1], xb[1]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a2[kw][mt], ga[mt][1], xb[1]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a2[kw][mt], ga[mt][1], xb[0]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a2[kw][mt], ga[mt][1], xb[0]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a2[kw][mt], ga[mt][0], xb[1]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a2[kw][mt], ga[mt][0], xb[1]);
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) ws_mfma(a1[kw][mt], ga[mt][0], xb[0]);
+      for (int mt = 0; mt < 2; ++mt) sp_mfma(a1[kw][mt], ga[mt][0], xb[0]);
     }
   };
 
@@ -287,18 +267,8 @@ __global__ __launch_bounds__(512) void conv_s2_wgrad_split_kernel(WsArgs p) {
   }
   // ---- bias partials (kernel row 0 of the first ci tile only; behind a barrier): the eight position quads of a channel in quad order ----
   if (p.want_db && ntile == 0 && kh == 0) {
-    float* red = reinterpret_cast<float*>(lds);       // [8 quads][64 channels]
     if (NBUF == 2) __syncthreads();                    // (the K loop of the two-buffer form does not end with a barrier)
-    if (is_g[0] || (on[1] && is_g[1])) {
-      red[pq * 64 + 4 * cq] = bs.x; red[pq * 64 + 4 * cq + 1] = bs.y; red[pq * 64 + 4 * cq + 2] = bs.z; red[pq * 64 + 4 * cq + 3] = bs.w;
-    }
-    __syncthreads();
-    if (tid < 64) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += red[i * 64 + tid];
-      p.dbslab[(size_t)chunk * p.Co + co0 + tid] = s;
-    }
+    sp_db_quads(reinterpret_cast<float*>(lds), is_g[0] || (on[1] && is_g[1]), pq, cq, bs, tid, p.dbslab, (size_t)chunk * p.Co + co0);
   }
 }
 
@@ -307,23 +277,13 @@ __global__ __launch_bounds__(512) void conv_s2_wgrad_split_kernel(WsArgs p) {
 // The plan of the stride-2 split weight gradient: a function of these seven integers only.  tiles = (Co / 64) ceil(Ci / 64) k blocks per
 // chunk at one block per CU; as many chunks as fit one round of the 256 CUs (7x7) or two (5x5: 170 tiles would leave a third of the CUs
 // idle in one), but a chunk no shorter than kWsMinPositions output pixels; whole images per chunk, ceil(n_img / chunks) each, no empty chunk
+// (conv_wgrad_chunks, conv_bwd.hip)
 bool conv_s2_wgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_floats, int* chunks_out) {
   if (!conv_s2_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return false;
   const int KK = KH * KW;
   const long long PP = (long long)(H / 2) * (W / 2);
   const long long tiles = (long long)(Co / 64) * ((Ci + 63) / 64) * KH;
-  long long want = (KH == 5 ? kWsSlots5 : kWsSlots7) / tiles;
-  const long long min_imgs = (kWsMinPositions + PP - 1) / PP;
-  const long long max_chunks = (n_img + min_imgs - 1) / min_imgs;
-  if (want > max_chunks) want = max_chunks;
-  if (want < 1) want = 1;
-  int chunks = (int)want;
-  for (;;) {       // settle on chunks == ceil(n_img / ceil(n_img / chunks)): no empty chunk
-    const int ipc = (n_img + chunks - 1) / chunks;
-    const int c2 = (n_img + ipc - 1) / ipc;
-    if (c2 == chunks) break;
-    chunks = c2;
-  }
+  const int chunks = conv_wgrad_chunks(n_img, PP, tiles, KH == 5 ? kWsSlots5 : kWsSlots7, kWsMinPositions);
   if (weight_floats) *weight_floats = (size_t)chunks * ((size_t)Co * Ci * KK + Co);
   if (chunks_out) *chunks_out = chunks;
   return true;

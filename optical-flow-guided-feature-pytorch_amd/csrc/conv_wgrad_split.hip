@@ -1,7 +1,7 @@
 // K4b's weight / bias gradient in split-fp32 arithmetic on the bf16 matrix pipe (offk_conv2d_backward_weight_split):
 //   dw[co][ci][kh][kw] = sum_q g_pad[q][co] * x_pad[q + (kh - pad) * pitch + (kw - pad)][ci],   db[co] = sum_q g_pad[q][co]
-// for one stride-1 fusion conv, k = 1 or 3.  Both operands are cut into THREE bf16 planes by truncation (cs_cut = ws_cut of
-// units_wgrad_split.hip = synth.cut3) and per 32-position step six of the nine plane products are issued on v_mfma_f32_16x16x32_bf16 in
+// for one stride-1 fusion conv, k = 1 or 3.  Both operands are cut into THREE bf16 planes by truncation (sp_cut of split_common.h =
+// synth.cut3) and per 32-position step six of the nine plane products are issued on v_mfma_f32_16x16x32_bf16 in
 // synth.SPLIT_PRODUCTS order with g in the role of w: g_l x_h, g_h x_l, g_m x_m, g_m x_h, g_h x_m into accumulator A2, g_h x_h into A1; steps
 // in increasing position order, the block's partial tile is A1 + A2, added once: synth.emulate_split_dot(form="units") over the block's chunk.
 // The slabs [chunk][Co][Ci k k] (+ [chunk][Co]) are summed in chunk order by the unchanged conv_wgrad_reduce_kernel (conv_bwd.hip).
@@ -30,6 +30,7 @@
 // eight quads of a step in a fixed order: nothing is split.
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace {
@@ -40,10 +41,6 @@ constexpr int kCsSlots1 = 1024;         // 1x1: four blocks per CU (24 KB of LDS
 constexpr int kCsMinPositions = 256;    // a chunk is at least eight steps long (unless the whole problem is shorter)
 constexpr int kCsGPlane = 4096;         // one plane of the g rows: 4 tiles x 4 k groups x 256 B
 constexpr int kCsXBase = 3 * kCsGPlane;
-
-typedef float csf4 __attribute__((ext_vector_type(4)));
-typedef unsigned csu4 __attribute__((ext_vector_type(4)));
-typedef unsigned csu2 __attribute__((ext_vector_type(2)));
 
 struct CsArgs {
   const float* x; int x_cs;       // channel offset and the block's first channel are added by the kernel
@@ -57,20 +54,6 @@ struct CsArgs {
   float* slab;                    // [chunks][Co][Ci * KK]
   float* dbslab;                  // [chunks][Co]
 };
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void cs_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned cs_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-__device__ __forceinline__ void cs_mfma(csf4& c, const csu4& a, const csu4& x) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 // pixel row of position q, or -1 where the position is a zero (pad column, zero row, outside [0, q_lim))
 template <int KS>
@@ -181,21 +164,15 @@ __global__ __launch_bounds__(KS == 3 ? 512 : 256) void conv_wgrad_split_kernel(C
 #pragma unroll
       for (int j = 0; j < NL; ++j) {
         const float v = i == 0 ? r[j].x : (i == 1 ? r[j].y : (i == 2 ? r[j].z : r[j].w));
-        cs_cut(v, h[j], m[j], l[j]);
+        sp_cut(v, h[j], m[j], l[j]);
       }
       const int rowoff = (((4 * (cq & 3) + i) ^ swz) << 4);
       if (is_g) {
-        char* d = gdst + rowoff;
-        *reinterpret_cast<csu2*>(d) = csu2{cs_pair(h[J0], h[J0 + 1]), cs_pair(h[J0 + 2], h[J0 + 3])};
-        *reinterpret_cast<csu2*>(d + kCsGPlane) = csu2{cs_pair(m[J0], m[J0 + 1]), cs_pair(m[J0 + 2], m[J0 + 3])};
-        *reinterpret_cast<csu2*>(d + 2 * kCsGPlane) = csu2{cs_pair(l[J0], l[J0 + 1]), cs_pair(l[J0 + 2], l[J0 + 3])};
+        sp_store_quad<3>(gdst + rowoff, kCsGPlane, h + J0, m + J0, l + J0);
       } else {
 #pragma unroll
         for (int kw = 0; kw < KS; ++kw) {      // image kw holds x_pad[q + kw - pad]: loads kw .. kw + 3
-          char* d = xdst + kw * ximg + rowoff;
-          *reinterpret_cast<csu2*>(d) = csu2{cs_pair(h[kw], h[kw + 1]), cs_pair(h[kw + 2], h[kw + 3])};
-          *reinterpret_cast<csu2*>(d + xplane) = csu2{cs_pair(m[kw], m[kw + 1]), cs_pair(m[kw + 2], m[kw + 3])};
-          *reinterpret_cast<csu2*>(d + 2 * xplane) = csu2{cs_pair(l[kw], l[kw + 1]), cs_pair(l[kw + 2], l[kw + 3])};
+          sp_store_quad<3>(xdst + kw * ximg + rowoff, xplane, h + kw, m + kw, l + kw);
         }
       }
     }
@@ -212,55 +189,31 @@ __global__ __launch_bounds__(KS == 3 ? 512 : 256) void conv_wgrad_split_kernel(C
     xoff[kh] = kCsXBase + xt0 * (NG * 256) + s * 256 + ((lr ^ (s & 3)) << 4);
   }
 
-  csf4 a1[KK][2][NTW], a2[KK][2][NTW];
+  spf4 a1[KK][2][NTW], a2[KK][2][NTW];
 #pragma unroll
   for (int t = 0; t < KK; ++t)
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < NTW; ++nt) { a1[t][mt][nt] = csf4{0.f, 0.f, 0.f, 0.f}; a2[t][mt][nt] = csf4{0.f, 0.f, 0.f, 0.f}; }
+      for (int nt = 0; nt < NTW; ++nt) { a1[t][mt][nt] = spf4{0.f, 0.f, 0.f, 0.f}; a2[t][mt][nt] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   auto mma_step = [&]() {
-    csu4 ga[2][3];
+    spu4 ga[2][3];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) ga[mt][q] = *reinterpret_cast<const csu4*>(lds + goff + mt * 1024 + q * kCsGPlane);
+      for (int q = 0; q < 3; ++q) ga[mt][q] = *reinterpret_cast<const spu4*>(lds + goff + mt * 1024 + q * kCsGPlane);
 #pragma unroll
     for (int kh = 0; kh < KS; ++kh)
 #pragma unroll
       for (int kw = 0; kw < KS; ++kw) {
         const int tap = kh * KS + kw;
-        csu4 xb[NTW][3];
+        spu4 xb[NTW][3];
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
-          for (int q = 0; q < 3; ++q) xb[nt][q] = *reinterpret_cast<const csu4*>(lds + xoff[kh] + kw * ximg + q * xplane + nt * (NG * 256));
-        // synth.SPLIT_PRODUCTS order (g plane, x plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a2[tap][mt][nt], ga[mt][2], xb[nt][0]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a2[tap][mt][nt], ga[mt][0], xb[nt][2]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a2[tap][mt][nt], ga[mt][1], xb[nt][1]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a2[tap][mt][nt], ga[mt][1], xb[nt][0]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a2[tap][mt][nt], ga[mt][0], xb[nt][1]);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) cs_mfma(a1[tap][mt][nt], ga[mt][0], xb[nt][0]);
+          for (int q = 0; q < 3; ++q) xb[nt][q] = *reinterpret_cast<const spu4*>(lds + xoff[kh] + kw * ximg + q * xplane + nt * (NG * 256));
+        sp_issue6<2, NTW>(a1[tap], a2[tap], ga, xb);      // g in the role of w
       }
   };
 
@@ -290,17 +243,7 @@ __global__ __launch_bounds__(KS == 3 ? 512 : 256) void conv_wgrad_split_kernel(C
     }
   // ---- bias partials (first ci tile only; the K loop ended with a barrier): the eight position quads of a channel in quad order ----
   if (p.want_db && ntile == 0) {
-    float* red = reinterpret_cast<float*>(lds);       // [8 quads][64 channels]
-    if (is_g) {
-      red[pq * 64 + 4 * cq] = bs.x; red[pq * 64 + 4 * cq + 1] = bs.y; red[pq * 64 + 4 * cq + 2] = bs.z; red[pq * 64 + 4 * cq + 3] = bs.w;
-    }
-    __syncthreads();
-    if (tid < 64) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += red[i * 64 + tid];
-      p.dbslab[(size_t)chunk * p.Co + co0 + tid] = s;
-    }
+    sp_db_quads(reinterpret_cast<float*>(lds), is_g, pq, cq, bs, tid, p.dbslab, (size_t)chunk * p.Co + co0);
   }
 }
 
@@ -317,24 +260,13 @@ bool conv_wgrad_split_supported(int n_img, int H, int W, int Ci, int Co, int KH,
 
 // The plan of the split weight gradient: a function of these seven integers only.  tiles = (Co / 64)(Ci / 64) blocks per chunk; as many
 // chunks as fit the resident slots in one round (k = 3: one block per CU; k = 1: four), but a chunk no shorter than kCsMinPositions
-// positions; whole images per chunk, ceil(n_img / chunks) each, no empty chunk
+// positions; whole images per chunk, ceil(n_img / chunks) each, no empty chunk (conv_wgrad_chunks, conv_bwd.hip)
 bool conv_wgrad_split_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_floats, int* chunks_out) {
   if (!conv_wgrad_split_supported(n_img, H, W, Ci, Co, KH, KW)) return false;
   const int KK = KH * KW;
   const long long PP = KH == 1 ? (long long)H * W : ((long long)H + 1) * cs_pitch(W, KH);
   const long long tiles = (long long)(Co / 64) * (Ci / 64);
-  long long want = (KH == 1 ? kCsSlots1 : kCsSlots3) / tiles;
-  const long long min_imgs = (kCsMinPositions + PP - 1) / PP;
-  const long long max_chunks = (n_img + min_imgs - 1) / min_imgs;
-  if (want > max_chunks) want = max_chunks;
-  if (want < 1) want = 1;
-  int chunks = (int)want;
-  for (;;) {       // settle on chunks == ceil(n_img / ceil(n_img / chunks))
-    const int ipc = (n_img + chunks - 1) / chunks;
-    const int c2 = (n_img + ipc - 1) / ipc;
-    if (c2 == chunks) break;
-    chunks = c2;
-  }
+  const int chunks = conv_wgrad_chunks(n_img, PP, tiles, KH == 1 ? kCsSlots1 : kCsSlots3, kCsMinPositions);
   if (weight_floats) *weight_floats = (size_t)chunks * ((size_t)Co * Ci * KK + Co);
   if (chunks_out) *chunks_out = chunks;
   return true;

@@ -2128,7 +2128,7 @@ int offk_conv2d_ex(void* stream, const float* x, int x_cstride, int x_coff, int 
   return OFFK_OK;
 }
 
-// ---- K4b: backward of one stride-1 fusion conv (conv_bwd.hip) ----
+// ---- K4b: backward of one fusion conv: stride 1 (conv_bwd.hip) or stride 2 (conv_bwd_s2.hip), exact fp32 or split-fp32 ----
 namespace {
 // a channels-last view [rows][cstride] that holds C channels at coff; nullptr = fine, else what is wrong with it
 const char* view_problem(const void* ptr, int cstride, int coff, int C) {
@@ -2138,9 +2138,9 @@ const char* view_problem(const void* ptr, int cstride, int coff, int C) {
   if (cstride < coff + C) return "cstride < coff + C";
   return nullptr;
 }
-bool views_overlap(const void* a, int a_cs, const void* b, int b_cs, long long rows) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), a1 = a0 + (size_t)rows * (size_t)a_cs * sizeof(float);
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(b), b1 = b0 + (size_t)rows * (size_t)b_cs * sizeof(float);
+bool views_overlap(const void* a, int a_cs, long long a_rows, const void* b, int b_cs, long long b_rows) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), a1 = a0 + (size_t)a_rows * (size_t)a_cs * sizeof(float);
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(b), b1 = b0 + (size_t)b_rows * (size_t)b_cs * sizeof(float);
   return a0 < b1 && b0 < a1;
 }
 int conv_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {
@@ -2151,19 +2151,151 @@ int conv_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int
   if (!conv_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
   return OFFK_OK;
 }
+int conv_s2_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {
+  if (n_img < 1 || H < 2 || W < 2) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (n_img >= 1, H, W >= 2)");
+  if (!(KH == KW && ((KH == 7 && pad == 3) || (KH == 5 && pad == 2))))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": the form must be 7x7 with pad 3 or 5x5 with pad 2 (stride 2)");
+  if ((H & 1) || (W & 1)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": H and W (the input map) must be even");
+  if (Ci < 32 || Co < 64 || Ci % 32 || Co % 64) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need Ci % 32 == 0 and Co % 64 == 0");
+  if (!conv_s2_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
+  return OFFK_OK;
+}
+
+// One row per (stride, arithmetic): what the entries of that form differ in.  The bodies below are the entries; a new form is a row.
+struct ConvBwdForm {
+  int (*shape)(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad);
+  int g_step;                          // g (the output's gradient) has (H / g_step)(W / g_step) rows per image
+  const char* plan_fail;               // what a plan that refuses a shape the shape check let through is reported as
+  // data gradient: scratch bytes, the launch, the plan entry named by "scratch too small (...)", must the scratch be 16-byte aligned
+  bool (*data_plan)(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* bytes);
+  hipError_t (*data_launch)(const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw, int Ci, int KS, int pad,
+                            float* dx, int dx_cs, int dx_coff, int accumulate, void* scratch, size_t plan_bytes, hipStream_t st, const char** why);
+  const char* data_plan_entry;
+  bool data_align16;
+  // weight gradient: scratch floats and K chunks, the launch, the plan entry named by "scratch too small (...)"
+  bool (*weight_plan)(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* floats, int* chunks);
+  hipError_t (*weight_launch)(const float* x, int x_cs, int x_coff, const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Ci, int Co,
+                              int KS, int relu_in, float* dw, float* db, int accumulate, float* scratch, int chunks, hipStream_t st);
+  const char* weight_plan_entry;
+};
+
+#define OFFK_DATA_PLAN_ARGS int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* bytes
+#define OFFK_DATA_LAUNCH_ARGS                                                                                                                  \
+  const float* g, int g_cs, int g_coff, int n_img, int H, int W, int Co, const float* w, int Ci, int KS, int pad, float* dx, int dx_cs, int dx_coff, \
+      int acc, void* scratch, size_t plan_bytes, hipStream_t st, const char** why
+bool split_bytes(bool ok, size_t wb, size_t gb, size_t* bytes) { *bytes = wb + gb; return ok; }
+
+const ConvBwdForm kConvBwdS1 = {
+    conv_bwd_shape, 1, ": unsupported shape",
+    [](OFFK_DATA_PLAN_ARGS) {
+      const bool ok = conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, bytes, nullptr, nullptr, nullptr);
+      *bytes *= sizeof(float);
+      return ok;
+    },
+    [](OFFK_DATA_LAUNCH_ARGS) {
+      return conv_bwd_data_launch(g, g_cs, g_coff, n_img, H, W, Co, w, Ci, KS, dx, dx_cs, dx_coff, acc, static_cast<float*>(scratch),
+                                  plan_bytes / sizeof(float), st, why);
+    },
+    "offk_conv2d_backward_plan", false,
+    [](int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* floats, int* chunks) {
+      return conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, floats, chunks, nullptr);
+    },
+    conv_bwd_weight_launch, "offk_conv2d_backward_plan"};
+const ConvBwdForm kConvBwdS1Split = {
+    conv_bwd_shape, 1, ": problem too large",
+    [](OFFK_DATA_PLAN_ARGS) {
+      size_t wb = 0, gb = 0;
+      return split_bytes(conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb), wb, gb, bytes);
+    },
+    [](OFFK_DATA_LAUNCH_ARGS) { return conv_dgrad_split_launch(g, g_cs, g_coff, n_img, H, W, Co, w, Ci, KS, pad, dx, dx_cs, dx_coff, acc, scratch, st); },
+    "offk_conv2d_backward_data_plan_split", true,
+    conv_wgrad_split_plan, conv_wgrad_split_launch, "offk_conv2d_backward_plan_split"};
+const ConvBwdForm kConvBwdS2 = {
+    conv_s2_bwd_shape, 2, ": unsupported shape",
+    [](OFFK_DATA_PLAN_ARGS) {
+      const bool ok = conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, bytes, nullptr, nullptr);
+      *bytes *= sizeof(float);
+      return ok;
+    },
+    [](OFFK_DATA_LAUNCH_ARGS) {
+      return conv_s2_bwd_data_launch(g, g_cs, g_coff, n_img, H, W, Co, w, Ci, KS, pad, dx, dx_cs, dx_coff, acc, static_cast<float*>(scratch), st);
+    },
+    "offk_conv2d_s2_backward_plan", false,
+    [](int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* floats, int* chunks) {
+      return conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, floats, chunks);
+    },
+    conv_s2_bwd_weight_launch, "offk_conv2d_s2_backward_plan"};
+const ConvBwdForm kConvBwdS2Split = {
+    conv_s2_bwd_shape, 2, ": problem too large",
+    [](OFFK_DATA_PLAN_ARGS) {
+      size_t wb = 0, gb = 0;
+      return split_bytes(conv_s2_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb), wb, gb, bytes);
+    },
+    [](OFFK_DATA_LAUNCH_ARGS) { return conv_s2_dgrad_split_launch(g, g_cs, g_coff, n_img, H, W, Co, w, Ci, KS, pad, dx, dx_cs, dx_coff, acc, scratch, st); },
+    "offk_conv2d_s2_backward_plan_split", true,
+    conv_s2_wgrad_split_plan, conv_s2_wgrad_split_launch, "offk_conv2d_s2_backward_weight_plan_split"};
+#undef OFFK_DATA_PLAN_ARGS
+#undef OFFK_DATA_LAUNCH_ARGS
+
+// A plan entry: the shape check, then the data gradient's scratch bytes and / or the weight gradient's scratch bytes and chunks (whatever
+// the entry returns; a null output pointer is skipped)
+int conv_bwd_plan_entry(const ConvBwdForm& f, const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, bool data, bool weight,
+                        size_t* data_scratch_bytes, size_t* weight_scratch_bytes, int* weight_chunks) {
+  if (int rc = f.shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
+  size_t db = 0, wf = 0;
+  int chunks = 0;
+  if ((data && !f.data_plan(n_img, H, W, Ci, Co, KH, KW, &db)) || (weight && !f.weight_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + f.plan_fail);
+  if (data_scratch_bytes) *data_scratch_bytes = db;
+  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
+  if (weight_chunks) *weight_chunks = chunks;
+  return OFFK_OK;
+}
+
+int conv_bwd_data_entry(const ConvBwdForm& f, const char* who, void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W,
+                        int Co, const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate,
+                        void* scratch, size_t scratch_bytes) {
+  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = f.shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
+  const long long g_rows = (long long)n_img * (H / f.g_step) * (W / f.g_step), dx_rows = (long long)n_img * H * W;
+  if (views_overlap(dx, dx_cstride, dx_rows, g, g_cstride, g_rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
+  size_t bytes = 0;
+  if (!f.data_plan(n_img, H, W, Ci, Co, KH, KW, &bytes)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + f.plan_fail);
+  if (scratch_bytes < bytes) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (" + f.data_plan_entry + ")");
+  if (f.data_align16 && reinterpret_cast<uintptr_t>(scratch) % 16)
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch must be 16-byte aligned");
+  const char* why = nullptr;
+  hipError_t e = f.data_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0, scratch, bytes,
+                               static_cast<hipStream_t>(stream), &why);
+  if (e != hipSuccess) return why ? fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": " + why) : fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
+
+int conv_bwd_weight_entry(const ConvBwdForm& f, const char* who, void* stream, const float* x, int x_cstride, int x_coff, const float* g,
+                          int g_cstride, int g_coff, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in,
+                          float* dw_oihw, float* db, int accumulate, void* scratch, size_t scratch_bytes) {
+  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
+  if (int rc = f.shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
+  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
+  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
+  size_t wf = 0;
+  int chunks = 0;
+  if (!f.weight_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + f.plan_fail);
+  if (scratch_bytes < wf * sizeof(float))
+    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (" + f.weight_plan_entry + ")");
+  hipError_t e = f.weight_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db, accumulate != 0,
+                                 static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail_hip(nullptr, e, who);
+  return OFFK_OK;
+}
 }  // namespace
 
 int offk_conv2d_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
                               size_t* weight_scratch_bytes, int* weight_chunks) {
-  const char* who = "offk_conv2d_backward_plan";
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t df = 0, wf = 0;
-  int chunks = 0;
-  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, &wf, &chunks, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (data_scratch_bytes) *data_scratch_bytes = df * sizeof(float);
-  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
-  if (weight_chunks) *weight_chunks = chunks;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS1, "offk_conv2d_backward_plan", n_img, H, W, Ci, Co, KH, KW, true, true, data_scratch_bytes,
+                             weight_scratch_bytes, weight_chunks);
 }
 
 int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_coff, const float* y, int y_cstride, int y_coff, int rows, int C,
@@ -2174,9 +2306,9 @@ int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_cof
   if (const char* w = view_problem(y, y_cstride, y_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": y: " + w);
   if (const char* w = view_problem(g, g_cstride, g_coff, C)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
   const bool in_place = g == dy && g_cstride == dy_cstride && g_coff == dy_coff;
-  if (!in_place && views_overlap(g, g_cstride, dy, dy_cstride, rows))
+  if (!in_place && views_overlap(g, g_cstride, rows, dy, dy_cstride, rows))
     return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g overlaps dy without being dy itself (same pointer, stride and offset)");
-  if (views_overlap(g, g_cstride, y, y_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g overlaps y");
+  if (views_overlap(g, g_cstride, rows, y, y_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g overlaps y");
   hipError_t e = relu_backward_launch(dy, dy_cstride, dy_coff, y, y_cstride, y_coff, rows, C, g, g_cstride, g_coff, accumulate != 0,
                                       static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail_hip(nullptr, e, who);
@@ -2186,79 +2318,33 @@ int offk_relu_backward(void* stream, const float* dy, int dy_cstride, int dy_cof
 int offk_conv2d_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
                               int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
                               size_t scratch_bytes) {
-  const char* who = "offk_conv2d_backward_data";
-  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
-  const long long rows = (long long)n_img * H * W;
-  if (views_overlap(dx, dx_cstride, g, g_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
-  size_t df = 0;
-  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, nullptr, nullptr, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (scratch_bytes < df * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_plan)");
-  const char* why = nullptr;
-  hipError_t e = conv_bwd_data_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, dx, dx_cstride, dx_coff, accumulate != 0,
-                                      static_cast<float*>(scratch), df, static_cast<hipStream_t>(stream), &why);
-  if (e != hipSuccess) return fail(nullptr, why ? OFFK_ERR_INVALID : OFFK_ERR_HIP, std::string(who) + ": " + (why ? why : hipGetErrorString(e)));
-  return OFFK_OK;
+  return conv_bwd_data_entry(kConvBwdS1, "offk_conv2d_backward_data", stream, g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, KW, pad, dx,
+                             dx_cstride, dx_coff, accumulate, scratch, scratch_bytes);
 }
 
 int offk_conv2d_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
                                 int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db, int accumulate,
                                 void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_backward_weight";
-  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, &wf, &chunks, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (scratch_bytes < wf * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_plan)");
-  hipError_t e = conv_bwd_weight_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
-                                        accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_weight_entry(kConvBwdS1, "offk_conv2d_backward_weight", stream, x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co,
+                               KH, KW, pad, relu_in, dw_oihw, db, accumulate, scratch, scratch_bytes);
 }
 
-// ---- K4b's weight gradient in split-fp32 arithmetic (conv_wgrad_split.hip) ----
+// ---- K4b in split-fp32 arithmetic (conv_wgrad_split.hip, conv_dgrad_split.hip) ----
 int offk_conv2d_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes, int* weight_chunks) {
-  const char* who = "offk_conv2d_backward_plan_split";
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
-  if (weight_chunks) *weight_chunks = chunks;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS1Split, "offk_conv2d_backward_plan_split", n_img, H, W, Ci, Co, KH, KW, false, true, nullptr,
+                             weight_scratch_bytes, weight_chunks);
 }
 
 int offk_conv2d_backward_weight_split(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff,
                                       int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
                                       int accumulate, void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_backward_weight_split";
-  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (scratch_bytes < wf * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_plan_split)");
-  hipError_t e = conv_wgrad_split_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
-                                         accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_weight_entry(kConvBwdS1Split, "offk_conv2d_backward_weight_split", stream, x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H,
+                               W, Ci, Co, KH, KW, pad, relu_in, dw_oihw, db, accumulate, scratch, scratch_bytes);
 }
 
-// ---- K4b's data gradient in split-fp32 arithmetic (conv_dgrad_split.hip) ----
 int offk_conv2d_backward_data_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes) {
-  const char* who = "offk_conv2d_backward_data_plan_split";
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t wb = 0, gb = 0;
-  if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (data_scratch_bytes) *data_scratch_bytes = wb + gb;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS1Split, "offk_conv2d_backward_data_plan_split", n_img, H, W, Ci, Co, KH, KW, true, false,
+                             data_scratch_bytes, nullptr, nullptr);
 }
 
 int offk_conv2d_backward_data_form_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, int* ci_per_block, int* pixels_per_block) {
@@ -2275,150 +2361,54 @@ int offk_conv2d_backward_data_form_split(int n_img, int H, int W, int Ci, int Co
 int offk_conv2d_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
                                     const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
                                     int accumulate, void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_backward_data_split";
-  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
-  const long long rows = (long long)n_img * H * W;
-  if (views_overlap(dx, dx_cstride, g, g_cstride, rows)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
-  size_t wb = 0, gb = 0;
-  if (!conv_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (scratch_bytes < wb + gb) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_backward_data_plan_split)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch must be 16-byte aligned");
-  hipError_t e = conv_dgrad_split_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0, scratch,
-                                         static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_data_entry(kConvBwdS1Split, "offk_conv2d_backward_data_split", stream, g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, KW,
+                             pad, dx, dx_cstride, dx_coff, accumulate, scratch, scratch_bytes);
 }
 
-// ---- K4b, stride 2: backward of the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip) ----
-namespace {
-int conv_s2_bwd_shape(const char* who, int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad) {
-  if (n_img < 1 || H < 2 || W < 2) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": bad argument (n_img >= 1, H, W >= 2)");
-  if (!(KH == KW && ((KH == 7 && pad == 3) || (KH == 5 && pad == 2))))
-    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": the form must be 7x7 with pad 3 or 5x5 with pad 2 (stride 2)");
-  if ((H & 1) || (W & 1)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": H and W (the input map) must be even");
-  if (Ci < 32 || Co < 64 || Ci % 32 || Co % 64) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": need Ci % 32 == 0 and Co % 64 == 0");
-  if (!conv_s2_bwd_supported(n_img, H, W, Ci, Co, KH, KW)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  return OFFK_OK;
-}
-}  // namespace
-
+// ---- K4b, stride 2: the 7x7 / 2 / 3 and 5x5 / 2 / 2 fusion convs (conv_bwd_s2.hip; conv_dgrad_s2_split.hip, conv_wgrad_s2_split.hip) ----
 int offk_conv2d_s2_backward_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes,
                                  size_t* weight_scratch_bytes, int* weight_chunks) {
-  const char* who = "offk_conv2d_s2_backward_plan";
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t df = 0, wf = 0;
-  int chunks = 0;
-  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (data_scratch_bytes) *data_scratch_bytes = df * sizeof(float);
-  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
-  if (weight_chunks) *weight_chunks = chunks;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS2, "offk_conv2d_s2_backward_plan", n_img, H, W, Ci, Co, KH, KW, true, true, data_scratch_bytes,
+                             weight_scratch_bytes, weight_chunks);
 }
 
 int offk_conv2d_s2_backward_data(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co, const float* w_oihw,
                                  int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff, int accumulate, void* scratch,
                                  size_t scratch_bytes) {
-  const char* who = "offk_conv2d_s2_backward_data";
-  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
-  const long long g_rows = (long long)n_img * (H / 2) * (W / 2), dx_rows = (long long)n_img * H * W;
-  const uintptr_t g0 = reinterpret_cast<uintptr_t>(g), g1 = g0 + (size_t)g_rows * (size_t)g_cstride * sizeof(float);
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dx), d1 = d0 + (size_t)dx_rows * (size_t)dx_cstride * sizeof(float);
-  if (g0 < d1 && d0 < g1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
-  size_t df = 0;
-  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, &df, nullptr, nullptr)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (scratch_bytes < df * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan)");
-  hipError_t e = conv_s2_bwd_data_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0,
-                                         static_cast<float*>(scratch), static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_data_entry(kConvBwdS2, "offk_conv2d_s2_backward_data", stream, g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, KW, pad,
+                             dx, dx_cstride, dx_coff, accumulate, scratch, scratch_bytes);
 }
 
-// ---- K4b, stride 2: the data gradient in split-fp32 arithmetic (conv_dgrad_s2_split.hip) ----
 int offk_conv2d_s2_backward_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_scratch_bytes) {
-  const char* who = "offk_conv2d_s2_backward_plan_split";
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t wb = 0, gb = 0;
-  if (!conv_s2_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (data_scratch_bytes) *data_scratch_bytes = wb + gb;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS2Split, "offk_conv2d_s2_backward_plan_split", n_img, H, W, Ci, Co, KH, KW, true, false, data_scratch_bytes,
+                             nullptr, nullptr);
 }
 
 int offk_conv2d_s2_backward_data_split(void* stream, const float* g, int g_cstride, int g_coff, int n_img, int H, int W, int Co,
                                        const float* w_oihw, int Ci, int KH, int KW, int pad, float* dx, int dx_cstride, int dx_coff,
                                        int accumulate, void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_s2_backward_data_split";
-  if (!w_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  if (const char* w = view_problem(dx, dx_cstride, dx_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx: " + w);
-  const long long g_rows = (long long)n_img * (H / 2) * (W / 2), dx_rows = (long long)n_img * H * W;
-  const uintptr_t g0 = reinterpret_cast<uintptr_t>(g), g1 = g0 + (size_t)g_rows * (size_t)g_cstride * sizeof(float);
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dx), d1 = d0 + (size_t)dx_rows * (size_t)dx_cstride * sizeof(float);
-  if (g0 < d1 && d0 < g1) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": dx overlaps g");
-  size_t wb = 0, gb = 0;
-  if (!conv_s2_dgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wb, &gb)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (scratch_bytes < wb + gb) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan_split)");
-  if (reinterpret_cast<uintptr_t>(scratch) % 16) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch must be 16-byte aligned");
-  hipError_t e = conv_s2_dgrad_split_launch(g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH, pad, dx, dx_cstride, dx_coff, accumulate != 0,
-                                            scratch, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_data_entry(kConvBwdS2Split, "offk_conv2d_s2_backward_data_split", stream, g, g_cstride, g_coff, n_img, H, W, Co, w_oihw, Ci, KH,
+                             KW, pad, dx, dx_cstride, dx_coff, accumulate, scratch, scratch_bytes);
 }
 
 int offk_conv2d_s2_backward_weight(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff, int n_img,
                                    int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw, float* db,
                                    int accumulate, void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_s2_backward_weight";
-  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_s2_bwd_plan(n_img, H, W, Ci, Co, KH, KW, nullptr, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": unsupported shape");
-  if (scratch_bytes < wf * sizeof(float)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_plan)");
-  hipError_t e = conv_s2_bwd_weight_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
-                                           accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_weight_entry(kConvBwdS2, "offk_conv2d_s2_backward_weight", stream, x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci,
+                               Co, KH, KW, pad, relu_in, dw_oihw, db, accumulate, scratch, scratch_bytes);
 }
 
-// ---- K4b, stride 2: the weight gradient in split-fp32 arithmetic (conv_wgrad_s2_split.hip) ----
 int offk_conv2d_s2_backward_weight_plan_split(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* weight_scratch_bytes,
                                               int* weight_chunks) {
-  const char* who = "offk_conv2d_s2_backward_weight_plan_split";
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, (KH - 1) / 2)) return rc;
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_s2_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (weight_scratch_bytes) *weight_scratch_bytes = wf * sizeof(float);
-  if (weight_chunks) *weight_chunks = chunks;
-  return OFFK_OK;
+  return conv_bwd_plan_entry(kConvBwdS2Split, "offk_conv2d_s2_backward_weight_plan_split", n_img, H, W, Ci, Co, KH, KW, false, true, nullptr,
+                             weight_scratch_bytes, weight_chunks);
 }
 
 int offk_conv2d_s2_backward_weight_split(void* stream, const float* x, int x_cstride, int x_coff, const float* g, int g_cstride, int g_coff,
                                          int n_img, int H, int W, int Ci, int Co, int KH, int KW, int pad, int relu_in, float* dw_oihw,
                                          float* db, int accumulate, void* scratch, size_t scratch_bytes) {
-  const char* who = "offk_conv2d_s2_backward_weight_split";
-  if (!dw_oihw || !scratch) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": null pointer");
-  if (int rc = conv_s2_bwd_shape(who, n_img, H, W, Ci, Co, KH, KW, pad)) return rc;
-  if (const char* w = view_problem(x, x_cstride, x_coff, Ci)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": x: " + w);
-  if (const char* w = view_problem(g, g_cstride, g_coff, Co)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": g: " + w);
-  size_t wf = 0;
-  int chunks = 0;
-  if (!conv_s2_wgrad_split_plan(n_img, H, W, Ci, Co, KH, KW, &wf, &chunks)) return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": problem too large");
-  if (scratch_bytes < wf * sizeof(float))
-    return fail(nullptr, OFFK_ERR_INVALID, std::string(who) + ": scratch too small (offk_conv2d_s2_backward_weight_plan_split)");
-  hipError_t e = conv_s2_wgrad_split_launch(x, x_cstride, x_coff, g, g_cstride, g_coff, n_img, H, W, Ci, Co, KH, relu_in != 0, dw_oihw, db,
-                                            accumulate != 0, static_cast<float*>(scratch), chunks, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail_hip(nullptr, e, who);
-  return OFFK_OK;
+  return conv_bwd_weight_entry(kConvBwdS2Split, "offk_conv2d_s2_backward_weight_split", stream, x, x_cstride, x_coff, g, g_cstride, g_coff, n_img,
+                               H, W, Ci, Co, KH, KW, pad, relu_in, dw_oihw, db, accumulate, scratch, scratch_bytes);
 }
 
 int offk_bottleneck_chain14(void* stream, const float* x, int x_cstride, int x_coff, int n_img, int Cin, int relu_in,

@@ -94,6 +94,20 @@ __device__ __forceinline__ float4 relu4(float4 v) {
   return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
 }
 
+// ---- the spatial branch's frame slice (quirk Q1) ---------------------------------------------------
+// output-pair row of frame f for the spatial branch, or -1 (see spatial_frames in the oracle): slice_mode 0 slices the flat frame axis
+// as the reference does (row f for f < P), slice_mode 1 takes the first L - 1 frames of every clip
+__device__ __forceinline__ int down_row(int f, int L, int P, int slice_mode) {
+  if (slice_mode == 0) return f < P ? f : -1;
+  const int b = f / L, t = f - b * L;
+  return t < L - 1 ? b * (L - 1) + t : -1;
+}
+// the same for frame t of clip b, where the caller has the two apart
+__device__ __forceinline__ int down_row(int b, int t, int L, int P, int slice_mode) {
+  if (slice_mode == 0) { const int f = b * L + t; return f < P ? f : -1; }
+  return t < L - 1 ? b * (L - 1) + t : -1;
+}
+
 // ---- reproducible dropout multiplier of the units' spatial branch (training) ------------------------
 // splitmix64 finaliser, the same integer function as offk_amd/synth.py (raw_u64 / dropout_keep): draw
 // q = (pair*HW + pixel)*8 + channel quad of the site's stream serves the quad's four channels, 16 bits each.

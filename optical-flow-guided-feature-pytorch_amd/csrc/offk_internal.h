@@ -43,6 +43,8 @@ hipError_t pack_conv_weight_launch(const float* src, int Co, int Ci, int KH, int
 
 // ---- K4b: backward of one stride-1 fusion conv, k = 1 or 3 (conv_bwd.hip, exact fp32) ----
 bool conv_bwd_supported(int n_img, int H, int W, int Ci, int Co, int KH, int KW);
+// K chunks of a conv weight gradient, the one rule of the four plans below (conv_bwd.hip); pure host code
+int conv_wgrad_chunks(int n_img, long long positions_per_image, long long tiles, int slots, int min_positions);
 // scratch floats of the data / weight gradient, K chunks of the weight gradient, K slices of the data gradient's conv; pure host code
 bool conv_bwd_plan(int n_img, int H, int W, int Ci, int Co, int KH, int KW, size_t* data_floats, size_t* weight_floats, int* chunks,
                    int* dgrad_splitk);

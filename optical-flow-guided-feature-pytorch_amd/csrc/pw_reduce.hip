@@ -32,13 +32,6 @@ constexpr int PW_BM = 128, PW_BN = 160, PW_TN = 5;
 int pw_blocks_for(int M) { return (M + PW_BM - 1) / PW_BM; }
 #endif
 
-// output-pair row of frame f for the spatial branch, or -1 (see spatial_frames in the oracle)
-__device__ __forceinline__ int down_row(int f, int L, int P, int slice_mode) {
-  if (slice_mode == 0) return f < P ? f : -1;
-  int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
-
 template <int NT>
 __device__ __forceinline__ void pw_mma(f32x16 (&acc)[PW_TN], const float* As, const float* Bs, int lane) {
   const int r = lane & 31, h = lane >> 5;

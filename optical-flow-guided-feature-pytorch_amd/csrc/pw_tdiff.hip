@@ -29,12 +29,6 @@ namespace offk {
 namespace {
 constexpr int PT_FT = 7;                 // frames (row tiles) per block
 constexpr int PT_BM = 32 * PT_FT, PT_BN = 160;
-
-// row of D for frame t of clip b (quirk Q1: reference_flat slices the flat frame axis)
-__device__ __forceinline__ int pt_down_row(int b, int t, int L, int P, int slice_mode) {
-  if (slice_mode == 0) { const int f = b * L + t; return f < P ? f : -1; }
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
 }  // namespace
 
 int pt_tgroups(int L) { return L <= PT_FT ? 1 : (L - 2) / (PT_FT - 1) + 1; }
@@ -304,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_kernel(PtParams p) {
     const int j = wave + 4 * half;
     // the frame shared with the next temporal group belongs to that group
     if (j < nf && (last_group || j < PT_FT - 1) && pix_ok) {
-      const int dr = pt_down_row(bl, t0 + j, L, p.P, p.slice_mode);
+      const int dr = down_row(bl, t0 + j, L, p.P, p.slice_mode);
       if (dr >= 0) {
         float* drow = S.D + ((size_t)dr * HW + pixl) * kDownCh + 4 * h;
 #pragma unroll
@@ -585,7 +579,7 @@ __global__ __launch_bounds__(256, 4) void pw_tdiff16_kernel(PtParams p) {
   for (int half = 0; half < 2; ++half) {
     const int j = wave + 4 * half;                 // (wave 3, half 1: j = 7 >= nf -- its duplicate tile is dropped here)
     if (j < nf && (last_group || j < PT_FT - 1) && pix_ok) {
-      const int dr = pt_down_row(bl, t0 + j, L, p.P, p.slice_mode);
+      const int dr = down_row(bl, t0 + j, L, p.P, p.slice_mode);
       if (dr >= 0) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {

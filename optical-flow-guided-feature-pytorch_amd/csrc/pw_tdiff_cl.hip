@@ -31,7 +31,7 @@ struct ClLoader {
   int it_g8[2];
   bool it_ok[2];
   int tid;
-  u32x4 mv[2][NLD];
+  spu4 mv[2][NLD];
 
   // the four lanes of a pixel take its four k groups (one line of the map); pixel bits 0 and 2 swapped against the lane order
   __device__ __forceinline__ ClLoader(const PtSite&, const BlockGeom& b) : tid(b.tid) {
@@ -54,12 +54,12 @@ struct ClLoader {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       if (it_ok[r]) {
-        const u32x4* src = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(k.xb) + (it_row[r] * k.cpart + k.kl + it_g8[r]) * ES);
+        const spu4* src = reinterpret_cast<const spu4*>(reinterpret_cast<const char*>(k.xb) + (it_row[r] * k.cpart + k.kl + it_g8[r]) * ES);
 #pragma unroll
         for (int n = 0; n < NLD; ++n) mv[r][n] = src[n];
       } else {
 #pragma unroll
-        for (int n = 0; n < NLD; ++n) mv[r][n] = u32x4{0u, 0u, 0u, 0u};
+        for (int n = 0; n < NLD; ++n) mv[r][n] = spu4{0u, 0u, 0u, 0u};
       }
     }
   }
@@ -70,22 +70,22 @@ struct ClLoader {
       if (tid + r * kThreads >= kItems) continue;
       char* const dst = xs + it_dst[r];
       if constexpr (FEAT == kFeatBf16) {
-        *reinterpret_cast<u32x4*>(dst) = mv[r][0];
+        *reinterpret_cast<spu4*>(dst) = mv[r][0];
       } else if constexpr (FEAT == kFeatF16) {
         unsigned v[8];                                       // element e in the e & 1 half of word e >> 1
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (e & 1) ? mv[r][0][e >> 1] >> 16 : mv[r][0][e >> 1] & 0xffffu;
-        u32x4 ph, pm;
+        spu4 ph, pm;
         cut2(v, ph, pm);
-        *reinterpret_cast<u32x4*>(dst) = ph;
-        *reinterpret_cast<u32x4*>(dst + kPlane) = pm;
+        *reinterpret_cast<spu4*>(dst) = ph;
+        *reinterpret_cast<spu4*>(dst + kPlane) = pm;
       } else {
         const unsigned v[8] = {mv[r][0].x, mv[r][0].y, mv[r][0].z, mv[r][0].w, mv[r][NLD - 1].x, mv[r][NLD - 1].y, mv[r][NLD - 1].z, mv[r][NLD - 1].w};
-        u32x4 ph, pm, pl;
+        spu4 ph, pm, pl;
         cut3(v, ph, pm, pl);
-        *reinterpret_cast<u32x4*>(dst) = ph;
-        *reinterpret_cast<u32x4*>(dst + kPlane) = pm;
-        *reinterpret_cast<u32x4*>(dst + 2 * kPlane) = pl;
+        *reinterpret_cast<spu4*>(dst) = ph;
+        *reinterpret_cast<spu4*>(dst + kPlane) = pm;
+        *reinterpret_cast<spu4*>(dst + 2 * kPlane) = pl;
       }
     }
   }

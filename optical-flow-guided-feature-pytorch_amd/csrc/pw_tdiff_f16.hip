@@ -79,12 +79,12 @@ struct Feat16Loader {
         const unsigned (&v)[8] = s == 0 ? v0 : v1;
         char* dst = xs + (f * 2 + (px >> 4)) * NPL * kPlane + g * 256 + (px & 15) * 16;
         if constexpr (F16) {
-          u32x4 ph, pm;
+          spu4 ph, pm;
           cut2(v, ph, pm);
-          *reinterpret_cast<u32x4*>(dst) = ph;
-          *reinterpret_cast<u32x4*>(dst + kPlane) = pm;
+          *reinterpret_cast<spu4*>(dst) = ph;
+          *reinterpret_cast<spu4*>(dst + kPlane) = pm;
         } else {
-          *reinterpret_cast<u32x4*>(dst) = u32x4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
+          *reinterpret_cast<spu4*>(dst) = spu4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
         }
       }
     }

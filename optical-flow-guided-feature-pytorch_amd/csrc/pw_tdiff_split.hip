@@ -33,6 +33,7 @@
 
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 
@@ -47,15 +48,8 @@ constexpr int PS_FRAME = 3 * PS_PLANE;                // planes h, m, l
 constexpr int PS_STAGE = (PS_FT + 1) * PS_FRAME;      // seven frames + frame slot 7: the two pieces of waves 2, 3 that have no frame (zeros)
 constexpr int PS_LDS = 2 * PS_RAW_STAGE + 2 * PS_STAGE;      // 81920 B = 64 granules of 1280 B: two blocks per CU (163840 B)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int ps_down_row(int b, int t, int L, int P, int slice_mode) {
-  if (slice_mode == 0) { const int f = b * L + t; return f < P ? f : -1; }
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
 }  // namespace
 
 __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
@@ -162,25 +156,25 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
     if (st == 4) { cr[2] = __uint_as_float(v[2]) - __uint_as_float(ch[2]); cr[3] = __uint_as_float(v[3]) - __uint_as_float(ch[3]); }
     char* dst = pl_wr + ps * PS_STAGE + fr * PS_FRAME;
     if (st == 5)
-      *reinterpret_cast<u32x2*>(dst) = u32x2{__builtin_amdgcn_perm(ch[1], ch[0], 0x07060302), __builtin_amdgcn_perm(ch[3], ch[2], 0x07060302)};
+      *reinterpret_cast<spu2*>(dst) = spu2{sp_pair(ch[0], ch[1]), sp_pair(ch[2], ch[3])};
     if (st == 6) { cm[0] = __float_as_uint(cr[0]) & 0xffff0000u; cm[1] = __float_as_uint(cr[1]) & 0xffff0000u; }
     if (st == 7) { cm[2] = __float_as_uint(cr[2]) & 0xffff0000u; cm[3] = __float_as_uint(cr[3]) & 0xffff0000u; }
     if (st == 8) { cl[0] = cr[0] - __uint_as_float(cm[0]); cl[1] = cr[1] - __uint_as_float(cm[1]); }      // <= 8 significant bits: the low halves are zero
     if (st == 9) { cl[2] = cr[2] - __uint_as_float(cm[2]); cl[3] = cr[3] - __uint_as_float(cm[3]); }
     if (st == 10)
-      *reinterpret_cast<u32x2*>(dst + PS_PLANE) = u32x2{__builtin_amdgcn_perm(cm[1], cm[0], 0x07060302), __builtin_amdgcn_perm(cm[3], cm[2], 0x07060302)};
+      *reinterpret_cast<spu2*>(dst + PS_PLANE) = spu2{sp_pair(cm[0], cm[1]), sp_pair(cm[2], cm[3])};
     if (st == 11)
-      *reinterpret_cast<u32x2*>(dst + 2 * PS_PLANE) = u32x2{__builtin_amdgcn_perm(__float_as_uint(cl[1]), __float_as_uint(cl[0]), 0x07060302),
-                                                            __builtin_amdgcn_perm(__float_as_uint(cl[3]), __float_as_uint(cl[2]), 0x07060302)};
+      *reinterpret_cast<spu2*>(dst + 2 * PS_PLANE) =
+          spu2{sp_pair(__float_as_uint(cl[0]), __float_as_uint(cl[1])), sp_pair(__float_as_uint(cl[2]), __float_as_uint(cl[3]))};
   };
 
   // ---- weights: image [kt][slab (4 gen + 1 down)][ct][plane][lane] x 16 B (pw_pack_split16_kernel) ----
-  u32x4 wg[2][2][3], wd[3];                // gen [set][ct][plane] (set = K-tile parity), down [plane] (the wave's ONE down channel tile)
+  spu4 wg[2][2][3], wd[3];                // gen [set][ct][plane] (set = K-tile parity), down [plane] (the wave's ONE down channel tile)
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
-    wd[q] = u32x4{0u, 0u, 0u, 0u};
+    wd[q] = spu4{0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int c = 0; c < 2; ++c) { wg[0][c][q] = u32x4{0u, 0u, 0u, 0u}; wg[1][c][q] = u32x4{0u, 0u, 0u, 0u}; }
+    for (int c = 0; c < 2; ++c) { wg[0][c][q] = spu4{0u, 0u, 0u, 0u}; wg[1][c][q] = spu4{0u, 0u, 0u, 0u}; }
   }
   i32x4 wdesc;
   {
@@ -214,23 +208,20 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
                                             "+v"(wg[set][1][0]), "+v"(wg[set][1][1]), "+v"(wg[set][1][2]) :: "memory")
 #define OFFK_WAIT_WD(N) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(wd[0]), "+v"(wd[1]), "+v"(wd[2]) :: "memory")
 
-  f32x4 a1[PS_FT][2], a2[PS_FT][2], d1[4], d2[4];       // [frame][channel tile]: A1 = sum w_h x_h, A2 = the five small products
+  spf4 a1[PS_FT][2], a2[PS_FT][2], d1[4], d2[4];       // [frame][channel tile]: A1 = sum w_h x_h, A2 = the five small products
 #pragma unroll
   for (int j = 0; j < PS_FT; ++j)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) { a1[j][c] = f32x4{0.f, 0.f, 0.f, 0.f}; a2[j][c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int c = 0; c < 2; ++c) { a1[j][c] = spf4{0.f, 0.f, 0.f, 0.f}; a2[j][c] = spf4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { d1[i] = f32x4{0.f, 0.f, 0.f, 0.f}; d2[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int i = 0; i < 4; ++i) { d1[i] = spf4{0.f, 0.f, 0.f, 0.f}; d2[i] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   // B operand of a frame out of plane stage st: three ds_read_b128
   const char* const xrd = planes + lg * PS_GS + li * 16;
   const int xoffD = fd0 * PS_FRAME;                     // down frames: fd0 + 2 i
-  auto rdx = [&](u32x4 (&x)[3], const int st, int foff) {
+  auto rdx = [&](spu4 (&x)[3], const int st, int foff) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) x[q] = *reinterpret_cast<const u32x4*>(xrd + st * PS_STAGE + foff + q * PS_PLANE);
-  };
-  auto mf = [&](f32x4& c, const u32x4& a, const u32x4& bb) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), c, 0, 0, 0);
+    for (int q = 0; q < 3; ++q) x[q] = *reinterpret_cast<const spu4*>(xrd + st * PS_STAGE + foff + q * PS_PLANE);
   };
 
   const int nkt = C / BK;
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
       if (m == 92) dma_piece(3, ST ^ 1);
       OFFK_SB;
     };
-    u32x4 x[2][3];
+    spu4 x[2][3];
     rdx(x[0], ST, 0);
     // all but DMA(kt + 2) [4] and Wd(kt) [3]: the gen weights of tile kt and the raw pieces of tile kt + 1 (a step older)
     if (ST == 0) OFFK_WAIT_STEP(7, 0); else OFFK_WAIT_STEP(7, 1);
@@ -273,22 +264,22 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
       if (j + 1 < PS_FT) rdx(x[(j + 1) & 1], ST, (j + 1) * PS_FRAME);
       else rdx(x[(j + 1) & 1], ST, xoffD);
       OFFK_SB;
-      const u32x4 (&w0)[3] = wg[ST][0];
-      const u32x4 (&w1)[3] = wg[ST][1];
-      const u32x4 (&xx)[3] = x[j & 1];
+      const spu4 (&w0)[3] = wg[ST][0];
+      const spu4 (&w1)[3] = wg[ST][1];
+      const spu4 (&xx)[3] = x[j & 1];
       const int m0 = 12 * j;
-      mf(a2[j][0], w0[2], xx[0]); side(m0 + 0);
-      mf(a2[j][1], w1[2], xx[0]); side(m0 + 1);
-      mf(a2[j][0], w0[0], xx[2]); side(m0 + 2);
-      mf(a2[j][1], w1[0], xx[2]); side(m0 + 3);
-      mf(a2[j][0], w0[1], xx[1]); side(m0 + 4);
-      mf(a2[j][1], w1[1], xx[1]); side(m0 + 5);
-      mf(a2[j][0], w0[1], xx[0]); side(m0 + 6);
-      mf(a2[j][1], w1[1], xx[0]); side(m0 + 7);
-      mf(a2[j][0], w0[0], xx[1]); side(m0 + 8);
-      mf(a2[j][1], w1[0], xx[1]); side(m0 + 9);
-      mf(a1[j][0], w0[0], xx[0]); side(m0 + 10);
-      mf(a1[j][1], w1[0], xx[0]); side(m0 + 11);
+      sp_mfma(a2[j][0], w0[2], xx[0]); side(m0 + 0);
+      sp_mfma(a2[j][1], w1[2], xx[0]); side(m0 + 1);
+      sp_mfma(a2[j][0], w0[0], xx[2]); side(m0 + 2);
+      sp_mfma(a2[j][1], w1[0], xx[2]); side(m0 + 3);
+      sp_mfma(a2[j][0], w0[1], xx[1]); side(m0 + 4);
+      sp_mfma(a2[j][1], w1[1], xx[1]); side(m0 + 5);
+      sp_mfma(a2[j][0], w0[1], xx[0]); side(m0 + 6);
+      sp_mfma(a2[j][1], w1[1], xx[0]); side(m0 + 7);
+      sp_mfma(a2[j][0], w0[0], xx[1]); side(m0 + 8);
+      sp_mfma(a2[j][1], w1[0], xx[1]); side(m0 + 9);
+      sp_mfma(a1[j][0], w0[0], xx[0]); side(m0 + 10);
+      sp_mfma(a1[j][1], w1[0], xx[0]); side(m0 + 11);
     }
     // the wave's down tiles: frames fd0 + 2 i (x[1] holds the first): six MFMAs each
     OFFK_WAIT_WD(9);                          // Wd(kt): all but Wg(kt + 1) [6] and DMA(kt + 3) pieces 0 - 2 [3]
@@ -296,14 +287,14 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
     for (int i = 0; i < 4; ++i) {
       if (i + 1 < 4) rdx(x[i & 1], ST, xoffD + 2 * (i + 1) * PS_FRAME);
       OFFK_SB;
-      const u32x4 (&xx)[3] = x[(i + 1) & 1];
+      const spu4 (&xx)[3] = x[(i + 1) & 1];
       const int m0 = 12 * PS_FT + 6 * i;
-      mf(d2[i], wd[2], xx[0]); side(m0 + 0);
-      mf(d2[i], wd[0], xx[2]); side(m0 + 1);
-      mf(d1[i], wd[0], xx[0]); side(m0 + 2);
-      mf(d2[i], wd[1], xx[1]); side(m0 + 3);
-      mf(d2[i], wd[1], xx[0]); side(m0 + 4);
-      mf(d2[i], wd[0], xx[1]); side(m0 + 5);
+      sp_mfma(d2[i], wd[2], xx[0]); side(m0 + 0);
+      sp_mfma(d2[i], wd[0], xx[2]); side(m0 + 1);
+      sp_mfma(d1[i], wd[0], xx[0]); side(m0 + 2);
+      sp_mfma(d2[i], wd[1], xx[1]); side(m0 + 3);
+      sp_mfma(d2[i], wd[1], xx[0]); side(m0 + 4);
+      sp_mfma(d2[i], wd[0], xx[1]); side(m0 + 5);
     }
     load_wd(kn);
     __syncthreads();                         // (the compiler's lgkmcnt(0) in front of it covers the plane writes)
@@ -357,30 +348,30 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
 #endif
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
-    const f32x4 bg = *reinterpret_cast<const f32x4*>(S.bias + wave * 32 + 16 * ct + 4 * kq_e);
+    const spf4 bg = *reinterpret_cast<const spf4*>(S.bias + wave * 32 + 16 * ct + 4 * kq_e);
 #pragma unroll
     for (int j = 0; j < PS_FT; ++j) {
-      const f32x4 v = (a1[j][ct] + a2[j][ct]) + bg;
-      a1[j][ct] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+      const spf4 v = (a1[j][ct] + a2[j][ct]) + bg;
+      a1[j][ct] = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
     }
   }
 #pragma unroll
   for (int j = 0; j + 1 < PS_FT; ++j)
     if (j + 1 < nf && pix_ok) {
       float* const trow = S.M + ((pair0 + j) * HW + pixl) * S.m_cs + S.m_coff + kDownCh + wave * 32 + 4 * kq_e;
-      *reinterpret_cast<f32x4*>(trow) = a1[j + 1][0] - a1[j][0];
-      *reinterpret_cast<f32x4*>(trow + 16) = a1[j + 1][1] - a1[j][1];
+      *reinterpret_cast<spf4*>(trow) = a1[j + 1][0] - a1[j][0];
+      *reinterpret_cast<spf4*>(trow + 16) = a1[j + 1][1] - a1[j][1];
     }
   {
     const int ctd_e = wave & 1, fd0_e = wave >> 1;
-    const f32x4 bd = *reinterpret_cast<const f32x4*>(S.bias_down + 16 * ctd_e + 4 * kq_e);
+    const spf4 bd = *reinterpret_cast<const spf4*>(S.bias_down + 16 * ctd_e + 4 * kq_e);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int j = fd0_e + 2 * i;                 // (waves 2, 3, i = 3: j = 7 >= nf -- the zero tile of frame slot 7 is dropped here)
       // the frame shared with the next temporal group belongs to that group
       if (j < nf && (last_group || j < PS_FT - 1) && pix_ok) {
-        const int dr = ps_down_row(bl, t0 + j, L, p.P, p.slice_mode);
-        if (dr >= 0) *reinterpret_cast<f32x4*>(S.D + ((size_t)dr * HW + pixl) * kDownCh + 16 * ctd_e + 4 * kq_e) = (d1[i] + d2[i]) + bd;
+        const int dr = down_row(bl, t0 + j, L, p.P, p.slice_mode);
+        if (dr >= 0) *reinterpret_cast<spf4*>(S.D + ((size_t)dr * HW + pixl) * kDownCh + 16 * ctd_e + 4 * kq_e) = (d1[i] + d2[i]) + bd;
       }
     }
   }

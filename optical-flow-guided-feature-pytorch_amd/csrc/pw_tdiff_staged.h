@@ -30,6 +30,7 @@
 #pragma once
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace staged {
@@ -49,9 +50,6 @@ struct Lds {
   static constexpr int kBytes = 2 * kStage;
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // what a Loader is built from: the block's site and its window of the site's pixel stream and frames
 struct BlockGeom {
   int HW, L;
@@ -60,32 +58,21 @@ struct BlockGeom {
   int tid;
 };
 
-__device__ __forceinline__ int down_row(int b, int t, int L, int P, int slice_mode) {
-  if (slice_mode == 0) { const int f = b * L + t; return f < P ? f : -1; }
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
-
-__device__ __forceinline__ u32x4 pack_hi(const unsigned (&v)[8]) {         // the upper halves of eight words, element e at bits 16 e
-  return u32x4{__builtin_amdgcn_perm(v[1], v[0], 0x07060302), __builtin_amdgcn_perm(v[3], v[2], 0x07060302),
-               __builtin_amdgcn_perm(v[5], v[4], 0x07060302), __builtin_amdgcn_perm(v[7], v[6], 0x07060302)};
+__device__ __forceinline__ spu4 pack_hi(const unsigned (&v)[8]) {         // the upper halves of eight words, element e at bits 16 e
+  return spu4{sp_pair(v[0], v[1]), sp_pair(v[2], v[3]), sp_pair(v[4], v[5]), sp_pair(v[6], v[7])};
 }
 
 // eight fp32 values -> the three bf16 planes, cut as pw_tdiff_split_kernel cuts (l has at most 8 significant bits: its low half is zero)
-__device__ __forceinline__ void cut3(const unsigned (&v)[8], u32x4& ph, u32x4& pm, u32x4& pl) {
+__device__ __forceinline__ void cut3(const unsigned (&v)[8], spu4& ph, spu4& pm, spu4& pl) {
   unsigned h[8], m[8], l[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    h[e] = v[e] & 0xffff0000u;
-    const float r = __uint_as_float(v[e]) - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r) & 0xffff0000u;
-    l[e] = __float_as_uint(r - __uint_as_float(m[e]));
-  }
+  for (int e = 0; e < 8; ++e) sp_cut(__uint_as_float(v[e]), h[e], m[e], l[e]);
   ph = pack_hi(h); pm = pack_hi(m); pl = pack_hi(l);
 }
 
 // eight fp16 bit patterns (the low halves of v) -> two planes, cut like pw_tdiff_split_kernel cuts x.float(): h = the upper 16 bits,
 // m = the upper 16 bits of x - h (x - h - m = +0 for every finite fp16)
-__device__ __forceinline__ void cut2(const unsigned (&v)[8], u32x4& ph, u32x4& pm) {
+__device__ __forceinline__ void cut2(const unsigned (&v)[8], spu4& ph, spu4& pm) {
   unsigned h[8], m[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -142,9 +129,9 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
   const int li = lane & 15, lg = lane >> 4;
 
   Loader ld(S, BlockGeom{HW, L, px0, npx, t0, nf, tid});
-  u32x4 wv[4] = {};
+  spu4 wv[4] = {};
   auto load_tile = [&](int kt) {
-    const u32x4* wsrc = reinterpret_cast<const u32x4*>(static_cast<const char*>(S.wt16s) + (size_t)kt * kWImg);
+    const spu4* wsrc = reinterpret_cast<const spu4*>(static_cast<const char*>(S.wt16s) + (size_t)kt * kWImg);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = tid + r * kThreads;
@@ -157,21 +144,18 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = tid + r * kThreads;
-      if (c < kWChunks) *reinterpret_cast<u32x4*>(sb + 16 * c) = wv[r];
+      if (c < kWChunks) *reinterpret_cast<spu4*>(sb + 16 * c) = wv[r];
     }
     ld.store(sb + kWImg);
   };
 
-  f32x4 a1[kFrames][2], a2[kFrames][2], d1[4], d2[4];        // as pw_tdiff_split_kernel: A1 = sum w_h x_h, A2 = the small products
+  spf4 a1[kFrames][2], a2[kFrames][2], d1[4], d2[4];        // as pw_tdiff_split_kernel: A1 = sum w_h x_h, A2 = the small products
 #pragma unroll
   for (int j = 0; j < kFrames; ++j)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) { a1[j][c] = f32x4{0.f, 0.f, 0.f, 0.f}; a2[j][c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int c = 0; c < 2; ++c) { a1[j][c] = spf4{0.f, 0.f, 0.f, 0.f}; a2[j][c] = spf4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { d1[i] = f32x4{0.f, 0.f, 0.f, 0.f}; d2[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  auto mf = [&](f32x4& c, const u32x4& a, const u32x4& bb) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bb), c, 0, 0, 0);
-  };
+  for (int i = 0; i < 4; ++i) { d1[i] = spf4{0.f, 0.f, 0.f, 0.f}; d2[i] = spf4{0.f, 0.f, 0.f, 0.f}; }
   const int ctd = wl & 1, fd0 = wl >> 1;
 
   const int nkt = C / BK;
@@ -182,44 +166,44 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
     const int st = kt & 1;
     if (kt + 1 < nkt) load_tile(kt + 1);
     const char* const sb = lds + st * L_::kStage;
-    u32x4 w0[3], w1[3], wd[3];
+    spu4 w0[3], w1[3], wd[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
-      w0[q] = *reinterpret_cast<const u32x4*>(sb + ((wl * 2 + 0) * 3 + q) * 1024 + lane * 16);
-      w1[q] = *reinterpret_cast<const u32x4*>(sb + ((wl * 2 + 1) * 3 + q) * 1024 + lane * 16);
-      wd[q] = *reinterpret_cast<const u32x4*>(sb + ((4 * 2 + ctd) * 3 + q) * 1024 + lane * 16);
+      w0[q] = *reinterpret_cast<const spu4*>(sb + ((wl * 2 + 0) * 3 + q) * 1024 + lane * 16);
+      w1[q] = *reinterpret_cast<const spu4*>(sb + ((wl * 2 + 1) * 3 + q) * 1024 + lane * 16);
+      wd[q] = *reinterpret_cast<const spu4*>(sb + ((4 * 2 + ctd) * 3 + q) * 1024 + lane * 16);
     }
     const char* const xrd = sb + kWImg + pt * NPL * kPlane + lg * 256 + (Loader::slot(li, lg) << 4);
-    auto rdx = [&](u32x4 (&x)[3], int f) {
+    auto rdx = [&](spu4 (&x)[3], int f) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        if (q < NPL) x[q] = *reinterpret_cast<const u32x4*>(xrd + f * L_::kXFrame + q * kPlane);
-        else x[q] = u32x4{0u, 0u, 0u, 0u};
+        if (q < NPL) x[q] = *reinterpret_cast<const spu4*>(xrd + f * L_::kXFrame + q * kPlane);
+        else x[q] = spu4{0u, 0u, 0u, 0u};
       }
     };
     // gen: per frame and channel tile pw_tdiff_split_kernel's sequence (planes 0 = h, 1 = m, 2 = l) without the products of +0 planes
 #pragma unroll
     for (int j = 0; j < kFrames; ++j) {
-      u32x4 x[3];
+      spu4 x[3];
       rdx(x, j);
-      mf(a2[j][0], w0[2], x[0]);
-      mf(a2[j][1], w1[2], x[0]);
+      sp_mfma(a2[j][0], w0[2], x[0]);
+      sp_mfma(a2[j][1], w1[2], x[0]);
       if constexpr (NPL > 2) {
-        mf(a2[j][0], w0[0], x[2]);
-        mf(a2[j][1], w1[0], x[2]);
+        sp_mfma(a2[j][0], w0[0], x[2]);
+        sp_mfma(a2[j][1], w1[0], x[2]);
       }
       if constexpr (NPL > 1) {
-        mf(a2[j][0], w0[1], x[1]);
-        mf(a2[j][1], w1[1], x[1]);
+        sp_mfma(a2[j][0], w0[1], x[1]);
+        sp_mfma(a2[j][1], w1[1], x[1]);
       }
-      mf(a2[j][0], w0[1], x[0]);
-      mf(a2[j][1], w1[1], x[0]);
+      sp_mfma(a2[j][0], w0[1], x[0]);
+      sp_mfma(a2[j][1], w1[1], x[0]);
       if constexpr (NPL > 1) {
-        mf(a2[j][0], w0[0], x[1]);
-        mf(a2[j][1], w1[0], x[1]);
+        sp_mfma(a2[j][0], w0[0], x[1]);
+        sp_mfma(a2[j][1], w1[0], x[1]);
       }
-      mf(a1[j][0], w0[0], x[0]);
-      mf(a1[j][1], w1[0], x[0]);
+      sp_mfma(a1[j][0], w0[0], x[0]);
+      sp_mfma(a1[j][1], w1[0], x[0]);
     }
     // the next K-tile into the other stage (read by nobody since the last barrier) between the gen and the down MFMAs: the cut's
     // vector work of one wave overlaps the MFMAs of the SIMD's other wave
@@ -228,14 +212,14 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (fd0 + 2 * i >= kFrames) continue;
-      u32x4 x[3];
+      spu4 x[3];
       rdx(x, fd0 + 2 * i);
-      mf(d2[i], wd[2], x[0]);
-      if constexpr (NPL > 2) mf(d2[i], wd[0], x[2]);
-      mf(d1[i], wd[0], x[0]);
-      if constexpr (NPL > 1) mf(d2[i], wd[1], x[1]);
-      mf(d2[i], wd[1], x[0]);
-      if constexpr (NPL > 1) mf(d2[i], wd[0], x[1]);
+      sp_mfma(d2[i], wd[2], x[0]);
+      if constexpr (NPL > 2) sp_mfma(d2[i], wd[0], x[2]);
+      sp_mfma(d1[i], wd[0], x[0]);
+      if constexpr (NPL > 1) sp_mfma(d2[i], wd[1], x[1]);
+      sp_mfma(d2[i], wd[1], x[0]);
+      if constexpr (NPL > 1) sp_mfma(d2[i], wd[0], x[1]);
     }
     __syncthreads();
   }
@@ -248,28 +232,28 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
   const size_t pair0 = (size_t)bl * (L - 1) + t0;
 #pragma unroll
   for (int ct = 0; ct < 2; ++ct) {
-    const f32x4 bg = *reinterpret_cast<const f32x4*>(S.bias + wl * 32 + 16 * ct + 4 * kq_e);
+    const spf4 bg = *reinterpret_cast<const spf4*>(S.bias + wl * 32 + 16 * ct + 4 * kq_e);
 #pragma unroll
     for (int j = 0; j < kFrames; ++j) {
-      const f32x4 v = (a1[j][ct] + a2[j][ct]) + bg;
-      a1[j][ct] = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+      const spf4 v = (a1[j][ct] + a2[j][ct]) + bg;
+      a1[j][ct] = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
     }
   }
 #pragma unroll
   for (int j = 0; j + 1 < kFrames; ++j)
     if (j + 1 < nf && pix_ok) {
       float* const trow = S.M + ((pair0 + j) * HW + pixl) * S.m_cs + S.m_coff + kDownCh + wl * 32 + 4 * kq_e;
-      *reinterpret_cast<f32x4*>(trow) = a1[j + 1][0] - a1[j][0];
-      *reinterpret_cast<f32x4*>(trow + 16) = a1[j + 1][1] - a1[j][1];
+      *reinterpret_cast<spf4*>(trow) = a1[j + 1][0] - a1[j][0];
+      *reinterpret_cast<spf4*>(trow + 16) = a1[j + 1][1] - a1[j][1];
     }
   {
-    const f32x4 bd = *reinterpret_cast<const f32x4*>(S.bias_down + 16 * ctd + 4 * kq_e);
+    const spf4 bd = *reinterpret_cast<const spf4*>(S.bias_down + 16 * ctd + 4 * kq_e);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int j = fd0 + 2 * i;
       if (j < nf && (last_group || j < kFrames - 1) && pix_ok) {
         const int dr = down_row(bl, t0 + j, L, p.P, p.slice_mode);
-        if (dr >= 0) *reinterpret_cast<f32x4*>(S.D + ((size_t)dr * HW + pixl) * kDownCh + 16 * ctd + 4 * kq_e) = (d1[i] + d2[i]) + bd;
+        if (dr >= 0) *reinterpret_cast<spf4*>(S.D + ((size_t)dr * HW + pixl) * kDownCh + 16 * ctd + 4 * kq_e) = (d1[i] + d2[i]) + bd;
       }
     }
   }

@@ -264,12 +264,6 @@ hipError_t units_bwd_launch(const UbParams& p, hipStream_t st) {
 // =====================================================================================================
 namespace {
 constexpr int WG_BM = 160, WG_BN = 128;
-
-__device__ __forceinline__ int wg_down_row(int f, int L, int P, int slice_mode) {
-  if (slice_mode == 0) return f < P ? f : -1;
-  const int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
 }  // namespace
 
 template <int V> struct WgVec { static constexpr int value = V; };   // X loader form known at compile time (-1: the runtime `vec`)
@@ -378,7 +372,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       const float* q = (!(p.dbg & 2) && kin + 4 * pq + j < HW) ? ga + (size_t)j * kGenCh : p.zeros;
       rg[j] = *reinterpret_cast<const float4*>(q);
     }
-    const int dr = wg_down_row(frame, p.L, p.P, p.slice_mode);
+    const int dr = down_row(frame, p.L, p.P, p.slice_mode);
     {
       const float* q = (dr >= 0 && kin + dpx < HW) ? S.dD + ((size_t)dr * HW + kin + dpx) * kDownCh + 4 * dcq : p.zeros;
       rg[4] = *reinterpret_cast<const float4*>(q);

@@ -1,7 +1,7 @@
 // Training side of the OFF units: the gradient w.r.t. the nine feature maps (offk_off_units_backward_feats).
 //   dX[frame n, pixel q, c] = sum_o dGpre[n, q, o] Wg[o, c] + sum_j dD[r(n), q, j] Wd[j, c]
 // from what K2b (units_bwd.hip) left in the train workspace -- dG_<site> [N*HW][128], dD_<site> [P*HW][32] -- and the gen / down
-// weights as fp32 rows [128][C] / [32][C].  r(n) is the row of frame n in the spatial slice (wg_down_row of K1b: flat slice
+// weights as fp32 rows [128][C] / [32][C].  r(n) is the row of frame n in the spatial slice (down_row of offk_common.h: flat slice
 // r = n for n < P; per-clip slice: frame (b, t), t < L - 1 -> b (L - 1) + t), none for a frame outside the slice.
 //
 // Per site a GEMM [N*HW rows] x [K = 160] x [C], all requested sites in ONE grouped launch.  A block owns DX_BM = 128 consecutive
@@ -45,12 +45,6 @@ static_assert(DX_LDS_FLOATS * 4 <= 160 * 1024, "one block per CU");
 static_assert(DX_BM * DX_A4 % DX_THREADS == 0 && kUnitCh * DX_BN / 4 % DX_THREADS == 0, "whole loader rounds");
 
 typedef float dxf4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int dx_down_row(int f, int L, int P, int slice_mode) {   // wg_down_row of units_bwd.hip
-  if (slice_mode == 0) return f < P ? f : -1;
-  const int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
 
 // ---- 16-bit output elements: one rounding to nearest-even, exact widening ----
 template <int OUT>
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx16_kernel(DxParams p) {
       const int idx = tid + DX_THREADS * (half * (AR / 2) + i), r = idx / DX_A4, c4 = idx - r * DX_A4;
       const int row = row0 + r;
       const int f = row / HW, px = row - f * HW;
-      const int dr = dx_down_row(f, p.L, p.P, p.slice_mode);
+      const int dr = down_row(f, p.L, p.P, p.slice_mode);
       const bool gen = c4 < kGenCh / 4;
       const float* base = gen ? S.dG : S.dD;
       const size_t off = gen ? (size_t)row * kGenCh + 4 * c4 : ((size_t)(dr < 0 ? 0 : dr) * HW + px) * kDownCh + 4 * (c4 - kGenCh / 4);

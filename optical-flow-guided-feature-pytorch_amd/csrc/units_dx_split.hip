@@ -4,7 +4,7 @@
 // remainder is exact in fp32, cut again, and again; synth.cut3), and per 32-k step six of the nine plane products are issued on
 // v_mfma_f32_16x16x32_bf16 in synth.SPLIT_PRODUCTS order -- w_l a_h, w_h a_l, w_m a_m, w_m a_h, w_h a_m into accumulator A2, w_h a_h into A1 --
 // five steps in increasing k (gen channels, then down), out = A1 + A2 once in the epilogue: synth.emulate_split_dot(form="units"), K = 160.
-// No split-K, no atomics, one fixed order: bit-reproducible.  r(n) is dx_down_row of units_dx.hip; a frame outside the slice multiplies
+// No split-K, no atomics, one fixed order: bit-reproducible.  r(n) is down_row of offk_common.h; a frame outside the slice multiplies
 // zeros (the cut of 0 is 0), rows past the site's end are zeros too and store nothing.
 //
 // TWO launches on the caller's stream (units_dx_split_launch):
@@ -29,6 +29,7 @@
 // rne16(widen(old) + new).
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace {
@@ -42,26 +43,6 @@ constexpr int XS_T_BYTES = (XS_THREADS / 64) * 32 * XS_TS * 4;
 constexpr int XS_WPIECE = 1024;                             // one (16-channel tile, k step, plane) piece of the weight image
 static_assert(XS_A_BYTES + XS_T_BYTES <= 160 * 1024, "one block per CU");
 static_assert(kUnitCh % 32 == 0 && kGenCh % 32 == 0, "whole k steps, gen / down split on a step boundary");
-
-typedef float xsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned xsu4 __attribute__((ext_vector_type(4)));
-typedef unsigned xsu2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int xs_down_row(int f, int L, int P, int slice_mode) {   // dx_down_row of units_dx.hip
-  if (slice_mode == 0) return f < P ? f : -1;
-  const int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void xs_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned xs_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
 
 template <int OUT>
 __device__ __forceinline__ unsigned xs_pack16(float lo, float hi) {     // element lo in bits 0..15 (the lower address)
@@ -85,10 +66,6 @@ __device__ __forceinline__ float xs_widen16(unsigned short b) {
   else return (float)__builtin_bit_cast(_Float16, b);
 }
 
-__device__ __forceinline__ void xs_mfma(xsf4& c, const xsu4& w, const xsu4& x) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
-
 }  // namespace
 
 // ---- 1. the weight pre-pass: [Wg ; Wd] as they are NOW -> plane image.  One wave per (16-channel tile, k step) of a site ----
@@ -108,11 +85,11 @@ __global__ __launch_bounds__(XS_THREADS) void units_dx_split_pack_kernel(DxsPara
   const float* src = k0 < kGenCh ? wg + (size_t)k0 * C + c : wd + (size_t)(k0 - kGenCh) * C + c;
   unsigned h[8], m[8], l[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) xs_cut(src[(size_t)j * C], h[j], m[j], l[j]);
+  for (int j = 0; j < 8; ++j) sp_cut(src[(size_t)j * C], h[j], m[j], l[j]);
   char* dst = img + (size_t)(ch16 * XS_KSTEPS + ks) * 3 * XS_WPIECE + lane * 16;
-  *reinterpret_cast<xsu4*>(dst) = xsu4{xs_pair(h[0], h[1]), xs_pair(h[2], h[3]), xs_pair(h[4], h[5]), xs_pair(h[6], h[7])};
-  *reinterpret_cast<xsu4*>(dst + XS_WPIECE) = xsu4{xs_pair(m[0], m[1]), xs_pair(m[2], m[3]), xs_pair(m[4], m[5]), xs_pair(m[6], m[7])};
-  *reinterpret_cast<xsu4*>(dst + 2 * XS_WPIECE) = xsu4{xs_pair(l[0], l[1]), xs_pair(l[2], l[3]), xs_pair(l[4], l[5]), xs_pair(l[6], l[7])};
+  *reinterpret_cast<spu4*>(dst) = spu4{sp_pair(h[0], h[1]), sp_pair(h[2], h[3]), sp_pair(h[4], h[5]), sp_pair(h[6], h[7])};
+  *reinterpret_cast<spu4*>(dst + XS_WPIECE) = spu4{sp_pair(m[0], m[1]), sp_pair(m[2], m[3]), sp_pair(m[4], m[5]), sp_pair(m[6], m[7])};
+  *reinterpret_cast<spu4*>(dst + 2 * XS_WPIECE) = spu4{sp_pair(l[0], l[1]), sp_pair(l[2], l[3]), sp_pair(l[4], l[5]), sp_pair(l[6], l[7])};
 }
 
 // ---- 2. the GEMM ----
@@ -142,24 +119,24 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
 
   // weight operands of one k step: 2 channel tiles x 3 planes, 16 B per lane each, from the plane image (index clamped, never conditional)
   const char* const wsrc = static_cast<const char*>(S.wimg) + lane * 16;
-  auto load_w = [&](xsu4 (&w)[2][3], int step) {
+  auto load_w = [&](spu4 (&w)[2][3], int step) {
     step = min(step, last_step);
     const int ct = step / XS_KSTEPS, ks = step - ct * XS_KSTEPS;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int ch16 = min(ct * 4 + wc * 2 + j, nch16 - 1);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) w[j][q] = *reinterpret_cast<const xsu4*>(wsrc + (size_t)((ch16 * XS_KSTEPS + ks) * 3 + q) * XS_WPIECE);
+      for (int q = 0; q < 3; ++q) w[j][q] = *reinterpret_cast<const spu4*>(wsrc + (size_t)((ch16 * XS_KSTEPS + ks) * 3 + q) * XS_WPIECE);
     }
   };
-  xsu4 wn[2][3];
+  spu4 wn[2][3];
   load_w(wn, 0);
 
   // ---- a = [dGpre | dD] of the block's rows, cut while staged (branch-free loads: what is masked out reads the zero page).  Unit
   //      u = wave + 4 i of 80: 16 rows (one row tile) x 16 k; a lane takes four k of one row: 64 B contiguous per row and lane quad ----
   {
     constexpr int NU = (XS_BM / 16) * (kUnitCh / 16) / (XS_THREADS / 64);     // 20 units per wave
-    xsf4 areg[NU];
+    spf4 areg[NU];
     const int lr = lane >> 2, lc = lane & 3;
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
@@ -170,21 +147,19 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
         if (row < M) src = S.dG + (size_t)row * kGenCh + k;
       } else {
         const int f = row / HW, px = row - f * HW;
-        const int dr = xs_down_row(f, p.L, p.P, p.slice_mode);
+        const int dr = down_row(f, p.L, p.P, p.slice_mode);
         if (row < M && dr >= 0) src = S.dD + ((size_t)dr * HW + px) * kDownCh + (k - kGenCh);
       }
-      areg[i] = *reinterpret_cast<const xsf4*>(src);
+      areg[i] = *reinterpret_cast<const spf4*>(src);
     }
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
       const int u = wave + 4 * i, rt = u / (kUnitCh / 16), cg = u - rt * (kUnitCh / 16);
       unsigned h[4], m[4], l[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) xs_cut(areg[i][j], h[j], m[j], l[j]);
+      for (int j = 0; j < 4; ++j) sp_cut(areg[i][j], h[j], m[j], l[j]);
       char* dst = Ap + rt * XS_RT_BYTES + (cg * 2 + (lc >> 1)) * 256 + lr * 16 + (lc & 1) * 8;
-      *reinterpret_cast<xsu2*>(dst) = xsu2{xs_pair(h[0], h[1]), xs_pair(h[2], h[3])};
-      *reinterpret_cast<xsu2*>(dst + XS_PLANE) = xsu2{xs_pair(m[0], m[1]), xs_pair(m[2], m[3])};
-      *reinterpret_cast<xsu2*>(dst + 2 * XS_PLANE) = xsu2{xs_pair(l[0], l[1]), xs_pair(l[2], l[3])};
+      sp_store_quad<3>(dst, XS_PLANE, h, m, l);
     }
   }
   __syncthreads();                   // the only block-wide barrier: the plane images are in place
@@ -199,26 +174,26 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
   // B operand (rows) of step s = 4 ks + rt of a channel tile: three ds_read_b128.  The reads of step s + 1 are issued BEFORE the MFMAs of step
   // s (two register sets, a scheduling barrier pins the order, as WaveAcc::mma_ktile does): with one wave per SIMD nothing else hides an
   // LDS latency.  The plane images serve every channel tile, so the last step of a tile reads step 0 of the next.
-  auto rdx = [&](xsu4 (&x)[3], int s) {
+  auto rdx = [&](spu4 (&x)[3], int s) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) x[q] = *reinterpret_cast<const xsu4*>(xsrc + (s & 3) * XS_RT_BYTES + (s >> 2) * 1024 + q * XS_PLANE);
+    for (int q = 0; q < 3; ++q) x[q] = *reinterpret_cast<const spu4*>(xsrc + (s & 3) * XS_RT_BYTES + (s >> 2) * 1024 + q * XS_PLANE);
   };
-  xsu4 xb[2][3];
+  spu4 xb[2][3];
   rdx(xb[0], 0);
 
   for (int ct = 0; ct < nct; ++ct) {
     const int cbase = ct * XS_BN + wc * 32;
     if (cbase >= C) break;           // wave-uniform: the half tile past C (C % 64 == 32) is the last one; no barrier follows
 
-    xsf4 a1[4][2], a2[4][2];         // [row tile][channel tile]: A1 = sum w_h a_h, A2 = the five small products
+    spf4 a1[4][2], a2[4][2];         // [row tile][channel tile]: A1 = sum w_h a_h, A2 = the five small products
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) { a1[rt][j] = xsf4{0.f, 0.f, 0.f, 0.f}; a2[rt][j] = xsf4{0.f, 0.f, 0.f, 0.f}; }
+      for (int j = 0; j < 2; ++j) { a1[rt][j] = spf4{0.f, 0.f, 0.f, 0.f}; a2[rt][j] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
 #pragma unroll
     for (int ks = 0; ks < XS_KSTEPS; ++ks) {
-      xsu4 w[2][3];
+      spu4 w[2][3];
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -228,22 +203,22 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
       for (int rt = 0; rt < 4; ++rt) {
         constexpr int NS = 4 * XS_KSTEPS;
         const int s = 4 * ks + rt;                       // (even: 20 steps per tile, the register sets keep their parity across tiles)
-        xsu4 (&x)[3] = xb[s & 1];
+        spu4 (&x)[3] = xb[s & 1];
         rdx(xb[(s + 1) & 1], (s + 1) % NS);
         __builtin_amdgcn_sched_barrier(0);
         // synth.SPLIT_PRODUCTS order (w plane, a plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a2[rt][j], w[j][2], x[0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[rt][j], w[j][2], x[0]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a2[rt][j], w[j][0], x[2]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[rt][j], w[j][0], x[2]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a2[rt][j], w[j][1], x[1]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[rt][j], w[j][1], x[1]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a2[rt][j], w[j][1], x[0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[rt][j], w[j][1], x[0]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a2[rt][j], w[j][0], x[1]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[rt][j], w[j][0], x[1]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) xs_mfma(a1[rt][j], w[j][0], x[0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a1[rt][j], w[j][0], x[0]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -255,23 +230,23 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
         const int row = row0 + wr * 64 + rt * 16 + lr16;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          xsf4 v = a1[rt][j] + a2[rt][j];
+          spf4 v = a1[rt][j] + a2[rt][j];
           const size_t at = (size_t)row * C + cbase + 16 * j + 4 * lq;      // a multiple of 4 elements: 16-byte / 8-byte aligned
           if (row < M) {
             if constexpr (OUT == kFeatF32) {
-              xsf4* o = reinterpret_cast<xsf4*>(static_cast<float*>(S.out) + at);
+              spf4* o = reinterpret_cast<spf4*>(static_cast<float*>(S.out) + at);
               if (p.accumulate) v = *o + v;
               *o = v;
             } else {
-              xsu2* o = reinterpret_cast<xsu2*>(static_cast<unsigned short*>(S.out) + at);
+              spu2* o = reinterpret_cast<spu2*>(static_cast<unsigned short*>(S.out) + at);
               if (p.accumulate) {
-                const xsu2 old = *o;
+                const spu2 old = *o;
                 v[0] += xs_widen16<OUT>((unsigned short)(old[0] & 0xFFFFu));
                 v[1] += xs_widen16<OUT>((unsigned short)(old[0] >> 16));
                 v[2] += xs_widen16<OUT>((unsigned short)(old[1] & 0xFFFFu));
                 v[3] += xs_widen16<OUT>((unsigned short)(old[1] >> 16));
               }
-              *o = xsu2{xs_pack16<OUT>(v[0], v[1]), xs_pack16<OUT>(v[2], v[3])};
+              *o = spu2{xs_pack16<OUT>(v[0], v[1]), xs_pack16<OUT>(v[2], v[3])};
             }
           }
         }
@@ -283,7 +258,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
       for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const xsf4 v = a1[rt][j] + a2[rt][j];
+          const spf4 v = a1[rt][j] + a2[rt][j];
 #pragma unroll
           for (int i = 0; i < 4; ++i) T[(16 * j + 4 * lq + i) * XS_TS + rt * 16 + lr16] = v[i];
         }

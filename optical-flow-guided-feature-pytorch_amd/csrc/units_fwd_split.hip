@@ -25,6 +25,7 @@
 // that spills or keeps anything in scratch memory (REGISTER_RESIDENT_KERNELS).
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace {
@@ -36,40 +37,6 @@ constexpr int FS_WTILE = FS_CT * 3 * FS_PIECE;       // 30720: the weight operan
 constexpr int FS_WITEMS = FS_WTILE / 16;             // 1920 16-byte items
 constexpr int FS_XPLANE = (FS_BM / 16) * FS_PIECE;   // 8192
 constexpr int FS_WCT = FS_CT / 2;                    // channel tiles of one wave
-
-typedef float fsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned fsu4 __attribute__((ext_vector_type(4)));
-typedef unsigned fsu2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int fs_down_row(int f, int L, int P, int slice_mode) {   // down_row of pw_reduce.hip
-  if (slice_mode == 0) return f < P ? f : -1;
-  const int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void fs_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned fs_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-// four consecutive k of one row -> 8 bytes in each of the first NPL plane images
-template <int NPL>
-__device__ __forceinline__ void fs_store_quad(char* dst, float v0, float v1, float v2, float v3) {
-  unsigned h[4], m[4], l[4];
-  fs_cut(v0, h[0], m[0], l[0]); fs_cut(v1, h[1], m[1], l[1]); fs_cut(v2, h[2], m[2], l[2]); fs_cut(v3, h[3], m[3], l[3]);
-  *reinterpret_cast<fsu2*>(dst) = fsu2{fs_pair(h[0], h[1]), fs_pair(h[2], h[3])};
-  if constexpr (NPL > 1) *reinterpret_cast<fsu2*>(dst + FS_XPLANE) = fsu2{fs_pair(m[0], m[1]), fs_pair(m[2], m[3])};
-  if constexpr (NPL > 2) *reinterpret_cast<fsu2*>(dst + 2 * FS_XPLANE) = fsu2{fs_pair(l[0], l[1]), fs_pair(l[2], l[3])};
-}
-
-__device__ __forceinline__ void fs_mfma(fsf4& c, const fsu4& w, const fsu4& x) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 template <int V> struct FsMode { static constexpr int value = V; };   // a loader mode known at compile time
 
@@ -91,11 +58,11 @@ __global__ __launch_bounds__(256) void units_fwd_split_pack_kernel(UfsParams p) 
   const float* src = (row < kGenCh ? wg + (size_t)row * C : wd + (size_t)(row - kGenCh) * C) + kt * BK + 8 * g;
   unsigned h[8], m[8], l[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) fs_cut(src[e], h[e], m[e], l[e]);
+  for (int e = 0; e < 8; ++e) sp_cut(src[e], h[e], m[e], l[e]);
   uint4* dst = img + (size_t)(kt * FS_CT + ct) * 3 * 64 + lane;
-  dst[0] = make_uint4(fs_pair(h[0], h[1]), fs_pair(h[2], h[3]), fs_pair(h[4], h[5]), fs_pair(h[6], h[7]));
-  dst[64] = make_uint4(fs_pair(m[0], m[1]), fs_pair(m[2], m[3]), fs_pair(m[4], m[5]), fs_pair(m[6], m[7]));
-  dst[128] = make_uint4(fs_pair(l[0], l[1]), fs_pair(l[2], l[3]), fs_pair(l[4], l[5]), fs_pair(l[6], l[7]));
+  dst[0] = make_uint4(sp_pair(h[0], h[1]), sp_pair(h[2], h[3]), sp_pair(h[4], h[5]), sp_pair(h[6], h[7]));
+  dst[64] = make_uint4(sp_pair(m[0], m[1]), sp_pair(m[2], m[3]), sp_pair(m[4], m[5]), sp_pair(m[6], m[7]));
+  dst[128] = make_uint4(sp_pair(l[0], l[1]), sp_pair(l[2], l[3]), sp_pair(l[4], l[5]), sp_pair(l[6], l[7]));
 }
 
 // FEAT: element type of the feature map (kFeatF32 / kFeatBf16 / kFeatF16), | kFeatCl: channels-last maps.  NPX: the planes such a map has.
@@ -166,7 +133,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
   // TWO steps in flight: rgN / wrN receive the loads of step kt + 2 while rg / wr (step kt + 1, taken over at the top of the step, where the
   // one wait for everything in flight stands) are cut behind the MFMAs of step kt without any wait of their own
   float4 rg[4], rgN[4];   // the map elements: fp32 values, or 16-bit elements as loaded (bit patterns, widened by the store)
-  fsu4 wr[4], wrN[4];     // the thread's items of the step's weight operands
+  spu4 wr[4], wrN[4];     // the thread's items of the step's weight operands
   auto load_x = [&](int k0, auto MT) {
     constexpr int MODE = decltype(MT)::value;
     if (!xl) return;
@@ -225,7 +192,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
     }
   };
   auto load_w = [&](int kt) {
-    const fsu4* src = reinterpret_cast<const fsu4*>(static_cast<const char*>(S.wimg) + (size_t)kt * FS_WTILE);
+    const spu4* src = reinterpret_cast<const spu4*>(static_cast<const char*>(S.wimg) + (size_t)kt * FS_WTILE);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (tid + FS_THREADS * j < FS_WITEMS) wrN[j] = src[tid + FS_THREADS * j];
@@ -257,7 +224,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
     constexpr int MODE = decltype(MT)::value;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (tid + FS_THREADS * j < FS_WITEMS) *reinterpret_cast<fsu4*>(buf + (tid + FS_THREADS * j) * 16) = wr[j];
+      if (tid + FS_THREADS * j < FS_WITEMS) *reinterpret_cast<spu4*>(buf + (tid + FS_THREADS * j) * 16) = wr[j];
     if (!xl) return;
     char* const Xp = buf + FS_WTILE;
     if constexpr (MODE == 0) {
@@ -266,33 +233,33 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
       for (int j = 0; j < 4; ++j) w[j] = FT == kFeatF32 ? rg[j] : widen4(rg[j]);
       // k row j's four pixels -> pixel i's four k, as K1 transposes them
       const int row = 4 * (lt >> 3), kq = lt & 7;
-      fs_store_quad<NPX>(quad_at(Xp, row, kq), w[0].x, w[1].x, w[2].x, w[3].x);
-      fs_store_quad<NPX>(quad_at(Xp, row + 1, kq), w[0].y, w[1].y, w[2].y, w[3].y);
-      fs_store_quad<NPX>(quad_at(Xp, row + 2, kq), w[0].z, w[1].z, w[2].z, w[3].z);
-      fs_store_quad<NPX>(quad_at(Xp, row + 3, kq), w[0].w, w[1].w, w[2].w, w[3].w);
+      sp_store_quad<NPX>(quad_at(Xp, row, kq), FS_XPLANE, w[0].x, w[1].x, w[2].x, w[3].x);
+      sp_store_quad<NPX>(quad_at(Xp, row + 1, kq), FS_XPLANE, w[0].y, w[1].y, w[2].y, w[3].y);
+      sp_store_quad<NPX>(quad_at(Xp, row + 2, kq), FS_XPLANE, w[0].z, w[1].z, w[2].z, w[3].z);
+      sp_store_quad<NPX>(quad_at(Xp, row + 3, kq), FS_XPLANE, w[0].w, w[1].w, w[2].w, w[3].w);
     } else if constexpr (MODE == 1) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float4 v = rg[r];
         if constexpr (FT != kFeatF32)
           v = make_float4(widen(__float_as_uint(v.x)), widen(__float_as_uint(v.y)), widen(__float_as_uint(v.z)), widen(__float_as_uint(v.w)));
-        fs_store_quad<NPX>(quad_at(Xp, lt & 127, (lt >> 7) + 2 * r), v.x, v.y, v.z, v.w);
+        sp_store_quad<NPX>(quad_at(Xp, lt & 127, (lt >> 7) + 2 * r), FS_XPLANE, v.x, v.y, v.z, v.w);
       }
     } else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float4 v = FT == kFeatF32 ? rg[r] : widen4(rg[r]);
-        fs_store_quad<NPX>(quad_at(Xp, (lt >> 3) + 32 * r, lt & 7), v.x, v.y, v.z, v.w);
+        sp_store_quad<NPX>(quad_at(Xp, (lt >> 3) + 32 * r, lt & 7), FS_XPLANE, v.x, v.y, v.z, v.w);
       }
     }
   };
 
   // accumulators [channel tile][row tile]: A1 = sum w_h x_h, A2 = the small products
-  fsf4 a1[FS_WCT][2], a2[FS_WCT][2];
+  spf4 a1[FS_WCT][2], a2[FS_WCT][2];
 #pragma unroll
   for (int ct = 0; ct < FS_WCT; ++ct)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { a1[ct][j] = fsf4{0.f, 0.f, 0.f, 0.f}; a2[ct][j] = fsf4{0.f, 0.f, 0.f, 0.f}; }
+    for (int j = 0; j < 2; ++j) { a1[ct][j] = spf4{0.f, 0.f, 0.f, 0.f}; a2[ct][j] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   const int lr16 = lane & 15, lq = lane >> 4;
   const int wrow = wave >> 1, wch = wave & 1;   // MFMA role: rows 32 wrow .. + 31, channel tiles 5 wch .. + 4
@@ -302,44 +269,44 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
   const int xoff = FS_WTILE + 2 * wrow * FS_PIECE + lq * 256 + ((lr16 ^ (lq << sh)) << 4);            // + j * FS_PIECE + plane * FS_XPLANE
 
   auto mma_tile = [&](const char* buf) {
-    fsu4 xb[2][NPX];
+    spu4 xb[2][NPX];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int q = 0; q < NPX; ++q) xb[j][q] = *reinterpret_cast<const fsu4*>(buf + xoff + j * FS_PIECE + q * FS_XPLANE);
+      for (int q = 0; q < NPX; ++q) xb[j][q] = *reinterpret_cast<const spu4*>(buf + xoff + j * FS_PIECE + q * FS_XPLANE);
     // the weight operands of channel tile ct + 1 are read BEFORE the MFMAs of tile ct (two register sets, a scheduling barrier pins the order)
-    fsu4 wb[2][3];
+    spu4 wb[2][3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) wb[0][q] = *reinterpret_cast<const fsu4*>(buf + woff + q * FS_PIECE);
+    for (int q = 0; q < 3; ++q) wb[0][q] = *reinterpret_cast<const spu4*>(buf + woff + q * FS_PIECE);
 #pragma unroll
     for (int ct = 0; ct < FS_WCT; ++ct) {
       if (ct >= nct) break;
-      fsu4 (&w)[3] = wb[ct & 1];
+      spu4 (&w)[3] = wb[ct & 1];
       if (ct + 1 < FS_WCT) {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) wb[(ct + 1) & 1][q] = *reinterpret_cast<const fsu4*>(buf + woff + (ct + 1) * 3 * FS_PIECE + q * FS_PIECE);
+        for (int q = 0; q < 3; ++q) wb[(ct + 1) & 1][q] = *reinterpret_cast<const spu4*>(buf + woff + (ct + 1) * 3 * FS_PIECE + q * FS_PIECE);
       }
       __builtin_amdgcn_sched_barrier(0);
       // synth.SPLIT_PRODUCTS order (w plane, x plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1.  A product with a plane
       // the map's type does not have is not issued (it would add +-0)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fs_mfma(a2[ct][j], w[2], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a2[ct][j], w[2], xb[j][0]);
       if constexpr (NPX > 2) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fs_mfma(a2[ct][j], w[0], xb[j][NPX > 2 ? 2 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[ct][j], w[0], xb[j][NPX > 2 ? 2 : 0]);
       }
       if constexpr (NPX > 1) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fs_mfma(a2[ct][j], w[1], xb[j][NPX > 1 ? 1 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[ct][j], w[1], xb[j][NPX > 1 ? 1 : 0]);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fs_mfma(a2[ct][j], w[1], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a2[ct][j], w[1], xb[j][0]);
       if constexpr (NPX > 1) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fs_mfma(a2[ct][j], w[0], xb[j][NPX > 1 ? 1 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[ct][j], w[0], xb[j][NPX > 1 ? 1 : 0]);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) fs_mfma(a1[ct][j], w[0], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a1[ct][j], w[0], xb[j][0]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -377,19 +344,19 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
     const int c = 16 * (wch * FS_WCT + ct) + 4 * lq;     // tiles 0..7: gen channels, 8, 9: down channels (wave-uniform per ct)
     const bool gen = wch * FS_WCT + ct < kGenCh / 16;
     const float* bp = gen ? S.bias + c : S.bias_down + (c - kGenCh);
-    const fsf4 bv = fsf4{bp[0], bp[1], bp[2], bp[3]};
+    const spf4 bv = spf4{bp[0], bp[1], bp[2], bp[3]};
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int m = m0 + 32 * wrow + 16 * j + lr16;
-      fsf4 v = (a1[ct][j] + a2[ct][j]) + bv;
+      spf4 v = (a1[ct][j] + a2[ct][j]) + bv;
       if (m >= M) continue;
       if (gen) {
-        v = fsf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-        *reinterpret_cast<fsf4*>(S.G + (size_t)m * kGenCh + c) = v;
+        v = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+        *reinterpret_cast<spf4*>(S.G + (size_t)m * kGenCh + c) = v;
       } else {
         const int f = m / HW, px = m - f * HW;
-        const int dr = fs_down_row(f, p.L, p.P, p.slice_mode);
-        if (dr >= 0) *reinterpret_cast<fsf4*>(S.D + ((size_t)dr * HW + px) * kDownCh + (c - kGenCh)) = v;
+        const int dr = down_row(f, p.L, p.P, p.slice_mode);
+        if (dr >= 0) *reinterpret_cast<spf4*>(S.D + ((size_t)dr * HW + px) * kDownCh + (c - kGenCh)) = v;
       }
     }
   }

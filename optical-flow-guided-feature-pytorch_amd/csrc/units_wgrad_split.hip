@@ -1,7 +1,7 @@
 // The weight gradient of the stacked 1x1 reduce convs in split-fp32 arithmetic (offk_off_units_backward_split): K1b's GEMM (units_bwd.hip)
 //   dW[m][c] = sum over (frame f, pixel q) a[(f,q)][m] X[f][c][q],   a = [dGpre (m 0..127) | dD at row r(f) (m 128..159), zeros outside the slice]
-// on the bf16 matrix pipe, DESIGN.md 5.1: both operands are cut into THREE bf16 planes by truncation (synth.cut3; xs_cut of units_dx_split.hip
-// is the same device form) and per 32-k step -- one K-tile: 32 pixels of one frame, pad pixels zeros, exactly K1b's tiles -- six of the nine plane
+// on the bf16 matrix pipe, DESIGN.md 5.1: both operands are cut into THREE bf16 planes by truncation (synth.cut3; sp_cut of split_common.h)
+// and per 32-k step -- one K-tile: 32 pixels of one frame, pad pixels zeros, exactly K1b's tiles -- six of the nine plane
 // products are issued on v_mfma_f32_16x16x32_bf16 in synth.SPLIT_PRODUCTS order with a in the role of w: a_l x_h, a_h x_l, a_m x_m, a_m x_h,
 // a_h x_m into accumulator A2, a_h x_h into A1; steps in increasing K-tile order, the block's partial tile is A1 + A2, added once.  That is
 // synth.emulate_split_dot(form="units") over the block's chunk of K-tiles; the slabs are then summed in chunk order by the unchanged
@@ -29,6 +29,7 @@
 // that spills or keeps anything in scratch memory (REGISTER_RESIDENT_KERNELS).
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 namespace offk {
 namespace {
@@ -38,40 +39,6 @@ constexpr int WS_DEPTH = 3;                          // K-tiles in flight in reg
 constexpr int WS_PIECE = 1024;                       // one 16-row tile of one plane: 4 k groups x 16 rows x 16 B
 constexpr int WS_APLANE = (WS_BM / 16) * WS_PIECE;   // 10240
 constexpr int WS_XPLANE = (WS_BN / 16) * WS_PIECE;   // 8192
-
-typedef float wsf4 __attribute__((ext_vector_type(4)));
-typedef unsigned wsu4 __attribute__((ext_vector_type(4)));
-typedef unsigned wsu2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int ws_down_row(int f, int L, int P, int slice_mode) {   // wg_down_row of units_bwd.hip
-  if (slice_mode == 0) return f < P ? f : -1;
-  const int b = f / L, t = f - b * L;
-  return t < L - 1 ? b * (L - 1) + t : -1;
-}
-
-// the truncating three-plane cut (synth.cut3): h, m in the upper 16 bits of the returned words, l's plane is the upper 16 bits of its word
-__device__ __forceinline__ void ws_cut(float x, unsigned& h, unsigned& m, unsigned& l) {
-  h = __float_as_uint(x) & 0xFFFF0000u;
-  const float r = x - __uint_as_float(h);
-  m = __float_as_uint(r) & 0xFFFF0000u;
-  l = __float_as_uint(r - __uint_as_float(m));
-}
-// the upper halves of two words as one: `lo` in bits 0..15 (the lower k)
-__device__ __forceinline__ unsigned ws_pair(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302); }
-
-// four consecutive k of one row -> 8 bytes in each of the first NPL plane images
-template <int NPL>
-__device__ __forceinline__ void ws_store_quad(char* dst, int plane_bytes, float v0, float v1, float v2, float v3) {
-  unsigned h[4], m[4], l[4];
-  ws_cut(v0, h[0], m[0], l[0]); ws_cut(v1, h[1], m[1], l[1]); ws_cut(v2, h[2], m[2], l[2]); ws_cut(v3, h[3], m[3], l[3]);
-  *reinterpret_cast<wsu2*>(dst) = wsu2{ws_pair(h[0], h[1]), ws_pair(h[2], h[3])};
-  if constexpr (NPL > 1) *reinterpret_cast<wsu2*>(dst + plane_bytes) = wsu2{ws_pair(m[0], m[1]), ws_pair(m[2], m[3])};
-  if constexpr (NPL > 2) *reinterpret_cast<wsu2*>(dst + 2 * plane_bytes) = wsu2{ws_pair(l[0], l[1]), ws_pair(l[2], l[3])};
-}
-
-__device__ __forceinline__ void ws_mfma(wsf4& c, const wsu4& a, const wsu4& x) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-}
 
 template <int V> struct WsVec { static constexpr int value = V; };   // X loader form known at compile time (-1: the runtime `vec`)
 
@@ -187,7 +154,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
       const float* ga = S.dG + ((size_t)frame * HW + kin + 4 * pq) * kGenCh + 4 * cq;
 #pragma unroll
       for (int j = 0; j < 4; ++j) qa[j] = (valid && is_a && kin + 4 * pq + j < HW) ? ga + (size_t)j * kGenCh : p.zeros;
-      const int dr = ws_down_row(frame, p.L, p.P, p.slice_mode);
+      const int dr = down_row(frame, p.L, p.P, p.slice_mode);
       qa[4] = (valid && is_a && dr >= 0 && kin + dpx < HW) ? S.dD + ((size_t)dr * HW + kin + dpx) * kDownCh + 4 * dcq : p.zeros;
     }
     const int k = kin + 4 * (lt & 7), kk = min(k, HW - 4);
@@ -273,10 +240,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
       bs_g.z += (rg[0].z + rg[1].z) + (rg[2].z + rg[3].z); bs_g.w += (rg[0].w + rg[1].w) + (rg[2].w + rg[3].w);
       bs_d.x += rg[4].x; bs_d.y += rg[4].y; bs_d.z += rg[4].z; bs_d.w += rg[4].w;
       // gen: pixel j's four channels -> channel i's four pixels, as K1b transposes them
-      ws_store_quad<3>(quad_at(Ap, 4 * cq, pq, 0), WS_APLANE, rg[0].x, rg[1].x, rg[2].x, rg[3].x);
-      ws_store_quad<3>(quad_at(Ap, 4 * cq + 1, pq, 0), WS_APLANE, rg[0].y, rg[1].y, rg[2].y, rg[3].y);
-      ws_store_quad<3>(quad_at(Ap, 4 * cq + 2, pq, 0), WS_APLANE, rg[0].z, rg[1].z, rg[2].z, rg[3].z);
-      ws_store_quad<3>(quad_at(Ap, 4 * cq + 3, pq, 0), WS_APLANE, rg[0].w, rg[1].w, rg[2].w, rg[3].w);
+      sp_store_quad<3>(quad_at(Ap, 4 * cq, pq, 0), WS_APLANE, rg[0].x, rg[1].x, rg[2].x, rg[3].x);
+      sp_store_quad<3>(quad_at(Ap, 4 * cq + 1, pq, 0), WS_APLANE, rg[0].y, rg[1].y, rg[2].y, rg[3].y);
+      sp_store_quad<3>(quad_at(Ap, 4 * cq + 2, pq, 0), WS_APLANE, rg[0].z, rg[1].z, rg[2].z, rg[3].z);
+      sp_store_quad<3>(quad_at(Ap, 4 * cq + 3, pq, 0), WS_APLANE, rg[0].w, rg[1].w, rg[2].w, rg[3].w);
       // down: one pixel (k = dpx), rows 128 + 4 dcq .. + 3: one 16-bit word per row and plane
       const int kg = dpx >> 3;
       const float dv[4] = {rg[4].x, rg[4].y, rg[4].z, rg[4].w};
@@ -284,7 +251,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
       for (int i = 0; i < 4; ++i) {
         const int row = kGenCh + 4 * dcq + i;
         unsigned h, m, l;
-        ws_cut(dv[i], h, m, l);
+        sp_cut(dv[i], h, m, l);
         char* dst = Ap + (row >> 4) * WS_PIECE + kg * 256 + (((row & 15) ^ kg) << 4) + (dpx & 7) * 2;
         *reinterpret_cast<unsigned short*>(dst) = (unsigned short)(h >> 16);
         *reinterpret_cast<unsigned short*>(dst + WS_APLANE) = (unsigned short)(m >> 16);
@@ -301,10 +268,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
           rg[j] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
         }
       }
-      ws_store_quad<NPX>(quad_at(Xp, 4 * cq, pq, 0), WS_XPLANE, rg[0].x, rg[1].x, rg[2].x, rg[3].x);
-      ws_store_quad<NPX>(quad_at(Xp, 4 * cq + 1, pq, 0), WS_XPLANE, rg[0].y, rg[1].y, rg[2].y, rg[3].y);
-      ws_store_quad<NPX>(quad_at(Xp, 4 * cq + 2, pq, 0), WS_XPLANE, rg[0].z, rg[1].z, rg[2].z, rg[3].z);
-      ws_store_quad<NPX>(quad_at(Xp, 4 * cq + 3, pq, 0), WS_XPLANE, rg[0].w, rg[1].w, rg[2].w, rg[3].w);
+      sp_store_quad<NPX>(quad_at(Xp, 4 * cq, pq, 0), WS_XPLANE, rg[0].x, rg[1].x, rg[2].x, rg[3].x);
+      sp_store_quad<NPX>(quad_at(Xp, 4 * cq + 1, pq, 0), WS_XPLANE, rg[0].y, rg[1].y, rg[2].y, rg[3].y);
+      sp_store_quad<NPX>(quad_at(Xp, 4 * cq + 2, pq, 0), WS_XPLANE, rg[0].z, rg[1].z, rg[2].z, rg[3].z);
+      sp_store_quad<NPX>(quad_at(Xp, 4 * cq + 3, pq, 0), WS_XPLANE, rg[0].w, rg[1].w, rg[2].w, rg[3].w);
     } else {
       if constexpr (FEAT != kFeatF32) {
 #pragma unroll
@@ -322,16 +289,16 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        ws_store_quad<NPX>(quad_at(Xp, (lt >> 3) + 32 * r, lt & 7, 1), WS_XPLANE, rg[r].x, rg[r].y, rg[r].z, rg[r].w);
+        sp_store_quad<NPX>(quad_at(Xp, (lt >> 3) + 32 * r, lt & 7, 1), WS_XPLANE, rg[r].x, rg[r].y, rg[r].z, rg[r].w);
     }
   };
 
   // accumulators [row tile][channel tile]: A1 = sum a_h x_h, A2 = the small products
-  wsf4 a1[WS_MT][2], a2[WS_MT][2];
+  spf4 a1[WS_MT][2], a2[WS_MT][2];
 #pragma unroll
   for (int mt = 0; mt < WS_MT; ++mt)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { a1[mt][j] = wsf4{0.f, 0.f, 0.f, 0.f}; a2[mt][j] = wsf4{0.f, 0.f, 0.f, 0.f}; }
+    for (int j = 0; j < 2; ++j) { a1[mt][j] = spf4{0.f, 0.f, 0.f, 0.f}; a2[mt][j] = spf4{0.f, 0.f, 0.f, 0.f}; }
 
   const int lr16 = lane & 15, lq = lane >> 4;
   // operand offsets inside a buffer: a + mt * WS_PIECE + plane * WS_APLANE, X + j * WS_PIECE + plane * WS_XPLANE
@@ -339,44 +306,44 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
   const int xoff = 3 * WS_APLANE + (2 * wc) * WS_PIECE + lq * 256 + ((lr16 ^ (lq << (CL ? 0 : 1))) << 4);
 
   auto mma_tile = [&](const char* buf) {
-    wsu4 xb[2][NPX];
+    spu4 xb[2][NPX];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int q = 0; q < NPX; ++q) xb[j][q] = *reinterpret_cast<const wsu4*>(buf + xoff + j * WS_PIECE + q * WS_XPLANE);
+      for (int q = 0; q < NPX; ++q) xb[j][q] = *reinterpret_cast<const spu4*>(buf + xoff + j * WS_PIECE + q * WS_XPLANE);
     // the a operands of row tile mt + 1 are read BEFORE the MFMAs of row tile mt (two register sets, a scheduling barrier pins the order,
     // as units_dx_split_kernel does)
-    wsu4 ab[2][3];
+    spu4 ab[2][3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) ab[0][q] = *reinterpret_cast<const wsu4*>(buf + aoff + q * WS_APLANE);
+    for (int q = 0; q < 3; ++q) ab[0][q] = *reinterpret_cast<const spu4*>(buf + aoff + q * WS_APLANE);
 #pragma unroll
     for (int mt = 0; mt < WS_MT; ++mt) {
-      wsu4 (&a)[3] = ab[mt & 1];
+      spu4 (&a)[3] = ab[mt & 1];
       if (mt + 1 < WS_MT) {
 #pragma unroll
-        for (int q = 0; q < 3; ++q) ab[(mt + 1) & 1][q] = *reinterpret_cast<const wsu4*>(buf + aoff + (mt + 1) * WS_PIECE + q * WS_APLANE);
+        for (int q = 0; q < 3; ++q) ab[(mt + 1) & 1][q] = *reinterpret_cast<const spu4*>(buf + aoff + (mt + 1) * WS_PIECE + q * WS_APLANE);
       }
       __builtin_amdgcn_sched_barrier(0);
       // synth.SPLIT_PRODUCTS order (a plane, x plane): (2, 0), (0, 2), (1, 1), (1, 0), (0, 1) -> A2; (0, 0) -> A1.  A product with a plane
       // the map's type does not have is not issued (it would add +-0)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ws_mfma(a2[mt][j], a[2], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a2[mt][j], a[2], xb[j][0]);
       if constexpr (NPX > 2) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ws_mfma(a2[mt][j], a[0], xb[j][NPX > 2 ? 2 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[mt][j], a[0], xb[j][NPX > 2 ? 2 : 0]);
       }
       if constexpr (NPX > 1) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ws_mfma(a2[mt][j], a[1], xb[j][NPX > 1 ? 1 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[mt][j], a[1], xb[j][NPX > 1 ? 1 : 0]);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ws_mfma(a2[mt][j], a[1], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a2[mt][j], a[1], xb[j][0]);
       if constexpr (NPX > 1) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) ws_mfma(a2[mt][j], a[0], xb[j][NPX > 1 ? 1 : 0]);
+        for (int j = 0; j < 2; ++j) sp_mfma(a2[mt][j], a[0], xb[j][NPX > 1 ? 1 : 0]);
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) ws_mfma(a1[mt][j], a[0], xb[j][0]);
+      for (int j = 0; j < 2; ++j) sp_mfma(a1[mt][j], a[0], xb[j][0]);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -432,7 +399,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
     for (int mt = 0; mt < WS_MT; ++mt)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const wsf4 v = a1[mt][j] + a2[mt][j];
+        const spf4 v = a1[mt][j] + a2[mt][j];
 #pragma unroll
         for (int i = 0; i < 4; ++i) out[(size_t)((wm * WS_MT + mt) * 16 + 4 * lq + i) * cpad + 16 * j] = v[i];
       }

@@ -25,6 +25,7 @@
 
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 
 #ifndef OFFK_GS_EXP
 #define OFFK_GS_EXP 0      /* timing experiments (tools/build_one.py -DOFFK_GS_EXP=mask): 1 no cut, 4 no U loads, 8 no V loads, 16 U from one K-tile */
@@ -33,9 +34,6 @@
 namespace offk {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int GS_BM = 64;                   // rows per item; channels per item: 64 CT (four waves x CT channel tiles of 16)
 constexpr int GS_GRP = 256;                 // one k group of a plane: 16 row slots x 16 B (8 bf16 = k 8g .. 8g + 7)
 constexpr int GS_PLANE = 4 * GS_GRP;        // 32 k
@@ -129,16 +127,16 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
   // the multiply
   int c_l = x_l, c_t = 0, c_nkt = 0, c_ysoff = 0, c_m0 = 0, c_n0 = 0;
 
-  u32x4 xr[2][2];                  // V registers [set = K-tile parity][row half]
-  u32x4 wr[2][CT][3];              // U planes [set][channel tile][plane]
+  spu4 xr[2][2];                  // V registers [set = K-tile parity][row half]
+  spu4 wr[2][CT][3];              // U planes [set][channel tile][plane]
   auto load_x = [&](const int set, const int r) {
-    xr[set][r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, x_off[r], x_soff + x_t * 128, 0));
+    xr[set][r] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(xrs, x_off[r], x_soff + x_t * 128, 0));
   };
   auto load_u = [&](const int set, const int n) {      // n = ct * 3 + plane
 #if defined(OFFK_GS_EXP) && (OFFK_GS_EXP & 16)     /* timing experiment: every step re-reads the item's first K-tile (cache-resident) */
-    wr[set][n / 3][n % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, u_voff, u_soff + n * 1024, 0));
+    wr[set][n / 3][n % 3] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(wrs, u_voff, u_soff + n * 1024, 0));
 #else
-    wr[set][n / 3][n % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, u_voff, u_soff + u_t * ukstep + n * 1024, 0));
+    wr[set][n / 3][n % 3] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(wrs, u_voff, u_soff + u_t * ukstep + n * 1024, 0));
 #endif
   };
   auto adv_x = [&]() {
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
   unsigned ch[4], cm[4];
   f32x2 cr[2], cl[2];
   auto cut_slice = [&](const int s, const int set, const int r, const int st) {
-    const u32x4& x = xr[set][r];
+    const spu4& x = xr[set][r];
     if (s == 0) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) ch[e] = x[e] & 0xffff0000u;
@@ -180,22 +178,18 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
       for (int e = 0; e < 2; ++e) cl[e] = cr[e] - f32x2{__uint_as_float(cm[2 * e]), __uint_as_float(cm[2 * e + 1])};     // <= 8 significant bits left
     } else {
       char* dst = pl_wr + st * GS_STAGE + r * 2 * GS_RT + (s - 4) * GS_PLANE;
-      u32x2 d;
-      if (s == 4) d = u32x2{__builtin_amdgcn_perm(x[1], x[0], 0x07060302), __builtin_amdgcn_perm(x[3], x[2], 0x07060302)};
-      else if (s == 5) d = u32x2{__builtin_amdgcn_perm(cm[1], cm[0], 0x07060302), __builtin_amdgcn_perm(cm[3], cm[2], 0x07060302)};
-      else d = u32x2{__builtin_amdgcn_perm(__float_as_uint(cl[0][1]), __float_as_uint(cl[0][0]), 0x07060302),
-                     __builtin_amdgcn_perm(__float_as_uint(cl[1][1]), __float_as_uint(cl[1][0]), 0x07060302)};
-      *reinterpret_cast<u32x2*>(dst) = d;
+      spu2 d;
+      if (s == 4) d = spu2{sp_pair(x[0], x[1]), sp_pair(x[2], x[3])};
+      else if (s == 5) d = spu2{sp_pair(cm[0], cm[1]), sp_pair(cm[2], cm[3])};
+      else d = spu2{sp_pair(__float_as_uint(cl[0][0]), __float_as_uint(cl[0][1])), sp_pair(__float_as_uint(cl[1][0]), __float_as_uint(cl[1][1]))};
+      *reinterpret_cast<spu2*>(dst) = d;
     }
   };
   constexpr int CUT_SLICES = 7;
 
-  f32x4 acc[NT], acs[NT];          // acc: sum w_h x_h (and, in store_item, the item's result); acs: the five small products
+  spf4 acc[NT], acs[NT];          // acc: sum w_h x_h (and, in store_item, the item's result); acs: the five small products
 #pragma unroll
-  for (int i = 0; i < NT; ++i) { acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; acs[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  auto mf = [&](f32x4 c, const u32x4& a, const u32x4& b) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  };
+  for (int i = 0; i < NT; ++i) { acc[i] = spf4{0.f, 0.f, 0.f, 0.f}; acs[i] = spf4{0.f, 0.f, 0.f, 0.f}; }
 #define OFFK_SB __builtin_amdgcn_sched_barrier(0)
 
   // the finished item: a lane holds channels 4 lg .. + 3 of row li.
@@ -211,13 +205,13 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
       // + bias, ReLU
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias) b4 = *reinterpret_cast<const f32x4*>(p.bias + c_n0 + (CT * wave + ct) * 16 + 4 * lg);
+        spf4 b4 = {0.f, 0.f, 0.f, 0.f};
+        if (p.bias) b4 = *reinterpret_cast<const spf4*>(p.bias + c_n0 + (CT * wave + ct) * 16 + 4 * lg);
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) {
-          f32x4& a = acc[rt * CT + ct];
+          spf4& a = acc[rt * CT + ct];
           a += b4;
-          if (p.relu) a = f32x4{fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)};
+          if (p.relu) a = spf4{fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)};
         }
       }
       if (p.pool_part) {
@@ -229,13 +223,13 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
           const int b1 = ((slab * 32) / p.pool_hw + 1) * p.pool_hw;
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
-            f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+            spf4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
               const int m = slab * 32 + h2 * 16 + li;
-              const f32x4 v = acc[(2 * sl + h2) * CT + ct];
+              const spf4 v = acc[(2 * sl + h2) * CT + ct];
               const bool in = m < argM, first = m < b1;
-              const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+              const spf4 z4 = {0.f, 0.f, 0.f, 0.f};
               s0 += in && first ? v : z4;
               s1 += in && !first ? v : z4;
             }
@@ -246,8 +240,8 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
             }
             if (li == 0 && slab * 32 < argM) {
               float* pp = p.pool_part + (size_t)slab * 2 * argCo + c_n0 + (CT * wave + ct) * 16 + 4 * lg;
-              *reinterpret_cast<f32x4*>(pp) = s0;
-              *reinterpret_cast<f32x4*>(pp + argCo) = s1;
+              *reinterpret_cast<spf4*>(pp) = s0;
+              *reinterpret_cast<spf4*>(pp + argCo) = s1;
             }
           }
         }
@@ -257,13 +251,13 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
     for (int i = 0; i < NT; ++i) {
       const int rt = i / CT;
       const int voff = li < argM - c_m0 - rt * 16 ? st_voff : GS_OOB;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i]), yrs, voff, ybase + (rt * 16 * y_rs + (i % CT) * 16) * 4, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(spu4, acc[i]), yrs, voff, ybase + (rt * 16 * y_rs + (i % CT) * 16) * 4, 0);
       OFFK_SB;
       asm volatile("s_nop 1");
       OFFK_SB;
     }
 #pragma unroll
-    for (int i = 0; i < NT; ++i) { acc[i] = f32x4{0.f, 0.f, 0.f, 0.f}; acs[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int i = 0; i < NT; ++i) { acc[i] = spf4{0.f, 0.f, 0.f, 0.f}; acs[i] = spf4{0.f, 0.f, 0.f, 0.f}; }
   };
 
   // ---- prologue: V(0) cut into stage 0, V(1) in registers, U(0) in registers ----
@@ -286,14 +280,14 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
   // One step: K-tile c_t of the multiply's item out of plane stage ST with the U registers of set ST; the cut of the next tile (register
   // set ST ^ 1) into plane stage ST ^ 1; V two tiles ahead into register set ST; U of the next tile into set ST ^ 1.
   auto step = [&](const int ST) -> bool {
-    u32x4 xb[4][3];
+    spu4 xb[4][3];
     const char* const rd = xrd + ST * GS_STAGE;
 #pragma unroll
-    for (int rt = 0; rt < 4; ++rt) xb[rt][0] = *reinterpret_cast<const u32x4*>(rd + rt * GS_RT);
+    for (int rt = 0; rt < 4; ++rt) xb[rt][0] = *reinterpret_cast<const spu4*>(rd + rt * GS_RT);
 #pragma unroll
-    for (int rt = 0; rt < 4; ++rt) xb[rt][2] = *reinterpret_cast<const u32x4*>(rd + rt * GS_RT + 2 * GS_PLANE);
+    for (int rt = 0; rt < 4; ++rt) xb[rt][2] = *reinterpret_cast<const spu4*>(rd + rt * GS_RT + 2 * GS_PLANE);
 #pragma unroll
-    for (int rt = 0; rt < 4; ++rt) xb[rt][1] = *reinterpret_cast<const u32x4*>(rd + rt * GS_RT + GS_PLANE);
+    for (int rt = 0; rt < 4; ++rt) xb[rt][1] = *reinterpret_cast<const spu4*>(rd + rt * GS_RT + GS_PLANE);
     OFFK_SB;
     // planes 0 = h, 1 = m, 2 = l; smallest products first: w_l x_h, w_h x_l, w_m x_m, w_m x_h, w_h x_m, w_h x_h
     constexpr int WP[6] = {2, 0, 1, 1, 0, 0}, XP[6] = {0, 2, 1, 0, 1, 0};
@@ -313,8 +307,8 @@ __global__ __launch_bounds__(256, OFFK_GS_BLOCKS) void wino_gemm_split_kernel(Wi
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         const int n = q * NT + i, rt = i / CT, ct = i % CT;
-        if (q < 5) acs[i] = mf(acs[i], wr[ST][ct][WP[q]], xb[rt][XP[q]]);
-        else acc[i] = mf(acc[i], wr[ST][ct][WP[q]], xb[rt][XP[q]]);
+        if (q < 5) sp_mfma(acs[i], wr[ST][ct][WP[q]], xb[rt][XP[q]]);
+        else sp_mfma(acc[i], wr[ST][ct][WP[q]], xb[rt][XP[q]]);
         if (n < NS) {
 #pragma unroll
           for (int j = (n * NJ + NS - 1) / NS; j < ((n + 1) * NJ + NS - 1) / NS; ++j) job(j);

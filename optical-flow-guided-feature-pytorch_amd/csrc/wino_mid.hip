@@ -25,14 +25,12 @@
 
 #include "offk_common.h"
 #include "offk_internal.h"
+#include "split_common.h"
 #include "winograd_common.h"
 
 namespace offk {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // byte offset of channel c of pixel slot px in a [slot][C] tile whose 16-byte chunks are XOR-swizzled by the slot: a ds_read_b128 of
 // (16 slots, one k quad) and a ds_write / ds_read_b32 of 64 consecutive channels of one slot are both conflict-free
 template <int C>
@@ -50,14 +48,12 @@ __device__ __forceinline__ int plane_off(int px, int c) {
 // one activation -> its three bf16 planes (truncating cut, as everywhere), 2-byte stores
 template <int LC>
 __device__ __forceinline__ void store_planes(char* xt, int px, int c, float v) {
-  const unsigned h = __float_as_uint(v) & 0xffff0000u;
-  const float r = v - __uint_as_float(h);
-  const unsigned m = __float_as_uint(r) & 0xffff0000u;
-  const float l = r - __uint_as_float(m);
+  unsigned h, m, l;
+  sp_cut(v, h, m, l);
   char* d = xt + plane_off<LC>(px, c);
   *reinterpret_cast<unsigned short*>(d) = (unsigned short)(h >> 16);
   *reinterpret_cast<unsigned short*>(d + kPlaneStride<LC>) = (unsigned short)(m >> 16);
-  *reinterpret_cast<unsigned short*>(d + 2 * kPlaneStride<LC>) = (unsigned short)(__float_as_uint(l) >> 16);
+  *reinterpret_cast<unsigned short*>(d + 2 * kPlaneStride<LC>) = (unsigned short)(l >> 16);
 }
 
 // stage A for one class: M -> relu(A^T M A + bias) -> LDS tile (+ HBM), lane = channel within a group of 64.  TWO channel groups at
@@ -178,10 +174,10 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
     // pixel slots 49 .. 63 of the x tile: stage A never writes them and stage B multiplies them (MFMA columns that are dropped behind
     // it) -- zeroed so that no uninitialised LDS word is ever read
     if constexpr (SPL) {      // the whole fourth pixel tile of the plane image (pixel 48 is written behind the barrier that follows)
-      for (int i = tid; i < kPtStride<XC> / 16; i += 256) reinterpret_cast<f32x4*>(lds + 3 * kPtStride<XC>)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = tid; i < kPtStride<XC> / 16; i += 256) reinterpret_cast<spf4*>(lds + 3 * kPtStride<XC>)[i] = spf4{0.f, 0.f, 0.f, 0.f};
       __syncthreads();
     } else {
-      for (int i = tid; i < 15 * XC / 4; i += 256) reinterpret_cast<f32x4*>(lds + 49 * (XC * 4))[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = tid; i < 15 * XC / 4; i += 256) reinterpret_cast<spf4*>(lds + 49 * (XC * 4))[i] = spf4{0.f, 0.f, 0.f, 0.f};
     }
   };
   auto stage_a = [&](auto half) {
@@ -204,24 +200,24 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
     const int li = lane & 15, kq = lane >> 4;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w1), 0, CMID * CIN * 4, 0x00020000);
     const int wvoff = ((c_first + wave * (CM / 4) + li) * CIN + 4 * kq) * 4;
-    auto w_load = [&](f32x4 (&w)[CT], const int s) {
+    auto w_load = [&](spf4 (&w)[CT], const int s) {
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, (16 * ct * CIN + 16 * s) * 4, 0);
-        w[ct] = f32x4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
+        const spu4 v = __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, (16 * ct * CIN + 16 * s) * 4, 0);
+        w[ct] = spf4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
       }
     };
     const char* const xrd = lds + li * (XC * 4);                    // + pt * 16 rows, + chunk (4 s + kq) ^ li   (s within the half)
-    auto x_load = [&](f32x4 (&x)[PT], const int s) {
+    auto x_load = [&](spf4 (&x)[PT], const int s) {
 #pragma unroll
       for (int pt = 0; pt < PT; ++pt)
-        x[pt] = *reinterpret_cast<const f32x4*>(xrd + pt * 16 * (XC * 4) + (((4 * s + kq) ^ li) << 4));
+        x[pt] = *reinterpret_cast<const spf4*>(xrd + pt * 16 * (XC * 4) + (((4 * s + kq) ^ li) << 4));
     };
-    f32x4 acc[PT][CT], acs[SPL ? PT : 1][SPL ? CT : 1];      // (split: acc = sum w_h x_h, acs = the five small products)
+    spf4 acc[PT][CT], acs[SPL ? PT : 1][SPL ? CT : 1];      // (split: acc = sum w_h x_h, acs = the five small products)
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct) { acc[pt][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; if constexpr (SPL) acs[pt][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      for (int ct = 0; ct < CT; ++ct) { acc[pt][ct] = spf4{0.f, 0.f, 0.f, 0.f}; if constexpr (SPL) acs[pt][ct] = spf4{0.f, 0.f, 0.f, 0.f}; }
     // split-fp32: the K-steps of 32 channels [t0, t0 + XC / 32) of the conv out of the plane image in LDS (which holds the channels from 32 t0 on)
     auto stage_b_split = [&](const int t0) {
       if constexpr (SPL) {
@@ -229,23 +225,20 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
         const __amdgpu_buffer_rsrc_t wps = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w1p), 0, CMID * CIN * 6, 0x00020000);
         const int ct0 = (c_first + wave * (CM / 4)) >> 4;
         const char* const prd = lds + kq * 256;          // + pt, + plane, + 4 t k groups; position li ^ 2 (g & 7)
-        auto mfs = [&](f32x4 c, const u32x4& w, const u32x4& x) {
-          return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
-        };
-        u32x4 wq[2][CT][3];
+        spu4 wq[2][CT][3];
         auto wl = [&](const int set, const int t) {
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
-              wq[set][ct][pl] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wps, lane * 16, (((t0 + t) * NCT + ct0 + ct) * 3 + pl) * 1024, 0));
+              wq[set][ct][pl] = __builtin_bit_cast(spu4, __builtin_amdgcn_raw_buffer_load_b128(wps, lane * 16, (((t0 + t) * NCT + ct0 + ct) * 3 + pl) * 1024, 0));
         };
-        u32x4 xq[2][3];
-        auto xl = [&](u32x4 (&x)[3], const int t, const int pt) {
+        spu4 xq[2][3];
+        auto xl = [&](spu4 (&x)[3], const int t, const int pt) {
           const int g = 4 * t + kq;
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl)
-            x[pl] = *reinterpret_cast<const u32x4*>(prd + pt * kPtStride<XC> + pl * kPlaneStride<XC> + 4 * t * 256 + ((li ^ (2 * (g & 7))) << 4));
+            x[pl] = *reinterpret_cast<const spu4*>(prd + pt * kPtStride<XC> + pl * kPlaneStride<XC> + 4 * t * 256 + ((li ^ (2 * (g & 7))) << 4));
         };
         wl(0, 0);
         xl(xq[0], 0, 0);
@@ -257,20 +250,20 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
             const int nx = t * PT + pt + 1;
             if (nx < NT * PT) xl(xq[nx & 1], nx / PT, nx % PT);
             __builtin_amdgcn_sched_barrier(0);
-            const u32x4 (&x)[3] = xq[(t * PT + pt) & 1];
+            const spu4 (&x)[3] = xq[(t * PT + pt) & 1];
             // planes 0 = h, 1 = m, 2 = l; the channel tiles' chains interleaved
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acs[pt][ct] = mfs(acs[pt][ct], wq[t & 1][ct][2], x[0]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acs[pt][ct], wq[t & 1][ct][2], x[0]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acs[pt][ct] = mfs(acs[pt][ct], wq[t & 1][ct][0], x[2]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acs[pt][ct], wq[t & 1][ct][0], x[2]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acc[pt][ct] = mfs(acc[pt][ct], wq[t & 1][ct][0], x[0]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acc[pt][ct], wq[t & 1][ct][0], x[0]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acs[pt][ct] = mfs(acs[pt][ct], wq[t & 1][ct][1], x[1]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acs[pt][ct], wq[t & 1][ct][1], x[1]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acs[pt][ct] = mfs(acs[pt][ct], wq[t & 1][ct][1], x[0]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acs[pt][ct], wq[t & 1][ct][1], x[0]);
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acs[pt][ct] = mfs(acs[pt][ct], wq[t & 1][ct][0], x[1]);
+            for (int ct = 0; ct < CT; ++ct) sp_mfma(acs[pt][ct], wq[t & 1][ct][0], x[1]);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -279,7 +272,7 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
     // the k steps [s0, s0 + KSH) out of the tile in LDS (which holds the channels from 16 s0 on)
     auto stage_b = [&](const int s0) {
       if constexpr (SPL) { stage_b_split(s0 / 2); return; }
-      f32x4 wq[3][CT], xv[2][PT];
+      spf4 wq[3][CT], xv[2][PT];
       w_load(wq[0], s0);
       if (KSH > 1) w_load(wq[1], s0 + 1);
       x_load(xv[0], 0);
@@ -288,8 +281,8 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
         if (s + 2 < KSH) w_load(wq[(s + 2) % 3], s0 + s + 2);         // weights two steps ahead of their MFMAs (L2 latency)
         if (s + 1 < KSH) x_load(xv[(s + 1) & 1], s + 1);
         __builtin_amdgcn_sched_barrier(0);
-        const f32x4 (&w)[CT] = wq[s % 3];
-        const f32x4 (&x)[PT] = xv[s & 1];
+        const spf4 (&w)[CT] = wq[s % 3];
+        const spf4 (&x)[PT] = xv[s & 1];
 #pragma unroll
         for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
@@ -322,14 +315,14 @@ __global__ __launch_bounds__(256, (KH == 2 || SPL) ? 3 : 2) void wino_mid_kernel
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
       const int ch = wave * (CM / 4) + 16 * ct + 4 * kq;             // channel within the block's slice
-      const f32x4 bb = *reinterpret_cast<const f32x4*>(a.b1 + c_first + ch);
+      const spf4 bb = *reinterpret_cast<const spf4*>(a.b1 + c_first + ch);
 #pragma unroll
       for (int pt = 0; pt < PT; ++pt) {
         const int px = 16 * pt + li;
-        f32x4 v = acc[pt][ct] + bb;
+        spf4 v = acc[pt][ct] + bb;
         if constexpr (SPL) v = (acc[pt][ct] + acs[pt][ct]) + bb;
         if (px < 49)
-          *reinterpret_cast<f32x4*>(lds + tile_off<CM>(px, ch)) = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
+          *reinterpret_cast<spf4*>(lds + tile_off<CM>(px, ch)) = spf4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
       }
     }
     __syncthreads();

@@ -660,31 +660,31 @@ def pack_conv_weight(w_oihw, out=None):
     return wp
 
 
-# ---- backward of one stride-1 fusion conv (offk_relu_backward / offk_conv2d_backward_*; csrc/conv_bwd.hip) ----
+# ---- backward of one fusion conv: stride 1 (csrc/conv_bwd.hip) and stride 2 (csrc/conv_bwd_s2.hip), exact fp32 or split-fp32 ----
 def _nhwc(t, name):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4):
         raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor [n, H, W, Cs]" % name)
     return t
 
 
+def _plan(entry, kinds, n_img, H, W, ci, co, ksize):
+    """One plan entry of the conv backward (host code): its outputs, of the ctypes types `kinds`, as a tuple -- or alone where it has one."""
+    outs = [kind() for kind in kinds]
+    k = int(ksize)
+    _lib.check(getattr(_lib.load(), entry)(int(n_img), int(H), int(W), int(ci), int(co), k, k, *[ctypes.byref(o) for o in outs]))
+    return outs[0].value if len(outs) == 1 else tuple([o.value for o in outs])
+
+
 def conv2d_backward_plan(n_img, H, W, ci, co, ksize):
     """offk_conv2d_backward_plan: (data_scratch_bytes, weight_scratch_bytes, weight_chunks) of one conv's backward -- host code, a function
     of these integers only.  The weight gradient's K chunks hold ceil(n_img / weight_chunks) images each, the last one what is left."""
-    lib = _lib.load()
-    d, w, c = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
-    _lib.check(lib.offk_conv2d_backward_plan(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d),
-                                             ctypes.byref(w), ctypes.byref(c)))
-    return d.value, w.value, c.value
+    return _plan("offk_conv2d_backward_plan", (ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int), n_img, H, W, ci, co, ksize)
 
 
 def conv2d_backward_plan_split(n_img, H, W, ci, co, ksize):
     """offk_conv2d_backward_plan_split: (weight_scratch_bytes, weight_chunks) of the split-fp32 weight gradient
     (conv2d_backward_weight(arith="f32split")) -- host code, a function of these integers only; the chunks are the split kernel's own."""
-    lib = _lib.load()
-    w, c = ctypes.c_size_t(0), ctypes.c_int(0)
-    _lib.check(lib.offk_conv2d_backward_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(w),
-                                                   ctypes.byref(c)))
-    return w.value, c.value
+    return _plan("offk_conv2d_backward_plan_split", (ctypes.c_size_t, ctypes.c_int), n_img, H, W, ci, co, ksize)
 
 
 def relu_backward(dy, y, out=None, accumulate=False, dy_coff=0, y_coff=0, out_coff=0, c=None):
@@ -709,121 +709,30 @@ def relu_backward(dy, y, out=None, accumulate=False, dy_coff=0, y_coff=0, out_co
 def conv2d_backward_data_plan_split(n_img, H, W, ci, co, ksize):
     """offk_conv2d_backward_data_plan_split: data_scratch_bytes of the split-fp32 data gradient (conv2d_backward_data(arith="f32split")) --
     host code, a function of these integers only: the three bf16 planes of the packed weight, then those of g, each rounded up to 256."""
-    lib = _lib.load()
-    d = ctypes.c_size_t(0)
-    _lib.check(lib.offk_conv2d_backward_data_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d)))
-    return d.value
+    return _plan("offk_conv2d_backward_data_plan_split", (ctypes.c_size_t,), n_img, H, W, ci, co, ksize)
 
 
 def conv2d_backward_data_form_split(n_img, H, W, ci, co, ksize):
     """offk_conv2d_backward_data_form_split: (ci_per_block, pixels_per_block) of the split-fp32 data gradient's GEMM -- host code, a function
     of these integers only; the result's bits do not depend on it."""
-    lib = _lib.load()
-    cb, pb = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(lib.offk_conv2d_backward_data_form_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(cb),
-                                                        ctypes.byref(pb)))
-    return cb.value, pb.value
+    return _plan("offk_conv2d_backward_data_form_split", (ctypes.c_int, ctypes.c_int), n_img, H, W, ci, co, ksize)
 
 
-def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0, arith="fp32"):
-    """dx (+)= the gradient of a stride-1 conv's input.  g: [n, H, W, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
-    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx).  scratch: the caller's uint8
-    buffer of exactly conv2d_backward_plan's data_scratch_bytes.  arith: "fp32" (offk_conv2d_backward_data, exact fp32 on the fp32 matrix
-    pipe) or "f32split" (offk_conv2d_backward_data_split: three bf16 planes per operand, six products on the bf16 pipe, include/offk.h has
-    the bound; its scratch is conv2d_backward_data_plan_split's bytes)."""
-    if arith not in DGRAD_ARITHS:
-        raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in DGRAD_ARITHS), arith))
-    lib = _lib.load()
-    _nhwc(g, "g")
-    n, H, W, gs = g.shape
-    Co, Ci, KH, KW = w_oihw.shape
-    if not (w_oihw.is_cuda and w_oihw.dtype == torch.float32 and w_oihw.is_contiguous()):
-        raise ValueError("w_oihw must be a contiguous fp32 CUDA/HIP tensor")
-    if dx is None:
-        if accumulate:
-            raise ValueError("accumulate needs the tensor to add to (dx)")
-        dx = torch.empty(n, H, W, Ci, dtype=torch.float32, device=g.device)
-    _nhwc(dx, "dx")
-    split = arith == "f32split"
-    if KH != KW:
-        nbytes = 0
-    else:
-        nbytes = conv2d_backward_data_plan_split(n, H, W, Ci, Co, KH) if split else conv2d_backward_plan(n, H, W, Ci, Co, KH)[0]
-    scratch = _given(scratch, (nbytes,), "scratch", g.device, torch.uint8)
-    entry = lib.offk_conv2d_backward_data_split if split else lib.offk_conv2d_backward_data
-    _lib.check(entry(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad), _ptr(dx),
-                     dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
-    return dx
+# the compute entries by (stride, arith)
+_DATA_ENTRIES = {(1, "fp32"): "offk_conv2d_backward_data", (1, "f32split"): "offk_conv2d_backward_data_split",
+                 (2, "fp32"): "offk_conv2d_s2_backward_data", (2, "f32split"): "offk_conv2d_s2_backward_data_split"}
+_WEIGHT_ENTRIES = {(1, "fp32"): "offk_conv2d_backward_weight", (1, "f32split"): "offk_conv2d_backward_weight_split",
+                   (2, "fp32"): "offk_conv2d_s2_backward_weight", (2, "f32split"): "offk_conv2d_s2_backward_weight_split"}
 
 
-def conv2d_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
-                           scratch=None, want_db=True, arith="fp32"):
-    """(dw, db) (+)= the weight and bias gradient of a stride-1 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
-    read max(x, 0)); g: [n, H, W, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co]: e.g. the parameters' .grad, written in
-    place (None: new tensors; want_db=False: no bias gradient, db comes back None).  scratch: the caller's uint8 buffer of exactly
-    conv2d_backward_plan's weight_scratch_bytes.  arith: "fp32" (offk_conv2d_backward_weight, exact fp32 on the fp32 matrix pipe) or
-    "f32split" (offk_conv2d_backward_weight_split: three bf16 planes per operand, six products on the bf16 pipe, include/offk.h has the
-    bound; its scratch is conv2d_backward_plan_split's weight_scratch_bytes)."""
-    if arith not in WGRAD_ARITHS:
-        raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in WGRAD_ARITHS), arith))
-    lib = _lib.load()
-    _nhwc(x, "x"), _nhwc(g, "g")
-    n, H, W, xs = x.shape
-    if g.shape[:3] != x.shape[:3]:
-        raise ValueError("x and g must agree in [n, H, W]")
-    Ci = xs - x_coff if ci is None else int(ci)
-    Co = g.shape[-1] - g_coff if co is None else int(co)
-    k = int(ksize)
-    if accumulate and (dw is None or (want_db and db is None)):
-        raise ValueError("accumulate needs the tensors to add to (dw, db)")
-    if dw is None:
-        dw = torch.empty(Co, Ci, k, k, dtype=torch.float32, device=x.device)
-    if db is None and want_db:
-        db = torch.empty(Co, dtype=torch.float32, device=x.device)
-    for t, name, numel in ((dw, "dw", Co * Ci * k * k), (db, "db", Co)):
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
-            raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
-    split = arith == "f32split"
-    nbytes = conv2d_backward_plan_split(n, H, W, Ci, Co, k)[0] if split else conv2d_backward_plan(n, H, W, Ci, Co, k)[1]
-    scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
-    entry = lib.offk_conv2d_backward_weight_split if split else lib.offk_conv2d_backward_weight
-    _lib.check(entry(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
-                     int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch), scratch.numel()))
-    return dw, db
-
-
-# ---- backward of the two stride-2 fusion convs, 7x7 / 2 / 3 and 5x5 / 2 / 2 (offk_conv2d_s2_backward_*; csrc/conv_bwd_s2.hip) ----
-def conv2d_s2_backward_plan(n_img, H, W, ci, co, ksize):
-    """offk_conv2d_s2_backward_plan: (data_scratch_bytes, weight_scratch_bytes, weight_chunks) of one stride-2 conv's backward -- host code, a
-    function of these integers only.  H, W: the INPUT map.  The weight gradient's K chunks hold ceil(n_img / weight_chunks) images each."""
-    lib = _lib.load()
-    d, w, c = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
-    _lib.check(lib.offk_conv2d_s2_backward_plan(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d),
-                                                ctypes.byref(w), ctypes.byref(c)))
-    return d.value, w.value, c.value
-
-
-def conv2d_s2_backward_plan_split(n_img, H, W, ci, co, ksize):
-    """offk_conv2d_s2_backward_plan_split: data_scratch_bytes of the split-fp32 data gradient (conv2d_s2_backward_data(arith="f32split")) --
-    host code, a function of these integers only: the three bf16 planes of the packed weight, then those of g, each rounded up to 256."""
-    lib = _lib.load()
-    d = ctypes.c_size_t(0)
-    _lib.check(lib.offk_conv2d_s2_backward_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize), ctypes.byref(d)))
-    return d.value
-
-
-def conv2d_s2_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0, arith="fp32"):
-    """dx (+)= the gradient of a stride-2 conv's input.  g: [n, H/2, W/2, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
-    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx, whose map is twice g's).
-    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's data_scratch_bytes.  arith: "fp32"
-    (offk_conv2d_s2_backward_data, exact fp32 on the fp32 matrix pipe) or "f32split" (offk_conv2d_s2_backward_data_split: three bf16 planes
-    per operand, six products on the bf16 pipe, include/offk.h has the bound; its scratch is conv2d_s2_backward_plan_split's bytes)."""
+def _conv_backward_data(stride, g, w_oihw, pad, dx, dx_coff, accumulate, scratch, g_coff, arith):
+    """conv2d_backward_data (stride 1) and conv2d_s2_backward_data (stride 2): g's map is dx's divided by the stride."""
     if arith not in DGRAD_ARITHS:
         raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in DGRAD_ARITHS), arith))
     lib = _lib.load()
     _nhwc(g, "g")
     n, OH, OW, gs = g.shape
-    H, W = 2 * OH, 2 * OW
+    H, W = stride * OH, stride * OW
     Co, Ci, KH, KW = w_oihw.shape
     if not (w_oihw.is_cuda and w_oihw.dtype == torch.float32 and w_oihw.is_contiguous()):
         raise ValueError("w_oihw must be a contiguous fp32 CUDA/HIP tensor")
@@ -832,44 +741,33 @@ def conv2d_s2_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False
             raise ValueError("accumulate needs the tensor to add to (dx)")
         dx = torch.empty(n, H, W, Ci, dtype=torch.float32, device=g.device)
     _nhwc(dx, "dx")
-    if tuple(dx.shape[:3]) != (n, H, W):
+    if stride == 2 and tuple(dx.shape[:3]) != (n, H, W):
         raise ValueError("dx must be [n, 2 * g's H, 2 * g's W, Cs]")
     split = arith == "f32split"
     if KH != KW:
         nbytes = 0
+    elif stride == 1:
+        nbytes = conv2d_backward_data_plan_split(n, H, W, Ci, Co, KH) if split else conv2d_backward_plan(n, H, W, Ci, Co, KH)[0]
     else:
         nbytes = conv2d_s2_backward_plan_split(n, H, W, Ci, Co, KH) if split else conv2d_s2_backward_plan(n, H, W, Ci, Co, KH)[0]
     scratch = _given(scratch, (nbytes,), "scratch", g.device, torch.uint8)
-    entry = lib.offk_conv2d_s2_backward_data_split if split else lib.offk_conv2d_s2_backward_data
-    _lib.check(entry(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad),
-                     _ptr(dx), dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
+    entry = getattr(lib, _DATA_ENTRIES[stride, arith])
+    _lib.check(entry(_stream(g.device), _ptr(g), gs, g_coff, n, H, W, Co, _ptr(w_oihw), Ci, KH, KW, int(pad), _ptr(dx),
+                     dx.shape[-1], dx_coff, int(bool(accumulate)), _ptr(scratch), scratch.numel()))
     return dx
 
 
-def conv2d_s2_backward_weight_plan_split(n_img, H, W, ci, co, ksize):
-    """offk_conv2d_s2_backward_weight_plan_split: (weight_scratch_bytes, weight_chunks) of the split-fp32 weight gradient of a stride-2 conv
-    (conv2d_s2_backward_weight(arith="f32split")) -- host code, a function of these integers only; the chunks are the split kernel's own."""
-    lib = _lib.load()
-    w, c = ctypes.c_size_t(0), ctypes.c_int(0)
-    _lib.check(lib.offk_conv2d_s2_backward_weight_plan_split(int(n_img), int(H), int(W), int(ci), int(co), int(ksize), int(ksize),
-                                                             ctypes.byref(w), ctypes.byref(c)))
-    return w.value, c.value
-
-
-def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
-                              scratch=None, want_db=True, arith="fp32"):
-    """(dw, db) (+)= the weight and bias gradient of a stride-2 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
-    read max(x, 0)); g: [n, H/2, W/2, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co] as in conv2d_backward_weight.
-    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's weight_scratch_bytes.  arith: "fp32"
-    (offk_conv2d_s2_backward_weight, exact fp32 on the fp32 matrix pipe) or "f32split" (offk_conv2d_s2_backward_weight_split: three bf16
-    planes per operand, six products on the bf16 pipe, include/offk.h has the K layout and the bound; its scratch is
-    conv2d_s2_backward_weight_plan_split's weight_scratch_bytes)."""
+def _conv_backward_weight(stride, x, g, ksize, pad, relu_in, x_coff, ci, g_coff, co, dw, db, accumulate, scratch, want_db, arith):
+    """conv2d_backward_weight (stride 1) and conv2d_s2_backward_weight (stride 2): g's map is x's divided by the stride."""
     if arith not in WGRAD_ARITHS:
         raise ValueError("arith must be one of %s, got %r" % (", ".join(repr(a) for a in WGRAD_ARITHS), arith))
     lib = _lib.load()
     _nhwc(x, "x"), _nhwc(g, "g")
     n, H, W, xs = x.shape
-    if tuple(g.shape[:3]) != (n, H // 2, W // 2) or H % 2 or W % 2:
+    if stride == 1:
+        if g.shape[:3] != x.shape[:3]:
+            raise ValueError("x and g must agree in [n, H, W]")
+    elif tuple(g.shape[:3]) != (n, H // 2, W // 2) or H % 2 or W % 2:
         raise ValueError("x must be [n, H, W, Xs] with even H and W, g [n, H / 2, W / 2, Gs]")
     Ci = xs - x_coff if ci is None else int(ci)
     Co = g.shape[-1] - g_coff if co is None else int(co)
@@ -884,12 +782,73 @@ def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
             raise ValueError("%s must be a contiguous fp32 CUDA/HIP tensor of %d elements" % (name, numel))
     split = arith == "f32split"
-    nbytes = conv2d_s2_backward_weight_plan_split(n, H, W, Ci, Co, k)[0] if split else conv2d_s2_backward_plan(n, H, W, Ci, Co, k)[1]
+    if stride == 1:
+        nbytes = conv2d_backward_plan_split(n, H, W, Ci, Co, k)[0] if split else conv2d_backward_plan(n, H, W, Ci, Co, k)[1]
+    else:
+        nbytes = conv2d_s2_backward_weight_plan_split(n, H, W, Ci, Co, k)[0] if split else conv2d_s2_backward_plan(n, H, W, Ci, Co, k)[1]
     scratch = _given(scratch, (nbytes,), "scratch", x.device, torch.uint8)
-    entry = lib.offk_conv2d_s2_backward_weight_split if split else lib.offk_conv2d_s2_backward_weight
+    entry = getattr(lib, _WEIGHT_ENTRIES[stride, arith])
     _lib.check(entry(_stream(x.device), _ptr(x), xs, x_coff, _ptr(g), g.shape[-1], g_coff, n, H, W, Ci, Co, k, k,
                      int(pad), int(bool(relu_in)), _ptr(dw), _ptr(db), int(bool(accumulate)), _ptr(scratch), scratch.numel()))
     return dw, db
+
+
+def conv2d_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0, arith="fp32"):
+    """dx (+)= the gradient of a stride-1 conv's input.  g: [n, H, W, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
+    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx).  scratch: the caller's uint8
+    buffer of exactly conv2d_backward_plan's data_scratch_bytes.  arith: "fp32" (offk_conv2d_backward_data, exact fp32 on the fp32 matrix
+    pipe) or "f32split" (offk_conv2d_backward_data_split: three bf16 planes per operand, six products on the bf16 pipe, include/offk.h has
+    the bound; its scratch is conv2d_backward_data_plan_split's bytes)."""
+    return _conv_backward_data(1, g, w_oihw, pad, dx, dx_coff, accumulate, scratch, g_coff, arith)
+
+
+def conv2d_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
+                           scratch=None, want_db=True, arith="fp32"):
+    """(dw, db) (+)= the weight and bias gradient of a stride-1 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
+    read max(x, 0)); g: [n, H, W, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co]: e.g. the parameters' .grad, written in
+    place (None: new tensors; want_db=False: no bias gradient, db comes back None).  scratch: the caller's uint8 buffer of exactly
+    conv2d_backward_plan's weight_scratch_bytes.  arith: "fp32" (offk_conv2d_backward_weight, exact fp32 on the fp32 matrix pipe) or
+    "f32split" (offk_conv2d_backward_weight_split: three bf16 planes per operand, six products on the bf16 pipe, include/offk.h has the
+    bound; its scratch is conv2d_backward_plan_split's weight_scratch_bytes)."""
+    return _conv_backward_weight(1, x, g, ksize, pad, relu_in, x_coff, ci, g_coff, co, dw, db, accumulate, scratch, want_db, arith)
+
+
+def conv2d_s2_backward_plan(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_s2_backward_plan: (data_scratch_bytes, weight_scratch_bytes, weight_chunks) of one stride-2 conv's backward -- host code, a
+    function of these integers only.  H, W: the INPUT map.  The weight gradient's K chunks hold ceil(n_img / weight_chunks) images each."""
+    return _plan("offk_conv2d_s2_backward_plan", (ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int), n_img, H, W, ci, co, ksize)
+
+
+def conv2d_s2_backward_plan_split(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_s2_backward_plan_split: data_scratch_bytes of the split-fp32 data gradient (conv2d_s2_backward_data(arith="f32split")) --
+    host code, a function of these integers only: the three bf16 planes of the packed weight, then those of g, each rounded up to 256."""
+    return _plan("offk_conv2d_s2_backward_plan_split", (ctypes.c_size_t,), n_img, H, W, ci, co, ksize)
+
+
+def conv2d_s2_backward_data(g, w_oihw, pad, dx=None, dx_coff=0, accumulate=False, scratch=None, g_coff=0, arith="fp32"):
+    """dx (+)= the gradient of a stride-2 conv's input.  g: [n, H/2, W/2, Gs] fp32 CUDA, channels [g_coff, g_coff + Co); w_oihw [Co, Ci, k, k]
+    (read in place); returns dx [n, H, W, Ci] (or writes channels [dx_coff, dx_coff + Ci) of the given dx, whose map is twice g's).
+    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's data_scratch_bytes.  arith: "fp32"
+    (offk_conv2d_s2_backward_data, exact fp32 on the fp32 matrix pipe) or "f32split" (offk_conv2d_s2_backward_data_split: three bf16 planes
+    per operand, six products on the bf16 pipe, include/offk.h has the bound; its scratch is conv2d_s2_backward_plan_split's bytes)."""
+    return _conv_backward_data(2, g, w_oihw, pad, dx, dx_coff, accumulate, scratch, g_coff, arith)
+
+
+def conv2d_s2_backward_weight_plan_split(n_img, H, W, ci, co, ksize):
+    """offk_conv2d_s2_backward_weight_plan_split: (weight_scratch_bytes, weight_chunks) of the split-fp32 weight gradient of a stride-2 conv
+    (conv2d_s2_backward_weight(arith="f32split")) -- host code, a function of these integers only; the chunks are the split kernel's own."""
+    return _plan("offk_conv2d_s2_backward_weight_plan_split", (ctypes.c_size_t, ctypes.c_int), n_img, H, W, ci, co, ksize)
+
+
+def conv2d_s2_backward_weight(x, g, ksize, pad, relu_in=False, x_coff=0, ci=None, g_coff=0, co=None, dw=None, db=None, accumulate=False,
+                              scratch=None, want_db=True, arith="fp32"):
+    """(dw, db) (+)= the weight and bias gradient of a stride-2 k x k conv.  x: [n, H, W, Xs], channels [x_coff, x_coff + ci) (relu_in: the conv
+    read max(x, 0)); g: [n, H/2, W/2, Gs], channels [g_coff, g_coff + co); dw [co, ci, k, k] and db [co] as in conv2d_backward_weight.
+    scratch: the caller's uint8 buffer of exactly conv2d_s2_backward_plan's weight_scratch_bytes.  arith: "fp32"
+    (offk_conv2d_s2_backward_weight, exact fp32 on the fp32 matrix pipe) or "f32split" (offk_conv2d_s2_backward_weight_split: three bf16
+    planes per operand, six products on the bf16 pipe, include/offk.h has the K layout and the bound; its scratch is
+    conv2d_s2_backward_weight_plan_split's weight_scratch_bytes)."""
+    return _conv_backward_weight(2, x, g, ksize, pad, relu_in, x_coff, ci, g_coff, co, dw, db, accumulate, scratch, want_db, arith)
 
 
 def bottleneck_chain14(x, w1, b1, w2_oihw, b2, w3, b3, res=None, relu_in=False, x_coff=0, y=None, y_coff=0, w2_packed=None):

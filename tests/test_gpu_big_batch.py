@@ -5,13 +5,13 @@ had run in the suite before:
 
   launch                       below the mark                                         at N = 2142 (read in csrc/ before the first run)
   ---------------------------  -----------------------------------------------------  -----------------------------------------------------------
-  K1  offk_pw_reduce,          pw_reduce_kernel<0, 1>: buffer descriptors per part     pw_reduce_kernel<0, 0> (pw_reduce.hip:430-437, :472-485):
-      offk_off_units           (pw_reduce.hip:205-208)                                 pointer loads, (size_t)frame * cpart ... (:213-234); G and D
-                                                                                       stores (size_t)m * 128, (size_t)dr * HW (:416-422)
+  K1  offk_pw_reduce,          pw_reduce_kernel<0, 1>: buffer descriptors per part     pw_reduce_kernel<0, 0> (pw_reduce.hip:423-430, :465-478):
+      offk_off_units           (pw_reduce.hip:198-201)                                 pointer loads, (size_t)frame * cpart ... (:206-227); G and D
+                                                                                       stores (size_t)m * 128, (size_t)dr * HW (:409-415)
   K1T offk_off_units_fused,    fp32 handle: pw_tdiff16_kernel; split handle:           BOTH handles: pw_tdiff_kernel<0, 0> in the 32-pixel block
-      offk_forward             pw_tdiff_split_kernel (pw_tdiff.hip:682, :738)          layout (pw_tdiff.hip:669-682, :736): `lean` is one flag per
+      offk_forward             pw_tdiff_split_kernel (pw_tdiff.hip:676, :732)          layout (pw_tdiff.hip:663-676, :730): `lean` is one flag per
                                                                                        launch, so all nine sites take it; pointer loads (size_t)
-                                                                                       (b L + t) * cpart (:155-158), stores (size_t) (:287-309).
+                                                                                       (b L + t) * cpart (:149-152), stores (size_t) (:281-303).
                                                                                        A split-fp32 handle therefore computes its units in fp32
                                                                                        arithmetic as soon as one map part has 2 GiB or more.
   K2  sobel_tdiff              one kernel on either side; every index is size_t (sobel_tdiff.hip:148-200, :221-293)
@@ -22,7 +22,7 @@ frames 2139 .. 2141 are the ones that hold and follow byte 2^31 (2^31 / 1 003 52
 clip" are the same one at this N.
 
 Which K1T kernel ran cannot be read from the per-launch trace: "units:pw_tdiff (K1T)" is marked once, before pw_tdiff_launch picks among
-pw_tdiff16_kernel, pw_tdiff_split_kernel and pw_tdiff_kernel<0, 0> (offk_api.hip:583, pw_tdiff.hip:733-741); the trace shows K1T against
+pw_tdiff16_kernel, pw_tdiff_split_kernel and pw_tdiff_kernel<0, 0> (offk_api.hip:583, pw_tdiff.hip:727-735); the trace shows K1T against
 K1 + K2 only.  The bits show the rest: with the whole 3b map both handle kinds must write the SAME bits into fusion_28 (one fp32 kernel),
 with the maps as parts the split handle's bits must differ from the fp32 handle's (its own split-fp32 kernel ran).  Tolerance: RTOL of tests/test_gpu_parity.py, max-normalised as test_pw_reduce_vs_oracle and the stage-tensor tests have it.
 
@@ -33,15 +33,15 @@ the nine maps 9.7 GB + the guarded copy of 3b 4.3 GB (2.15 GB of it the margin) 
 
 offk_forward at the same N is the first run of the fusion stage with Winograd arrays past 4 GiB (V of the 7x7 / 2 conv is
 225 x 9 P x 320 x 4 B = 4.76 GB at P = 1836).  Read before it ran: the transforms index V / M / x / y with size_t (winograd.hip:44-69,
-:116-142, winograd7.hip:91-102, :170, wino_mid.hip:70-148); the fp32 batched GEMM builds one buffer descriptor PER PROBLEM from a 64-bit
+:116-142, winograd7.hip:91-102, :170, wino_mid.hip:66-144); the fp32 batched GEMM builds one buffer descriptor PER PROBLEM from a 64-bit
 problem offset, its per-problem extents checked below 0x7fffff00 (wino_gemm.hip:90-96, :155, :208-215); the split GEMM takes whole-array
-descriptors only while every array is below 0x7fffff00 bytes and otherwise hands over to the fp32 one (wino_gemm_split.hip:384-393);
+descriptors only while every array is below 0x7fffff00 bytes and otherwise hands over to the fp32 one (wino_gemm_split.hip:378-387);
 the direct convs, chains and heads are the kernels of tests/test_gpu_big_slabs.py (fusion_14 at P = 1836 is 1.52 GB, below the chains'
 refusal).  Logits and stage tensors of the checked clips against the oracle's single-clip forward.
 
 offk_forward_parts with spec.SITE_PARTS at the same N: every part is below the mark (the widest, 96 channels of 3b, is 0.64 GB), so the
 buffer-descriptor kernels run -- pw_tdiff16_kernel on the fp32 handle and pw_tdiff_split_kernel on the split one, one descriptor per
-part, extents below 0x7fffff00 by the same check, stores (size_t) (pw_tdiff.hip:413-416, :563-593; pw_tdiff_split.hip:118-121, :352-383).
+part, extents below 0x7fffff00 by the same check, stores (size_t) (pw_tdiff.hip:407-410, :557-587; pw_tdiff_split.hip:112-115, :343-374).
 
 The training side of the units on the same fp32 maps (offk_off_units_train, offk_off_units_backward, offk_off_units_backward_feats):
 test_units_training_side_at_n_2142, whose docstring has the index widths of units_bwd.hip and units_dx.hip.  16-bit maps of 2 GiB:
@@ -348,8 +348,8 @@ def test_keep_rows_is_a_window_of_the_whole_mask():
 def test_units_training_side_at_n_2142(world):
     """offk_off_units_train + offk_off_units_backward + offk_off_units_backward_feats on the fp32 maps with 3b past 2 GiB.  Read first:
     K1 / K2 as above with the dropout draw index (unsigned long long)pair * HW (sobel_tdiff.hip:286); units_bwd.hip's K2b and K1b index
-    with (size_t)frame * HW, (size_t)frame * xfs (:99-104, :141-203, :375-437); units_dx.hip with (size_t)row * C, ((size_t)ef * C + c) *
-    HW (:118-246); no buffer descriptor in either.
+    with (size_t)frame * HW, (size_t)frame * xfs (:99-104, :141-203, :369-431); units_dx.hip with (size_t)row * C, ((size_t)ef * C + c) *
+    HW (:112-240); no buffer descriptor in either.
     The output gradients are non-zero in the checked clips only, so the reference is the oracle on those clips as a batch of their
     own (per-clip slicing; their windows of the dropout mask; the device's own ReLU decisions, checked against the oracle's as
     tests/test_gpu_backward.py does): every unit-parameter gradient within that file's RTOL, the feature-map gradient of the checked

@@ -6,7 +6,7 @@
       the gradient views are nevertheless real and of the full size, so that a library that did NOT refuse would stay inside them.
   the inference side (offk_forward_typed on a split-fp32 handle) RUNS: the 16-bit units kernel is a pointer loader,
       ((size_t)frame * cpart + kl + 8 g) * HW + px (pw_tdiff_f16.hip:39-56), its stores (size_t)(pair0 + j) * HW ... * m_cs
-      (pw_tdiff_staged.h:247-272), no buffer descriptor anywhere in pw_tdiff_f16.hip, pw_tdiff_cl.hip (size_t it_row * cpart, :47-57) or
+      (pw_tdiff_staged.h:231-256), no buffer descriptor anywhere in pw_tdiff_f16.hip, pw_tdiff_cl.hip (size_t it_row * cpart, :47-57) or
       pw_tdiff_staged.h.  At P = 3672 fusion_28 (3.7 GB) and fusion_14 (3.0 GB) are past 2 GiB as well: their readers and writers are the
       kernels of tests/test_gpu_big_slabs.py (pointer loaders and stores, the fp32 chain for 28c), the Winograd V array is 9.5 GB
       (winograd7.hip:127 and :150 index it with size_t, one GEMM descriptor per problem).

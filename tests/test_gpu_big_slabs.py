@@ -25,27 +25,27 @@ row-or-image index x stride; entries without a constant have no size check of th
   offk_bottleneck_chain14        x: (n 196 cs - coff) 4 < 0x7fffffff,         chain14_kernel | refused "chain14: input     y, res: size_t
                                  offk_api.hip:932, chain_fused.hip:508        beyond 31-bit byte offsets"                  (chain_fused.hip:287, :327)
   offk_bottleneck_chain14_split  x as above; y: n 196 cs 4 < 0x7fffff00,      chain14_split_kernel | refused "chain14      res: size_t
-                                 chain_split.hip:378-379                      (split-fp32): need ... input and output      (chain_split.hip:156)
+                                 chain_split.hip:366-367                      (split-fp32): need ... input and output      (chain_split.hip:144)
                                                                               below 2^31 bytes"
   offk_winograd_conv3x3 / 5x5s2  none on x, y, res (V, M are dense scratch:   one input and one output transform           size_t (winograd.hip:44,
                                  wino_gemm.hip:212-215 picks their GEMM)                                                  :94, :137-142)
   offk_winograd_conv7x7s2        none on x, y                                 one input and one output transform           size_t (winograd7.hip:91,
                                                                                                                            :102, :170)
-  offk_winograd_between / _ex    none on x                                    one kernel per arithmetic                    size_t (wino_mid.hip:107)
+  offk_winograd_between / _ex    none on x                                    one kernel per arithmetic                    size_t (wino_mid.hip:103)
   offk_head                      none                                         head_kernel                                  size_t (heads.hip:50, :71, :77)
   offk_head_train                n H W, n classes <= 0x7fffffff,              runs | refused "problem too large"            size_t (head_bwd.hip:59,
-  offk_head_backward             offk_api.hip:2564 (counts, not bytes)                                                     :73, :82, :139-181)
+  offk_head_backward             offk_api.hip:2627 (counts, not bytes)                                                     :73, :82, :139-181)
   offk_relu_backward             none                                         relu_bwd_kernel                              size_t (conv_bwd.hip:237-243)
   offk_conv2d_backward_data      (H + 2)(W + 2) n <= 0x7fffffff - 4096,       runs as offk_conv2d of the transposed        as offk_conv2d; accumulate
                                  conv_bwd.hip:254 (positions, not bytes)      problem | refused "problem too large"        reads dx as the residual
   offk_conv2d_backward_weight    as above                                     conv_wgrad_kernel                            long long (conv_bwd.hip:58,
                                                                                                                            :97, :112)
   offk_conv2d_backward_weight    positions + 2 pitch + 4096 < 0x7fffffff,     conv_wgrad_split kernel | refused            long long
-    _split                       conv_wgrad_split.hip:313                                                                  (conv_wgrad_split.hip:133-158)
+    _split                       conv_wgrad_split.hip:256                                                                  (conv_wgrad_split.hip:116-141)
   offk_conv2d_s2_backward_data   positions, n H W <= 0x7fffffff,              one kernel | refused "problem too large"     size_t (conv_bwd_s2.hip:134,
   offk_conv2d_s2_backward_weight conv_bwd_s2.hip:375                                                                       :181, :272, :285)
   offk_conv2d_s2_backward_data   M + 16 tiles <= 0x7fffffff,                  one kernel pair | refused                    size_t (conv_dgrad_s2_split
-    _split                       conv_dgrad_s2_split.hip:308                                                               .hip:122-124, :272)
+    _split                       conv_dgrad_s2_split.hip:263                                                               .hip:122-124, :272)
   offk_nhwc_to_nchw              none (n <= 65535: the grid's z)              nhwc_to_nchw_kernel                          size_t (heads.hip:478, :483)
   offk_sobel_tdiff               none on M (m_cstride, m_coff)                one kernel per algo                          size_t (sobel_tdiff.hip:148-200,
                                                                                                                            :221-293)
