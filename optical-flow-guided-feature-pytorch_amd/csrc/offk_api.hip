@@ -9,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "offk_internal.h"
@@ -89,6 +90,20 @@ const int kSiteFusion[kNumSites] = {0, 0, 1, 1, 1, 1, 1, 2, 2};
 const int kSiteCoff[kNumSites] = {0, 160, 0, 160, 320, 480, 640, 0, 160};
 const int kFusionC[3] = {320, 1056, 832};
 
+// Workspace regions, one id space.  A per-site family takes kNumSites ids from its enumerator on: site_region(R_G, s).  What each region
+// is called, how large it is and which handles have it: kRegions, behind the handle.
+enum Region {
+  R_G, R_D = R_G + kNumSites,                                                      // K1's outputs per site
+  R_DG = R_D + kNumSites, R_DD = R_DG + kNumSites, R_DWP = R_DD + kNumSites,      // training side: K2b's outputs per site
+  R_WGS = R_DWP + kNumSites, R_WGB = R_WGS + kNumSites,                            // ... K1b's partial slabs per site
+  R_FUSION_28 = R_WGB + kNumSites, R_FUSION_14, R_FUSION_7,
+  R_XT_28, R_T1_28, R_SA_28, R_SB_28, R_XU_14, R_U1_14, R_SA_14, R_XV_7, R_V1_7, R_SUM_7,
+  R_LOGIT_7, R_LOGIT_14, R_LOGIT_28, R_POOLED_7, R_POOLED_14, R_POOLED_28, R_POOLPART_28, R_POOLPART_7, R_POOLPART_14,
+  R_WINO_V, R_WINO_M, R_POOLPART_14T, R_POOLPART_7T, R_SPLITK, kNumRegions
+};
+constexpr Region site_region(Region family, int site) { return Region(family + site); }
+const Region kFusionRegion[3] = {R_FUSION_28, R_FUSION_14, R_FUSION_7};      // by kSiteFusion
+
 struct ConvSpec { const char* key; int Co, Ci, K, stride, pad; };
 enum ConvId {
   C_T28, C1_28A, C2_28A, C3_28A, CB_28A, C1_28B, C2_28B, C3_28B, C1_28C, C2_28C, C3_28C,
@@ -136,7 +151,17 @@ struct HeadSpec { const char* key; int C; };
 const HeadSpec kHeads[3] = {{"fc_action_motion", 1024}, {"fc_action_motion_28", 256}, {"fc_action_motion_14", 512}};
 const char* kSobelKey = "sobel_edge_diagonal.conv.weight";
 
+// (the first six: the unit parameters of a site, each its own row of kUnitParams and its own UnitParam record on the handle)
 enum SlotKind { SK_GEN_W, SK_GEN_B, SK_DOWN_W, SK_DOWN_B, SK_DW_W, SK_DW_B, SK_SOBEL, SK_CONV_W, SK_CONV_B, SK_FC_W, SK_FC_B };
+constexpr int kNumUnitParams = SK_DW_B + 1;
+// one unit parameter of one site on a handle; slot < 0: the variant has no such parameter
+struct UnitParam {
+  float* own = nullptr;          // the library's copy (offk_set_weight), in the layout its kernels read
+  const float* bound = nullptr;  // the caller's own tensor, reference layout, read at launch time (offk_bind_weight); nullptr: the copy is read
+  int slot = -1;                 // its index in offk_handle::slots
+  size_t grad_off = 0;           // where its gradient starts in the caller's gradient buffer, floats (offk_unit_grad_slot)
+};
+struct RegionSpan { size_t off = 0, bytes = 0; bool on = false; };      // on: the handle has the region
 struct Slot {
   std::string key;
   std::vector<int64_t> shape;
@@ -184,13 +209,8 @@ struct offk_handle {
   float* pw_b[kNumSites] = {};   // [160]
   float* dw_w[kNumSites] = {};   // [9][32]
   float* dw_b[kNumSites] = {};   // [32] or null
-  // unit parameters bound in place (offk_bind_weight): the caller's own tensors, reference layouts, read at launch time
-  const float* bnd_gen_w[kNumSites] = {};   // [128][C]
-  const float* bnd_gen_b[kNumSites] = {};   // [128]
-  const float* bnd_down_w[kNumSites] = {};  // [32][C]
-  const float* bnd_down_b[kNumSites] = {};  // [32]
-  const float* bnd_dw_w[kNumSites] = {};    // [32][1][3][3]
-  const float* bnd_dw_b[kNumSites] = {};    // [32]
+  UnitParam unit[kNumSites][kNumUnitParams];   // the six parameters of a site's unit, by SlotKind: copy, binding, slot, gradient (kUnitParams)
+  int sobel_slot = -1;           // the slot of kSobelKey (diag variant)
   float* sobel_w = nullptr;      // shared [9][32] (diag variant)
   bool sobel_taps4 = false;      // the loaded Sobel weight is zero outside the four taps of util.py:61 -> K2's four-tap path
   float* conv_w[kNumConvs] = {};
@@ -224,8 +244,7 @@ struct offk_handle {
   size_t train_ws_bytes = 0;
   bool units_bwd_done = false;   // an offk_off_units_backward* call has been enqueued since offk_create: dG_<site> / dD_<site> hold a backward's output
   int wg_kpb = 0;                // 32-pixel K-tiles one pw_wgrad block walks
-  std::map<std::string, std::pair<size_t, size_t>> grad_slots;   // key -> (offset, count) in floats
-  size_t grad_floats = 0;
+  size_t grad_floats = 0;        // the caller's gradient buffer: every UnitParam::grad_off of the handle lies in it
 
   int conv_cfg[kNumConvs];       // tile plan per fusion conv (-1 = automatic)
   int conv_splitk[kNumConvs];    // K-split per fusion conv (0 = automatic)
@@ -237,8 +256,8 @@ struct offk_handle {
   bool sum7_pending = false;     // a forward skipped merged_7 and offk_stage_tensors has not run it since
   bool fold_pool = true;         // 7- / 14-head: average pool in the producing conv's epilogue + MFMA FC (OFFK_FOLD_POOL=0: pool + fc kernels)
   std::vector<void*> allocs;
-  // workspace plan
-  std::map<std::string, std::pair<size_t, size_t>> regions;
+  // workspace plan (plan_workspace walks kRegions)
+  RegionSpan regions[kNumRegions];
   size_t ws_bytes = 0;
   // profiling: 0 off, 1 per-stage events, 2 per-launch trace (one event in front of every launch group, by name)
   int profiling = 0;
@@ -308,15 +327,9 @@ void add_slot(offk_handle* h, const std::string& key, std::vector<int64_t> shape
   h->slots.push_back(std::move(s));
 }
 
-void add_region(offk_handle* h, const std::string& name, size_t nfloats) {
-  size_t off = align_up(h->ws_bytes, 256);
-  h->regions[name] = std::make_pair(off, nfloats * sizeof(float));
-  h->ws_bytes = off + nfloats * sizeof(float);
-}
-
-float* region(const offk_handle* h, void* ws, const char* name) {
-  auto it = h->regions.find(name);
-  return reinterpret_cast<float*>(static_cast<char*>(ws) + it->second.first);
+// nullptr: the handle has no such region
+float* region(const offk_handle* h, void* ws, Region r) {
+  return h->regions[r].on ? reinterpret_cast<float*>(static_cast<char*>(ws) + h->regions[r].off) : nullptr;
 }
 
 // S-blocks of the units' backward: 7-row strips at 28x28, whole planes below (two LDS tiles per block; shorter
@@ -327,90 +340,162 @@ void ub_plan(int H, int* strips, int* rows) {
 }
 constexpr int kUbTpix = 8;     // pixels per T-block of the backward: one task per thread (as K2, sobel_tdiff.hip st_tpix)
 
+// ---- the six parameters of a site's OFF unit: ONE table, in the order of their slots (offk_missing_weights reports the first unset one) and
+// of their gradients in the caller's buffer.  offk_create, plan_workspace, offk_set_weight, offk_bind_weight, site_weights_ready and
+// the backward's reduce go by it; the per-site state is offk_handle::unit.  A new bindable parameter is a row. ----
+constexpr int64_t kC = -1;       // in a shape: the site's channel count
+struct UnitParamSpec {
+  const char* prefix; const char* suffix;      // the key: <prefix><site><suffix>
+  SlotKind kind;                               // = its row
+  int ndim; int64_t shape[4];                  // of the reference's tensor
+  bool dw;                                     // a depthwise parameter: on the learned-depthwise variant only, and what K2 / K2b read (else: K1 / K1b / dX)
+  float* (offk_handle::*buf)[kNumSites];       // the library's copy lives in this per-site buffer of the handle ...
+  int buf_row;                                 // ... from this row on: gen and down share one, [gen 128 ; down 32] rows -- the pack kernels read it whole
+  bool repack_dw;                              // offk_set_weight stages it through repack_dw_launch ([32][1][3][3] -> [9][32]); else a plain copy
+  float* WrSite::*grad;                        // where the reduce kernel is told the destination of its gradient
+};
+const char kGenKey[] = "motion_conv_gen_", kDownKey[] = "motion_spatial_down_", kDwKey[] = "motion_spatial_grad_";
+const UnitParamSpec kUnitParams[kNumUnitParams] = {
+    {kGenKey, ".weight", SK_GEN_W, 4, {kGenCh, kC, 1, 1}, false, &offk_handle::pw_w, 0, false, &WrSite::gen_w},
+    {kGenKey, ".bias", SK_GEN_B, 1, {kGenCh}, false, &offk_handle::pw_b, 0, false, &WrSite::gen_b},
+    {kDownKey, ".weight", SK_DOWN_W, 4, {kDownCh, kC, 1, 1}, false, &offk_handle::pw_w, kGenCh, false, &WrSite::down_w},
+    {kDownKey, ".bias", SK_DOWN_B, 1, {kDownCh}, false, &offk_handle::pw_b, kGenCh, false, &WrSite::down_b},
+    {kDwKey, ".weight", SK_DW_W, 4, {kDownCh, 1, 3, 3}, true, &offk_handle::dw_w, 0, true, &WrSite::dw_w},
+    {kDwKey, ".bias", SK_DW_B, 1, {kDownCh}, true, &offk_handle::dw_b, 0, false, &WrSite::dw_b}};
+std::vector<int64_t> unit_shape(const UnitParamSpec& p, int C) {
+  std::vector<int64_t> shape(p.shape, p.shape + p.ndim);
+  std::replace(shape.begin(), shape.end(), kC, (int64_t)C);
+  return shape;
+}
+size_t unit_count(const UnitParamSpec& p, int C) {
+  size_t n = 1;
+  for (int i = 0; i < p.ndim; ++i) n *= (size_t)(p.shape[i] == kC ? C : p.shape[i]);
+  return n;
+}
+// the parameter a launch reads: the tensor bound in place if there is one, else the library's copy
+struct ParamPtr { const float* p; bool bound; };
+ParamPtr unit_param(const offk_handle* h, int site, SlotKind k) {
+  const UnitParam& u = h->unit[site][k];
+  return ParamPtr{u.bound ? u.bound : u.own, u.bound != nullptr};
+}
+// the first site with a gen / down weight bound in place (the operand-order images of the fused units kernel are packed from the copies); -1: none
+int bound_contraction_site(const offk_handle* h) {
+  for (int s = 0; s < kNumSites; ++s)
+    if (unit_param(h, s, SK_GEN_W).bound || unit_param(h, s, SK_DOWN_W).bound) return s;
+  return -1;
+}
+
+// ---- the workspace regions: ONE table, in layout order.  plan_workspace walks it, offk_workspace_region finds names in it, everything
+// else goes by id.  A new region is an enumerator and a row. ----
+enum { PER_SITE = 1, TRAIN = 2 };      // PER_SITE: a family, "<name><site>" at site_region(id, site); TRAIN: behind the forward layout (offk_train_workspace_bytes)
+#define OFFK_REGION_ARGS const offk_handle* h, size_t N, size_t P, int s      /* s: the site of a family's region */
+struct RegionRow {
+  Region id;
+  const char* name;
+  int flags;
+  size_t (*floats)(OFFK_REGION_ARGS);
+  bool (*exists)(const offk_handle* h) = nullptr;      // nullptr: on every handle
+};
+size_t site_hw(int s) { return (size_t)kSites[s].H * kSites[s].H; }
+size_t wg_chunks(const offk_handle* h, size_t N, int s) { return (N * ((site_hw(s) + 31) / 32) + h->wg_kpb - 1) / h->wg_kpb; }      // K1b's K chunks of a site
+const RegionRow kRegions[] = {
+    // (a run of families is laid out site by site: G_3a, D_3a, G_3b, ...)
+    {R_G, "G_", PER_SITE, [](OFFK_REGION_ARGS) { return N * site_hw(s) * kGenCh; }},
+    {R_D, "D_", PER_SITE, [](OFFK_REGION_ARGS) { return P * site_hw(s) * kDownCh; }},
+    {R_FUSION_28, "fusion_28", 0, [](OFFK_REGION_ARGS) { return P * 784 * 320; }},
+    {R_FUSION_14, "fusion_14", 0, [](OFFK_REGION_ARGS) { return P * 196 * 1056; }},
+    {R_FUSION_7, "fusion_7", 0, [](OFFK_REGION_ARGS) { return P * 49 * 832; }},
+    // fusion@28 temporaries, 14x14 maps
+    {R_XT_28, "xt_28", 0, [](OFFK_REGION_ARGS) { return P * 196 * 128; }},   // [t2 (c2 output) | x0 (pre-ReLU 7x7 output)]: input of the merged c3+branch conv
+    {R_T1_28, "t1_28", 0, [](OFFK_REGION_ARGS) { return P * 196 * 64; }},
+    {R_SA_28, "sa_28", 0, [](OFFK_REGION_ARGS) { return P * 196 * 256; }},
+    {R_SB_28, "sb_28", 0, [](OFFK_REGION_ARGS) { return P * 196 * 256; }},
+    // fusion@14 temporaries, 7x7 maps
+    {R_XU_14, "xu_14", 0, [](OFFK_REGION_ARGS) { return P * 49 * 256; }},    // [u2 | x1]
+    {R_U1_14, "u1_14", 0, [](OFFK_REGION_ARGS) { return P * 49 * 128; }},
+    {R_SA_14, "sa_14", 0, [](OFFK_REGION_ARGS) { return P * 49 * 512; }},
+    // fusion@7
+    {R_XV_7, "xv_7", 0, [](OFFK_REGION_ARGS) { return P * 49 * 512; }},      // [v2 | x2]
+    {R_V1_7, "v1_7", 0, [](OFFK_REGION_ARGS) { return P * 49 * 256; }},
+    {R_SUM_7, "sum_7", 0, [](OFFK_REGION_ARGS) { return P * 49 * 1024; }},
+    // per-pair logits when consensus averages them afterwards
+    {R_LOGIT_7, "logit_7", 0, [](OFFK_REGION_ARGS) { return P * (size_t)h->cfg.num_classes; }},
+    {R_LOGIT_14, "logit_14", 0, [](OFFK_REGION_ARGS) { return P * (size_t)h->cfg.num_classes; }},
+    {R_LOGIT_28, "logit_28", 0, [](OFFK_REGION_ARGS) { return P * (size_t)h->cfg.num_classes; }},
+    {R_POOLED_7, "pooled_7", 0, [](OFFK_REGION_ARGS) { return P * 1024; }},
+    {R_POOLED_14, "pooled_14", 0, [](OFFK_REGION_ARGS) { return P * 512; }},
+    {R_POOLED_28, "pooled_28", 0, [](OFFK_REGION_ARGS) { return P * 256; }},
+    {R_POOLPART_28, "poolpart_28", 0, [](OFFK_REGION_ARGS) { return (size_t)4 * P * 256; }},   // 28-head: max-pooled cells summed per block of pool rows (maxpool_rows_kernel)
+    // average pools of the 7- and 14-heads folded into the producing conv: per 32-row slab, two partial column sums
+    {R_POOLPART_7, "poolpart_7", 0, [](OFFK_REGION_ARGS) { return ((P * 49 + 31) / 32) * 2 * 1024; }},
+    {R_POOLPART_14, "poolpart_14", 0, [](OFFK_REGION_ARGS) { return ((P * 49 + 31) / 32) * 2 * 512; }},
+    // Winograd path of the 3x3 convs at 7x7: transformed input [121][P][Ci <= 832], GEMM output [121][P][Co <= 512], per-tile sums of
+    // sum_14b for the 14-head.  wino_v, widest: the polyphase 7x7 / 2 conv (9 P tiles x 225 x 320 floats: 1.0 GB at P = 384), then the
+    // polyphase 5x5 / 2 conv (400 P x 1056)
+    {R_WINO_V, "wino_v", 0, [](OFFK_REGION_ARGS) { return std::max((size_t)kWinoUnits4 * P * 1056, (size_t)kWino7Tiles * P * kWino7Units * 320); }},
+    {R_WINO_M, "wino_m", 0, [](OFFK_REGION_ARGS) { return (size_t)kWinoPoints * P * 512; }},    // (7x7: 64 x 9 P x 64 is smaller)
+    {R_POOLPART_14T, "poolpart_14t", 0, [](OFFK_REGION_ARGS) { return (size_t)4 * P * 512; }},
+    {R_POOLPART_7T, "poolpart_7t", 0, [](OFFK_REGION_ARGS) { return (size_t)4 * P * 512; },      // per-tile sums of xv_7 = [v2 | x2]
+     [](const offk_handle* h) { return h->pool_first7; }},
+    {R_SPLITK, "splitk", 0, [](OFFK_REGION_ARGS) { return h->splitk_floats; }},
+    // training side (offk_off_units_backward*)
+    {R_DG, "dG_", PER_SITE | TRAIN, [](OFFK_REGION_ARGS) { return N * site_hw(s) * kGenCh; }},
+    {R_DD, "dD_", PER_SITE | TRAIN, [](OFFK_REGION_ARGS) { return P * site_hw(s) * kDownCh; }},
+    {R_DWP, "dwp_", PER_SITE | TRAIN, [](OFFK_REGION_ARGS) {
+       int strips, rows;
+       ub_plan(kSites[s].H, &strips, &rows);
+       return P * strips * 10 * kDownCh;
+     }},
+    {R_WGS, "wgs_", PER_SITE | TRAIN, [](OFFK_REGION_ARGS) { return wg_chunks(h, N, s) * kUnitCh * ((size_t)((kSites[s].C + 127) / 128) * 128); }},
+    {R_WGB, "wgb_", PER_SITE | TRAIN, [](OFFK_REGION_ARGS) { return wg_chunks(h, N, s) * kUnitCh; }}};
+constexpr int kNumRegionRows = sizeof(kRegions) / sizeof(kRegions[0]);
+
+// the id behind a name (offk_workspace_region); kNumRegions: no region is called that
+Region region_by_name(const char* name) {
+  for (const RegionRow& row : kRegions) {
+    const size_t n = (row.flags & PER_SITE) ? strlen(row.name) : 0;
+    if (!n && !strcmp(name, row.name)) return row.id;
+    for (int s = 0; n && s < kNumSites; ++s)
+      if (!strncmp(name, row.name, n) && !strcmp(name + n, kSites[s].name)) return site_region(row.id, s);
+  }
+  return kNumRegions;
+}
+
 void plan_workspace(offk_handle* h) {
   const size_t N = h->N, P = h->P;
-  for (int s = 0; s < kNumSites; ++s) {
-    size_t hw = (size_t)kSites[s].H * kSites[s].H;
-    add_region(h, std::string("G_") + kSites[s].name, N * hw * kGenCh);
-    add_region(h, std::string("D_") + kSites[s].name, P * hw * kDownCh);
-  }
-  add_region(h, "fusion_28", P * 784 * 320);
-  add_region(h, "fusion_14", P * 196 * 1056);
-  add_region(h, "fusion_7", P * 49 * 832);
-  // fusion@28 temporaries, 14x14 maps
-  add_region(h, "xt_28", P * 196 * 128);   // [t2 (c2 output) | x0 (pre-ReLU 7x7 output)]: input of the merged c3+branch conv
-  add_region(h, "t1_28", P * 196 * 64);
-  add_region(h, "sa_28", P * 196 * 256);
-  add_region(h, "sb_28", P * 196 * 256);
-  // fusion@14 temporaries, 7x7 maps
-  add_region(h, "xu_14", P * 49 * 256);    // [u2 | x1]
-  add_region(h, "u1_14", P * 49 * 128);
-  add_region(h, "sa_14", P * 49 * 512);
-  // fusion@7
-  add_region(h, "xv_7", P * 49 * 512);     // [v2 | x2]
-  add_region(h, "v1_7", P * 49 * 256);
-  add_region(h, "sum_7", P * 49 * 1024);
-  // per-pair logits when consensus averages them afterwards
-  add_region(h, "logit_7", P * (size_t)h->cfg.num_classes);
-  add_region(h, "logit_14", P * (size_t)h->cfg.num_classes);
-  add_region(h, "logit_28", P * (size_t)h->cfg.num_classes);
-  add_region(h, "pooled_7", P * 1024);
-  add_region(h, "pooled_14", P * 512);
-  add_region(h, "pooled_28", P * 256);
-  add_region(h, "poolpart_28", (size_t)4 * P * 256);   // 28-head: max-pooled cells summed per block of pool rows (maxpool_rows_kernel)
-  // average pools of the 7- and 14-heads folded into the producing conv: per 32-row slab, two partial column sums
-  add_region(h, "poolpart_7", ((P * 49 + 31) / 32) * 2 * 1024);
-  add_region(h, "poolpart_14", ((P * 49 + 31) / 32) * 2 * 512);
-  // Winograd path of the 3x3 convs at 7x7 (fp32): transformed input [121][P][Ci <= 832], GEMM output [121][P][Co <= 512],
-  // per-tile sums of sum_14b for the 14-head
-  if (h->cfg.precision == OFFK_PRECISION_FP32) {
-    // widest: the polyphase 7x7 / 2 conv (9 P tiles x 225 x 320 floats: 1.0 GB at P = 384), then the polyphase 5x5 / 2 conv (400 P x 1056)
-    add_region(h, "wino_v", std::max((size_t)kWinoUnits4 * P * 1056, (size_t)kWino7Tiles * P * kWino7Units * 320));
-    add_region(h, "wino_m", (size_t)kWinoPoints * P * 512);    // (7x7: 64 x 9 P x 64 is smaller)
-    add_region(h, "poolpart_14t", (size_t)4 * P * 512);
-    if (h->pool_first7) add_region(h, "poolpart_7t", (size_t)4 * P * 512);      // per-tile sums of xv_7 = [v2 | x2]
-  }
   // split-K partial slabs: room for 8 slices of the widest large-K conv output (7x7: [P*196, 64], 3x3 @7: [P*49, 256]) -- up
   // to 64 at small P, where the plans split deeper (conv2d_auto_plan); a conv whose plan needs more gets as many as fit
   h->splitk_floats = (size_t)std::min<size_t>(64, std::max<size_t>(8, 1536 / P)) * P * 196 * 64;
-  add_region(h, "splitk", h->splitk_floats);
-  h->ws_bytes = align_up(h->ws_bytes, 256);
-
-  // ---- training side: backward regions behind the forward layout (offk_train_workspace_bytes) ----
-  const size_t fwd_bytes = h->ws_bytes;
   long long work = 0;   // (K-tile, channel slab) steps of the grouped weight-gradient GEMM
-  for (int s = 0; s < kNumSites; ++s) {
-    const int hw = kSites[s].H * kSites[s].H;
-    work += (long long)N * ((hw + 31) / 32) * ((kSites[s].C + 127) / 128);
-  }
+  for (int s = 0; s < kNumSites; ++s) work += (long long)N * ((site_hw(s) + 31) / 32) * ((kSites[s].C + 127) / 128);
   h->wg_kpb = (int)std::max<long long>(4, (work + 1535) / 1536);
-  for (int s = 0; s < kNumSites; ++s) {
-    const size_t hw = (size_t)kSites[s].H * kSites[s].H;
-    const std::string n = kSites[s].name;
-    int strips, rows;
-    ub_plan(kSites[s].H, &strips, &rows);
-    const size_t kt_total = N * ((hw + 31) / 32), nchunks = (kt_total + h->wg_kpb - 1) / h->wg_kpb;
-    const size_t cpad = (size_t)((kSites[s].C + 127) / 128) * 128;
-    add_region(h, "dG_" + n, N * hw * kGenCh);
-    add_region(h, "dD_" + n, P * hw * kDownCh);
-    add_region(h, "dwp_" + n, P * strips * 10 * kDownCh);
-    add_region(h, "wgs_" + n, nchunks * kUnitCh * cpad);
-    add_region(h, "wgb_" + n, nchunks * kUnitCh);
-    auto slot = [&](const std::string& key, size_t count) {
-      h->grad_slots[key] = std::make_pair(h->grad_floats, count);
-      h->grad_floats += count;
-    };
-    slot("motion_conv_gen_" + n + ".weight", (size_t)kGenCh * kSites[s].C);
-    slot("motion_conv_gen_" + n + ".bias", kGenCh);
-    slot("motion_spatial_down_" + n + ".weight", (size_t)kDownCh * kSites[s].C);
-    slot("motion_spatial_down_" + n + ".bias", kDownCh);
-    if (h->cfg.variant != OFFK_VARIANT_DIAG_SOBEL) {
-      slot("motion_spatial_grad_" + n + ".weight", (size_t)kDownCh * 9);
-      slot("motion_spatial_grad_" + n + ".bias", kDownCh);
-    }
+
+  size_t end = 0, fwd_end = 0;
+  for (int i = 0, j; i < kNumRegionRows; i = j) {
+    const int flags = kRegions[i].flags;
+    for (j = i + 1; (flags & PER_SITE) && j < kNumRegionRows && kRegions[j].flags == flags; ++j) {}      // rows [i, j): one region, or a run of families
+    for (int s = 0; s < ((flags & PER_SITE) ? kNumSites : 1); ++s)
+      for (int r = i; r < j; ++r) {
+        const RegionRow& row = kRegions[r];
+        if (row.exists && !row.exists(h)) continue;
+        RegionSpan& sp = h->regions[site_region(row.id, s)];
+        sp.off = align_up(end, 256);
+        sp.bytes = row.floats(h, N, P, s) * sizeof(float);
+        sp.on = true;
+        end = sp.off + sp.bytes;
+        if (!(flags & TRAIN)) fwd_end = end;
+      }
   }
-  h->train_ws_bytes = align_up(h->ws_bytes, 256);
-  h->ws_bytes = fwd_bytes;
+  h->ws_bytes = align_up(fwd_end, 256);
+  h->train_ws_bytes = align_up(end, 256);      // the forward layout with the backward's regions behind it
+
+  // the caller's gradient buffer: per site, the parameters the variant has, in table order
+  for (int s = 0; s < kNumSites; ++s)
+    for (const UnitParamSpec& p : kUnitParams)
+      if (h->unit[s][p.kind].slot >= 0) {
+        h->unit[s][p.kind].grad_off = h->grad_floats;
+        h->grad_floats += unit_count(p, kSites[s].C);
+      }
 }
 
 struct DeviceGuard {
@@ -428,43 +513,43 @@ int check_ready(offk_handle* h) {
   return OFFK_OK;
 }
 
-bool slot_set(const offk_handle* h, const std::string& key) {
-  auto it = h->index.find(key);
-  return it != h->index.end() && h->slots[it->second].set;
-}
-
+// need_pw: the four 1x1 parameters of the site (K1, K1b, dX); need_dw: its depthwise ones, or the shared Sobel weight (K2, K2b)
 int site_weights_ready(offk_handle* h, int site, bool need_pw, bool need_dw) {
-  const std::string n = kSites[site].name;
-  if (need_pw)
-    for (const char* k : {"motion_conv_gen_", "motion_spatial_down_"})
-      for (const char* sfx : {".weight", ".bias"})
-        if (!slot_set(h, std::string(k) + n + sfx)) return fail(h, OFFK_ERR_MISSING_WEIGHT, std::string("weight not set: ") + k + n + sfx);
-  if (need_dw) {
-    if (h->cfg.variant == OFFK_VARIANT_DIAG_SOBEL) {
-      if (!slot_set(h, kSobelKey)) return fail(h, OFFK_ERR_MISSING_WEIGHT, std::string("weight not set: ") + kSobelKey);
-    } else {
-      for (const char* sfx : {".weight", ".bias"})
-        if (!slot_set(h, "motion_spatial_grad_" + n + sfx)) return fail(h, OFFK_ERR_MISSING_WEIGHT, "weight not set: motion_spatial_grad_" + n + sfx);
-    }
-  }
+  auto ready = [&](int slot) { return h->slots[slot].set ? OFFK_OK : fail(h, OFFK_ERR_MISSING_WEIGHT, "weight not set: " + h->slots[slot].key); };
+  for (const UnitParamSpec& p : kUnitParams)
+    if ((p.dw ? need_dw : need_pw) && h->unit[site][p.kind].slot >= 0) TRY(ready(h->unit[site][p.kind].slot));
+  if (need_dw && h->sobel_slot >= 0) TRY(ready(h->sobel_slot));
   return OFFK_OK;
 }
 
 void pw_weight_ptrs(const offk_handle* h, int site, const float** w, const float** w_down, const float** b,
                     const float** b_down) {
-  const float* own = h->pw_w[site];
-  *w = h->bnd_gen_w[site] ? h->bnd_gen_w[site] : own;
-  *w_down = h->bnd_down_w[site] ? h->bnd_down_w[site] : own + (size_t)kGenCh * kSites[site].C;
-  *b = h->bnd_gen_b[site] ? h->bnd_gen_b[site] : h->pw_b[site];
-  *b_down = h->bnd_down_b[site] ? h->bnd_down_b[site] : h->pw_b[site] + kGenCh;
+  *w = unit_param(h, site, SK_GEN_W).p;
+  *w_down = unit_param(h, site, SK_DOWN_W).p;
+  *b = unit_param(h, site, SK_GEN_B).p;
+  *b_down = unit_param(h, site, SK_DOWN_B).p;
+}
+
+// What the per-site records of the units' launches share, filled where a record has the fields: the map as channel groups (xp / cp /
+// nparts; fp == nullptr: none to fill), C, HW and the row count M = N HW (PtSite's M is its fusion buffer: not that one).
+template <class S, class = void> struct has_parts : std::false_type {};
+template <class S> struct has_parts<S, std::void_t<decltype(S::nparts)>> : std::true_type {};
+template <class S, class = void> struct has_rows : std::false_type {};
+template <class S> struct has_rows<S, std::enable_if_t<std::is_same<decltype(S::M), int>::value>> : std::true_type {};
+template <class S>
+void fill_site_shape(const offk_handle* h, int site, const offk_feat_parts* fp, S* o) {
+  if constexpr (has_parts<S>::value) {
+    for (int q = 0; q < 4; ++q) { o->xp[q] = q < fp->n_parts ? fp->data[q] : nullptr; o->cp[q] = q < fp->n_parts ? fp->channels[q] : 0; }
+    o->nparts = fp->n_parts;
+  }
+  o->C = kSites[site].C; o->HW = kSites[site].H * kSites[site].H;
+  if constexpr (has_rows<S>::value) o->M = h->N * o->HW;
 }
 
 void fill_pw_site(const offk_handle* h, int site, const offk_feat_parts& fp, float* G, float* D, PwSite* o) {
-  for (int q = 0; q < 4; ++q) { o->xp[q] = q < fp.n_parts ? fp.data[q] : nullptr; o->cp[q] = q < fp.n_parts ? fp.channels[q] : 0; }
-  o->nparts = fp.n_parts;
+  fill_site_shape(h, site, &fp, o);
   pw_weight_ptrs(h, site, &o->w, &o->w_down, &o->bias, &o->bias_down);
   o->G = G; o->D = D;
-  o->C = kSites[site].C; o->HW = kSites[site].H * kSites[site].H; o->M = h->N * o->HW;
   o->blk_begin = 0;
 }
 void fill_st_site(const offk_handle* h, int site, const float* G, const float* D, float* M, int m_cs, int m_coff, StSite* o) {
@@ -472,9 +557,9 @@ void fill_st_site(const offk_handle* h, int site, const float* G, const float* D
   // one unit = [S 32 | T 128] of a channels-last row (RGB_OFF.py:616); the kernel takes the two halves as separate views
   o->Ms = M; o->s_cs = m_cs; o->s_coff = m_coff; o->Mt = M; o->t_cs = m_cs; o->t_coff = m_coff + kDownCh;
   const bool sobel = h->cfg.variant == OFFK_VARIANT_DIAG_SOBEL;
-  o->dw = sobel ? h->sobel_w : (h->bnd_dw_w[site] ? h->bnd_dw_w[site] : h->dw_w[site]);
-  o->dw_ref = !sobel && h->bnd_dw_w[site] != nullptr;
-  o->db = sobel ? nullptr : (h->bnd_dw_b[site] ? h->bnd_dw_b[site] : h->dw_b[site]);
+  o->dw = sobel ? h->sobel_w : unit_param(h, site, SK_DW_W).p;
+  o->dw_ref = !sobel && unit_param(h, site, SK_DW_W).bound;
+  o->db = sobel ? nullptr : unit_param(h, site, SK_DW_B).p;
   o->H = kSites[site].H;
   st_plan(o->H, &o->strips, &o->rows);
   st_recips(o->H, &o->wrecip, &o->twrecip);
@@ -497,12 +582,11 @@ int run_sobel_tdiff_all(offk_handle* h, hipStream_t st, void* ws, int algo, cons
   sp.nsites = kNumSites; sp.B = h->cfg.batch; sp.L = h->cfg.length;
   sp.drop_thresh = drop.thresh; sp.drop_scale = drop.scale;
   sp.zeros = h->zero_page;
-  const char* fus[3] = {"fusion_28", "fusion_14", "fusion_7"};
   sp.taps4 = h->cfg.variant == OFFK_VARIANT_DIAG_SOBEL && h->sobel_taps4;
   int sblk = 0, tblk = 0;
   for (int s = 0; s < kNumSites; ++s) {
-    fill_st_site(h, s, region(h, ws, (std::string("G_") + kSites[s].name).c_str()),
-                 region(h, ws, (std::string("D_") + kSites[s].name).c_str()), region(h, ws, fus[kSiteFusion[s]]),
+    fill_st_site(h, s, region(h, ws, site_region(R_G, s)),
+                 region(h, ws, site_region(R_D, s)), region(h, ws, kFusionRegion[kSiteFusion[s]]),
                  kFusionC[kSiteFusion[s]], kSiteCoff[s], &sp.s[s]);
     sp.s[s].s_begin = sblk;
     sp.s[s].drop_base = drop_stream_base(drop.seed, s);
@@ -620,8 +704,8 @@ int run_off_units(offk_handle* h, hipStream_t st, const offk_feat_parts feats[],
   int blk = 0;
   for (int i = 0; i < kNumSites; ++i) {
     int s = kPwOrder[i];
-    fill_pw_site(h, s, feats[s], region(h, ws, (std::string("G_") + kSites[s].name).c_str()),
-                 region(h, ws, (std::string("D_") + kSites[s].name).c_str()), &pp.s[i]);
+    fill_pw_site(h, s, feats[s], region(h, ws, site_region(R_G, s)),
+                 region(h, ws, site_region(R_D, s)), &pp.s[i]);
     pp.s[i].blk_begin = blk;
     blk += pw_blocks_for(pp.s[i].M);
   }
@@ -653,14 +737,11 @@ int run_off_units_split(offk_handle* h, hipStream_t st, const offk_feat_parts fe
   for (int i = 0; i < kNumSites; ++i) {
     const int s = kPwOrder[i];
     UfsSite& o = up.s[i];
-    const offk_feat_parts& fp = feats[s];
-    for (int q = 0; q < 4; ++q) { o.xp[q] = q < fp.n_parts ? fp.data[q] : nullptr; o.cp[q] = q < fp.n_parts ? fp.channels[q] : 0; }
-    o.nparts = fp.n_parts;
+    fill_site_shape(h, s, &feats[s], &o);
     pw_weight_ptrs(h, s, &o.wg, &o.wd, &o.bias, &o.bias_down);
     o.wimg = h->fwd_split_w[s];
-    o.G = region(h, ws, (std::string("G_") + kSites[s].name).c_str());
-    o.D = region(h, ws, (std::string("D_") + kSites[s].name).c_str());
-    o.C = kSites[s].C; o.HW = kSites[s].H * kSites[s].H; o.M = h->N * o.HW;
+    o.G = region(h, ws, site_region(R_G, s));
+    o.D = region(h, ws, site_region(R_D, s));
     o.blk_begin = blk; o.pack_begin = pblk;
     blk += pw_blocks_for(o.M);
     pblk += units_fwd_split_pack_blocks(o.C);
@@ -690,25 +771,19 @@ int run_off_units_fused(offk_handle* h, hipStream_t st, const offk_feat_parts fe
   pt.tgroups = pt_tgroups(h->cfg.length);
   pt.zeros = h->zero_page;
   // the operand-order weight image is the library's own copy: not with contraction weights bound in place
-  pt.bdirect = 1;
+  pt.bdirect = bound_contraction_site(h) < 0;
   pt.f32split = h->f32split;
-  for (int s = 0; s < kNumSites; ++s)
-    if (h->bnd_gen_w[s] || h->bnd_down_w[s]) pt.bdirect = 0;
-  const char* fus[3] = {"fusion_28", "fusion_14", "fusion_7"};
   for (int i = 0; i < kNumSites; ++i) {      // (the block layout -- chunks, leftover blocks, blk_begin, total_blocks -- is the launchers')
     const int s = kPwOrder[i];
     PtSite& o = pt.s[i];
-    const offk_feat_parts& fp = feats[s];
-    for (int q = 0; q < 4; ++q) { o.xp[q] = q < fp.n_parts ? fp.data[q] : nullptr; o.cp[q] = q < fp.n_parts ? fp.channels[q] : 0; }
-    o.nparts = fp.n_parts;
+    fill_site_shape(h, s, &feats[s], &o);
     pw_weight_ptrs(h, s, &o.w, &o.w_down, &o.bias, &o.bias_down);
     o.wt = nullptr;
     o.wt16 = h->pw_wt16[s];
     o.wt16s = h->pw_wt16s[s];
-    o.D = region(h, ws, (std::string("D_") + kSites[s].name).c_str());
-    o.M = region(h, ws, fus[kSiteFusion[s]]);
+    o.D = region(h, ws, site_region(R_D, s));
+    o.M = region(h, ws, kFusionRegion[kSiteFusion[s]]);
     o.m_cs = kFusionC[kSiteFusion[s]]; o.m_coff = kSiteCoff[s];
-    o.C = kSites[s].C; o.HW = kSites[s].H * kSites[s].H;
   }
   if (ev) HIP_TRY(h, hipEventRecord(ev[0], st));
   TRY(launch_k1t(h, st, pt, feat_dtype, cl));
@@ -947,7 +1022,7 @@ struct Fwd {
   FcPooledJobs fcj{};              // the folded-pool FCs of the heads, launched together behind the last stage (fc_pooled_multi_kernel)
   bool wino, w7, mid, w5, chained, fold, fold14t, pool7;      // the paths of this call (init)
 
-  float* reg(const char* name) const { return region(h, ws, name); }
+  float* reg(Region r) const { return region(h, ws, r); }
 
   // stage_only (offk_stage_tensors): a launch outside a forward -- it takes no stage events
   int init(offk_handle* handle, hipStream_t st, void* workspace, float* o7, float* o14, float* o28, bool stage_only = false) {
@@ -979,11 +1054,11 @@ struct Fwd {
     fold = h->fold_pool && generic(h->conv_cfg[C3_14B]) && generic(h->merged_cfg[2]);
     fold14t = wino && h->fold_pool;      // (the Winograd output transform of sum_14b leaves per-tile sums)
     pool7 = h->pool_first7 && mid && fold14t && h->derived[merged_slot(2)].head;      // (the 7-head from the per-tile sums of xv_7)
-    F14 = reg("fusion_14"); F7 = reg("fusion_7"); splitk = reg("splitk");
-    wino_V = wino ? reg("wino_v") : nullptr;
-    wino_M = wino ? reg("wino_m") : nullptr;
+    F14 = reg(R_FUSION_14); F7 = reg(R_FUSION_7); splitk = reg(R_SPLITK);
+    wino_V = wino ? reg(R_WINO_V) : nullptr;
+    wino_M = wino ? reg(R_WINO_M) : nullptr;
     const bool cons = h->cfg.consensus == OFFK_CONSENSUS_AVG;
-    l7 = cons ? reg("logit_7") : out7; l14 = cons ? reg("logit_14") : out14; l28 = cons ? reg("logit_28") : out28;
+    l7 = cons ? reg(R_LOGIT_7) : out7; l14 = cons ? reg(R_LOGIT_14) : out14; l28 = cons ? reg(R_LOGIT_28) : out28;
     fcj.n_img = n; fcj.ncls = h->cfg.num_classes;
     return OFFK_OK;
   }
@@ -1118,10 +1193,10 @@ struct Fwd {
 
   // head k (kHeads order) from the pooled partial sums `part` its producing launch left (heads.hip: fc_pooled), or -- part == nullptr: the
   // paths that cannot fold the pool into that launch (LDS-patch tiles, OFFK_FOLD_POOL=0) -- pool_kernel + fc_kernel on its output x
-  int head(int k, float* logits, const float* part, int tiles, const float* x, int x_cs, int x_coff, int Hh, int maxpool, const char* pooled_name) {
+  int head(int k, float* logits, const float* part, int tiles, const float* x, int x_cs, int x_coff, int Hh, int maxpool, Region pooled_region) {
     const int C = kHeads[k].C;
     if (part) { fcj.job[fcj.njobs++] = FcPooledJob{part, 49, tiles, C, h->fc_w[k], h->fc_b[k], logits}; return OFFK_OK; }
-    float* pooled = reg(pooled_name);
+    float* pooled = reg(pooled_region);
     TRY(trace_mark(h, s, k == 0 ? "head_7 (pool + fc)" : k == 1 ? "head_28 (pool + fc)" : "head_14 (pool + fc)"));
     hipError_t e = pool_launch(x, x_cs, x_coff, n, Hh, Hh, C, maxpool, pooled, s);
     if (e == hipSuccess) e = fc_launch(pooled, n, C, h->fc_w[k], h->fc_b[k], h->cfg.num_classes, logits, s);
@@ -1137,7 +1212,7 @@ struct Fwd {
 
   // ---- fusion @28 -> 14x14 (RGB_OFF.py:655-685) and the 28-head (:782-787) ----
   int fusion28() {
-    float *F28 = reg("fusion_28"), *xt = reg("xt_28"), *t1 = reg("t1_28"), *sa = reg("sa_28"), *sb = reg("sb_28");
+    float *F28 = reg(R_FUSION_28), *xt = reg(R_XT_28), *t1 = reg(R_T1_28), *sa = reg(R_SA_28), *sb = reg(R_SB_28);
     // xt = [t2 | x0] per pixel: c3(t2) + branch(x0) (:663-666) is then ONE 1x1 conv over 128 channels
     // :657 x0, pre-ReLU kept for the branch
     if (w7) TRY(wino_conv(C_T28, View{F28, 320, 0}, nullptr, 0, 0, 0, xt, 128, 64, nullptr));
@@ -1166,24 +1241,24 @@ struct Fwd {
     if (!out28) return OFFK_OK;
     float* pp = nullptr;     // the 28-head only reads sum_28c: pool-row partial sums + the FC as an MFMA GEMM instead of pool_kernel + fc_kernel
     if (h->fold_pool) {
-      pp = reg("poolpart_28");
+      pp = reg(R_POOLPART_28);
       TRY(trace_mark(h, s, "head_28 (max pool rows)"));
       HIP_TRY(h, maxpool_rows_launch(F14, 1056, 800, n, 14, 14, 256, pp, s));
     }
-    return head(1, l28, pp, 1, F14, 1056, 800, 14, 1, "pooled_28");
+    return head(1, l28, pp, 1, F14, 1056, 800, 14, 1, R_POOLED_28);
   }
 
   // ---- fusion @14 -> 7x7 (RGB_OFF.py:759-780) and the 14-head (:789-793) ----
   int fusion14() {
-    float *xu = reg("xu_14"), *u1 = reg("u1_14"), *s14 = reg("sa_14");                           // xu = [u2 | x1]
+    float *xu = reg(R_XU_14), *u1 = reg(R_U1_14), *s14 = reg(R_SA_14);                           // xu = [u2 | x1]
     TRY(conv_t_c1_c2(C_T14, w5, 14, View{F14, 1056, 0}, C1_14A, C2_14A, xu, 256, u1,                // :762-767
                      "motion_conv_trans_14 out + motion_conv1_trans_14a + motion_conv2_trans_14a in [winograd: between]"));
     TRY(conv_merged(1, 7, View{xu, 256, 0}, RO, s14, 512, 0));                                   // :768-771
     TRY(conv(C1_14B, 7, View{s14, 512, 0}, nullptr, 0, 0, RP, u1, 128, 0));                     // :773-774
     // the 14-head's average pool of sum_14b: per-tile sums from the Winograd output transform (fold14t), or per-slab column sums from
     // the direct conv's epilogue (fold)
-    float* pp14t = fold14t ? reg("poolpart_14t") : nullptr;
-    float* pp14 = !wino && fold ? reg("poolpart_14") : nullptr;
+    float* pp14t = fold14t ? reg(R_POOLPART_14T) : nullptr;
+    float* pp14 = !wino && fold ? reg(R_POOLPART_14) : nullptr;
     if (mid) {            // :775-780: c2_14b's output feeds c3_14b alone -- output transform, ReLU and input transform in one launch
       TRY(wino_in(C2_14B, View{u1, 128, 0}));
       TRY(wino_mm(C2_14B));
@@ -1198,13 +1273,13 @@ struct Fwd {
       TRY(conv(C3_14B, 7, View{xu, 256, 0}, s14, 512, 0, RP | RO, F7, 832, 320, pp14));          // :777-780 -> cat at :832
     }
     if (ev) HIP_TRY(h, hipEventRecord(ev[4], s));
-    return head(2, l14, pp14t ? pp14t : pp14, pp14t ? 1 : 0, F7, 832, 320, 7, 0, "pooled_14");      // only reads sum_14b
+    return head(2, l14, pp14t ? pp14t : pp14, pp14t ? 1 : 0, F7, 832, 320, 7, 0, R_POOLED_14);      // only reads sum_14b
   }
 
   // ---- fusion @7 (RGB_OFF.py:831-841) and the 7-head (:843-847) ----
   int fusion7() {
-    float *xv = reg("xv_7"), *v1 = reg("v1_7"), *s7 = reg("sum_7");                              // xv = [v2 | x2]
-    float* pp7t = pool7 ? reg("poolpart_7t") : nullptr;
+    float *xv = reg(R_XV_7), *v1 = reg(R_V1_7), *s7 = reg(R_SUM_7);                              // xv = [v2 | x2]
+    float* pp7t = pool7 ? reg(R_POOLPART_7T) : nullptr;
     TRY(conv_t_c1_c2(C_T7, wino, 7, View{F7, 832, 0}, C1_7, C2_7, xv, 512, v1,                      // :833-838
                      "motion_conv_trans out + motion_conv1_trans + motion_conv2_trans in [winograd: between]", pp7t));
     if (pool7) {
@@ -1216,13 +1291,13 @@ struct Fwd {
       if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
       return OFFK_OK;
     }
-    float* pp7 = fold ? reg("poolpart_7") : nullptr;      // the 7-head's average pool in the merged conv's epilogue
+    float* pp7 = fold ? reg(R_POOLPART_7) : nullptr;      // the 7-head's average pool in the merged conv's epilogue
     TRY(merged7());
     if (ev) HIP_TRY(h, hipEventRecord(ev[5], s));
-    return head(0, l7, pp7, 0, s7, 1024, 0, 7, 0, "pooled_7");
+    return head(0, l7, pp7, 0, s7, 1024, 0, 7, 0, R_POOLED_7);
   }
   // :839-841 (no ReLU): sum_7 from xv_7, and with `fold` the pooled sums of the 7-head in its epilogue (fusion7; offk_stage_tensors)
-  int merged7() { return conv_merged(2, 7, View{reg("xv_7"), 512, 0}, 0, reg("sum_7"), 1024, 0, fold ? reg("poolpart_7") : nullptr); }
+  int merged7() { return conv_merged(2, 7, View{reg(R_XV_7), 512, 0}, 0, reg(R_SUM_7), 1024, 0, fold ? reg(R_POOLPART_7) : nullptr); }
 
   // ---- the folded-pool FCs of all heads in one launch, segment consensus (Flow_OFF.py:874-876) ----
   int heads() {
@@ -1287,24 +1362,24 @@ int offk_create(const offk_config* cfg, offk_handle** out) {
   DeviceGuard guard(cfg->device);
   int rc = OFFK_OK;
   for (int s = 0; s < kNumSites && rc == OFFK_OK; ++s) {
-    const std::string n = kSites[s].name;
     const int C = kSites[s].C;
-    add_slot(h, "motion_conv_gen_" + n + ".weight", {kGenCh, C, 1, 1}, SK_GEN_W, s);
-    add_slot(h, "motion_conv_gen_" + n + ".bias", {kGenCh}, SK_GEN_B, s);
-    add_slot(h, "motion_spatial_down_" + n + ".weight", {kDownCh, C, 1, 1}, SK_DOWN_W, s);
-    add_slot(h, "motion_spatial_down_" + n + ".bias", {kDownCh}, SK_DOWN_B, s);
+    const bool learned_dw = cfg->variant == OFFK_VARIANT_RGB_LEARNED_DW;
     rc = dev_alloc(h, &h->pw_w[s], (size_t)kUnitCh * C);
     if (rc == OFFK_OK && cfg->precision == OFFK_PRECISION_FP32) rc = dev_alloc(h, &h->pw_wt16[s], (size_t)kUnitCh * C);
     if (rc == OFFK_OK && h->f32split) rc = dev_alloc(h, &h->pw_wt16s[s], (size_t)kUnitCh * C * 3 / 2);
     if (rc == OFFK_OK) rc = dev_alloc(h, &h->pw_b[s], kUnitCh);
-    if (cfg->variant == OFFK_VARIANT_RGB_LEARNED_DW && rc == OFFK_OK) {
-      add_slot(h, "motion_spatial_grad_" + n + ".weight", {kDownCh, 1, 3, 3}, SK_DW_W, s);
-      add_slot(h, "motion_spatial_grad_" + n + ".bias", {kDownCh}, SK_DW_B, s);
-      rc = dev_alloc(h, &h->dw_w[s], 9 * kDownCh);
-      if (rc == OFFK_OK) rc = dev_alloc(h, &h->dw_b[s], kDownCh);
+    if (rc == OFFK_OK && learned_dw) rc = dev_alloc(h, &h->dw_w[s], 9 * kDownCh);
+    if (rc == OFFK_OK && learned_dw) rc = dev_alloc(h, &h->dw_b[s], kDownCh);
+    for (const UnitParamSpec& p : kUnitParams) {
+      if (rc != OFFK_OK || (p.dw && !learned_dw)) continue;
+      UnitParam& u = h->unit[s][p.kind];
+      u.own = (h->*p.buf)[s] + p.buf_row * (unit_count(p, C) / p.shape[0]);
+      u.slot = (int)h->slots.size();
+      add_slot(h, std::string(p.prefix) + kSites[s].name + p.suffix, unit_shape(p, C), p.kind, s);
     }
   }
   if (cfg->variant == OFFK_VARIANT_DIAG_SOBEL && rc == OFFK_OK) {
+    h->sobel_slot = (int)h->slots.size();
     add_slot(h, kSobelKey, {kDownCh, 1, 3, 3}, SK_SOBEL, 0);
     rc = dev_alloc(h, &h->sobel_w, 9 * kDownCh);
   }
@@ -1430,13 +1505,12 @@ int offk_set_weight(offk_handle* h, const char* key, const float* data, const in
   };
   int rc = OFFK_OK;
   const int i = s.idx;
+  UnitParam* unit = s.kind < kNumUnitParams ? &h->unit[i][s.kind] : nullptr;
   switch (s.kind) {
-    case SK_GEN_W: rc = copy(h->pw_w[i]); break;
-    case SK_DOWN_W: rc = copy(h->pw_w[i] + (size_t)kGenCh * kSites[i].C); break;
-    case SK_GEN_B: rc = copy(h->pw_b[i]); break;
-    case SK_DOWN_B: rc = copy(h->pw_b[i] + kGenCh); break;
-    case SK_DW_W: rc = staged([&](const float* t) { return repack_dw_launch(t, h->dw_w[i], nullptr); }); break;
-    case SK_DW_B: rc = copy(h->dw_b[i]); break;
+    case SK_GEN_W: case SK_GEN_B: case SK_DOWN_W: case SK_DOWN_B: case SK_DW_W: case SK_DW_B:
+      if (kUnitParams[s.kind].repack_dw) rc = staged([&](const float* t) { return repack_dw_launch(t, unit->own, nullptr); });
+      else rc = copy(unit->own);
+      break;
     case SK_SOBEL: {
       rc = staged([&](const float* t) { return repack_dw_launch(t, h->sobel_w, nullptr); });
       // frozen parameter (util.py:72), but it travels in checkpoints: take the four-tap path only for weights that
@@ -1462,15 +1536,7 @@ int offk_set_weight(offk_handle* h, const char* key, const float* data, const in
   }
   if (rc == OFFK_OK) {
     s.set = true;
-    switch (s.kind) {       // an explicit copy replaces an earlier in-place binding of the same key
-      case SK_GEN_W: h->bnd_gen_w[i] = nullptr; break;
-      case SK_GEN_B: h->bnd_gen_b[i] = nullptr; break;
-      case SK_DOWN_W: h->bnd_down_w[i] = nullptr; break;
-      case SK_DOWN_B: h->bnd_down_b[i] = nullptr; break;
-      case SK_DW_W: h->bnd_dw_w[i] = nullptr; break;
-      case SK_DW_B: h->bnd_dw_b[i] = nullptr; break;
-      default: break;
-    }
+    if (unit) unit->bound = nullptr;       // an explicit copy replaces an earlier in-place binding of the same key
   }
   if (s.kind == SK_CONV_W || s.kind == SK_CONV_B) h->merged_dirty = true;
   if (s.kind == SK_CONV_W) h->derived_dirty = true;
@@ -1509,18 +1575,10 @@ int offk_bind_weight(offk_handle* h, const char* key, const float* device_data, 
       (void)hipGetLastError();
     }
   }
-  const int i = s.idx;
-  switch (s.kind) {
-    case SK_GEN_W: h->bnd_gen_w[i] = device_data; break;
-    case SK_GEN_B: h->bnd_gen_b[i] = device_data; break;
-    case SK_DOWN_W: h->bnd_down_w[i] = device_data; break;
-    case SK_DOWN_B: h->bnd_down_b[i] = device_data; break;
-    case SK_DW_W: h->bnd_dw_w[i] = device_data; break;
-    case SK_DW_B: h->bnd_dw_b[i] = device_data; break;
-    default:
-      return fail(h, OFFK_ERR_INVALID, "offk_bind_weight: only the OFF units' parameters (motion_conv_gen_*, motion_spatial_down_*, "
-                                       "motion_spatial_grad_*) can be bound in place: " + k);
-  }
+  if (s.kind >= kNumUnitParams)
+    return fail(h, OFFK_ERR_INVALID, "offk_bind_weight: only the OFF units' parameters (motion_conv_gen_*, motion_spatial_down_*, "
+                                     "motion_spatial_grad_*) can be bound in place: " + k);
+  h->unit[s.idx][s.kind].bound = device_data;
   s.set = true;
   return OFFK_OK;
 }
@@ -1540,10 +1598,10 @@ size_t offk_workspace_bytes(const offk_handle* h) { return h ? h->ws_bytes : 0; 
 
 int offk_workspace_region(const offk_handle* h, const char* name, size_t* offset_bytes, size_t* nbytes) {
   if (!h || !name) return OFFK_ERR_INVALID;
-  auto it = h->regions.find(name);
-  if (it == h->regions.end()) { h->err = std::string("unknown workspace region: ") + name; return OFFK_ERR_INVALID; }
-  if (offset_bytes) *offset_bytes = it->second.first;
-  if (nbytes) *nbytes = it->second.second;
+  const Region r = region_by_name(name);
+  if (r == kNumRegions || !h->regions[r].on) { h->err = std::string("unknown workspace region: ") + name; return OFFK_ERR_INVALID; }
+  if (offset_bytes) *offset_bytes = h->regions[r].off;
+  if (nbytes) *nbytes = h->regions[r].bytes;
   return OFFK_OK;
 }
 
@@ -1675,10 +1733,9 @@ static int check_feat(offk_handle* h, const FeatKind& k, int feat_dtype, const o
   if (!k.cl && h->cfg.feat_layout == OFFK_FEAT_NHWC) return fail(h, OFFK_ERR_INVALID, f + maps + "are NCHW-only (this handle is NHWC)");
   if (!h->fused_units)
     return fail(h, OFFK_ERR_INVALID, f + maps + "need the fused units kernel (the handle was created with OFFK_FUSED_UNITS=0)");
-  for (int s = 0; s < kNumSites; ++s)
-    if (h->bnd_gen_w[s] || h->bnd_down_w[s])
-      return fail(h, OFFK_ERR_INVALID, f + maps + "need the library's own unit weights (a gen / down weight is bound through offk_bind_weight: " +
-                                           kSites[s].name + ")");
+  if (const int s = bound_contraction_site(h); s >= 0)
+    return fail(h, OFFK_ERR_INVALID, f + maps + "need the library's own unit weights (a gen / down weight is bound through offk_bind_weight: " +
+                                         kSites[s].name + ")");
   TRY(check_parts(h, parts));
   for (int s = 0; s < kNumSites; ++s)
     for (int q = 0; q < parts[s].n_parts; ++q)
@@ -1791,10 +1848,11 @@ int offk_unit_grad_slot(const offk_handle* h, const char* key, size_t* offset_fl
   if (!h || !key) return OFFK_ERR_INVALID;
   std::string k(key);
   if (k.rfind("module.", 0) == 0) k = k.substr(7);
-  auto it = h->grad_slots.find(k);
-  if (it == h->grad_slots.end()) { h->err = "no unit gradient for key: " + k; return OFFK_ERR_INVALID; }
-  if (offset_floats) *offset_floats = it->second.first;
-  if (count) *count = it->second.second;
+  auto it = h->index.find(k);
+  const Slot* s = it == h->index.end() ? nullptr : &h->slots[it->second];
+  if (!s || s->kind >= kNumUnitParams) { h->err = "no unit gradient for key: " + k; return OFFK_ERR_INVALID; }
+  if (offset_floats) *offset_floats = h->unit[s->idx][s->kind].grad_off;
+  if (count) *count = unit_count(kUnitParams[s->kind], kSites[s->idx].C);
   return OFFK_OK;
 }
 
@@ -1823,7 +1881,7 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
   hipStream_t st = static_cast<hipStream_t>(stream);
   void* ws = workspace;
   const bool learned_dw = h->cfg.variant != OFFK_VARIANT_DIAG_SOBEL;
-  auto reg = [&](const char* prefix, int s) { return region(h, ws, (std::string(prefix) + kSites[s].name).c_str()); };
+  auto reg = [&](Region family, int s) { return region(h, ws, site_region(family, s)); };
 
   // K2b: dM -> dGpre, dD, depthwise partials
   UbParams up;
@@ -1834,12 +1892,12 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
   int nsblocks[kNumSites];
   for (int s = 0; s < kNumSites; ++s) {
     UbSite& u = up.s[s];
-    u.G = reg("G_", s); u.D = reg("D_", s);
-    u.dw = learned_dw ? (h->bnd_dw_w[s] ? h->bnd_dw_w[s] : h->dw_w[s]) : h->sobel_w;
-    u.dw_ref = learned_dw && h->bnd_dw_w[s] != nullptr;
+    u.G = reg(R_G, s); u.D = reg(R_D, s);
+    u.dw = learned_dw ? unit_param(h, s, SK_DW_W).p : h->sobel_w;
+    u.dw_ref = learned_dw && unit_param(h, s, SK_DW_W).bound;
     u.gm = gm[s].data; u.gm_cs = gm[s].cstride; u.gm_coff = gm[s].coff;
-    u.dG = reg("dG_", s); u.dD = reg("dD_", s);
-    u.dw_part = learned_dw ? reg("dwp_", s) : nullptr;
+    u.dG = reg(R_DG, s); u.dD = reg(R_DD, s);
+    u.dw_part = learned_dw ? reg(R_DWP, s) : nullptr;
     u.drop_base = drop_stream_base(drop.seed, s);
     u.H = kSites[s].H;
     ub_plan(u.H, &u.strips, &u.rows);
@@ -1866,20 +1924,17 @@ static int off_units_backward(offk_handle* h, void* stream, const float* const f
   for (int i = 0; i < kNumSites; ++i) {
     const int s = kPwOrder[i];
     WgSite& w = wp.s[i];
-    w.xp[0] = feats[s]; w.cp[0] = kSites[s].C; w.nparts = 1;
-    w.dG = reg("dG_", s); w.dD = reg("dD_", s); w.slab = reg("wgs_", s); w.bpart = reg("wgb_", s);
-    w.C = kSites[s].C; w.HW = kSites[s].H * kSites[s].H;
+    const offk_feat_parts whole = whole_map(s, feats[s]);
+    fill_site_shape(h, s, &whole, &w);
+    w.dG = reg(R_DG, s); w.dD = reg(R_DD, s); w.slab = reg(R_WGS, s); w.bpart = reg(R_WGB, s);
     w.tpf = (w.HW + 31) / 32; w.kt_total = h->N * w.tpf;
     w.ntiles = (w.C + 127) / 128; w.nchunks = (w.kt_total + h->wg_kpb - 1) / h->wg_kpb;
     w.blk_begin = blk;
     blk += w.nchunks * w.ntiles;
     WrSite& r = rp.s[i];
-    r.slab = w.slab; r.bpart = w.bpart; r.dw_part = learned_dw ? reg("dwp_", s) : nullptr;
-    const std::string n = kSites[s].name;
-    auto dst = [&](const std::string& key) { return grads + h->grad_slots[key].first; };
-    r.gen_w = dst("motion_conv_gen_" + n + ".weight"); r.gen_b = dst("motion_conv_gen_" + n + ".bias");
-    r.down_w = dst("motion_spatial_down_" + n + ".weight"); r.down_b = dst("motion_spatial_down_" + n + ".bias");
-    if (learned_dw) { r.dw_w = dst("motion_spatial_grad_" + n + ".weight"); r.dw_b = dst("motion_spatial_grad_" + n + ".bias"); }
+    r.slab = w.slab; r.bpart = w.bpart; r.dw_part = learned_dw ? reg(R_DWP, s) : nullptr;
+    for (const UnitParamSpec& p : kUnitParams)      // (a parameter the variant lacks: nullptr, rp is zeroed)
+      if (h->unit[s][p.kind].slot >= 0) r.*p.grad = grads + h->unit[s][p.kind].grad_off;
     r.C = w.C; r.cpad = w.ntiles * 128; r.nchunks = w.nchunks; r.nsblocks = nsblocks[s];
   }
   wp.total_blocks = blk;
@@ -2008,11 +2063,11 @@ static int off_units_backward_feats_split(offk_handle* h, hipStream_t st, void* 
     DxsSite& d = dp.s[n++];
     const float *b, *bd;
     pw_weight_ptrs(h, s, &d.wg, &d.wd, &b, &bd);
-    d.dG = region(h, workspace, (std::string("dG_") + kSites[s].name).c_str());
-    d.dD = region(h, workspace, (std::string("dD_") + kSites[s].name).c_str());
+    d.dG = region(h, workspace, site_region(R_DG, s));
+    d.dD = region(h, workspace, site_region(R_DD, s));
     d.wimg = h->dx_split_w[s];
     d.out = dfeats[s];
-    d.C = kSites[s].C; d.HW = kSites[s].H * kSites[s].H; d.M = h->N * d.HW;
+    fill_site_shape(h, s, nullptr, &d);
     d.blk_begin = blk; d.pack_begin = pblk;
     blk += (d.M + units_dx_split_rows_per_block() - 1) / units_dx_split_rows_per_block();
     pblk += units_dx_split_pack_blocks(d.C);
@@ -2065,10 +2120,10 @@ static int off_units_backward_feats(offk_handle* h, void* stream, void* workspac
     DxSite& d = dp.s[n++];
     const float *b, *bd;
     pw_weight_ptrs(h, s, &d.wg, &d.wd, &b, &bd);
-    d.dG = region(h, workspace, (std::string("dG_") + kSites[s].name).c_str());
-    d.dD = region(h, workspace, (std::string("dD_") + kSites[s].name).c_str());
+    d.dG = region(h, workspace, site_region(R_DG, s));
+    d.dD = region(h, workspace, site_region(R_DD, s));
     d.out = dfeats[s];
-    d.C = kSites[s].C; d.HW = kSites[s].H * kSites[s].H; d.M = h->N * d.HW;
+    fill_site_shape(h, s, nullptr, &d);
     d.blk_begin = blk;
     blk += (d.M + units_dx_rows_per_block() - 1) / units_dx_rows_per_block();
   }
