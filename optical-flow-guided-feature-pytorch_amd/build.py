@@ -21,7 +21,7 @@ SOURCES = ("offk_api.hip", "pw_reduce.hip", "pw_reduce_f16.hip", "pw_reduce_cl.h
 # sources that #include another source: {source: (what it includes, ...)}
 INCLUDED_SOURCES = {"pw_reduce_f16.hip": ("pw_reduce.hip",), "pw_reduce_cl.hip": ("pw_reduce.hip",), "units_bwd_cl.hip": ("units_bwd.hip",),
                     "units_dx_f16.hip": ("units_dx.hip",)}
-HEADERS = ("offk_common.h", "offk_internal.h", "pw_tdiff_staged.h", "winograd_common.h", "conv_dgrad_split_common.h", "split_common.h", os.path.join("..", "..", "include", "offk.h"))
+HEADERS = ("offk_common.h", "offk_internal.h", "units_common.h", "pw_tdiff_staged.h", "winograd_common.h", "conv_dgrad_split_common.h", "split_common.h", os.path.join("..", "..", "include", "offk.h"))
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=fast"]
 # heads.hip: no SLP vectoriser.  It pairs the FC accumulators of neighbouring classes into v_pk_fma_f32 with

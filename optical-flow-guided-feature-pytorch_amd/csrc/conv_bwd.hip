@@ -15,6 +15,7 @@
 //   The next K-tile's rows are loaded into registers before the MFMAs of the current one and stored to LDS behind them.
 // The partial tiles go to slab [chunk][Co][Ci * k * k] (the layout of dw itself) and the column sums of g to [chunk][Co] behind the
 // slabs; conv_wgrad_reduce_kernel adds the slabs in chunk order -- the split-K rule of the library: the same bits on every run.
+#include "offk_common.h"
 #include "offk_internal.h"
 
 namespace offk {
@@ -39,11 +40,6 @@ struct WgradArgs {
   float* dbslab;                   // [chunks][Co]
   float* dw; float* db; int accumulate;
 };
-
-__device__ __forceinline__ float4 relu4(float4 v) {
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  return v;
-}
 
 // pixel row index of padded position q (>= 0 and < n_img * PP is the caller's business), or -1 on the zero ring
 template <int KS>

@@ -21,6 +21,7 @@
 //   instead costs 16 / 14 (7x7) or 8 / 7 (5x5) of the MFMAs; measured, profiles/fusion_bwd/README.md.
 //   A last ci tile of 32 loads zeros for its upper half and does not store it.
 //   Slabs [chunk][Co][Ci * k * k] + [chunk][Co] and the reduce in chunk order are conv_bwd.hip's.
+#include "offk_common.h"
 #include "offk_internal.h"
 
 namespace offk {
@@ -34,11 +35,6 @@ constexpr int kLd = 80;           // LDS stride of a [k][64 channels] row: rows 
 constexpr int kLdG = 36;          // LDS stride of a [pixel][32 co] row of the data gradient: 16-byte aligned rows
 constexpr int kS2Slots = 512;     // weight gradient: two blocks of four waves per CU on 256 CUs
 constexpr int kS2MinPositions = 256;
-
-__device__ __forceinline__ float4 relu4(float4 v) {
-  v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-  return v;
-}
 
 // ---------------------------------------------------------------- data gradient ----------------------------------------------------------------
 struct S2DgradArgs {

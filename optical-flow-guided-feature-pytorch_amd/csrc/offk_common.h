@@ -87,6 +87,13 @@ __device__ __forceinline__ int xcd_contiguous(int j, int n) {
   return (c < r ? c * (q + 1) : r * (q + 1) + (c - r) * q) + idx;
 }
 
+// The coarse form, for a whole grid of `total` blocks (the two units weight gradients): hardware blocks c, c + 8, c + 16 ... (one XCD)
+// take the logical blocks c * (total / 8) ..., consecutive ones, which share an operand; the total % 8 blocks at the end keep their ids.
+__device__ __forceinline__ unsigned xcd_strided(unsigned bid, unsigned total) {
+  const unsigned t8 = total & ~7u;
+  return bid < t8 ? (bid & 7u) * (t8 >> 3) + (bid >> 3) : bid;
+}
+
 // row (M index) of accumulator register `reg` for a lane in half `h` (lane>>5)
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 

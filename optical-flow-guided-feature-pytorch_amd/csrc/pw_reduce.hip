@@ -21,8 +21,7 @@
 // because the 16-bit instantiations in the same code object changed the register allocation of the fp32 ones.
 #include <cstdlib>
 
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 
 namespace offk {
 
@@ -68,20 +67,6 @@ __device__ __forceinline__ void stf(float* q, float v) {
   else *q = v;
 }
 
-// 16-bit feature maps (FEAT = kFeatBf16 / kFeatF16): an element widened to the exact fp32 value it stands for.
-// bf16 is the upper half of an fp32 word; fp16 goes through the hardware conversion, which keeps subnormals.
-template <int FEAT>
-__device__ __forceinline__ float widen16(unsigned h) {   // h: the element in the low 16 bits, upper bits zero
-  if (FEAT == kFeatBf16) return __uint_as_float(h << 16);
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
-}
-template <int FEAT>
-__device__ __forceinline__ float4 widen16x4(unsigned lo, unsigned hi) {   // four consecutive elements in two words
-  if (FEAT == kFeatBf16)
-    return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u));
-  return make_float4(widen16<FEAT>(lo & 0xffffu), widen16<FEAT>(lo >> 16), widen16<FEAT>(hi & 0xffffu), widen16<FEAT>(hi >> 16));
-}
-
 // LEAN: buffer-descriptor addressing of the weights and of the NCHW quad loader (mode 0), unconditional prefetch pinned
 // in front of the MFMAs -- as pw_tdiff.hip; needs every feature-map part and the weight tables below 2^31 bytes.
 // FEAT: element type of the feature map (enum offk_feat_dtype), for 16-bit maps | kFeatCl where they are channels-last (fp32
@@ -103,9 +88,9 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   float* As = reinterpret_cast<float*>(lds);                    // fp32: [128][LDS_K] then [160][LDS_K]
   float* Bs = As + PW_BM * LDS_K;
 
-  // block -> site: field-wise scalar select chain over the (few) table entries; indexing
-  // the by-value kernarg array with a runtime index (or copying a whole entry) goes
-  // through scratch memory
+  // block -> site: field-wise scalar select chain over the (few) table entries; indexing the by-value kernarg array with a runtime
+  // index goes through scratch memory.  This kernel keeps its own list of members: with the whole entry copied (OFFK_PICK_SITE) the
+  // LEAN form spills 89 scalar registers instead of 33 and the pointer form takes two more vector registers.
   PwSite S;
   int nblk_site;
 #define OFFK_PW_PICK(i)                                                                              \
@@ -158,16 +143,9 @@ __global__ __launch_bounds__(256, 2) void pw_reduce_kernel(PwParams p) {
   const int koff = mode == 0 ? 4 * (tid & 7) : (mode == 1 ? 4 * (tid >> 7) : 4 * (tid & 7));
   // channel k0 (a multiple of 32) -> (part, channel within the part); parts are whole multiples of 32
   // channels, so a K-tile never straddles two of them.  Uniform across the block: scalar selects.
-  auto locate = [&](int k0, const float*& xb, int& cpart, int& kl) {
-    xb = S.xp[0]; cpart = S.cp[0]; kl = k0;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
-  };
+
+  // (through a lambda: with part_at called where the loaders stand, the 16-bit and NCHW forms come out one s_nop shorter)
+  auto locate = [&](int k0, const float*& xb, int& cpart, int& kl) { part_at(S, k0, xb, cpart, kl); };
 
   float4 rg[4 + PW_TN];   // prefetch registers: 4 x A, then 5 x B (one array: two arrays end up in scratch)
   // weight rows (tid>>3) + 32 r: r = 0..3 gen rows, r = 4 the down rows (their own pointer: bound parameters need not be adjacent)

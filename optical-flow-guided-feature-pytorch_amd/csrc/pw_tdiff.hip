@@ -21,8 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 
 namespace offk {
 
@@ -50,6 +49,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_kernel(PtParams p) {
   float* As = reinterpret_cast<float*>(lds);                    // fp32: [224][LDS_K] then [160][LDS_K]
   float* Bs = As + PT_BM * LDS_K;
 
+  // (its own list of members, as pw_reduce_kernel: with the whole entry copied (OFFK_PICK_SITE) both forms change their branches and waits)
   PtSite S;
   int nblk_site;
 #define OFFK_PT_PICK(i)                                                                                \
@@ -88,16 +88,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_kernel(PtParams p) {
   const int sh = !LEAN && k0px < HW ? k0px - kkpx : 0;           // and shifted into place (HW % 4 != 0 only)
   const bool px_ok = k0px < HW && b + cq < p.B;
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-  auto locate = [&](int k0, const float*& xb, int& cpart, int& kl) {
-    xb = S.xp[0]; cpart = S.cp[0]; kl = k0;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
-  };
+  auto locate = [&](int k0, const float*& xb, int& cpart, int& kl) { part_at(S, k0, xb, cpart, kl); };
   constexpr int NRG = 8 + 5;          // A: frame fs (4 k-rows), frame fs+4 (4 k-rows); B: 5 weight rows
   float4 rg[NRG];
   const float* wbase = S.w + (size_t)(tid >> 3) * C + 4 * (tid & 7);
@@ -344,11 +335,7 @@ __global__ __launch_bounds__(256, 4) void pw_tdiff16_kernel(PtParams p) {
 
   // the block's site: nine compares on blk_begin, then ONE site's fields (the unrolled pick-by-copy of the other kernels loads
   // every field of all nine sites first: ~7 k of this kernel's 18 k prologue cycles, and a block is only ~200 k cycles long)
-  int si = 0;
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)blockIdx.x >= p.s[i].blk_begin) si = i;
-  si = __builtin_amdgcn_readfirstlane(si);
+  OFFK_SITE_INDEX(si, p, (int)blockIdx.x)
   const PtSite& S0 = p.s[si];
   PtSite S;
   S.bias = S0.bias; S.D = S0.D; S.M = S0.M; S.m_cs = S0.m_cs; S.bias_down = S0.bias_down; S.wt = S0.wt16;
@@ -356,7 +343,7 @@ __global__ __launch_bounds__(256, 4) void pw_tdiff16_kernel(PtParams p) {
   S.blk_begin = S0.blk_begin; S.nparts = S0.nparts; S.qpc = S0.qpc;
 #pragma unroll
   for (int q = 0; q < 4; ++q) { S.xp[q] = S0.xp[q]; S.cp[q] = S0.cp[q]; }
-  const int nblk_site = (si + 1 < p.nsites ? p.s[si + 1].blk_begin : p.total_blocks) - S.blk_begin;
+  const int nblk_site = OFFK_SITE_BLOCKS(p, si, S);
   const int C = S.C, HW = S.HW, L = p.L;
   int local = xcd_contiguous((int)blockIdx.x - S.blk_begin, nblk_site);
   const int tg = local % p.tgroups; local /= p.tgroups;
@@ -396,6 +383,7 @@ __global__ __launch_bounds__(256, 4) void pw_tdiff16_kernel(PtParams p) {
   i32x4 dm_desc = {0, 0, 0, 0};
   int dm_fstride = 0, dm_s0 = 0, dm_voff = 0;
   auto dma_prep = [&](int kt) {
+    // (this kernel's own walk: its waits are hand-counted, and through part_at three of its scalar compares change form)
     const float* xb = S.xp[0]; int cpart = S.cp[0], kl = kt * BK;
     if (S.nparts > 1 && kl >= S.cp[0]) {
       kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];

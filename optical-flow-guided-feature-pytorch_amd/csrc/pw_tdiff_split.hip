@@ -31,8 +31,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 #include "split_common.h"
 
 namespace offk {
@@ -57,11 +56,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
   char* const planes = lds + 2 * PS_RAW_STAGE;
 
   // ---- the block's site and its (clip, pixels, temporal group): as pw_tdiff16_kernel ----
-  int si = 0;
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)blockIdx.x >= p.s[i].blk_begin) si = i;
-  si = __builtin_amdgcn_readfirstlane(si);
+  OFFK_SITE_INDEX(si, p, (int)blockIdx.x)
   const PtSite& S0 = p.s[si];
   PtSite S;
   S.bias = S0.bias; S.D = S0.D; S.M = S0.M; S.m_cs = S0.m_cs; S.bias_down = S0.bias_down; S.wt = static_cast<const float*>(S0.wt16s);
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
   S.blk_begin = S0.blk_begin; S.nparts = S0.nparts; S.qpc = S0.qpc;
 #pragma unroll
   for (int q = 0; q < 4; ++q) { S.xp[q] = S0.xp[q]; S.cp[q] = S0.cp[q]; }
-  const int nblk_site = (si + 1 < p.nsites ? p.s[si + 1].blk_begin : p.total_blocks) - S.blk_begin;
+  const int nblk_site = OFFK_SITE_BLOCKS(p, si, S);
   const int C = S.C, HW = S.HW, L = p.L;
   int local = xcd_contiguous((int)blockIdx.x - S.blk_begin, nblk_site);
   const int tg = local % p.tgroups; local /= p.tgroups;
@@ -101,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void pw_tdiff_split_kernel(PtParams p) {
   i32x4 dm_desc = {0, 0, 0, 0};
   int dm_fstride = 0, dm_s0 = 0, dm_voff = 0;
   auto dma_prep = [&](int kt) {
+    // (this kernel's own walk, as pw_tdiff16_kernel's: its waits are hand-counted, and through part_at its scalar moves change order)
     const float* xb = S.xp[0]; int cpart = S.cp[0], kl = kt * BK;
     if (S.nparts > 1 && kl >= S.cp[0]) {
       kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];

@@ -28,8 +28,7 @@
 // its gen and down MFMAs), one barrier per K-tile.
 // LDS: 2 x (30 KB + 7 x 2 x NPL KB) = 88 | 116 | 144 KB: one block (eight waves) per CU.  Compiler-scheduled: no counted waits.
 #pragma once
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 #include "split_common.h"
 
 namespace offk {
@@ -76,7 +75,7 @@ __device__ __forceinline__ void cut2(const unsigned (&v)[8], spu4& ph, spu4& pm)
   unsigned h[8], m[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float x = (float)__builtin_bit_cast(_Float16, (unsigned short)v[e]);
+    const float x = widen16<kFeatF16>(v[e] & 0xffffu);
     h[e] = __float_as_uint(x) & 0xffff0000u;
     m[e] = __float_as_uint(x - __uint_as_float(h[e])) & 0xffff0000u;
   }
@@ -84,18 +83,8 @@ __device__ __forceinline__ void cut2(const unsigned (&v)[8], spu4& ph, spu4& pm)
 }
 
 // the part (channel group) of the site's map that holds K-tile kt: its base, its channels, the K-tile's first channel in it (scalar)
-struct PartK { const float* xb; int cpart, kl; };
-__device__ __forceinline__ PartK part_of_ktile(const PtSite& S, int kt) {
-  PartK k{S.xp[0], S.cp[0], kt * BK};
-  if (S.nparts > 1 && k.kl >= S.cp[0]) {
-    k.kl -= S.cp[0]; k.xb = S.xp[1]; k.cpart = S.cp[1];
-    if (S.nparts > 2 && k.kl >= S.cp[1]) {
-      k.kl -= S.cp[1]; k.xb = S.xp[2]; k.cpart = S.cp[2];
-      if (S.nparts > 3 && k.kl >= S.cp[2]) { k.kl -= S.cp[2]; k.xb = S.xp[3]; k.cpart = S.cp[3]; }
-    }
-  }
-  return k;
-}
+using PartK = Part;
+__device__ __forceinline__ PartK part_of_ktile(const PtSite& S, int kt) { return part_at(S, kt * BK); }
 
 // One block of a staged units kernel.  Loader:
 //   Loader(S, geom)       sets up the thread's items of a K-tile's maps
@@ -107,13 +96,9 @@ __device__ __forceinline__ void units_block(const PtParams& p) {
   using L_ = Lds<NPL>;
   extern __shared__ __attribute__((aligned(16))) char lds[];        // [stage 2] { weight image 30 KB | maps [frame][tile][plane] }
 
-  int si = 0;
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)blockIdx.x >= p.s[i].blk_begin) si = i;
-  si = __builtin_amdgcn_readfirstlane(si);
+  OFFK_SITE_INDEX(si, p, (int)blockIdx.x)
   const PtSite& S = p.s[si];
-  const int nblk_site = (si + 1 < p.nsites ? p.s[si + 1].blk_begin : p.total_blocks) - S.blk_begin;
+  const int nblk_site = OFFK_SITE_BLOCKS(p, si, S);
   const int C = S.C, HW = S.HW, L = p.L;
   int local = xcd_contiguous((int)blockIdx.x - S.blk_begin, nblk_site);
   const int tg = local % p.tgroups;

@@ -32,8 +32,7 @@
 // Algorithmic HBM bytes per (clip, site): H*H*4*(128*L + 192*(L-1))  (SURVEY.md 8d).
 #include <cstdlib>
 
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 
 namespace offk {
 
@@ -122,19 +121,8 @@ __global__ __launch_bounds__(ST_THREADS, 7) void sobel_tdiff_kernel(StParams p) 
   const bool is_t = t_after > t_before;
   const int ridx = is_t ? (int)t_before : (int)(bid - t_before);
 
-  // ---- role index -> site: field-wise scalar select chain (see pw_reduce.hip) ----
-  StSite S;
-#define OFFK_ST_PICK(i)                                                                                         \
-  S.G = p.s[i].G; S.D = p.s[i].D; S.dw = p.s[i].dw; S.db = p.s[i].db; S.Ms = p.s[i].Ms; S.Mt = p.s[i].Mt;       \
-  S.dw_ref = p.s[i].dw_ref;                                                                                     \
-  S.H = p.s[i].H; S.s_cs = p.s[i].s_cs; S.s_coff = p.s[i].s_coff; S.t_cs = p.s[i].t_cs; S.t_coff = p.s[i].t_coff; \
-  S.strips = p.s[i].strips; S.rows = p.s[i].rows; S.s_begin = p.s[i].s_begin; S.t_begin = p.s[i].t_begin;       \
-  S.tchunks = p.s[i].tchunks; S.drop_base = p.s[i].drop_base; S.wrecip = p.s[i].wrecip; S.twrecip = p.s[i].twrecip;
-  OFFK_ST_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && ridx >= (is_t ? p.s[i].t_begin : p.s[i].s_begin)) { OFFK_ST_PICK(i) }
-#undef OFFK_ST_PICK
+  // ---- role index -> site ----
+  OFFK_PICK_SITE(S, p, ridx >= (is_t ? p.s[i].t_begin : p.s[i].s_begin))
   const int H = S.H, W = S.H, HW = H * H;
   const int L = p.L, T = L - 1;
   const int tid = threadIdx.x;

@@ -17,8 +17,7 @@
 //
 // This file is compiled twice: as it is, and through units_bwd_cl.hip with OFFK_UNITS_BWD_CL defined (the channels-last X loader
 // forms of pw_wgrad_kernel and pw_wgrad_cl_launch alone), so that the forms of this object keep the code they have.
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 
 namespace offk {
 
@@ -74,18 +73,7 @@ __global__ __launch_bounds__(UB_THREADS, 2) void units_bwd_kernel(UbParams p) { 
   const bool is_t = t_after > t_before;
   const int ridx = is_t ? (int)t_before : (int)(bid - t_before);
 
-  UbSite S;
-#define OFFK_UB_PICK(i)                                                                                        \
-  S.G = p.s[i].G; S.D = p.s[i].D; S.dw = p.s[i].dw; S.gm = p.s[i].gm; S.gm_cs = p.s[i].gm_cs;                    \
-  S.dw_ref = p.s[i].dw_ref;                                                                                      \
-  S.gm_coff = p.s[i].gm_coff; S.dG = p.s[i].dG; S.dD = p.s[i].dD; S.dw_part = p.s[i].dw_part;                    \
-  S.drop_base = p.s[i].drop_base; S.H = p.s[i].H; S.strips = p.s[i].strips; S.rows = p.s[i].rows;                \
-  S.tchunks = p.s[i].tchunks; S.s_begin = p.s[i].s_begin; S.t_begin = p.s[i].t_begin;
-  OFFK_UB_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && ridx >= (is_t ? p.s[i].t_begin : p.s[i].s_begin)) { OFFK_UB_PICK(i) }
-#undef OFFK_UB_PICK
+  OFFK_PICK_SITE(S, p, ridx >= (is_t ? p.s[i].t_begin : p.s[i].s_begin))
   const int H = S.H, W = S.H, HW = H * H;
   const int L = p.L, T = L - 1;
   const int tid = threadIdx.x;
@@ -290,23 +278,8 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
 
   // XCD-aware order: consecutive logical blocks (the channel slabs of one K-chunk, which share the A operand)
   // land on the same XCD / L2
-  unsigned bid = blockIdx.x;
-  {
-    const unsigned t8 = (unsigned)p.total_blocks & ~7u;
-    if (bid < t8) bid = (bid & 7u) * (t8 >> 3) + (bid >> 3);
-  }
-  WgSite S;
-#define OFFK_WG_PICK(i)                                                                                   \
-  S.dG = p.s[i].dG; S.dD = p.s[i].dD; S.slab = p.s[i].slab; S.bpart = p.s[i].bpart; S.C = p.s[i].C;         \
-  S.HW = p.s[i].HW; S.tpf = p.s[i].tpf; S.kt_total = p.s[i].kt_total; S.ntiles = p.s[i].ntiles;              \
-  S.blk_begin = p.s[i].blk_begin; S.nparts = p.s[i].nparts;                                                 \
-  S.xp[0] = p.s[i].xp[0]; S.xp[1] = p.s[i].xp[1]; S.xp[2] = p.s[i].xp[2]; S.xp[3] = p.s[i].xp[3];           \
-  S.cp[0] = p.s[i].cp[0]; S.cp[1] = p.s[i].cp[1]; S.cp[2] = p.s[i].cp[2]; S.cp[3] = p.s[i].cp[3];
-  OFFK_WG_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)bid >= p.s[i].blk_begin) { OFFK_WG_PICK(i) }
-#undef OFFK_WG_PICK
+  const unsigned bid = xcd_strided(blockIdx.x, (unsigned)p.total_blocks);
+  OFFK_PICK_SITE(S, p, (int)bid >= p.s[i].blk_begin)
   const int C = S.C, HW = S.HW;
   const int local = (int)bid - S.blk_begin;
   const int chunk = local / S.ntiles, nt = local - chunk * S.ntiles;
@@ -322,14 +295,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int cb = nt * WG_BN + 32 * r;
-    const float* xb = S.xp[0]; int cpart = S.cp[0], kl = cb;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
+    const auto [xb, cpart, kl] = part_at(S, cb);
     xok[r] = cb < C;
     xrow[r] = FEAT == kFeatF32 ? xb + (size_t)kl * HW     // (16-bit maps: the same element offset in 2-byte units)
                                : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + (size_t)kl * HW);
@@ -341,14 +307,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
   int xcs = 0;
   if constexpr (CL) {
     const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const float* xb = S.xp[0]; int cpart = S.cp[0], kl = nt * WG_BN + 32 * wv;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
+    const auto [xb, cpart, kl] = part_at(S, nt * WG_BN + 32 * wv);
     xcl = FT == kFeatF32 ? xb + kl : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + kl);
     xcs = cpart;
   }
@@ -445,10 +404,6 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       }
     }
   };
-  auto widen = [](unsigned h) {   // one 16-bit element (upper bits zero) -> the fp32 value it stands for
-    if (FT == kFeatBf16) return __uint_as_float(h << 16);
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);   // hardware conversion: keeps subnormals
-  };
   auto store_tile = [&](auto VT) {
     if constexpr (CL) {
       // pixel j's four channels -> channel i's four pixels, straight into LDS as for dG below (the prefetch registers are left as
@@ -458,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       for (int j = 0; j < 4; ++j) {
         if constexpr (FT != kFeatF32) {
           const unsigned a = (unsigned)rx[j], b = (unsigned)(rx[j] >> 32);
-          x[j] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+          x[j] = widen16x4<FT>(a, b);
         } else {
           x[j] = rg[5 + j];
           // (pins the quad here: without it hipcc gathers the transposed register quads right behind the loads, in front of the MFMAs)
@@ -475,10 +430,10 @@ __global__ __launch_bounds__(256, 2) void pw_wgrad_kernel(WgParams p) {
       for (int r = 0; r < 4; ++r) {
         if constexpr (decltype(VT)::value == 1) {
           const unsigned a = (unsigned)rx[r], b = (unsigned)(rx[r] >> 32);
-          rg[5 + r] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+          rg[5 + r] = widen16x4<FT>(a, b);
         } else {
-          rg[5 + r] = make_float4(widen(__float_as_uint(rg[5 + r].x)), widen(__float_as_uint(rg[5 + r].y)),
-                                  widen(__float_as_uint(rg[5 + r].z)), widen(__float_as_uint(rg[5 + r].w)));
+          rg[5 + r] = make_float4(widen16<FT>(__float_as_uint(rg[5 + r].x)), widen16<FT>(__float_as_uint(rg[5 + r].y)),
+                                  widen16<FT>(__float_as_uint(rg[5 + r].z)), widen16<FT>(__float_as_uint(rg[5 + r].w)));
         }
       }
     } else {
@@ -606,16 +561,7 @@ hipError_t pw_wgrad_launch(const WgParams& p, hipStream_t st) {
 // reductions into the caller's gradient buffer (reference parameter layouts), fixed summation order
 // =====================================================================================================
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WrParams p) {
-  WrSite S;
-#define OFFK_WR_PICK(i)                                                                                        \
-  S.slab = p.s[i].slab; S.bpart = p.s[i].bpart; S.dw_part = p.s[i].dw_part; S.gen_w = p.s[i].gen_w;              \
-  S.gen_b = p.s[i].gen_b; S.down_w = p.s[i].down_w; S.down_b = p.s[i].down_b; S.dw_w = p.s[i].dw_w;              \
-  S.dw_b = p.s[i].dw_b; S.C = p.s[i].C; S.cpad = p.s[i].cpad; S.nchunks = p.s[i].nchunks; S.nsblocks = p.s[i].nsblocks;
-  OFFK_WR_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)blockIdx.y == i) { OFFK_WR_PICK(i) }
-#undef OFFK_WR_PICK
+  OFFK_PICK_SITE(S, p, (int)blockIdx.y == i)
   const int tid = threadIdx.x;
   const int C = S.C;
   const int nq = kUnitCh * (C >> 2);              // float4 outputs of the two weight matrices

@@ -30,8 +30,7 @@
 //
 // This file is compiled twice: as it is (the two fp32 kernels and units_dx_launch), and through units_dx_f16.hip with
 // OFFK_UNITS_DX_F16 defined (the four 16-bit kernels and units_dx16_launch alone), so that the fp32 kernels keep the code they have.
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 
 namespace offk {
 namespace {
@@ -63,11 +62,6 @@ __device__ __forceinline__ unsigned short dx_round16(float v) {
   if constexpr (OUT == kFeatBf16) return (unsigned short)(dx_pack16<OUT>(v, 0.f) & 0xFFFFu);
   else return __builtin_bit_cast(unsigned short, (_Float16)v);
 }
-template <int OUT>
-__device__ __forceinline__ float dx_widen16(unsigned short b) {
-  if constexpr (OUT == kFeatBf16) return __builtin_bit_cast(float, (unsigned)b << 16);
-  else return (float)__builtin_bit_cast(_Float16, b);
-}
 
 }  // namespace
 
@@ -86,15 +80,7 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx16_kernel(DxParams p) {
   float* Ts = Bs + kUnitCh * DX_BN;              // [4 waves][32][DX_TS]
 
   const int bid = (int)blockIdx.x;
-  DxSite S;
-#define OFFK_DX_PICK(i)                                                                                      \
-  S.dG = p.s[i].dG; S.dD = p.s[i].dD; S.wg = p.s[i].wg; S.wd = p.s[i].wd; S.out = p.s[i].out; S.C = p.s[i].C; \
-  S.HW = p.s[i].HW; S.M = p.s[i].M; S.blk_begin = p.s[i].blk_begin;
-  OFFK_DX_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && bid >= p.s[i].blk_begin) { OFFK_DX_PICK(i) }
-#undef OFFK_DX_PICK
+  OFFK_PICK_SITE(S, p, bid >= p.s[i].blk_begin)
   const int C = S.C, HW = S.HW, M = S.M;
   const int row0 = (bid - S.blk_begin) * DX_BM;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -205,8 +191,8 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx16_kernel(DxParams p) {
             unsigned* o = reinterpret_cast<unsigned*>(o16 + (size_t)row * C + cbase + (r32 & ~1));
             if (p.accumulate) {
               const unsigned old = *o;
-              lo += dx_widen16<OUT>((unsigned short)(old & 0xFFFFu));
-              hi += dx_widen16<OUT>((unsigned short)(old >> 16));
+              lo += widen16<OUT>((unsigned short)(old & 0xFFFFu));
+              hi += widen16<OUT>((unsigned short)(old >> 16));
             }
             *o = dx_pack16<OUT>(lo, hi);
           }
@@ -238,7 +224,7 @@ __global__ __launch_bounds__(DX_THREADS, 1) void units_dx16_kernel(DxParams p) {
           for (int ch = 0; ch < 32; ++ch) {
             const float v = T[ch * DX_TS + lane];
             unsigned short* oc = o + (size_t)ch * HW;
-            *oc = dx_round16<OUT>(p.accumulate ? dx_widen16<OUT>(*oc) + v : v);
+            *oc = dx_round16<OUT>(p.accumulate ? widen16<OUT>(*oc) + v : v);
           }
         }
       }

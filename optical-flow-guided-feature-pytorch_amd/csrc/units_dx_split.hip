@@ -27,8 +27,7 @@
 // six output forms share everything up to the accumulators; the epilogues are units_dx.hip's contracts: fp32 stores the sum, a 16-bit form
 // rounds each finished fp32 sum ONCE to nearest-even (v_cvt_pk_bf16_f32 / v_cvt_f16_f32), accumulate stores old + new, respectively
 // rne16(widen(old) + new).
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 #include "split_common.h"
 
 namespace offk {
@@ -59,11 +58,6 @@ template <int OUT>
 __device__ __forceinline__ unsigned short xs_round16(float v) {
   if constexpr (OUT == kFeatBf16) return (unsigned short)(xs_pack16<OUT>(v, 0.f) & 0xFFFFu);
   else return __builtin_bit_cast(unsigned short, (_Float16)v);
-}
-template <int OUT>
-__device__ __forceinline__ float xs_widen16(unsigned short b) {
-  if constexpr (OUT == kFeatBf16) return __builtin_bit_cast(float, (unsigned)b << 16);
-  else return (float)__builtin_bit_cast(_Float16, b);
 }
 
 }  // namespace
@@ -100,15 +94,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
   float* const Ts = reinterpret_cast<float*>(xs_lds + XS_A_BYTES);  // NCHW: [4 waves][32][XS_TS]
 
   const int bid = (int)blockIdx.x;
-  DxsSite S;
-#define OFFK_XS_PICK(i)                                                                                          \
-  S.dG = p.s[i].dG; S.dD = p.s[i].dD; S.wimg = p.s[i].wimg; S.out = p.s[i].out; S.C = p.s[i].C; S.HW = p.s[i].HW; \
-  S.M = p.s[i].M; S.blk_begin = p.s[i].blk_begin;
-  OFFK_XS_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && bid >= p.s[i].blk_begin) { OFFK_XS_PICK(i) }
-#undef OFFK_XS_PICK
+  OFFK_PICK_SITE(S, p, bid >= p.s[i].blk_begin)
   const int C = S.C, HW = S.HW, M = S.M;
   const int row0 = (bid - S.blk_begin) * XS_BM;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -241,10 +227,10 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
               spu2* o = reinterpret_cast<spu2*>(static_cast<unsigned short*>(S.out) + at);
               if (p.accumulate) {
                 const spu2 old = *o;
-                v[0] += xs_widen16<OUT>((unsigned short)(old[0] & 0xFFFFu));
-                v[1] += xs_widen16<OUT>((unsigned short)(old[0] >> 16));
-                v[2] += xs_widen16<OUT>((unsigned short)(old[1] & 0xFFFFu));
-                v[3] += xs_widen16<OUT>((unsigned short)(old[1] >> 16));
+                v[0] += widen16<OUT>((unsigned short)(old[0] & 0xFFFFu));
+                v[1] += widen16<OUT>((unsigned short)(old[0] >> 16));
+                v[2] += widen16<OUT>((unsigned short)(old[1] & 0xFFFFu));
+                v[3] += widen16<OUT>((unsigned short)(old[1] >> 16));
               }
               *o = spu2{xs_pack16<OUT>(v[0], v[1]), xs_pack16<OUT>(v[2], v[3])};
             }
@@ -281,7 +267,7 @@ __global__ __launch_bounds__(XS_THREADS, 1) void units_dx_split_kernel(DxsParams
           for (int ch = 0; ch < 32; ++ch) {
             const float v = T[ch * XS_TS + lane];
             unsigned short* oc = o + (size_t)ch * HW;
-            *oc = xs_round16<OUT>(p.accumulate ? xs_widen16<OUT>(*oc) + v : v);
+            *oc = xs_round16<OUT>(p.accumulate ? widen16<OUT>(*oc) + v : v);
           }
         }
       }

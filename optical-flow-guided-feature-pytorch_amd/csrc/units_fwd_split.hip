@@ -23,8 +23,7 @@
 // the other buffer behind them with no wait of its own; ONE barrier per step.  (With the loads of step kt + 1 issued in the same step and
 // waited for in front of the cut the train forward was 0.03 - 0.18 ms slower)  build.py refuses a form of this kernel
 // that spills or keeps anything in scratch memory (REGISTER_RESIDENT_KERNELS).
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 #include "split_common.h"
 
 namespace offk {
@@ -75,19 +74,16 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];   // two such buffers
 
   // block -> site: a uniform index into the by-value table, as pw_tdiff_split_kernel (the field-wise select chain of K1 over nine
-  // entries of this size left scalar registers spilt)
-  int si = 0;
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)blockIdx.x >= p.s[i].blk_begin) si = i;
-  si = __builtin_amdgcn_readfirstlane(si);
+  // entries of this size left scalar registers spilt); then the members this kernel reads, one by one (`S = p.s[si]` copies the whole
+  // entry through vector registers: 60 fewer v_mov, other branches -- not the parent's code)
+  OFFK_SITE_INDEX(si, p, (int)blockIdx.x)
   const UfsSite& S0 = p.s[si];
   UfsSite S;
   S.wimg = S0.wimg; S.bias = S0.bias; S.bias_down = S0.bias_down; S.G = S0.G; S.D = S0.D;
   S.C = S0.C; S.HW = S0.HW; S.M = S0.M; S.blk_begin = S0.blk_begin; S.nparts = S0.nparts;
 #pragma unroll
   for (int q = 0; q < 4; ++q) { S.xp[q] = S0.xp[q]; S.cp[q] = S0.cp[q]; }
-  const int nblk_site = (si + 1 < p.nsites ? p.s[si + 1].blk_begin : p.total_blocks) - S.blk_begin;
+  const int nblk_site = OFFK_SITE_BLOCKS(p, si, S);
   const int C = S.C, HW = S.HW, M = S.M;
   const int m0 = xcd_contiguous((int)blockIdx.x - S.blk_begin, nblk_site) * FS_BM;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -117,16 +113,6 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
     fr = mm / HW; pix = mm - fr * HW;
   }
   const int koff = mode == 1 ? 4 * (lt >> 7) : 4 * (lt & 7);
-  auto locate = [&](int k0, const float*& xb, int& cpart, int& kl) {
-    xb = S.xp[0]; cpart = S.cp[0]; kl = k0;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
-  };
 
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   typedef unsigned u2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
     constexpr int MODE = decltype(MT)::value;
     if (!xl) return;
     const float* xb; int cpart, kl;
-    locate(k0, xb, cpart, kl);
+    part_at(S, k0, xb, cpart, kl);
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (FT == kFeatF32) {
       if constexpr (MODE == 0) {
@@ -204,14 +190,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
       rg[j] = rgN[j]; wr[j] = wrN[j];
     }
   };
-  auto widen = [](unsigned h) {   // one 16-bit element (upper bits zero) -> the fp32 value it stands for
-    if (FT == kFeatBf16) return __uint_as_float(h << 16);
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);   // hardware conversion: keeps subnormals
-  };
-  auto widen4 = [&](const float4& v) {   // four consecutive 16-bit elements in v.x, v.y
-    const unsigned a = __float_as_uint(v.x), b = __float_as_uint(v.y);
-    return make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
-  };
+  auto widen4 = [](const float4& v) { return widen16x4<FT>(__float_as_uint(v.x), __float_as_uint(v.y)); };   // four consecutive 16-bit elements in v.x, v.y
   // where the 8 bytes of (row, k quad kq) lie in a plane image.  Inside a (tile, k group) piece row r sits at r ^ (kg << sh): sh = 0 where
   // a thread stores four rows of one k quad (mode 0), 1 where it stores one row (modes 1, 2), as in units_wgrad_split.hip
   const int sh = mode == 0 ? 0 : 1;
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(FS_THREADS, 1) void units_fwd_split_kernel(UfsParam
       for (int r = 0; r < 4; ++r) {
         float4 v = rg[r];
         if constexpr (FT != kFeatF32)
-          v = make_float4(widen(__float_as_uint(v.x)), widen(__float_as_uint(v.y)), widen(__float_as_uint(v.z)), widen(__float_as_uint(v.w)));
+          v = make_float4(widen16<FT>(__float_as_uint(v.x)), widen16<FT>(__float_as_uint(v.y)), widen16<FT>(__float_as_uint(v.z)), widen16<FT>(__float_as_uint(v.w)));
         sp_store_quad<NPX>(quad_at(Xp, lt & 127, (lt >> 7) + 2 * r), FS_XPLANE, v.x, v.y, v.z, v.w);
       }
     } else {

@@ -27,8 +27,7 @@
 // on bf16 maps, whose steps have half the MFMAs, at depth one and at depth three alike; with the role-free, unconditional load sequence
 // of load_tile the waits leave the ten newest loads in flight (DESIGN.md section 8 has the times).  build.py refuses a form of this kernel
 // that spills or keeps anything in scratch memory (REGISTER_RESIDENT_KERNELS).
-#include "offk_common.h"
-#include "offk_internal.h"
+#include "units_common.h"
 #include "split_common.h"
 
 namespace offk {
@@ -55,23 +54,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];   // two such buffers
 
   // XCD-aware order, as K1b
-  unsigned bid = blockIdx.x;
-  {
-    const unsigned t8 = (unsigned)p.total_blocks & ~7u;
-    if (bid < t8) bid = (bid & 7u) * (t8 >> 3) + (bid >> 3);
-  }
-  WgSite S;
-#define OFFK_WS_PICK(i)                                                                                   \
-  S.dG = p.s[i].dG; S.dD = p.s[i].dD; S.slab = p.s[i].slab; S.bpart = p.s[i].bpart; S.C = p.s[i].C;         \
-  S.HW = p.s[i].HW; S.tpf = p.s[i].tpf; S.kt_total = p.s[i].kt_total; S.ntiles = p.s[i].ntiles;              \
-  S.blk_begin = p.s[i].blk_begin; S.nparts = p.s[i].nparts;                                                 \
-  S.xp[0] = p.s[i].xp[0]; S.xp[1] = p.s[i].xp[1]; S.xp[2] = p.s[i].xp[2]; S.xp[3] = p.s[i].xp[3];           \
-  S.cp[0] = p.s[i].cp[0]; S.cp[1] = p.s[i].cp[1]; S.cp[2] = p.s[i].cp[2]; S.cp[3] = p.s[i].cp[3];
-  OFFK_WS_PICK(0)
-#pragma unroll
-  for (int i = 1; i < kNumSites; ++i)
-    if (i < p.nsites && (int)bid >= p.s[i].blk_begin) { OFFK_WS_PICK(i) }
-#undef OFFK_WS_PICK
+  const unsigned bid = xcd_strided(blockIdx.x, (unsigned)p.total_blocks);
+  OFFK_PICK_SITE(S, p, (int)bid >= p.s[i].blk_begin)
   const int C = S.C, HW = S.HW;
   const int local = (int)bid - S.blk_begin;
   const int chunk = local / S.ntiles, nt = local - chunk * S.ntiles;
@@ -91,14 +75,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int cb = nt * WS_BN + 32 * r;
-    const float* xb = S.xp[0]; int cpart = S.cp[0], kl = cb;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
+    const auto [xb, cpart, kl] = part_at(S, cb);
     xok[r] = cb < C;
     xrow[r] = FEAT == kFeatF32 ? xb + (size_t)kl * HW
                                : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + (size_t)kl * HW);
@@ -108,14 +85,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
   const float* xcl = nullptr;
   int xcs = 0;
   if constexpr (CL) {
-    const float* xb = S.xp[0]; int cpart = S.cp[0], kl = nt * WS_BN + 32 * wc;
-    if (S.nparts > 1 && kl >= S.cp[0]) {
-      kl -= S.cp[0]; xb = S.xp[1]; cpart = S.cp[1];
-      if (S.nparts > 2 && kl >= S.cp[1]) {
-        kl -= S.cp[1]; xb = S.xp[2]; cpart = S.cp[2];
-        if (S.nparts > 3 && kl >= S.cp[2]) { kl -= S.cp[2]; xb = S.xp[3]; cpart = S.cp[3]; }
-      }
-    }
+    const auto [xb, cpart, kl] = part_at(S, nt * WS_BN + 32 * wc);
     xcl = FT == kFeatF32 ? xb + kl : reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(xb) + kl);
     xcs = cpart;
   }
@@ -219,10 +189,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
       }
     }
   };
-  auto widen = [](unsigned h) {   // one 16-bit element (upper bits zero) -> the fp32 value it stands for
-    if (FT == kFeatBf16) return __uint_as_float(h << 16);
-    return (float)__builtin_bit_cast(_Float16, (unsigned short)h);   // hardware conversion: keeps subnormals
-  };
   // where the 8 bytes of (row, pixel quad kq) lie in a plane image; swz_shift: see the head of the file
   auto quad_at = [](char* img, int row, int kq, int swz_shift) {
     const int kg = kq >> 1;
@@ -265,7 +231,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const unsigned a = (unsigned)rx[j], b = (unsigned)(rx[j] >> 32);
-          rg[j] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+          rg[j] = widen16x4<FT>(a, b);
         }
       }
       sp_store_quad<NPX>(quad_at(Xp, 4 * cq, pq, 0), WS_XPLANE, rg[0].x, rg[1].x, rg[2].x, rg[3].x);
@@ -278,10 +244,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void pw_wgrad_split_kernel(WgParams 
         for (int r = 0; r < 4; ++r) {
           if constexpr (decltype(VT)::value == 1) {
             const unsigned a = (unsigned)rx[r], b = (unsigned)(rx[r] >> 32);
-            rg[r] = make_float4(widen(a & 0xffffu), widen(a >> 16), widen(b & 0xffffu), widen(b >> 16));
+            rg[r] = widen16x4<FT>(a, b);
           } else {
-            rg[r] = make_float4(widen(__float_as_uint(rg[r].x)), widen(__float_as_uint(rg[r].y)),
-                                widen(__float_as_uint(rg[r].z)), widen(__float_as_uint(rg[r].w)));
+            rg[r] = make_float4(widen16<FT>(__float_as_uint(rg[r].x)), widen16<FT>(__float_as_uint(rg[r].y)),
+                                widen16<FT>(__float_as_uint(rg[r].z)), widen16<FT>(__float_as_uint(rg[r].w)));
           }
         }
       } else {
