@@ -150,7 +150,7 @@ ENTRIES = collections.OrderedDict([
         ("k1", (Operand("x", 2 * 7 * 7, 512, "in"), Operand("g", 2 * 7 * 7, 128, "in"))),
         ("k3", (Operand("x", 2 * 5 * 3, 128, "in"), Operand("g", 2 * 5 * 3, 128, "in"))),
     ])),
-    # tests/conv_bwd_s2.py SHAPES: (2, 6, 10, 64, 64) for the 7x7 and (2, 6, 4, 160, 64) for the 5x5; g is the half-size map
+    # tests/conv_bwd.py (S2) SHAPES: (2, 6, 10, 64, 64) for the 7x7 and (2, 6, 4, 160, 64) for the 5x5; g is the half-size map
     ("conv2d_s2_backward_data", collections.OrderedDict([
         ("k7", (Operand("g", 2 * 3 * 5, 64, "in"), Operand("dx", 2 * 6 * 10, 64, "out"))),
         ("k5", (Operand("g", 2 * 3 * 2, 64, "in"), Operand("dx", 2 * 6 * 4, 160, "out"))),

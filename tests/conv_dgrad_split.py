@@ -1,6 +1,6 @@
 """What the tests of the stride-1 fusion convs' split-fp32 data gradient share (tests/test_conv_dgrad_split_abi.py on the CPU,
-tests/test_gpu_conv_dgrad_split.py on the GPU): the operands of csrc/conv_dgrad_split.hip in its K order, the CPU model of its arithmetic
-and the inequality both files assert.  A helper module like tests/conv_s2_dgrad_split.py: numpy only, no torch, no tests of its own.
+tests/test_gpu_conv_dgrad_split.py on the GPU): the operands of csrc/conv_dgrad_split.hip in its K order and the CPU model of its arithmetic;
+the inequality both files assert of them is tests/split_bound.py's.  A helper module like tests/conv_s2_dgrad_split.py: numpy only, no torch, no tests of its own.
 
 The K order is the one include/offk.h states for offk_conv2d_backward_data_split:
     dx[n, h, w, ci] = sum_{kh, kw, co} g[n, h + pad - kh, w + pad - kw, co] * w[co, ci, kh, kw],   pad = (k - 1) / 2,
@@ -11,7 +11,6 @@ import numpy as np
 
 from offk_amd import synth
 
-EPS = synth.SPLIT_EPS
 
 
 def operands(g, w):
@@ -57,22 +56,3 @@ def emulate(g, w, skip=None):
 def terms(g, w):
     """(ref64, dropped64, sum |g w|), each [n, H, W, Ci]: synth.split_terms with the weight as w"""
     return tuple(np.asarray(p, dtype=np.float64).reshape(_shape(g, w)) for p in synth.split_terms(*operands(g, w)))
-
-
-def c_acc(emulated, ref, dropped, mag):
-    return float(synth.split_c_acc(emulated, ref, dropped, mag).max())
-
-
-def excess_map(got, ref, dropped, mag, A, base=None):
-    """per element |got - exact| - (|dropped64| + A 2^-24 sum |g w| + 2^-24 |ref64| [+ 2^-24 |exact| when accumulating onto `base`]) with
-    exact = ref64 (+ base): <= 0 where the inequality holds"""
-    bound = np.abs(dropped) + A * EPS * mag + EPS * np.abs(ref)
-    exact = ref
-    if base is not None:
-        exact = ref + np.asarray(base, dtype=np.float64)
-        bound = bound + EPS * np.abs(exact)
-    return np.abs(np.asarray(got, dtype=np.float64) - exact) - bound
-
-
-def excess(got, ref, dropped, mag, A, base=None):
-    return float(excess_map(got, ref, dropped, mag, A, base).max())

@@ -1,6 +1,6 @@
 """What the tests of the stride-2 fusion convs' split-fp32 data gradient share (tests/test_conv_s2_dgrad_split_abi.py on the CPU,
-tests/test_gpu_conv_s2_dgrad_split.py on the GPU): the per-phase operands of csrc/conv_dgrad_s2_split.hip in its K order, the CPU model of
-its arithmetic and the inequality both files assert.  A helper module like tests/conv_wgrad_split.py: numpy only, no torch, no tests of its own.
+tests/test_gpu_conv_s2_dgrad_split.py on the GPU): the per-phase operands of csrc/conv_dgrad_s2_split.hip in its K order and the CPU model
+of its arithmetic; the inequality both files assert of them is tests/split_bound.py's.  A helper module like tests/conv_wgrad_split.py: numpy only, no torch, no tests of its own.
 
 The K order is the one include/offk.h states for offk_conv2d_s2_backward_data_split.  An input pixel is (2a + r, 2b + s); per axis and phase
 bit r the taps are the kernel elements k0 + 2 t (k0 = (r + pad) & 1, t = 0 .. ntap - 1), and tap t reads g at a + d0 - t with
@@ -11,7 +11,6 @@ import numpy as np
 
 from offk_amd import synth
 
-EPS = synth.SPLIT_EPS
 FORMS = {7: 3, 5: 2}           # kernel size -> padding; stride 2
 PHASES = ((0, 0), (0, 1), (1, 0), (1, 1))
 
@@ -83,22 +82,3 @@ def terms(g, w):
     n, OH, OW, _ = np.shape(g)
     per = [synth.split_terms(*operands(g, w, r, s)) for r, s in PHASES]
     return tuple(_assemble([p[i] for p in per], n, OH, OW, np.shape(w)[1], np.float64) for i in range(3))
-
-
-def c_acc(emulated, ref, dropped, mag):
-    return float(synth.split_c_acc(emulated, ref, dropped, mag).max())
-
-
-def excess_map(got, ref, dropped, mag, A, base=None):
-    """per element |got - exact| - (|dropped64| + A 2^-24 sum |g w| + 2^-24 |ref64| [+ 2^-24 |exact| when accumulating onto `base`]) with
-    exact = ref64 (+ base): <= 0 where the inequality holds"""
-    bound = np.abs(dropped) + A * EPS * mag + EPS * np.abs(ref)
-    exact = ref
-    if base is not None:
-        exact = ref + np.asarray(base, dtype=np.float64)
-        bound = bound + EPS * np.abs(exact)
-    return np.abs(np.asarray(got, dtype=np.float64) - exact) - bound
-
-
-def excess(got, ref, dropped, mag, A, base=None):
-    return float(excess_map(got, ref, dropped, mag, A, base).max())

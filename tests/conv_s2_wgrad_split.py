@@ -1,6 +1,6 @@
 """What the tests of the stride-2 fusion convs' split-fp32 weight gradient share (tests/test_conv_s2_wgrad_split_abi.py on the CPU,
-tests/test_gpu_conv_s2_wgrad_split.py on the GPU): the K layout of csrc/conv_wgrad_s2_split.hip in numpy, the CPU model of its CHUNKED
-arithmetic and the inequality both files assert.  A helper module like tests/conv_wgrad_split.py: no tests of its own, no torch.
+tests/test_gpu_conv_s2_wgrad_split.py on the GPU): the K layout of csrc/conv_wgrad_s2_split.hip in numpy and the CPU model of its CHUNKED
+arithmetic; the inequality both files assert of them is tests/split_bound.py's.  A helper module like tests/conv_wgrad_split.py: no tests of its own, no torch.
 
 The K order is the one include/offk.h states for offk_conv2d_s2_backward_weight_split.  K runs over the OUTPUT pixels, real pixels only:
 q = (img * OH + oh) * OW + ow with OH = H / 2, OW = W / 2, PP = OH * OW positions per image, images back to back.  Tap (kh, kw) pairs g at q
@@ -12,7 +12,6 @@ import numpy as np
 
 from offk_amd import synth
 
-EPS = synth.SPLIT_EPS
 KT = 32                                   # positions per MFMA step
 PADS = {7: 3, 5: 2}
 
@@ -68,16 +67,3 @@ def terms(G, taps, k):
     xs = np.concatenate([taps[(kh, kw)] for kh in range(k) for kw in range(k)], axis=1)
     out = synth.split_terms(np.ascontiguousarray(G.T), np.ascontiguousarray(xs.T))
     return tuple(np.ascontiguousarray(t.reshape(k, k, Ci, Co).transpose(3, 2, 0, 1)) for t in out)
-
-
-def c_acc(emulated, ref, dropped, mag):
-    return float(synth.split_c_acc(emulated, ref, dropped, mag).max())
-
-
-def excess_map(got, ref, dropped, mag, A):
-    """per element |got - ref64| - (|dropped64| + A 2^-24 sum|g x| + 2^-24 |ref64|): <= 0 where the inequality holds"""
-    return np.abs(np.asarray(got, dtype=np.float64) - ref) - (np.abs(dropped) + A * EPS * mag + EPS * np.abs(ref))
-
-
-def excess(got, ref, dropped, mag, A):
-    return float(excess_map(got, ref, dropped, mag, A).max())

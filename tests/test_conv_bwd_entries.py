@@ -13,8 +13,8 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib
 
-from . import conv_bwd as cb
-from . import conv_bwd_s2 as s2
+from .conv_bwd import S1 as cb
+from .conv_bwd import S2 as s2
 from . import test_conv_bwd_abi as s1_abi
 from . import test_conv_bwd_s2_abi as s2_abi
 from . import test_conv_dgrad_split_abi as s1_dgrad
@@ -73,7 +73,7 @@ def refused(lib, entry, args):
 
 
 def plan_shapes():
-    """[(id, H, ci, co, k, the plan entries of its stride)]: tests/conv_bwd.FUSION_SHAPES and tests/conv_bwd_s2.REAL"""
+    """[(id, H, ci, co, k, the plan entries of its stride)]: tests/conv_bwd.S1.FUSION_SHAPES and tests/conv_bwd.S2.REAL"""
     out = [("%dx%d_%dto%d_k%d" % (H, H, ci, co, k), H, ci, co, k, PLANS_S1) for H, ci, co, k in cb.FUSION_SHAPES]
     return out + [(key, H, ci, co, k, PLANS_S2) for key, ci, co, k, H in s2.REAL]
 

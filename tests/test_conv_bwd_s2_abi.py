@@ -10,7 +10,7 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib
 
-from . import conv_bwd_s2 as cs
+from .conv_bwd import S2 as cs
 
 ENTRIES = ("offk_conv2d_s2_backward_data", "offk_conv2d_s2_backward_weight", "offk_conv2d_s2_backward_plan")
 

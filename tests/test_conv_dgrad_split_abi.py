@@ -15,10 +15,11 @@ import numpy as np
 import pytest
 
 import offk_amd  # noqa: F401
-from offk_amd import _lib, synth
+from offk_amd import _lib
 
-from . import conv_bwd as cb
+from .conv_bwd import S1 as cb
 from . import conv_dgrad_split as dg
+from . import split_bound as sb
 from . import test_conv_bwd_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -241,32 +242,13 @@ def test_the_operands_summed_directly_equal_the_reference(built, c):
     assert Wm[ci, (kh * c.k + kw) * c.co + co] == w[co, ci, kh, kw]
 
 
-WORST = [(3, 2, 5, 3, 64, 64), (1, 2, 5, 3, 64, 128)]                   # k, n, H, W, ci, co
 WORST_IDS = ["k3_2x5x3_64to64", "k1_2x5x3_64to128"]
-
-
-def worst_inputs(shape, pattern, signs):
-    """g [n, H, W, co] and w [co, ci, k, k] on one worst-case mantissa; signs "alternating" flips g ONLY, along co (flipping both operands
-    along co would cancel nothing)"""
-    k, n, H, W, ci, co = shape
-    g = synth.make_adversarial((n, H, W, co), pattern, signs, seed=31, relu=(pattern == 0x7FFFFF), k_axis=-1)
-    w = synth.make_adversarial((co, ci, k, k), pattern, "same", seed=32) * np.float32(2.0 ** -4)
-    return g, w
 
 
 @pytest.mark.parametrize("signs", ["same", "alternating"])
 @pytest.mark.parametrize("pattern", [0x00FFFF, 0x7FFFFF, 0x7F7F7F])
-@pytest.mark.parametrize("shape", WORST, ids=WORST_IDS)
+@pytest.mark.parametrize("shape", cb.WORST, ids=WORST_IDS)
 def test_the_gpu_inequality_discriminates_in_the_kernels_k_order(shape, pattern, signs):
-    g, w = worst_inputs(shape, pattern, signs)
+    g, w = cb.worst_inputs(shape, pattern, signs)
     ref, dropped, mag = dg.terms(g, w)
-    emu = dg.emulate(g, w)
-    c = dg.c_acc(emu, ref, dropped, mag)
-    A = max(1.0, 2.0 * c)
-    print("k %d pattern 0x%06X %-11s: emulated c_acc %.3f, A %.3f, dropped max %.3f of %.3f" % (
-        shape[0], pattern, signs, c, A, float((np.abs(dropped) / np.maximum(dg.EPS * mag, 1e-300)).max()), synth.SPLIT_DROP_BOUND))
-    assert dg.excess(emu, ref, dropped, mag, A) <= 0.0
-    assert float((np.abs(dropped) - synth.SPLIT_DROP_BOUND * dg.EPS * mag).max()) <= 0.0
-    assert np.array_equal(emu[mag == 0], np.zeros(int((mag == 0).sum()), dtype=np.float32))
-    for skip in range(len(synth.SPLIT_PRODUCTS)):
-        assert dg.excess(dg.emulate(g, w, skip=skip), ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])
+    sb.assert_discriminates("k %d pattern 0x%06X %-11s" % (shape[0], pattern, signs), lambda skip: dg.emulate(g, w, skip=skip), ref, dropped, mag)

@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 import offk_amd  # noqa: F401
-from offk_amd import _lib, synth
+from offk_amd import _lib
 
-from . import conv_bwd_s2 as cs
+from .conv_bwd import S2 as cs
 from . import conv_s2_dgrad_split as ds
+from . import split_bound as sb
 from . import test_conv_bwd_s2_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,33 +173,11 @@ def test_the_operands_summed_directly_equal_the_reference(built, c):
     assert sorted(ds.phase_taps(c.k, r, s) for r, s in ds.PHASES) == ([9, 12, 12, 16] if c.k == 7 else [4, 6, 6, 9])
 
 
-WORST = [(7, 2, 6, 10, 64, 64), (5, 2, 6, 4, 96, 64)]
-
-
-def worst_inputs(shape, pattern, signs):
-    """g [n, H / 2, W / 2, co] and w [co, ci, k, k] on one worst-case mantissa; signs "alternating" flips g ONLY, along co (flipping both
-    operands along co would cancel nothing)"""
-    k, n, H, W, ci, co = shape
-    g = synth.make_adversarial((n, H // 2, W // 2, co), pattern, signs, seed=21, relu=(pattern == 0x7FFFFF), k_axis=-1)
-    w = synth.make_adversarial((co, ci, k, k), pattern, "same", seed=22) * np.float32(2.0 ** -4)
-    return g, w
-
-
 @pytest.mark.parametrize("signs", ["same", "alternating"])
 @pytest.mark.parametrize("pattern", [0x00FFFF, 0x7FFFFF, 0x7F7F7F])
-@pytest.mark.parametrize("shape", WORST, ids=["k7_2x6x10_64to64", "k5_2x6x4_96to64"])
+@pytest.mark.parametrize("shape", cs.WORST, ids=["k7_2x6x10_64to64", "k5_2x6x4_96to64"])
 def test_the_gpu_inequality_discriminates_in_the_kernels_k_order(shape, pattern, signs):
-    g, w = worst_inputs(shape, pattern, signs)
+    g, w = cs.worst_inputs(shape, pattern, signs)
     ref, dropped, mag = ds.terms(g, w)
-    emu = ds.emulate(g, w)
-    c = ds.c_acc(emu, ref, dropped, mag)
-    A = max(1.0, 2.0 * c)
-    print("k %d pattern 0x%06X %-11s: emulated c_acc %.3f, A %.3f, dropped max %.3f of %.3f" % (
-        shape[0], pattern, signs, c, A, float((np.abs(dropped) / np.maximum(ds.EPS * mag, 1e-300)).max()), synth.SPLIT_DROP_BOUND))
-    assert ds.excess(emu, ref, dropped, mag, A) <= 0.0
-    assert float((np.abs(dropped) - synth.SPLIT_DROP_BOUND * ds.EPS * mag).max()) <= 0.0
-    assert np.array_equal(emu[mag == 0], np.zeros(int((mag == 0).sum()), dtype=np.float32))
-    for skip in range(len(synth.SPLIT_PRODUCTS)):
-        lost = ds.excess_map(ds.emulate(g, w, skip=skip), ref, dropped, mag, A)
-        for r, s in ds.PHASES:
-            assert float(lost[:, r::2, s::2, :].max()) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip], r, s)
+    sb.assert_discriminates("k %d pattern 0x%06X %-11s" % (shape[0], pattern, signs), lambda skip: ds.emulate(g, w, skip=skip), ref, dropped, mag,
+                            parts=[(slice(None), slice(r, None, 2), slice(s, None, 2)) for r, s in ds.PHASES])      # in every phase

@@ -16,15 +16,16 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib, synth
 
-from . import conv_bwd_s2 as s2
+from .conv_bwd import S2 as s2
 from . import conv_s2_wgrad_split as ws
+from . import split_bound as sb
 from . import test_conv_bwd_s2_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHT, PLAN = "offk_conv2d_s2_backward_weight_split", "offk_conv2d_s2_backward_weight_plan_split"
 FP32 = "offk_conv2d_s2_backward_weight"
 
-# weight_chunks of the split plan at n_img = 1, 6, 384 for tests/conv_bwd_s2.REAL: the 7x7 has 35 tiles of one kernel row (7 chunks = 245
+# weight_chunks of the split plan at n_img = 1, 6, 384 for tests/conv_bwd.S2.REAL: the 7x7 has 35 tiles of one kernel row (7 chunks = 245
 # blocks, one round of one block per CU), the 5x5 170 (3 chunks = 510 blocks, two rounds); a chunk is at least 256 positions long
 PLAN_CHUNKS = {"motion_conv_trans_28": (1, 3, 7), "motion_conv_trans_14": (1, 1, 3)}
 
@@ -132,7 +133,7 @@ def test_db_may_be_null_short_scratch_names_the_plan_and_plan_refusals(built):
 @pytest.mark.parametrize("c", s2.cases(), ids=s2.case_id)
 def test_the_layout_pairs_every_tap_with_its_pixels(c):
     """the K layout against the definition: the helper's operands summed in fp64 over the position order equal torch's dW and db, at the
-    ten cases of tests/conv_bwd_s2.py (the plan-chosen n replaced by 5: the layout does not depend on the plan)"""
+    ten cases of tests/conv_bwd.py (S2) (the plan-chosen n replaced by 5: the layout does not depend on the plan)"""
     c = c if c.n is not None else c._replace(n=5)
     for relu_in in (False, True):
         inp, ref = s2.cached(c, "int", relu_in)
@@ -158,16 +159,8 @@ def test_the_gpu_inequality_discriminates_in_the_kernels_layout(shape, pattern, 
     G, taps = ws.operands(g, x, k)
     bounds = ws.chunk_bounds(n, H, W, n)                 # one image per chunk: the reduce's additions are part of the form
     ref, dropped, mag = ws.terms(G, taps, k)
-    emu = ws.emulate_chunked(G, taps, bounds, k)
-    c = ws.c_acc(emu, ref, dropped, mag)
-    A = max(1.0, 2.0 * c)
-    print("k %d pattern 0x%06X %-11s: emulated c_acc %.3f, A %.3f, dropped max %.3f" % (
-        k, pattern, signs, c, A, float((np.abs(dropped) / np.maximum(ws.EPS * mag, 1e-300)).max())))
-    assert ws.excess(emu, ref, dropped, mag, A) <= 0.0
-    assert np.array_equal(emu[mag == 0], np.zeros(int((mag == 0).sum()), dtype=np.float32))
-    for skip in range(len(synth.SPLIT_PRODUCTS)):
-        lost = ws.emulate_chunked(G, taps, bounds, k, skip=skip)
-        assert ws.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])
+    sb.assert_discriminates("k %d pattern 0x%06X %-11s" % (k, pattern, signs), lambda skip: ws.emulate_chunked(G, taps, bounds, k, skip=skip),
+                            ref, dropped, mag)
 
 
 def test_fusion_conv_keyword():

@@ -14,14 +14,15 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib, synth
 
-from . import conv_bwd as cb
+from .conv_bwd import S1 as cb
 from . import conv_wgrad_split as cs
+from . import split_bound as sb
 from . import test_conv_bwd_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHT, PLAN = "offk_conv2d_backward_weight_split", "offk_conv2d_backward_plan_split"
 
-# weight_chunks of the split plan at n_img = 1, 6, 384 for tests/conv_bwd.FUSION_SHAPES, in that order
+# weight_chunks of the split plan at n_img = 1, 6, 384 for tests/conv_bwd.S1.FUSION_SHAPES, in that order
 PLAN_CHUNKS = {(14, 64, 64, 1): (1, 3, 192), (14, 64, 64, 3): (1, 3, 192), (14, 64, 256, 1): (1, 3, 192), (14, 256, 64, 1): (1, 3, 192),
                (7, 128, 128, 1): (1, 1, 64), (7, 128, 128, 3): (1, 2, 64), (7, 128, 512, 1): (1, 1, 64), (7, 512, 128, 1): (1, 1, 64),
                (7, 128, 512, 3): (1, 2, 16), (7, 832, 256, 3): (1, 2, 4), (7, 256, 256, 1): (1, 1, 64), (7, 256, 256, 3): (1, 2, 16),
@@ -190,13 +191,5 @@ def test_the_gpu_inequality_discriminates_in_the_kernels_layout(shape, pattern, 
     G, taps = cs.operands(g, x, k)
     bounds = cs.chunk_bounds(n, H, W, k, n)                # one image per chunk: the reduce's additions are part of the form
     ref, dropped, mag = cs.terms(G, taps, k)
-    emu = cs.emulate_chunked(G, taps, bounds, k)
-    c = cs.c_acc(emu, ref, dropped, mag)
-    A = max(1.0, 2.0 * c)
-    print("k %d pattern 0x%06X %-11s: emulated c_acc %.3f, A %.3f, dropped max %.3f" % (
-        k, pattern, signs, c, A, float((np.abs(dropped) / np.maximum(cs.EPS * mag, 1e-300)).max())))
-    assert cs.excess(emu, ref, dropped, mag, A) <= 0.0
-    assert np.array_equal(emu[mag == 0], np.zeros(int((mag == 0).sum()), dtype=np.float32))
-    for skip in range(len(synth.SPLIT_PRODUCTS)):
-        lost = cs.emulate_chunked(G, taps, bounds, k, skip=skip)
-        assert cs.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])
+    sb.assert_discriminates("k %d pattern 0x%06X %-11s" % (k, pattern, signs), lambda skip: cs.emulate_chunked(G, taps, bounds, k, skip=skip),
+                            ref, dropped, mag)

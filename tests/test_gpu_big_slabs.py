@@ -69,8 +69,8 @@ from offk_amd import _lib, spec
 from oracle import off_oracle as orc
 
 from . import arena, big, exact
-from . import conv_bwd as cb
-from . import conv_bwd_s2 as cs2
+from .conv_bwd import S1 as cb
+from .conv_bwd import S2 as cs2
 from . import exact_fusion as ef
 from . import exact_wino as ew
 from . import head_bwd as hb

@@ -9,6 +9,9 @@ tap read a row off, one K-tile that straddles an image boundary wrongly is a fai
 The same cases run once more with relu_in = 1 and with x, g and dx as the middle slices of three-times-wider buffers, every buffer
 carved from a guarded arena (tests/arena.py) whose sentinels must be intact afterwards; the outer slices hold NaN (x, g) or must keep
 their sentinel (dx).
+
+The bodies the two strides share are tests/conv_grad_checks.py's, written against tests/conv_bwd.py's forms; this file keeps the test
+names, the parametrize lists and what this stride alone has.
 """
 import pytest
 import torch
@@ -16,8 +19,10 @@ import torch
 import offk_amd  # noqa: F401
 
 from . import arena
-from . import conv_bwd as cb
+from . import conv_grad_checks as chk
 from . import exact
+from .conv_bwd import S1 as cb
+from .conv_grad_checks import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -25,110 +30,20 @@ CASES = cb.cases()
 IDS = [cb.case_id(c) for c in CASES]
 
 
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def resolve(rt, c):
-    """the plan-chosen case: n such that the weight gradient runs in >= 3 chunks with a shorter last one (asserted here)"""
-    if c.n is not None:
-        return c
-    n = cb.chunked_n(rt.conv2d_backward_plan, c)
-    chunks = rt.conv2d_backward_plan(n, c.H, c.W, c.ci, c.co, c.k)[2]
-    ipc = -(-n // chunks)
-    assert chunks >= 3, (n, chunks)
-    assert 0 < n - (chunks - 1) * ipc < ipc, (n, chunks, ipc)
-    return c._replace(n=n)
-
-
-def nan_bytes(n):
-    return torch.full(((n + 3) // 4,), NAN, device="cuda").view(torch.uint8)[:n]
-
-
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
 @pytest.mark.parametrize("c", CASES, ids=IDS)
 def test_dense_equals_fp64(rt, c, accumulate):
-    c = resolve(rt, c)
-    inp, ref = cb.cached(c, "int", False)
-    cb.check_caps(c, inp, ref)
-    pad = (c.k - 1) // 2
-    x, g, w = inp["x"].cuda(), inp["g"].cuda(), inp["w"].cuda()
-    dbytes, wbytes, _ = rt.conv2d_backward_plan(c.n, c.H, c.W, c.ci, c.co, c.k)
-    if accumulate:
-        dx, dw, db = inp["dx0"].cuda(), inp["dw0"].cuda(), inp["db0"].cuda()
-    else:
-        dx, dw, db = (torch.full(s, NAN, device="cuda") for s in ((c.n, c.H, c.W, c.ci), (c.co, c.ci, c.k, c.k), (c.co,)))
-    rt.conv2d_backward_data(g, w, pad, dx=dx, accumulate=accumulate, scratch=nan_bytes(dbytes))
-    rt.conv2d_backward_weight(x, g, c.k, pad, dw=dw, db=db, accumulate=accumulate, scratch=nan_bytes(wbytes))
-    torch.cuda.synchronize()
-    base = {"dX": inp["dx0"].double(), "dW": inp["dw0"].double(), "db": inp["db0"].double()} if accumulate else {}
-    mm = exact.Mismatches()
-    for name, got in (("dX", dx), ("dW", dw), ("db", db)):
-        mm.check(got.cpu(), ref[name] + base.get(name, 0.0), "%s %s" % (cb.case_id(c), name))
-    mm.raise_if_any()
-    if c.k == 3 and c.H == 1 and c.W == 1 and not accumulate:
-        taps = dw.cpu().reshape(c.co, c.ci, 9)
-        assert torch.equal(taps[:, :, [0, 1, 2, 3, 5, 6, 7, 8]], torch.zeros(c.co, c.ci, 8)), "a 1x1 map feeds the centre tap only"
-        assert bool((taps[:, :, 4] != 0).any())
+    chk.exact_dense(rt, cb, c, accumulate)
 
 
 def test_bias_gradient_is_optional(rt):
-    c = CASES[0]
-    inp, ref = cb.cached(c, "int", False)
-    dw, db = rt.conv2d_backward_weight(inp["x"].cuda(), inp["g"].cuda(), c.k, 0, want_db=False)
-    assert db is None
-    exact.assert_exact(dw.cpu(), ref["dW"], "dW without db")
+    chk.exact_bias_optional(rt, cb, CASES[0])
 
 
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
 @pytest.mark.parametrize("c", CASES, ids=IDS)
 def test_relu_in_and_channel_slices_in_a_guarded_arena(rt, c, accumulate):
-    c = resolve(rt, c)
-    inp, ref = cb.cached(c, "int", True)
-    _, plain = cb.cached(c, "int", False)
-    cb.check_caps(c, inp, ref)
-    cb.check_caps(c, inp, plain)
-    pad = (c.k - 1) // 2
-    n, H, W, ci, co, k = c.n, c.H, c.W, c.ci, c.co, c.k
-    dbytes, wbytes, _ = rt.conv2d_backward_plan(n, H, W, ci, co, k)
-    px = n * H * W
-    A = arena.Arena.for_sizes([px * 3 * ci * 4, px * 3 * co * 4, px * 3 * ci * 4, co * ci * k * k * 4, co * 4, co * ci * k * k * 4, dbytes, wbytes])
-    xb = A.empty("x", (n, H, W, 3 * ci))               # outer slices: the arena's NaN sentinel
-    gb = A.empty("g", (n, H, W, 3 * co))
-    dxb = A.empty("dx", (n, H, W, 3 * ci))
-    xb[..., ci:2 * ci] = inp["x"].cuda()
-    gb[..., co:2 * co] = inp["g"].cuda()
-    w = A.put("w", inp["w"].cuda())
-    if accumulate:
-        dxb[..., ci:2 * ci] = inp["dx0"].cuda()
-        dw, db = A.put("dw", inp["dw0"].cuda()), A.put("db", inp["db0"].cuda())
-    else:
-        dw, db = A.empty("dw", (co, ci, k, k)), A.empty("db", (co,))
-    sd, sw = A.carve("data_scratch", dbytes), A.carve("weight_scratch", wbytes)
-    rt.conv2d_backward_data(gb, w, pad, dx=dxb, dx_coff=ci, accumulate=accumulate, scratch=sd, g_coff=co)
-    rt.conv2d_backward_weight(xb, gb, k, pad, relu_in=True, x_coff=ci, ci=ci, g_coff=co, co=co, dw=dw, db=db, accumulate=accumulate, scratch=sw)
-    torch.cuda.synchronize()
-    mm = exact.Mismatches()
-    dx_mid = dxb[..., ci:2 * ci].cpu()
-    b = (lambda name: inp[name].double()) if accumulate else (lambda name: 0.0)
-    mm.check(dx_mid, plain["dX"] + b("dx0"), "%s dX (before the mask)" % cb.case_id(c))
-    mm.check(dw.cpu(), ref["dW"] + b("dw0"), "%s dW, relu_in" % cb.case_id(c))
-    mm.check(db.cpu(), ref["db"] + b("db0"), "%s db" % cb.case_id(c))
-    # OFFK_CONV_RELU_IN's mask on the conv's dX: in place, mask = the conv's input
-    rt.relu_backward(dxb, xb, out=dxb, dy_coff=ci, y_coff=ci, out_coff=ci, c=ci)
-    torch.cuda.synchronize()
-    want = (plain["dX"] + b("dx0")) * (inp["x"] > 0).double()
-    got = dxb[..., ci:2 * ci].cpu().double()
-    assert torch.equal(got, want), "%s: masked dX differs at %d elements" % (cb.case_id(c), int((got != want).sum()))
-    if not accumulate:
-        assert torch.equal(got, ref["dX"]), "the masked dX is autograd's dX of conv(relu(x))"
-    mm.raise_if_any()
-    assert A.untouched(dxb[..., :ci]) and A.untouched(dxb[..., 2 * ci:]), "dx's neighbour slices were written"
-    assert A.untouched(xb[..., :ci]) and A.untouched(gb[..., 2 * co:])
-    A.check()
+    chk.exact_relu_in_slices(rt, cb, c, accumulate)
 
 
 def test_relu_backward_special_values(rt):

@@ -1,7 +1,7 @@
 """The stride-2 fusion convs' data gradient in split-fp32 arithmetic on the bf16 matrix pipe (offk_conv2d_s2_backward_data_split,
 csrc/conv_dgrad_s2_split.hip; runtime.conv2d_s2_backward_data(arith="f32split"), FusionConv2d(dgrad_arith="f32split")).
 
- 1. exact integers: dX EQUAL to the fp64 reference at all ten cases of tests/conv_bwd_s2.cases() (both real shapes at n = 1, the half ci
+ 1. exact integers: dX EQUAL to the fp64 reference at all ten cases of tests/conv_bwd.S2.cases() (both real shapes at n = 1, the half ci
     tiles 96 / 160 / 1056, the non-square 6x10 and 6x4 maps, the 2x2 map with M = 1), with and without accumulate, and again on middle
     channel slices of g and dx inside a NaN-guarded arena;
  2. 17-bit integers: three non-zero planes in g against single-plane weights and the reverse: equal to fp64 -- the plane indexing of the
@@ -11,43 +11,32 @@ csrc/conv_dgrad_s2_split.hip; runtime.conv2d_s2_backward_data(arith="f32split"),
     c_acc the CPU EMULATION's accumulation constant on the same operands in the kernel's K order (tests/conv_s2_dgrad_split.py) -- never
     the kernel's output; tests/test_conv_s2_dgrad_split_abi.py shows on the CPU that losing any one issued product breaks it;
  4. the same inequality on normal data at both real shapes (n = 1); emulated against measured c_acc and the fp32 entry's error are printed;
- 5. discipline: equal bits from NaN- and -3-filled scratch, graph replay == eager, a refused call writes nothing;  6. the module."""
-import numpy as np
+ 5. discipline: equal bits from NaN- and -3-filled scratch, graph replay == eager, a refused call writes nothing;  6. the module.
+
+The bodies the two strides share are tests/conv_grad_checks.py's, written against tests/conv_bwd.py's forms; this file keeps the test
+names, the parametrize lists and what this stride alone has."""
 import pytest
 import torch
 
 import offk_amd  # noqa: F401
-from offk_amd import _lib, synth
+from offk_amd import _lib
 
 from . import arena
-from . import conv_bwd_s2 as cs
-from . import conv_s2_dgrad_split as ds
-from . import exact
-from .test_conv_s2_dgrad_split_abi import WORST, worst_inputs
+from . import conv_grad_checks as chk
+from .conv_bwd import S2 as cs
+from .conv_grad_checks import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-NAN = float("nan")
 CASES = cs.cases()
 IDS = [cs.case_id(c) for c in CASES]
 
 
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
 def resolve(rt, c):
-    return cs.resolve(rt.conv2d_s2_backward_plan, c)
-
-
-def filled_bytes(n, value=NAN):
-    return torch.full(((n + 3) // 4,), value, device="cuda").view(torch.uint8)[:n]
+    return chk.resolve(rt, cs, c)
 
 
 def split_dgrad(rt, g, w, k, **kw):
-    return rt.conv2d_s2_backward_data(g, w, cs.FORMS[k], arith="f32split", **kw)
+    return chk.split_dgrad(rt, cs, g, w, k, **kw)
 
 
 # ---- 1. exact integers ----
@@ -55,129 +44,39 @@ def split_dgrad(rt, g, w, k, **kw):
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
 @pytest.mark.parametrize("c", CASES, ids=IDS)
 def test_dense_equals_fp64(rt, c, accumulate):
-    c = resolve(rt, c)
-    inp, ref = cs.cached(c, "int", False)
-    cs.check_caps(c, inp, ref)
-    nbytes = rt.conv2d_s2_backward_plan_split(c.n, c.H, c.W, c.ci, c.co, c.k)
-    dx = inp["dx0"].cuda() if accumulate else torch.full((c.n, c.H, c.W, c.ci), NAN, device="cuda")
-    split_dgrad(rt, inp["g"].cuda(), inp["w"].cuda(), c.k, dx=dx, accumulate=accumulate, scratch=filled_bytes(nbytes))
-    torch.cuda.synchronize()
-    exact.assert_exact(dx.cpu(), ref["dX"] + (inp["dx0"].double() if accumulate else 0.0), "%s dX" % cs.case_id(c))
+    chk.dgrad_dense(rt, cs, resolve(rt, c), accumulate)
 
 
 @pytest.mark.parametrize("accumulate", [False, True], ids=["write", "accumulate"])
 @pytest.mark.parametrize("c", CASES, ids=IDS)
 def test_channel_slices_in_a_guarded_arena(rt, c, accumulate):
-    c = resolve(rt, c)
-    inp, ref = cs.cached(c, "int", False)
-    n, H, W, ci, co, k = c.n, c.H, c.W, c.ci, c.co, c.k
-    nbytes = rt.conv2d_s2_backward_plan_split(n, H, W, ci, co, k)
-    A = arena.Arena.for_sizes([n * (H // 2) * (W // 2) * 3 * co * 4, n * H * W * 3 * ci * 4, co * ci * k * k * 4, nbytes])
-    gb = A.empty("g", (n, H // 2, W // 2, 3 * co))             # outer slices: the arena's NaN sentinel
-    dxb = A.empty("dx", (n, H, W, 3 * ci))
-    gb[..., co:2 * co] = inp["g"].cuda()
-    if accumulate:
-        dxb[..., ci:2 * ci] = inp["dx0"].cuda()
-    w = A.put("w", inp["w"].cuda())
-    s = A.carve("scratch", nbytes)
-    split_dgrad(rt, gb, w, k, g_coff=co, dx=dxb, dx_coff=ci, accumulate=accumulate, scratch=s)
-    torch.cuda.synchronize()
-    exact.assert_exact(dxb[..., ci:2 * ci].cpu(), ref["dX"] + (inp["dx0"].double() if accumulate else 0.0), "%s dX slice" % cs.case_id(c))
-    assert A.untouched(dxb[..., :ci]) and A.untouched(dxb[..., 2 * ci:]) and A.untouched(gb[..., :co]) and A.untouched(gb[..., 2 * co:])
-    assert torch.equal(w.cpu(), inp["w"]), "the weight is read in place"
-    A.check()
+    chk.dgrad_slices(rt, cs, resolve(rt, c), accumulate)
 
 
 # ---- 2. 17-bit integers ----
 
-def wide_ints(seed, shape, one_in):
-    """sparse odd integers of 17 significant bits, either sign: bit 16, seven random bits, bit 8, seven random bits, bit 0 -- the leading
-    plane takes bits 16 .. 9, the middle one bits 8 .. 1, the last one bit 0"""
-    hi = exact.ints(exact.stream(seed, 1, 0), shape, 0, 127)
-    lo = exact.ints(exact.stream(seed, 2, 0), shape, 0, 127)
-    sign = exact.ints(exact.stream(seed, 3, 0), shape, 0, 1) * 2 - 1
-    on = (exact.ints(exact.stream(seed, 4, 0), shape, 0, one_in - 1) == 0).float()
-    return (65536 + hi * 512 + 256 + lo * 2 + 1) * sign * on
-
-
 @pytest.mark.parametrize("side", ["g", "w"])
-@pytest.mark.parametrize("c", [cs.Case(7, 2, 6, 10, 64, 64), cs.Case(5, 2, 6, 4, 96, 64)], ids=cs.case_id)
+@pytest.mark.parametrize("c", chk.WIDE[2, "dgrad"][1], ids=cs.case_id)
 def test_wide_integers_equal_fp64(rt, c, side):
-    inp = dict(cs.int_inputs(c))
-    inp[side] = wide_ints(0x5D2 + c.k + (7 if side == "g" else 0), tuple(inp[side].shape), 64 if side == "g" else 256)
-    v = inp[side].numpy()
-    nz = v != 0
-    h, m, l = synth.cut3(v)
-    assert nz.sum() > v.size // 1024 and bool((h[nz] != 0).all() and (m[nz] != 0).all() and (l[nz] != 0).all()), "three non-zero planes"
-    assert bool((np.abs(v[nz]) >= 65536).all() and (np.abs(v[nz]) < 131072).all() and (v[nz] % 2 != 0).all()), "17 significant bits, odd"
-    ref = cs.reference(c, inp, False)
-    cap = float(ref["dX_abs"].max())
-    assert cap < cs.LIMIT, "%s: sum of |terms| %.0f is not below 2^23" % (cs.case_id(c), cap)
-    assert float(ref["dX"].abs().max()) >= 65536
-    dx = split_dgrad(rt, inp["g"].cuda(), inp["w"].cuda(), c.k)
-    torch.cuda.synchronize()
-    exact.assert_exact(dx.cpu(), ref["dX"], "%s dX, wide %s" % (cs.case_id(c), side))
+    chk.dgrad_wide(rt, cs, c, side)
 
 
 # ---- 3. / 4. the inequality ----
 
 def check_inequality(rt, what, k, g, w, dx_gpu, base=None):
-    """asserts the inequality per element of dX; returns (emulated c_acc, measured accumulation constant, the fp32 entry's error in the same
-    unit).  g [n, OH, OW, co], w [co, ci, k, k]: numpy"""
-    ref, dropped, mag = ds.terms(g, w)
-    emu = ds.emulate(g, w)
-    ce = ds.c_acc(emu, ref, dropped, mag)
-    A = max(1.0, 2.0 * ce)
-    got = dx_gpu.cpu().numpy()
-    assert ds.excess(emu, ref, dropped, mag, A) <= 0.0, "the emulation itself"
-    f32 = rt.conv2d_s2_backward_data(torch.from_numpy(g).cuda(), torch.from_numpy(w).cuda(), cs.FORMS[k]).cpu().numpy()
-    cf = float((np.abs(f32.astype(np.float64) - ref) / np.maximum(ds.EPS * mag, 1e-300)).max())
-    if base is None:
-        cg = ds.c_acc(got, ref, dropped, mag)
-        print("%s: emulated c_acc %.3f, A %.3f, gpu accumulation %.3f, dropped max %.3f; the fp32 entry's error %.3f (all x 2^-24 sum|g w|)" % (
-            what, ce, A, cg, float((np.abs(dropped) / np.maximum(ds.EPS * mag, 1e-300)).max()), cf))
-    else:
-        cg = float("nan")
-    ex = ds.excess_map(got, ref, dropped, mag, A, base=base)
-    assert float(ex.max()) <= 0.0, "%s: %d of %d elements break the inequality, worst excess %.3g" % (what, int((ex > 0).sum()), ex.size, float(ex.max()))
-    if base is None:
-        zero = mag == 0
-        assert np.array_equal(got[zero], np.zeros(int(zero.sum()), dtype=np.float32)), "an element without terms is exactly 0"
-    return ce, cg, cf
+    return chk.dgrad_inequality(rt, cs, what, k, g, w, dx_gpu, base=base)
 
 
-ADV = [(p, s) for p in (0x00FFFF, 0x7FFFFF, 0x7F7F7F) for s in ("same", "alternating")]
-
-
-@pytest.mark.parametrize("pattern,signs", ADV, ids=["0x%06X_%s" % a for a in ADV])
-@pytest.mark.parametrize("shape", WORST, ids=["k7_2x6x10_64to64", "k5_2x6x4_96to64"])
+@pytest.mark.parametrize("pattern,signs", chk.ADV, ids=chk.ADV_IDS)
+@pytest.mark.parametrize("shape", cs.WORST, ids=["k7_2x6x10_64to64", "k5_2x6x4_96to64"])
 def test_worst_case_mantissas(rt, shape, pattern, signs):
-    """g alternates in sign along co (the contraction index) in the "alternating" mode: sum g w << sum |g w|."""
-    g, w = worst_inputs(shape, pattern, signs)
-    for v in (g, w):
-        nz = v != 0
-        assert bool(((v.view(np.uint32) & 0x7FFFFF) == pattern)[nz].all()) and nz.sum() > v.size // 4
-    dx = split_dgrad(rt, torch.from_numpy(g).cuda(), torch.from_numpy(w).cuda(), shape[0])
-    torch.cuda.synchronize()
-    check_inequality(rt, "worst case k%d 0x%06X %-11s" % (shape[0], pattern, signs), shape[0], g, w, dx)
+    chk.dgrad_worst(rt, cs, "k%d" % shape[0], shape, pattern, signs)
 
 
 @pytest.mark.parametrize("real", cs.REAL, ids=[r[0] for r in cs.REAL])
 def test_normal_data_within_the_bound(rt, real):
     key, ci, co, k, H = real
-    c = cs.Case(k, 1, H, H, ci, co)
-    inp = cs.normal_inputs(c)
-    g, w = inp["g"].numpy(), inp["w"].numpy()
-    dx = split_dgrad(rt, inp["g"].cuda(), inp["w"].cuda(), k)
-    torch.cuda.synchronize()
-    check_inequality(rt, "normal data %s" % key, k, g, w, dx)
-    # accumulate: one more 2^-24 |result|
-    gen = torch.Generator().manual_seed(7)
-    base = torch.randn(1, H, H, ci, generator=gen)
-    dxa = base.cuda()
-    split_dgrad(rt, inp["g"].cuda(), inp["w"].cuda(), k, dx=dxa, accumulate=True)
-    torch.cuda.synchronize()
-    check_inequality(rt, "normal data %s, accumulate" % key, k, g, w, dxa, base=base.numpy())
+    chk.dgrad_normal(rt, cs, key, cs.Case(k, 1, H, H, ci, co))
 
 
 # ---- 5. discipline ----
@@ -187,35 +86,7 @@ DISCIPLINE = [cs.Case(7, 3, 14, 14, 96, 128), cs.Case(5, 2, 6, 4, 160, 64)]
 
 @pytest.mark.parametrize("c", DISCIPLINE, ids=cs.case_id)
 def test_scratch_contents_never_show_and_replay_equals_eager(rt, c):
-    inp = cs.normal_inputs(c)
-    g, w = inp["g"].cuda(), inp["w"].cuda()
-    nbytes = rt.conv2d_s2_backward_plan_split(c.n, c.H, c.W, c.ci, c.co, c.k)
-    A = arena.Arena.for_sizes([c.n * c.H * c.W * c.ci * 4, nbytes] * 3)
-
-    def buffers(tag, fill):
-        b = {"dx": A.empty("dx" + tag, (c.n, c.H, c.W, c.ci)), "s": A.carve("scratch" + tag, nbytes)}
-        if fill is not None:
-            b["s"].view(torch.float32).fill_(fill)
-        return b
-
-    def run(b):
-        split_dgrad(rt, g, w, c.k, dx=b["dx"], scratch=b["s"])
-
-    first, second, cap = buffers("1", None), buffers("2", -3.0), buffers("3", None)        # NaN sentinel | -3 | NaN sentinel
-    run(first)
-    run(second)
-    torch.cuda.synchronize()
-    assert arena.same_bits(first["dx"], second["dx"]), "dx depends on what the scratch held"
-    assert not bool(first["dx"].isnan().any())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):                       # one stream: the three launches of the entry in order
-        run(cap)
-    for _ in range(2):
-        cap["dx"].fill_(NAN)
-        graph.replay()
-        torch.cuda.synchronize()
-        assert arena.same_bits(cap["dx"], first["dx"]), "replay differs from the eager run"
-    A.check()
+    chk.dgrad_discipline(rt, cs, c)
 
 
 def test_a_refused_call_writes_nothing(rt):

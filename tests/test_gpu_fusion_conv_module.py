@@ -29,7 +29,7 @@ from torch.nn.grad import conv2d_weight
 
 import offk_amd  # noqa: F401
 
-from . import conv_bwd as cb
+from .conv_bwd import S1 as cb
 from . import exact
 
 pytestmark = pytest.mark.gpu

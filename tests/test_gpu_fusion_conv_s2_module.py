@@ -22,7 +22,7 @@ from torch.nn.grad import conv2d_weight
 
 import offk_amd  # noqa: F401
 
-from . import conv_bwd_s2 as cs
+from .conv_bwd import S2 as cs
 from . import exact
 
 pytestmark = pytest.mark.gpu

@@ -17,7 +17,7 @@ import torch.nn as nn
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
-from . import conv_bwd as cb
+from .conv_bwd import S1 as cb
 from . import featmaps as fx
 from . import head_bwd as hb
 from . import ranges as rg

@@ -24,8 +24,8 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
 from . import arena
-from . import conv_bwd as cb
-from . import conv_bwd_s2 as cs2
+from .conv_bwd import S1 as cb
+from .conv_bwd import S2 as cs2
 from . import featmaps as fx
 from . import head_bwd as hb
 from . import ranges as rg

@@ -32,6 +32,7 @@ from oracle import off_oracle as orc
 from . import arena as arena_mod
 from . import exact
 from . import featmaps as fm
+from . import split_bound as sb
 from . import test_gpu_exact as gx
 from . import test_gpu_feat_grad as fg
 from . import units_fwd_split as fs
@@ -109,7 +110,7 @@ def check_site(tag, h, B, L, slice_mode, si, x, w160, bias, max_rows=None, defau
     X = x.float().permute(0, 2, 3, 1).reshape(N * HW, C).cpu().numpy()
     ref, dropped, mag = fs.terms(w160, X, bias)
     rows = sample(N * HW, max_rows)
-    c_emu = fs.c_acc(fs.emulate(w160, X[rows], bias), ref[rows], dropped[rows], mag[rows])
+    c_emu = sb.c_acc(fs.emulate(w160, X[rows], bias), ref[rows], dropped[rows], mag[rows])
     A = max(1.0, 2.0 * c_emu)
     G = h.region("G_" + site, 128).cpu().numpy().astype(np.float64)
     Dg = h.region("D_" + site, 32).view(-1, HW, 32).cpu().numpy().astype(np.float64)
@@ -118,10 +119,10 @@ def check_site(tag, h, B, L, slice_mode, si, x, w160, bias, max_rows=None, defau
     D = np.stack([Dg[dr[n]] for n in frames]).reshape(-1, 32)
     drows = np.concatenate([np.arange(n * HW, (n + 1) * HW) for n in frames])
     assert sorted(dr[n] for n in frames) == list(range(Dg.shape[0]))
-    unit = np.maximum(fs.EPS * mag, 1e-300)
+    unit = np.maximum(sb.EPS * mag, 1e-300)
     g, d = slice(0, fs.GEN), slice(fs.GEN, 160)
-    over_g = fs.over(G, np.maximum(ref[:, g], 0.0), dropped[:, g], mag[:, g], A)
-    over_d = fs.over(D, ref[drows, d], dropped[drows, d], mag[drows, d], A)
+    over_g = sb.excess_map(G, np.maximum(ref[:, g], 0.0), dropped[:, g], mag[:, g], A)
+    over_d = sb.excess_map(D, ref[drows, d], dropped[drows, d], mag[drows, d], A)
     pos = G > 0
     c_gpu = max(float((np.abs(G - (ref - dropped)[:, g]) / unit[:, g])[pos].max()) if pos.any() else 0.0,
                 float((np.abs(D - (ref - dropped)[drows, d]) / unit[drows, d]).max()))

@@ -33,6 +33,7 @@ from oracle import off_oracle as orc
 from . import arena as arena_mod
 from . import exact
 from . import featmaps as fm
+from . import split_bound as sb
 from . import test_gpu_exact as gx
 from . import test_gpu_feat_grad as fg
 from . import wgrad_split as ws
@@ -101,9 +102,9 @@ def check_inequality(tag, got, a, x, kpb, got32=None, max_cols=None):
     cols = np.arange(C)
     if max_cols is not None and C > max_cols:
         cols = np.unique(np.concatenate((cols[:32], cols[-32:], cols[::max(1, C // (max_cols - 64))])))
-    c_emu = ws.c_acc(ws.emulate_chunked(a, x[:, cols], kpb), ref[cols], dropped[cols], mag[cols])
+    c_emu = sb.c_acc(ws.emulate_chunked(a, x[:, cols], kpb), ref[cols], dropped[cols], mag[cols])
     A = max(1.0, 2.0 * c_emu)
-    unit = np.maximum(ws.EPS * mag, 1e-300)
+    unit = np.maximum(sb.EPS * mag, 1e-300)
     err = np.abs(got - ref)
     c_gpu = float((np.abs(got - (ref - dropped)) / unit).max())
     line = "%s: c_acc emulated %.3f (%d of %d columns) -> A %.3f | gpu accumulation %.3f | dropped (exact) max %.3f | err max %.3e rms %.3e" % (
@@ -114,7 +115,7 @@ def check_inequality(tag, got, a, x, kpb, got32=None, max_cols=None):
     print(line)
     zero = mag == 0
     assert not got[zero].any(), "%s: %d elements with sum|a x| = 0 are not exactly 0" % (tag, int((got[zero] != 0).sum()))
-    over = err - (np.abs(dropped) + A * ws.EPS * mag + ws.EPS * np.abs(ref))
+    over = err - (np.abs(dropped) + A * sb.EPS * mag + sb.EPS * np.abs(ref))
     assert float(over.max()) <= 0.0, "%s: element %d misses the limit by %.3e (err %.3e)" % (tag, int(over.argmax()), float(over.max()),
                                                                                             float(err.reshape(-1)[over.argmax()]))
     return c_emu, c_gpu

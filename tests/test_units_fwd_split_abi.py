@@ -15,6 +15,7 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib, synth
 
+from . import split_bound as sb
 from . import units_fwd_split as fs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,23 +123,23 @@ def test_the_gpu_inequality_discriminates(K, pattern, signs, form):
     w = synth.make_adversarial((160, K), pattern, "same", seed=3)
     x = fs.as_map_form(synth.make_adversarial((M, K), pattern if form == "f32" else 0x7FE000, signs, seed=4, relu=(pattern == 0x7FFFFF)) * np.float32(2.0 ** -4), form)
     nplanes = {"f32": 3, "f16": 2, "bf16": 1}[form]
-    assert fs.planes_used(x) == nplanes and fs.planes_used(w) == 3
+    assert sb.planes_used(x) == nplanes and sb.planes_used(w) == 3
     ref, dropped, mag = fs.terms(w, x)
     if form == "bf16":
         assert not dropped.any()                                     # nothing is dropped on bf16 maps
     emu = fs.emulate(w, x)
-    c = fs.c_acc(emu, ref, dropped, mag)
+    c = sb.c_acc(emu, ref, dropped, mag)
     A = max(1.0, 2.0 * c)
     print("K %4d pattern 0x%06X %-11s %-4s maps: emulated c_acc %.3f, A %.3f, dropped max %.3f" % (
-        K, pattern, signs, form, c, A, float((np.abs(dropped) / np.maximum(fs.EPS * mag, 1e-300)).max())))
-    assert fs.excess(emu, ref, dropped, mag, A) <= 0.0
+        K, pattern, signs, form, c, A, float((np.abs(dropped) / np.maximum(sb.EPS * mag, 1e-300)).max())))
+    assert sb.excess(emu, ref, dropped, mag, A) <= 0.0
     # the ReLU is 1-Lipschitz: the bound of the pre-activation holds for G against max(ref64, 0)
     G, _D = fs.outputs(emu)
-    assert fs.excess(G, np.maximum(ref[:, :fs.GEN], 0.0), dropped[:, :fs.GEN], mag[:, :fs.GEN], A) <= 0.0
+    assert sb.excess(G, np.maximum(ref[:, :fs.GEN], 0.0), dropped[:, :fs.GEN], mag[:, :fs.GEN], A) <= 0.0
     for skip in range(len(synth.SPLIT_PRODUCTS)):
         lost = fs.emulate(w, x, skip=skip)
-        if skip in fs.NOT_ISSUED[nplanes]:
+        if skip in sb.NOT_ISSUED[nplanes]:
             # a product the form does not issue adds exact zeros: the three- / five-product kernel computes the six-product values
             assert np.array_equal(lost, emu), (skip, synth.SPLIT_PRODUCTS[skip])
         else:
-            assert fs.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])
+            assert sb.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])

@@ -14,6 +14,7 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib, synth
 
+from . import split_bound as sb
 from . import wgrad_split as ws
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,20 +117,20 @@ def test_the_gpu_inequality_discriminates_in_the_chunked_form(pattern, signs, fo
     a = synth.make_adversarial((K, 160), pattern, "same", seed=3, relu=(pattern == 0x7FFFFF))
     x = as_map_form(synth.make_adversarial((K, C), pattern if form == "f32" else 0x7FE000, signs, seed=4, k_axis=0) * np.float32(2.0 ** -4), form)
     nplanes = {"f32": 3, "f16": 2, "bf16": 1}[form]
-    assert ws.planes_used(x) == nplanes and ws.planes_used(a) == 3
+    assert sb.planes_used(x) == nplanes and sb.planes_used(a) == 3
     ref, dropped, mag = ws.terms(a, x)
     if form == "bf16":
         assert not dropped.any()                                     # nothing is dropped on bf16 maps
     emu = ws.emulate_chunked(a, x, kpb)
-    c = ws.c_acc(emu, ref, dropped, mag)
+    c = sb.c_acc(emu, ref, dropped, mag)
     A = max(1.0, 2.0 * c)
     print("pattern 0x%06X %-11s %-4s maps: emulated c_acc %.3f, A %.3f, dropped max %.3f" % (
-        pattern, signs, form, c, A, float((np.abs(dropped) / np.maximum(ws.EPS * mag, 1e-300)).max())))
-    assert ws.excess(emu, ref, dropped, mag, A) <= 0.0
+        pattern, signs, form, c, A, float((np.abs(dropped) / np.maximum(sb.EPS * mag, 1e-300)).max())))
+    assert sb.excess(emu, ref, dropped, mag, A) <= 0.0
     for skip in range(len(synth.SPLIT_PRODUCTS)):
         lost = ws.emulate_chunked(a, x, kpb, skip=skip)
-        if skip in ws.NOT_ISSUED[nplanes]:
+        if skip in sb.NOT_ISSUED[nplanes]:
             # a product the form does not issue adds exact zeros: the three- / five-product kernel computes the six-product values
             assert np.array_equal(lost, emu), (skip, synth.SPLIT_PRODUCTS[skip])
         else:
-            assert ws.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])
+            assert sb.excess(lost, ref, dropped, mag, A) > 0.0, (skip, synth.SPLIT_PRODUCTS[skip])

@@ -1,6 +1,6 @@
 """What the tests of the split-fp32 units forward share (tests/test_units_fwd_split_abi.py on the CPU, tests/test_gpu_units_fwd_split.py on
-the GPU): the CPU model of csrc/units_fwd_split.hip's arithmetic and the inequality both files assert.  A helper module like
-tests/wgrad_split.py: no tests of its own, no torch.
+the GPU): the CPU model of csrc/units_fwd_split.hip's arithmetic; the inequality both files assert of it is tests/split_bound.py's.  A helper
+module like tests/wgrad_split.py: no tests of its own, no torch.
 
 The kernel's contraction index is the channel: one 32-k MFMA step per 32 consecutive channels over the whole C, in increasing order, no
 chunks -- synth.emulate_split_dot(form="units") over the whole C as it stands; then v = (A1 + A2) + bias in fp32, G = max(v, 0) for
@@ -9,7 +9,6 @@ import numpy as np
 
 from offk_amd import synth
 
-EPS = synth.SPLIT_EPS
 GEN = 128
 
 
@@ -38,25 +37,6 @@ def terms(w, x, bias=None):
     return ref, dropped, mag
 
 
-def c_acc(emulated, ref, dropped, mag):
-    return float(synth.split_c_acc(emulated, ref, dropped, mag).max())
-
-
-def over(got, ref, dropped, mag, A):
-    """per element |got - ref64| - (|dropped64| + A 2^-24 magnitude + 2^-24 |ref64|): <= 0 where the inequality holds"""
-    return np.abs(np.asarray(got, dtype=np.float64) - ref) - (np.abs(dropped) + A * EPS * mag + EPS * np.abs(ref))
-
-
-def excess(got, ref, dropped, mag, A):
-    return float(over(got, ref, dropped, mag, A).max())
-
-
-def planes_used(x):
-    """How many bf16 planes the values of x need: 1 (bf16-valued), 2 (fp16-valued, or any value of <= 16 significant bits), 3."""
-    _h, m, l = synth.cut3(x)
-    return 3 if l.any() else (2 if m.any() else 1)
-
-
 def as_map_form(x, form):
     """fp32 values a map of that form can hold: "f32" as they are, "bf16" truncated to the leading plane, "f16" rounded to fp16."""
     if form == "bf16":
@@ -64,8 +44,3 @@ def as_map_form(x, form):
     if form == "f16":
         return x.astype(np.float16).astype(np.float32)
     return x
-
-
-# SPLIT_PRODUCTS indices a map form does not issue (their x plane does not exist): bf16 maps have x_h only, fp16 maps x_h and x_m
-NOT_ISSUED = {1: tuple(i for i, (_a, b) in enumerate(synth.SPLIT_PRODUCTS) if b > 0), 2: tuple(i for i, (_a, b) in enumerate(synth.SPLIT_PRODUCTS) if b > 1),
-              3: ()}

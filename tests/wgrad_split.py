@@ -1,6 +1,6 @@
 """What the tests of the split-fp32 weight gradient share (tests/test_wgrad_split_abi.py on the CPU, tests/test_gpu_wgrad_split.py on the
-GPU): the CPU model of csrc/units_wgrad_split.hip's CHUNKED arithmetic and the inequality both files assert.  A helper module like
-tests/arena.py: no tests of its own, no torch.
+GPU): the CPU model of csrc/units_wgrad_split.hip's CHUNKED arithmetic; the inequality both files assert of it is tests/split_bound.py's.  A
+helper module like tests/arena.py: no tests of its own, no torch.
 
 The kernel's contraction index runs over K-tiles: 32 pixels of one frame, ceil(HW / 32) tiles per frame, pad pixels zeros.  A block
 owns `kpb` consecutive K-tiles (a chunk) and runs synth.emulate_split_dot(form="units") over them -- one 32-k MFMA step per K-tile, a in
@@ -9,7 +9,6 @@ import numpy as np
 
 from offk_amd import synth
 
-EPS = synth.SPLIT_EPS
 KT = 32                                   # pixels per K-tile
 
 
@@ -41,23 +40,3 @@ def terms(a, x):
     """(ref64, dropped64, sum|a x|) of dW^T [C, 160] = x^T a: synth.split_terms with a as w.  `dropped` is what the planes of THESE operands
     drop: all of a_m x_l + a_l x_m + a_l x_l for fp32 maps, a_l x_m alone where x is fp16-valued (x_l = 0), nothing where it is bf16-valued."""
     return synth.split_terms(np.ascontiguousarray(np.asarray(a, dtype=np.float32).T), np.ascontiguousarray(np.asarray(x, dtype=np.float32).T))
-
-
-def c_acc(emulated, ref, dropped, mag):
-    return float(synth.split_c_acc(emulated, ref, dropped, mag).max())
-
-
-def excess(got, ref, dropped, mag, A):
-    """max over elements of |got - ref64| - (|dropped64| + A 2^-24 sum|a x| + 2^-24 |ref64|): <= 0 where the inequality holds."""
-    return float((np.abs(np.asarray(got, dtype=np.float64) - ref) - (np.abs(dropped) + A * EPS * mag + EPS * np.abs(ref))).max())
-
-
-def planes_used(x):
-    """How many bf16 planes the values of x need: 1 (bf16-valued), 2 (fp16-valued, or any value of <= 16 significant bits), 3."""
-    _h, m, l = synth.cut3(x)
-    return 3 if l.any() else (2 if m.any() else 1)
-
-
-# SPLIT_PRODUCTS indices a map form does not issue (their x plane does not exist): bf16 maps have x_h only, fp16 maps x_h and x_m
-NOT_ISSUED = {1: tuple(i for i, (_a, b) in enumerate(synth.SPLIT_PRODUCTS) if b > 0), 2: tuple(i for i, (_a, b) in enumerate(synth.SPLIT_PRODUCTS) if b > 1),
-              3: ()}
