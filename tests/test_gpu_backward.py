@@ -4,7 +4,7 @@ autograd (oracle/off_oracle.py, pinned to the reference's gradients by tests/tes
 and against the committed gradient goldens.
 
 Tolerance: gradients are sums of up to N*H*W ~ 3.5e5 products; RTOL = 2e-4 of each tensor's max magnitude
-(the north_star bar is 1e-3), written here.
+(the north_star bar is 1e-3), written in tests/units_grad.py with the helpers this file shares with the other units files.
 """
 import os
 
@@ -16,63 +16,9 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
+from .units_grad import DROP_P, RTOL, cotangents, dev, device_relu_masks, grad_views, rel_err, rt, unit_drop  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-RTOL = 2e-4
-DROP_P = 0.8
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from offk_amd import runtime
-    return runtime
-
-
-def dev(a):
-    t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-    return t.cuda().contiguous()
-
-
-def rel_err(got, ref):
-    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
-    return float((got - ref).abs().max() / max(float(ref.abs().max()), 1e-30))
-
-
-def cotangents(P):
-    return [torch.from_numpy(synth.uniform_values(0xC07 + i, P * spec.NUM_CLASSES, 1.0).reshape(P, spec.NUM_CLASSES))
-            for i in range(3)]
-
-
-def unit_drop(seed, P, p=DROP_P):
-    return [torch.from_numpy(synth.dropout_keep(seed, si, P, H, p)).float() / (1.0 - p)
-            for si, (_n, _c, H) in enumerate(spec.SITES)]
-
-
-def grad_views(dm):
-    """nine [P,160,H,H] -> the three fusion-buffer gradients, channels-last, + per-site (tensor, coff)."""
-    groups = ((0, 1), (2, 3, 4, 5, 6), (7, 8))
-    views = [None] * spec.NUM_SITES
-    for grp in groups:
-        buf = dev(torch.cat([dm[i] for i in grp], dim=1).permute(0, 2, 3, 1).contiguous())
-        for k, i in enumerate(grp):
-            views[i] = (buf, 160 * k)
-    return views
-
-
-def device_relu_masks(h, feats_cpu, w, B, L, slack=1e-5):
-    """The ReLU decisions the device took (saved G > 0) as nine [N,128,H,H] 0/1 tensors, after checking that
-    they differ from the oracle's own only for pre-activations within rounding distance of zero."""
-    masks = []
-    for (site, _c, H), x in zip(spec.SITES, feats_cpu):
-        G = h.region("G_" + site, 128).view(B * L, H * H, 128).permute(0, 2, 1).reshape(B * L, 128, H, H).cpu()
-        with torch.no_grad():
-            pre = torch.nn.functional.conv2d(x, w["motion_conv_gen_%s.weight" % site], w["motion_conv_gen_%s.bias" % site])
-        mask = (G > 0)
-        flip = mask != (pre > 0)
-        assert int(flip.sum()) <= 5 + slack * flip.numel(), site
-        if flip.any():
-            assert float(pre[flip].abs().max()) < slack * max(1.0, float(pre.abs().max())), site
-        masks.append(mask.float())
-    return masks
 
 
 def make(rt, B, L, variant, slice_mode=spec.SLICE_FLAT, precision="fp32"):

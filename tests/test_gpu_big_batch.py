@@ -355,7 +355,7 @@ def test_units_training_side_at_n_2142(world):
     tests/test_gpu_backward.py does): every unit-parameter gradient within that file's RTOL, the feature-map gradient of the checked
     clips within it too, and the feature-map gradient of EVERY other clip exactly zero."""
     from offk_amd import runtime as rt
-    from .test_gpu_backward import RTOL as RTOL_GRAD
+    from .units_grad import RTOL as RTOL_GRAD
     wd = world
     h = rt.OffForward(B, L, spec.VARIANT_RGB, spec.SLICE_PER_CLIP, False, precision="fp32", training=True)
     assert h.load_state_dict(synth.make_weights(spec.VARIANT_RGB)) == []

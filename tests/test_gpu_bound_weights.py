@@ -24,7 +24,7 @@ from offk_amd import spec, synth
 
 from . import weight_updates as wu
 from .arena import same_bits
-from .test_gpu_feat_grad import random_views
+from .units_grad import random_views
 from .test_gpu_parity import HANDLE_PRECISIONS, dev, rt  # noqa: F401
 from .test_gpu_weight_updates import CONFIGS, differing, feats, run
 

@@ -1,44 +1,28 @@
 """16-bit feature maps on split-fp32 handles (offk_forward_typed, offk_forward_parts_typed, offk_off_units_fused_typed;
 csrc/pw_tdiff_f16.hip).  The contract is equality, not a tolerance: for finite maps everything the 16-bit path computes is
 torch.equal to what the same handle computes from the maps upcast to fp32 (include/offk.h)."""
-import ctypes
-
 import pytest
 import torch
 
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
+from . import featmaps as fm
 from .featmaps import (  # noqa: F401
-    bit_maps, heavy_maps, relu_maps, rt, unit_regions, make_handle)
+    bit_maps, heavy_maps, relu_maps, rt, make_handle)
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
+KIND = fm.KINDS["typed"]
+DTYPES = KIND.dtypes
 
 
 def units_equal(h, x16):
-    h.workspace.fill_(0xff)                            # (NaN in every float: what the units leave unwritten shows)
-    h.off_units_fused([x.float() for x in x16])
-    ref = unit_regions(h)
-    h.workspace.fill_(0xff)
-    h.off_units_fused(x16)
-    got = unit_regions(h)
-    torch.cuda.synchronize()
-    for a, b in zip(got, ref):
-        assert torch.isfinite(a).all()
-        assert torch.equal(a, b)
+    fm.units_equal(h, KIND, x16)
 
 
 def split_parts(x, i):
-    """Channel groups of map i in concat order (multiples of 32; 1 .. 4 groups by site)."""
-    C = x.shape[1]
-    cuts = [[C], [C // 2 // 32 * 32, C], [64, 128, C], [32, 96, 224, C]][i % 4]
-    parts, a = [], 0
-    for b in cuts:
-        parts.append(x[:, a:b].contiguous())
-        a = b
-    return parts
+    return fm.split_parts(KIND, x, i)
 
 
 # ---- 1. the units stage ----
@@ -121,54 +105,13 @@ def test_forward_f16_against_oracle(rt):
 
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_forward_typed_capture_and_determinism(rt, name):
-    B, L = 3, 7
-    h = make_handle(rt, B, L)
-    x16 = relu_maps(B, L, DTYPES[name], 21)
-    arr = h._feat_array(x16, rt._check_dev16)
-    fdt = _lib.FEAT_BF16 if name == "bf16" else _lib.FEAT_F16
-    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
-
-    def launch():
-        _lib.check(h.lib.offk_forward_typed(h._h, rt._stream(h.device), fdt, arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
-                                            ctypes.c_void_p(h.workspace.data_ptr())), h._h)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    eager = [o.clone() for o in out]
-    again = h.forward(x16)
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(eager, again))
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
-    for o in out:
-        o.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(eager, out))
+    fm.forward_capture_and_determinism(rt, KIND, name)
 
 
 # ---- 6. what is refused, before any launch ----
 
-def _raw_call(h, rt, fdt, x16):
-    """offk_forward_typed straight through ctypes (no Python-side checks); returns (rc, message)."""
-    arr = (ctypes.c_void_p * spec.NUM_SITES)(*[x.data_ptr() for x in x16])
-    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
-    rc = h.lib.offk_forward_typed(h._h, rt._stream(h.device), fdt, arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
-                                  ctypes.c_void_p(h.workspace.data_ptr()))
-    return rc, h.lib.offk_last_error(h._h).decode()
-
-
 def _assert_refused(h, rt, fdt, x16, needle):
-    h.workspace.fill_(0x5a)
-    torch.cuda.synchronize()
-    rc, msg = _raw_call(h, rt, fdt, x16)
-    torch.cuda.synchronize()
-    assert rc == -1 and needle in msg, (rc, msg)
-    assert bool((h.workspace == 0x5a).all())              # nothing was enqueued
+    fm.assert_forward_refused(h, rt, KIND, fdt, x16, needle)
 
 
 def test_refusals(rt, monkeypatch):
@@ -216,48 +159,17 @@ def test_refusals(rt, monkeypatch):
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_nonfinite_maps(rt, name):
     """Inf / NaN in a 16-bit map: every D row it touches is non-finite in all 32 channels; every other unit output stays finite."""
-    B, L = 2, 3
-    dt = DTYPES[name]
-    x16 = relu_maps(B, L, dt, 5)
-    x16[0][1, 7, 3, 4] = float("inf")                  # site 3a, frame 1 (clip 0), pixel (3, 4)
-    x16[8][2, 100, 5, 6] = float("nan")                # site 5b, frame 2 (clip 0), pixel (5, 6)
-    h = make_handle(rt, B, L)
-    h.off_units_fused(x16)
-    torch.cuda.synchronize()
-    P = h.P
-    D3a = h.region("D_3a", 32).view(P, 28, 28, 32)
-    D5b = h.region("D_5b", 32).view(P, 7, 7, 32)
-    assert not torch.isfinite(D3a[1, 3, 4]).any() and not torch.isfinite(D5b[2, 5, 6]).any()
-    m3 = torch.ones(P, 28, 28, dtype=torch.bool, device="cuda")
-    m3[1, 3, 4] = False
-    m5 = torch.ones(P, 7, 7, dtype=torch.bool, device="cuda")
-    m5[2, 5, 6] = False
-    assert torch.isfinite(D3a[m3]).all() and torch.isfinite(D5b[m5]).all()
+    fm.nonfinite_maps(rt, KIND, name)
 
 
 # ---- 8. the modules under torch.autocast ----
-
-class ToyBackbone(torch.nn.Module):
-    """Nine maps of the inception shapes out of a 3-channel 28 x 28 input (1x1 convs after average pooling) and a score."""
-
-    def __init__(self):
-        super().__init__()
-        self.convs = torch.nn.ModuleList(torch.nn.Conv2d(3, C, 1) for _, C, _ in spec.SITES)
-        self.fc = torch.nn.Linear(3, spec.NUM_CLASSES)
-
-    def forward(self, x):
-        feats = []
-        for (_, _C, H), conv in zip(spec.SITES, self.convs):
-            feats.append(torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous())
-        return feats, self.fc(x.mean(dim=(2, 3)))
-
 
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_bninception_off_under_autocast(rt, name):
     from offk_amd.off_module import BNInception_OFF
     B, L = 2, 3
     torch.manual_seed(0)
-    bb = ToyBackbone().cuda()
+    bb = fm.ToyBackbone(score=True).cuda()
     model = BNInception_OFF(num_classes=spec.NUM_CLASSES, batch=B, length=L, variant="rgb", backbone=bb, precision="f32split").cuda()
     model.off.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(spec.VARIANT_RGB).items()})
     x = torch.randn(B * L, 3, 28, 28, device="cuda")

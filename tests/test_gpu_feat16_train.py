@@ -12,50 +12,30 @@ import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 from oracle import off_oracle as orc
 
+from . import featmaps as fm
 from .featmaps import (  # noqa: F401
-    DROP_P, DROP_SEED, _units_node, cotangents, device_relu_masks, grad_views, maps_of_kind, oracle_dm, rel_err,
-    relu_maps, rt, run_units, unit_drop, written, make_train_handle as make_handle)
+    DROP_P, DROP_SEED, STEMS, ToyBackbone, _units_node, cotangents, device_relu_masks, grad_views, maps_of_kind, oracle_dm, rel_err,
+    relu_maps, rt, unit_drop, make_train_handle as make_handle)
+from .units_grad import RTOL          # the fp32 path's bound against the oracle
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
+KIND = fm.KINDS["typed"]
+DTYPES = KIND.dtypes
 VARIANTS = {"rgb": spec.VARIANT_RGB, "flow": spec.VARIANT_FLOW}
 SHAPES = [(1, 2), (2, 3), (3, 4), (5, 7), (2, 9)]
-RTOL = 2e-4          # tests/test_gpu_backward.py's bound for the fp32 path against the oracle
 
 
 def assert_forward_equal(h, x16):
-    x32 = [x.float() for x in x16]
-    for train in (False, True):
-        ref = run_units(h, x32, train)
-        got = run_units(h, x16, train)
-        torch.cuda.synchronize()
-        assert len(got) == 27
-        for (name, a), (_n, b) in zip(got, ref):
-            assert a.dtype == torch.float32 and torch.isfinite(a).all(), (name, train)
-            assert torch.equal(a, b), (name, train)
+    fm.assert_forward_equal(h, KIND, x16)
 
 
 def assert_backward_equal(h, x16, views):
-    """The flat gradient buffer of the typed backward equals the untyped one's on x.float(): overwritten, and accumulated onto a
-    pre-filled buffer.  Each backward follows the forward on the same maps (G / D are bit-equal either way)."""
-    x32 = [x.float() for x in x16]
-    n = h.new_unit_grads().numel()
-    g = torch.Generator(device="cuda").manual_seed(n)
-    fill = torch.randn(n, device="cuda", generator=g)
-    res = {}
-    for tag, x in (("f32", x32), ("x16", x16)):
-        h.off_units_train(x, DROP_SEED, DROP_P)
-        over = torch.full((n,), float("nan"), device="cuda")
-        h.off_units_backward(x, views, DROP_SEED, DROP_P, grads=over, accumulate=False)
-        acc = fill.clone()
-        h.off_units_backward(x, views, DROP_SEED, DROP_P, grads=acc, accumulate=True)
-        res[tag] = (over, acc)
-    torch.cuda.synchronize()
-    for a, b in zip(res["x16"], res["f32"]):
-        assert a.dtype == torch.float32 and torch.isfinite(a).all()
-        assert torch.equal(a, b)
-    assert not torch.equal(res["x16"][1], fill) and float(res["x16"][0].abs().max()) > 0
+    fm.assert_backward_equal(h, KIND, x16, views)
+
+
+def _assert_refused(h, rt, fdt, x16, views, needle, stems=STEMS):
+    fm.assert_refused(h, rt, KIND, fdt, [x.data_ptr() for x in x16], views, needle, stems)
 
 
 # ---- 1. forward equality ----
@@ -134,17 +114,6 @@ def test_backward_16bit_maps_vs_oracle(rt, name, variant, seed):
 
 
 # ---- 5. OFFUnits behind an autocast backbone ----
-
-class ToyBackbone(torch.nn.Module):
-    """Nine maps of the inception shapes out of a 3-channel 28 x 28 input (1x1 convs after average pooling)."""
-
-    def __init__(self):
-        super().__init__()
-        self.convs = torch.nn.ModuleList(torch.nn.Conv2d(3, C, 1) for _, C, _ in spec.SITES)
-
-    def forward(self, x):
-        return [torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous() for (_, _C, H), conv in zip(spec.SITES, self.convs)]
-
 
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_off_units_under_autocast(rt, name):
@@ -233,81 +202,10 @@ def test_off_units_under_autocast(rt, name):
 def test_train_and_backward_capture(rt, name):
     """off_units_train followed by off_units_backward on 16-bit maps, captured in a torch.cuda.graph and replayed twice:
     bit-identical to the eager run."""
-    B, L = 3, 4
-    h = make_handle(rt, B, L)
-    x16 = relu_maps(B, L, DTYPES[name], 21)
-    views = grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT))
-    grads = h.new_unit_grads()
-
-    def launch():
-        h.off_units_train(x16, DROP_SEED, DROP_P)
-        h.off_units_backward(x16, views, DROP_SEED, DROP_P, grads=grads, accumulate=False)
-
-    launch()
-    torch.cuda.synchronize()
-    eager_g, eager_w = grads.clone(), written(h)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()                                       # warm-up on the capture stream
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
-    for _ in range(2):
-        grads.fill_(float("nan"))
-        h.workspace.fill_(0xff)
-        g.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(grads, eager_g)
-        for (n, a), (_n, b) in zip(written(h), eager_w):
-            assert torch.equal(a, b), n
+    fm.train_and_backward_capture(rt, KIND, name)
 
 
 # ---- 7. what is refused, before any launch ----
-
-def _raw_calls(h, rt, fdt, x16, views, grads, entries):
-    """The typed entries named in `entries` straight through ctypes (no Python-side checks); [(entry, rc, message)]."""
-    arr = (ctypes.c_void_p * spec.NUM_SITES)(*[x.data_ptr() for x in x16])
-    gv = (_lib.OffkGradView * spec.NUM_SITES)()
-    for i, (t, coff) in enumerate(views):
-        gv[i].data, gv[i].cstride, gv[i].coff = t.data_ptr(), t.shape[-1], int(coff)
-    ws, st = ctypes.c_void_p(h.workspace.data_ptr()), rt._stream(h.device)
-    G = torch.zeros(h.N * 28 * 28, 128, device="cuda")
-    D = torch.zeros(h.P * 28 * 28, 32, device="cuda")
-    out = []
-    for entry, call in (
-            ("offk_pw_reduce_typed", lambda: h.lib.offk_pw_reduce_typed(h._h, st, fdt, 0, ctypes.c_void_p(x16[0].data_ptr()),
-                                                                        ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(D.data_ptr()))),
-            ("offk_off_units_typed", lambda: h.lib.offk_off_units_typed(h._h, st, fdt, arr, ws)),
-            ("offk_off_units_train_typed", lambda: h.lib.offk_off_units_train_typed(h._h, st, fdt, arr, ws, DROP_SEED, DROP_P)),
-            ("offk_off_units_backward_typed", lambda: h.lib.offk_off_units_backward_typed(h._h, st, fdt, arr, gv, ws, DROP_SEED, DROP_P,
-                                                                                          ctypes.c_void_p(grads.data_ptr()), 0))):
-        if entry not in entries:
-            continue
-        rc = call()
-        out.append((entry, rc, h.lib.offk_last_error(h._h).decode()))
-    torch.cuda.synchronize()
-    assert not G.any() and not D.any()
-    return out
-
-
-ENTRIES = ("offk_pw_reduce_typed", "offk_off_units_typed", "offk_off_units_train_typed", "offk_off_units_backward_typed")
-
-
-def _assert_refused(h, rt, fdt, x16, views, needle, entries=ENTRIES):
-    h.workspace.fill_(0x5a)
-    grads = torch.full((h.new_unit_grads().numel(),), 3.25, device="cuda")
-    torch.cuda.synchronize()
-    seen = 0
-    for entry, rc, msg in _raw_calls(h, rt, fdt, x16, views, grads, entries):
-        assert rc == -1 and needle in msg and entry in msg, (entry, rc, msg)
-        seen += 1
-    assert seen == len(entries)
-    torch.cuda.synchronize()
-    assert bool((h.workspace == 0x5a).all()) and bool((grads == 3.25).all())      # nothing was enqueued
-
 
 def test_refusals(rt):
     B, L = 2, 3
@@ -327,7 +225,7 @@ def test_refusals(rt):
         bad[site].copy_(s)
         assert bad[site].data_ptr() % 8 == 2
         _assert_refused(h, rt, _lib.FEAT_BF16, bad, views, "8-byte aligned",
-                        ENTRIES if site == 0 else ENTRIES[1:])
+                        STEMS if site == 0 else STEMS[1:])
         with pytest.raises(_lib.OffkError, match="8-byte aligned"):
             h.off_units_train(bad, DROP_SEED, DROP_P)
     # null maps

@@ -1,26 +1,21 @@
 """torch.channels_last feature maps on split-fp32 handles (offk_forward_cl, offk_forward_parts_cl, offk_off_units_fused_cl;
 csrc/pw_tdiff_cl.hip).  The contract is equality, not a tolerance: for finite maps everything the channels-last path computes is
 torch.equal to what the same handle computes from the contiguous (NCHW) copy of the same logical tensor (include/offk.h)."""
-import ctypes
-
 import pytest
 import torch
 
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
+from . import featmaps as fm
 from .featmaps import (  # noqa: F401
-    bit_maps, bit_maps32, heavy_maps, relu_maps, rt, unit_regions, make_handle)
+    bit_maps, bit_maps32, heavy_maps, relu_maps, rt, to_cl, make_handle)
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
-FDT = {"f32": _lib.FEAT_F32, "bf16": _lib.FEAT_BF16, "f16": _lib.FEAT_F16}
+KIND = fm.KINDS["cl"]
+DTYPES = KIND.dtypes
 RTOL = 2e-4                                            # tests/test_gpu_parity.py's, of the tensor's max magnitude
-
-
-def to_cl(x):
-    return x.contiguous(memory_format=torch.channels_last)
 
 
 def to_nchw(x):
@@ -28,32 +23,11 @@ def to_nchw(x):
 
 
 def units_equal(h, x):
-    """off_units_fused on the channels_last copies == off_units_fused on the contiguous copies, every region finite."""
-    xn, xc = [to_nchw(t) for t in x], [to_cl(t) for t in x]
-    assert all(t.is_contiguous() for t in xn)
-    assert all(c.shape == t.shape and not c.is_contiguous() and c.is_contiguous(memory_format=torch.channels_last) for c, t in zip(xc, xn))
-    assert h.takes_channels_last(xc) and not h.takes_channels_last(xn)
-    h.workspace.fill_(0xff)                            # (NaN in every float: what the units leave unwritten shows)
-    h.off_units_fused(xn)
-    ref = unit_regions(h)
-    h.workspace.fill_(0xff)
-    h.off_units_fused(xc)
-    got = unit_regions(h)
-    torch.cuda.synchronize()
-    for a, b in zip(got, ref):
-        assert torch.isfinite(a).all() and torch.isfinite(b).all()
-        assert torch.equal(a, b)
+    fm.units_equal(h, KIND, x)
 
 
 def split_parts(x, i):
-    """Channel groups of map i in concat order (multiples of 32; 1 .. 4 groups by site), each channels_last on its own."""
-    C = x.shape[1]
-    cuts = [[C], [C // 2 // 32 * 32, C], [64, 128, C], [32, 96, 224, C]][i % 4]
-    parts, a = [], 0
-    for b in cuts:
-        parts.append(to_cl(x[:, a:b]))
-        a = b
-    return parts
+    return fm.split_parts(KIND, x, i)
 
 
 # ---- 1. the units stage ----
@@ -152,54 +126,13 @@ def test_off_subnetwork_takes_channels_last_maps(rt):
 
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_forward_cl_capture_and_determinism(rt, name):
-    B, L = 3, 7
-    h = make_handle(rt, B, L)
-    xc = [to_cl(t) for t in relu_maps(B, L, DTYPES[name], 21)]
-    arr = h._feat_array(xc, rt._check_dev_cl)
-    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
-
-    def launch():
-        _lib.check(h.lib.offk_forward_cl(h._h, rt._stream(h.device), FDT[name], arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
-                                         ctypes.c_void_p(h.workspace.data_ptr())), h._h)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    eager = [o.clone() for o in out]
-    assert all(torch.isfinite(o).all() for o in eager)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
-    for o in out:
-        o.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(eager, out))
-    again = h.forward(xc)
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(eager, again))
+    fm.forward_capture_and_determinism(rt, KIND, name)
 
 
 # ---- 6. what is refused, before any launch ----
 
-def _raw_call(h, rt, fdt, xs):
-    """offk_forward_cl straight through ctypes (no Python-side checks); returns (rc, message)."""
-    arr = (ctypes.c_void_p * spec.NUM_SITES)(*[x.data_ptr() for x in xs])
-    out = [torch.empty(h.out_rows(), spec.NUM_CLASSES, device="cuda") for _ in range(3)]
-    rc = h.lib.offk_forward_cl(h._h, rt._stream(h.device), fdt, arr, *[ctypes.c_void_p(o.data_ptr()) for o in out],
-                               ctypes.c_void_p(h.workspace.data_ptr()))
-    return rc, h.lib.offk_last_error(h._h).decode()
-
-
 def _assert_refused(h, rt, fdt, xs, needle):
-    h.workspace.fill_(0x5a)
-    torch.cuda.synchronize()
-    rc, msg = _raw_call(h, rt, fdt, xs)
-    torch.cuda.synchronize()
-    assert rc == -1 and needle in msg, (rc, msg)
-    assert bool((h.workspace == 0x5a).all())              # nothing was enqueued
+    fm.assert_forward_refused(h, rt, KIND, fdt, xs, needle)
 
 
 def test_refusals(rt, monkeypatch):
@@ -246,19 +179,4 @@ def test_refusals(rt, monkeypatch):
 @pytest.mark.parametrize("name", list(DTYPES))
 def test_nonfinite_maps(rt, name):
     """Inf / NaN in a channels_last map: every D row it touches is non-finite in all 32 channels; every other unit output stays finite."""
-    B, L = 2, 3
-    x = relu_maps(B, L, DTYPES[name], 5)
-    x[0][1, 7, 3, 4] = float("inf")                    # site 3a, frame 1 (clip 0), pixel (3, 4)
-    x[8][2, 100, 5, 6] = float("nan")                  # site 5b, frame 2 (clip 0), pixel (5, 6)
-    h = make_handle(rt, B, L)
-    h.off_units_fused([to_cl(t) for t in x])
-    torch.cuda.synchronize()
-    P = h.P
-    D3a = h.region("D_3a", 32).view(P, 28, 28, 32)
-    D5b = h.region("D_5b", 32).view(P, 7, 7, 32)
-    assert not torch.isfinite(D3a[1, 3, 4]).any() and not torch.isfinite(D5b[2, 5, 6]).any()
-    m3 = torch.ones(P, 28, 28, dtype=torch.bool, device="cuda")
-    m3[1, 3, 4] = False
-    m5 = torch.ones(P, 7, 7, dtype=torch.bool, device="cuda")
-    m5[2, 5, 6] = False
-    assert torch.isfinite(D3a[m3]).all() and torch.isfinite(D5b[m5]).all()
+    fm.nonfinite_maps(rt, KIND, name)

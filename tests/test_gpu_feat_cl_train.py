@@ -3,8 +3,6 @@ offk_off_units_train_cl, offk_off_units_backward_cl; the channels-last loaders o
 csrc/units_bwd.hip).  The contract is equality, not a tolerance: everything a _cl call writes -- G, D, the unit channels of the
 fusion buffers, the flat gradient buffer -- is torch.equal to what the NCHW call of the same dtype writes from the contiguous
 copies of the same logical tensors (include/offk.h).  All inputs here are finite, so no case is left out of the equality."""
-import ctypes
-
 import pytest
 import torch
 
@@ -12,58 +10,32 @@ import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 from oracle import off_oracle as orc
 
+from . import featmaps as fm
 from .featmaps import (  # noqa: F401
-    DROP_P, DROP_SEED, _units_node, cotangents, device_relu_masks, grad_views, maps_of_kind, oracle_dm, rel_err,
-    relu_maps, rt, run_units, unit_drop, written, make_train_handle as make_handle)
+    DROP_P, DROP_SEED, STEMS, ToyBackbone, _units_node, cotangents, device_relu_masks, grad_views, maps_of_kind, oracle_dm, rel_err,
+    relu_maps, rt, run_units, to_cl, unit_drop, make_train_handle as make_handle)
+from .units_grad import RTOL          # the fp32 path's bound against the oracle
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+KIND = fm.KINDS["cl"]
+DTYPES = KIND.dtypes
 VARIANTS = {"rgb": spec.VARIANT_RGB, "flow": spec.VARIANT_FLOW}
 SHAPES = [(1, 2), (2, 3), (3, 4), (5, 7), (2, 9)]
-RTOL = 2e-4          # tests/test_gpu_backward.py's bound for the fp32 path against the oracle
 CLAST = torch.channels_last
 
 
-def to_cl(xs):
-    """The channels_last copies of contiguous maps: same logical tensors, physically [N, H, H, C]."""
-    out = [x.contiguous(memory_format=CLAST) for x in xs]
-    assert all(not c.is_contiguous() and c.is_contiguous(memory_format=CLAST) and torch.equal(c, x) for c, x in zip(out, xs))
-    return out
-
-
 def assert_forward_equal(h, x):
-    """x: contiguous maps.  off_units and off_units_train on their channels_last copies write what they write on x."""
-    xcl = to_cl(x)
-    for train in (False, True):
-        ref = run_units(h, x, train)
-        got = run_units(h, xcl, train)
-        torch.cuda.synchronize()
-        assert len(got) == 27
-        for (name, a), (_n, b) in zip(got, ref):
-            assert a.dtype == torch.float32 and torch.isfinite(a).all(), (name, train)
-            assert torch.equal(a, b), (name, train)
+    """x: contiguous maps."""
+    fm.assert_forward_equal(h, KIND, x)
 
 
 def assert_backward_equal(h, x, views):
-    """The flat gradient buffer of the backward on the channels_last copies equals the one on the contiguous maps x:
-    overwritten, and accumulated onto a pre-filled buffer.  Each backward follows the forward on the same maps."""
-    n = h.new_unit_grads().numel()
-    g = torch.Generator(device="cuda").manual_seed(n)
-    fill = torch.randn(n, device="cuda", generator=g)
-    res = {}
-    for tag, xs in (("nchw", x), ("cl", to_cl(x))):
-        h.off_units_train(xs, DROP_SEED, DROP_P)
-        over = torch.full((n,), float("nan"), device="cuda")
-        h.off_units_backward(xs, views, DROP_SEED, DROP_P, grads=over, accumulate=False)
-        acc = fill.clone()
-        h.off_units_backward(xs, views, DROP_SEED, DROP_P, grads=acc, accumulate=True)
-        res[tag] = (over, acc)
-    torch.cuda.synchronize()
-    for a, b in zip(res["cl"], res["nchw"]):
-        assert a.dtype == torch.float32 and torch.isfinite(a).all()
-        assert torch.equal(a, b)
-    assert not torch.equal(res["cl"][1], fill) and float(res["cl"][0].abs().max()) > 0
+    fm.assert_backward_equal(h, KIND, x, views)
+
+
+def _assert_refused(h, rt, fdt, ptrs, views, needle, stems=STEMS, kind=KIND):
+    fm.assert_refused(h, rt, kind, fdt, ptrs, views, needle, stems)
 
 
 # ---- 1. forward equality ----
@@ -143,19 +115,6 @@ def test_backward_channels_last_maps_vs_oracle(rt, name, variant, seed):
 
 # ---- 5. OFFUnits behind a channels_last backbone ----
 
-class ToyBackbone(torch.nn.Module):
-    """Nine maps of the inception shapes out of a 3-channel 28 x 28 input (1x1 convs after average pooling), handed over in
-    torch.channels_last as a backbone run in that memory format does."""
-
-    def __init__(self):
-        super().__init__()
-        self.convs = torch.nn.ModuleList(torch.nn.Conv2d(3, C, 1) for _, C, _ in spec.SITES)
-
-    def forward(self, x):
-        return [torch.relu(conv(torch.nn.functional.avg_pool2d(x, 28 // H))).contiguous(memory_format=CLAST)
-                for (_, _C, H), conv in zip(spec.SITES, self.convs)]
-
-
 @pytest.mark.parametrize("name", ["none", "bf16", "f16"])
 def test_off_units_behind_channels_last_backbone(rt, name):
     from offk_amd.off_module import OFFUnits
@@ -165,7 +124,7 @@ def test_off_units_behind_channels_last_backbone(rt, name):
     dt = torch.float32 if name == "none" else DTYPES[name]
     autocast = (lambda: contextlib.nullcontext()) if name == "none" else (lambda: torch.autocast("cuda", dtype=dt))
     torch.manual_seed(0)
-    bb = ToyBackbone().cuda().requires_grad_(False)                 # the frozen backbone
+    bb = ToyBackbone(CLAST).cuda().requires_grad_(False)            # the frozen backbone
     wnp = synth.make_weights(spec.VARIANT_RGB)
     wg = {k: t.cuda() for k, t in orc.to_torch_weights(wnp).items()}
     cot = [c.cuda() for c in cotangents(P)]
@@ -246,82 +205,10 @@ def test_off_units_behind_channels_last_backbone(rt, name):
 def test_train_and_backward_capture(rt, name):
     """off_units_train followed by off_units_backward on channels_last maps, captured in a torch.cuda.graph on one stream and
     replayed twice: bit-identical to the eager run."""
-    B, L = 3, 4
-    h = make_handle(rt, B, L)
-    xcl = to_cl(relu_maps(B, L, DTYPES[name], 21))
-    views = grad_views(oracle_dm(spec.VARIANT_RGB, B, L, spec.SLICE_FLAT))
-    grads = h.new_unit_grads()
-
-    def launch():
-        h.off_units_train(xcl, DROP_SEED, DROP_P)
-        h.off_units_backward(xcl, views, DROP_SEED, DROP_P, grads=grads, accumulate=False)
-
-    launch()
-    torch.cuda.synchronize()
-    eager_g, eager_w = grads.clone(), written(h)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()                                       # warm-up on the capture stream
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
-    for _ in range(2):
-        grads.fill_(float("nan"))
-        h.workspace.fill_(0xff)
-        g.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(grads, eager_g)
-        for (n, a), (_n, b) in zip(written(h), eager_w):
-            assert torch.equal(a, b), n
+    fm.train_and_backward_capture(rt, KIND, name)
 
 
 # ---- 7. what is refused, before any launch; and which handles are not ----
-
-ENTRIES = ("offk_pw_reduce", "offk_off_units", "offk_off_units_train", "offk_off_units_backward")      # + "_cl" (or "_typed")
-
-
-def _raw_calls(h, rt, fdt, ptrs, views, grads, entries, suffix="_cl"):
-    """The entries named in `entries` (+ suffix) straight through ctypes (no Python-side checks); [(entry, rc, message)]."""
-    arr = (ctypes.c_void_p * spec.NUM_SITES)(*ptrs)
-    gv = (_lib.OffkGradView * spec.NUM_SITES)()
-    for i, (t, coff) in enumerate(views):
-        gv[i].data, gv[i].cstride, gv[i].coff = t.data_ptr(), t.shape[-1], int(coff)
-    ws, st = ctypes.c_void_p(h.workspace.data_ptr()), rt._stream(h.device)
-    G = torch.zeros(h.N * 28 * 28, 128, device="cuda")
-    D = torch.zeros(h.P * 28 * 28, 32, device="cuda")
-    fn = lambda stem: getattr(h.lib, stem + suffix)
-    out = []
-    for entry, call in (
-            ("offk_pw_reduce" + suffix, lambda: fn("offk_pw_reduce")(h._h, st, fdt, 0, ctypes.c_void_p(ptrs[0]),
-                                                                    ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(D.data_ptr()))),
-            ("offk_off_units" + suffix, lambda: fn("offk_off_units")(h._h, st, fdt, arr, ws)),
-            ("offk_off_units_train" + suffix, lambda: fn("offk_off_units_train")(h._h, st, fdt, arr, ws, DROP_SEED, DROP_P)),
-            ("offk_off_units_backward" + suffix, lambda: fn("offk_off_units_backward")(h._h, st, fdt, arr, gv, ws, DROP_SEED, DROP_P,
-                                                                                      ctypes.c_void_p(grads.data_ptr()), 0))):
-        if entry[:-len(suffix)] not in entries:
-            continue
-        rc = call()
-        out.append((entry, rc, h.lib.offk_last_error(h._h).decode()))
-    torch.cuda.synchronize()
-    assert not G.any() and not D.any()
-    return out
-
-
-def _assert_refused(h, rt, fdt, ptrs, views, needle, entries=ENTRIES, suffix="_cl"):
-    h.workspace.fill_(0x5a)
-    grads = torch.full((h.new_unit_grads().numel(),), 3.25, device="cuda")
-    torch.cuda.synchronize()
-    seen = 0
-    for entry, rc, msg in _raw_calls(h, rt, fdt, ptrs, views, grads, entries, suffix):
-        assert rc == -1 and needle in msg and entry in msg, (entry, rc, msg)
-        seen += 1
-    assert seen == len(entries)
-    torch.cuda.synchronize()
-    assert bool((h.workspace == 0x5a).all()) and bool((grads == 3.25).all())      # nothing was enqueued
-
 
 def test_refusals(rt):
     B, L = 2, 3
@@ -333,8 +220,8 @@ def test_refusals(rt):
     # an unknown dtype
     _assert_refused(h, rt, 7, ptrs, views, "unknown feat_dtype")
     # a null map: site 3a for pw_reduce (its own wording), the last site for the nine-map entries
-    _assert_refused(h, rt, _lib.FEAT_F32, [None] + ptrs[1:], views, "bad argument", ENTRIES[:1])
-    _assert_refused(h, rt, _lib.FEAT_BF16, ptrs[:8] + [None], views, "null feature map", ENTRIES[1:])
+    _assert_refused(h, rt, _lib.FEAT_F32, [None] + ptrs[1:], views, "bad argument", STEMS[:1])
+    _assert_refused(h, rt, _lib.FEAT_BF16, ptrs[:8] + [None], views, "null feature map", STEMS[1:])
     # a map whose pointer is 4 mod 16: site 3a for pw_reduce, and another site for the nine-map entries
     for site in (0, 4):
         s = x[site]
@@ -347,7 +234,7 @@ def test_refusals(rt):
         bad[site] = off
         for fdt in (_lib.FEAT_F32, _lib.FEAT_F16):
             _assert_refused(h, rt, fdt, [t.data_ptr() for t in bad], views, "16-byte aligned (site %s)" % spec.SITES[site][0],
-                            ENTRIES if site == 0 else ENTRIES[1:])
+                            STEMS if site == 0 else STEMS[1:])
         with pytest.raises(_lib.OffkError, match="16-byte aligned"):
             h.off_units_train(bad, DROP_SEED, DROP_P)
         if site == 0:
@@ -376,7 +263,7 @@ def test_refusals(rt):
     # an NHWC handle's _typed calls are refused as before, and so is its untyped backward
     hn = make_handle(rt, B, L, feat_layout=1)
     x16 = [t.to(torch.bfloat16) for t in x]
-    _assert_refused(hn, rt, _lib.FEAT_BF16, [t.data_ptr() for t in x16], views, "NCHW", suffix="_typed")
+    _assert_refused(hn, rt, _lib.FEAT_BF16, [t.data_ptr() for t in x16], views, "NCHW", kind=fm.KINDS["typed"])
     nhwc = [t.permute(0, 2, 3, 1).contiguous() for t in x]
     with pytest.raises(_lib.OffkError, match="NCHW feature maps only"):
         hn.off_units_backward(nhwc, views, DROP_SEED, DROP_P)

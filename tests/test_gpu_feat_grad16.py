@@ -25,36 +25,17 @@ from offk_amd import _lib, spec, synth
 
 from . import arena as arena_mod
 from . import exact
-from .test_gpu_feat_grad import Case, case, dev, make_units, module_cots, random_views
+from . import units_dx_checks as checks
+from .units_dx_checks import LAYOUTS, old_values
+from .units_grad import DX_TYPED as FORM
+from .units_grad import Case, bits16, case, dev, make_units, module_cots, random_views, rows16, rt, same_bits16  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DTYPES = [torch.bfloat16, torch.float16]
+DTYPES = list(FORM.dtypes)
 DT_IDS = ["bf16", "fp16"]
-LAYOUTS = ["nchw", "cl"]
 SHAPES = [(1, 2, spec.VARIANT_RGB, spec.SLICE_FLAT), (2, 3, spec.VARIANT_RGB, spec.SLICE_FLAT), (3, 4, spec.VARIANT_RGB, spec.SLICE_PER_CLIP),
           (5, 9, spec.VARIANT_FLOW, spec.SLICE_PER_CLIP)]
 IDS = ["b1l2", "b2l3_flat", "b3l4_clip", "b5l9_clip_flow"]
-FEAT = {torch.bfloat16: _lib.FEAT_BF16, torch.float16: _lib.FEAT_F16}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    from offk_amd import runtime
-    return runtime
-
-
-def bits16(t):
-    return t.contiguous().view(torch.int16)
-
-
-def same_bits16(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(bits16(a), bits16(b))
-
-
-def rows16(t, layout):
-    """[N, C, H, H] 16-bit result of either layout -> [N * HW, C], on the device."""
-    assert t.dim() == 4 and (t.permute(0, 2, 3, 1).is_contiguous() if layout == "cl" else t.is_contiguous())
-    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
 
 
 # ---- 1. the rounding, pinned independently of the fp32 kernel ----
@@ -169,12 +150,6 @@ def test_rounding_is_nearest_even(rt, dtype, layout):
 
 # ---- 2. the contract ----
 
-def old_values(like, seed, scale):
-    gen = torch.Generator(device="cuda").manual_seed(seed)
-    return [(scale * float(t.float().abs().max()) * torch.randn(t.shape, device="cuda", generator=gen)).to(t.dtype).contiguous(
-        memory_format=torch.channels_last if not t.is_contiguous() else torch.contiguous_format) for t in like]
-
-
 def check_contract(h, dtype, what):
     """dx16 == dx32.to(dtype); accumulate: (old.float() + dx32).to(dtype); both layouts the same bits."""
     dx32 = h.off_units_backward_feats(layout="nchw")
@@ -234,58 +209,15 @@ def test_contract_on_exact_integer_inputs(rt, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
 def test_two_runs_and_a_graph_replay_are_equal(rt, dtype):
-    c = case(rt, 3, 4, spec.VARIANT_RGB, spec.SLICE_PER_CLIP, 7)
-    c.run()
-    first = c.h.off_units_backward_feats(layout="nchw", dtype=dtype)
-    again = c.h.off_units_backward_feats(layout="nchw", dtype=dtype)
-    torch.cuda.synchronize()
-    assert all(float(a.float().abs().max()) > 0 and same_bits16(a, b) for a, b in zip(first, again))
-    # backward + the 16-bit dX call in one graph, one replay, for either layout
-    grads = c.h.new_unit_grads()
-    outs = {"nchw": [torch.empty_like(t) for t in first], "cl": [torch.empty_like(t, memory_format=torch.channels_last) for t in first]}
-
-    def launch():
-        c.backward(grads=grads)
-        for layout in LAYOUTS:
-            c.h.off_units_backward_feats(layout=layout, out=outs[layout], dtype=dtype)
-
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
-    for layout in LAYOUTS:
-        for t in outs[layout]:
-            t.fill_(float("nan"))
-    g.replay()
-    torch.cuda.synchronize()
-    for layout in LAYOUTS:
-        assert all(same_bits16(a, b.contiguous()) for a, b in zip(first, outs[layout])), layout
+    checks.equal_bits(FORM, case(rt, 3, 4, spec.VARIANT_RGB, spec.SLICE_PER_CLIP, 7), (dtype,))
 
 
+# (the id names the maps' form, the dtype beside it is the gradient's: fp32 channels_last maps hand out an fp16 gradient here)
 @pytest.mark.parametrize("kind,dtype", [("typed_bf16", torch.bfloat16), ("cl_f32", torch.float16), ("cl_f16", torch.float16)],
                          ids=["typed_bf16", "cl_f32", "cl_f16"])
 def test_same_bits_after_the_plain_typed_and_cl_backward(rt, kind, dtype):
     """The three backward forms leave the same dG / dD on the same logical maps, so the 16-bit dX is the same too."""
-    B, L = 2, 3
-    c = Case(rt, B, L, spec.VARIANT_RGB, spec.SLICE_FLAT, 7)
-    dt = {"typed_bf16": torch.bfloat16, "cl_f32": torch.float32, "cl_f16": torch.float16}[kind]
-    x = [f.to(dt) for f in c.feats]
-    plain = [t.float() for t in x]
-    other = [t.contiguous(memory_format=torch.channels_last) for t in x] if kind.startswith("cl") else x
-    res = []
-    for feats in (plain, other):
-        c.forward(feats)
-        c.backward(feats)
-        res.append([c.h.off_units_backward_feats(layout=layout, dtype=dtype) for layout in LAYOUTS])
-    torch.cuda.synchronize()
-    for lay in range(2):
-        for a, b in zip(res[0][lay], res[1][lay]):
-            assert float(a.float().abs().max()) > 0 and same_bits16(a.contiguous(), b.contiguous())
+    checks.same_bits_after_the_other_backwards(FORM, Case(rt, 2, 3, spec.VARIANT_RGB, spec.SLICE_FLAT, 7), kind, dtype)
 
 
 # ---- 3. memory discipline ----
@@ -295,95 +227,18 @@ def test_same_bits_after_the_plain_typed_and_cl_backward(rt, kind, dtype):
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
 @pytest.mark.parametrize("B,L,slice_mode", [(1, 2, spec.SLICE_FLAT), (3, 4, spec.SLICE_PER_CLIP)], ids=["b1l2", "b3l4_clip"])
 def test_memory_discipline(rt, B, L, slice_mode, dtype, layout, accumulate):
-    """Every output is a carve of exactly its 2-byte elements inside one arena of sentinel (each 16-bit half of the sentinel word is
-    a NaN of both types): the bands on both sides of all nine and the carves of the skipped sites keep every half-word."""
-    c = case(rt, B, L, spec.VARIANT_RGB, slice_mode, 7)
-    c.run()
-    shapes = spec.feature_shapes(B, L)
-    ar = arena_mod.Arena.for_sizes([2 * int(np.prod(s)) for s in shapes])
-    skipped = (1, 6)
-    want = c.h.off_units_backward_feats(layout=layout, dtype=dtype)
-    dx32 = c.h.off_units_backward_feats(layout=layout)
-    old = old_values(want, 5, 1.0)
-
-    def carve(i):
-        n, ch, hh, _ = shapes[i]
-        shape = (n, ch, hh, hh) if layout == "nchw" else (n, hh, hh, ch)
-        if accumulate and i not in skipped:
-            t = ar.put("dx_%d" % i, old[i] if layout == "nchw" else old[i].permute(0, 2, 3, 1))
-        else:
-            t = ar.empty("dx_%d" % i, shape, dtype=dtype)
-        assert t.data_ptr() % 16 == 0 and t.element_size() == 2
-        return t if layout == "nchw" else t.permute(0, 3, 1, 2)
-
-    bufs = [carve(i) for i in range(9)]
-    got = c.h.off_units_backward_feats(sites=[i for i in range(9) if i not in skipped], layout=layout,
-                                       out=[None if i in skipped else b for i, b in enumerate(bufs)], accumulate=accumulate, dtype=dtype)
-    torch.cuda.synchronize()
-    ar.check()
-    for i in range(9):
-        if i in skipped:
-            assert got[i] is None and ar.untouched(bufs[i] if layout == "nchw" else bufs[i].permute(0, 2, 3, 1))
-        else:
-            assert not bool(torch.isnan(got[i].float()).any())
-            assert torch.equal(got[i], (old[i].float() + dx32[i]).to(dtype) if accumulate else want[i]), spec.SITES[i][0]
+    checks.memory_discipline(FORM, case(rt, B, L, spec.VARIANT_RGB, slice_mode, 7), layout, dtype, accumulate)
 
 
 # ---- 4. refusals ----
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
 def test_refusals_leave_the_outputs_untouched(rt, dtype):
-    B, L = 1, 2
-    shapes = spec.feature_shapes(B, L)
-    outs = [torch.full(tuple(s), float("nan"), device="cuda", dtype=dtype) for s in shapes]
-    keep = [bits16(t).clone() for t in outs]
-    arr = (ctypes.c_void_p * 9)(*[t.data_ptr() for t in outs])
-    lib = _lib.load()
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fd = FEAT[dtype]
-
-    def refused(h, ws, a, gd, layout, needle):
-        rc = lib.offk_off_units_backward_feats_typed(h._h, stream, ws, gd, a, layout, 0)
-        assert rc == -1 and needle in lib.offk_last_error(h._h), lib.offk_last_error(h._h)
-
-    h = rt.OffForward(B, L, spec.VARIANT_RGB, training=True)
-    assert h.load_state_dict(synth.make_weights(spec.VARIANT_RGB)) == []
-    ws = ctypes.c_void_p(h.workspace.data_ptr())
-    # a fresh handle: no backward has run on it
-    refused(h, ws, arr, fd, _lib.FEAT_NCHW, b"no offk_off_units_backward has run")
-    feats = [dev(f) for f in synth.make_features(B, L, 3)]
-    h.off_units(feats)
-    h.off_units_backward(feats, random_views(B * (L - 1))[1])
-    for bad in (3, -1, 4):
-        refused(h, ws, arr, bad, _lib.FEAT_NCHW, b"grad_dtype must be")
-    refused(h, ws, arr, fd, 2, b"layout must be")
-    mis = (ctypes.c_void_p * 9)(*[t.data_ptr() for t in outs])
-    mis[4] = outs[4].data_ptr() + 2                      # aligned for its element, not to 16 bytes
-    refused(h, ws, mis, fd, _lib.FEAT_NHWC, b"16-byte aligned")
-    over = (ctypes.c_void_p * 9)(*[t.data_ptr() for t in outs])
-    over[8] = h.workspace.data_ptr() + 256
-    refused(h, ws, over, fd, _lib.FEAT_NCHW, b"overlaps the workspace")
-    # ... and one that begins in front of the workspace and ends 16 bytes inside it (its size counted in 2-byte elements)
-    n8 = 2 * int(np.prod(shapes[8]))
-    over[8] = h.workspace.data_ptr() - n8 + 16
-    refused(h, ws, over, fd, _lib.FEAT_NCHW, b"overlaps the workspace")
-    # the wrapper: out= of another dtype than the one asked for
-    with pytest.raises(ValueError, match="bf16" if dtype == torch.bfloat16 else "fp16"):
-        h.off_units_backward_feats(out=[t.float() for t in outs], dtype=dtype)
-    with pytest.raises(ValueError, match="fp32"):
-        h.off_units_backward_feats(out=outs)
-    with pytest.raises(ValueError, match="dtype must be"):
-        h.off_units_backward_feats(dtype=torch.float64)
-    # all nine NULL: OFFK_OK, nothing enqueued
-    assert lib.offk_off_units_backward_feats_typed(h._h, stream, ws, fd, (ctypes.c_void_p * 9)(), _lib.FEAT_NCHW, 0) == 0
-    assert h.off_units_backward_feats(sites=[], dtype=dtype) == [None] * 9
-    torch.cuda.synchronize()
-    assert all(torch.equal(bits16(t), k) for t, k in zip(outs, keep))
+    h, lib, stream, ws = checks.refusals(rt, FORM, dtype)
     # OFFK_FEAT_F32 through the typed entry is the fp32 entry: same bits
     a = h.off_units_backward_feats(layout="nchw")
     b = [torch.empty_like(t) for t in a]
-    assert lib.offk_off_units_backward_feats_typed(h._h, stream, ws, _lib.FEAT_F32, (ctypes.c_void_p * 9)(*[t.data_ptr() for t in b]),
-                                                   _lib.FEAT_NCHW, 0) == 0
+    assert FORM.raw(lib, h._h, stream, ws, _lib.FEAT_F32, (ctypes.c_void_p * 9)(*[t.data_ptr() for t in b]), _lib.FEAT_NCHW) == 0
     torch.cuda.synchronize()
     assert all(arena_mod.same_bits(x, y) for x, y in zip(a, b))
 

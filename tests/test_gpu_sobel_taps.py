@@ -21,9 +21,8 @@ from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
 from . import exact
-from . import test_gpu_backward as bw
 from . import test_gpu_exact as ge
-from . import test_gpu_feat_grad as fg
+from . import units_grad as ug
 from . import weight_updates as wu
 from .arena import same_bits
 from .test_gpu_parity import HANDLE_PRECISIONS, _check_sobel_tdiff, dev, make_handle, rt  # noqa: F401
@@ -120,8 +119,8 @@ def test_sobel_tdiff_vs_oracle_with_a_dense_weight(rt, algo):
         _check_sobel_tdiff(h, w, B, L, site, FLOW, algo)
 
 
-class DenseCase(fg.Case):
-    """tests/test_gpu_feat_grad.py's Case (a training handle after forward + backward on random dM) on the dense Sobel weight."""
+class DenseCase(ug.Case):
+    """tests/units_grad.py's Case (a training handle after forward + backward on random dM) on the dense Sobel weight."""
 
     def __init__(self, rt, B, L, slice_mode, seed):
         self.B, self.L, self.variant, self.slice_mode, self.seed = B, L, FLOW, slice_mode, seed
@@ -132,8 +131,8 @@ class DenseCase(fg.Case):
         self.w = orc.to_torch_weights(self.wnp)
         self.feats_np = synth.make_features(B, L, 2 if B == 2 else 3)
         self.feats = [dev(f) for f in self.feats_np]
-        self.bufs, self.views = fg.random_views(self.P)
-        self.drop = (0, 0.0) if seed is None else (seed, fg.DROP_P)
+        self.bufs, self.views = ug.random_views(self.P)
+        self.drop = (0, 0.0) if seed is None else (seed, ug.DROP_P)
 
 
 @pytest.mark.parametrize("B,L,slice_mode,seed", [(2, 3, spec.SLICE_FLAT, None), (3, 4, spec.SLICE_PER_CLIP, 7)], ids=["b2l3_eval", "b3l4_clip_drop"])
@@ -146,22 +145,22 @@ def test_units_and_backward_vs_oracle_with_a_dense_weight(rt, B, L, slice_mode, 
     dx = c.h.off_units_backward_feats(layout="nchw")
     torch.cuda.synchronize()
     tf = [torch.from_numpy(f) for f in c.feats_np]
-    drops = None if seed is None else fg.unit_drop(seed, c.P)
+    drops = None if seed is None else ug.unit_drop(seed, c.P)
     with torch.no_grad():
         m_ref = [orc.off_unit(x, c.w, site, B, L, FLOW, slice_mode, None if drops is None else drops[si])
                  for si, ((site, _c, _h), x) in enumerate(zip(spec.SITES, tf))]
     for (site, _C, H), (reg, cs, coff), ref in zip(spec.SITES, ge.UNIT_SLOTS, m_ref):
         m = c.h.region(reg, cs).view(c.P, H, H, cs)[..., coff:coff + spec.UNIT_CH].permute(0, 3, 1, 2)
-        assert bw.rel_err(m[:, :spec.DOWN_CH], ref[:, :spec.DOWN_CH]) < bw.RTOL, site
-        assert bw.rel_err(m, ref) < bw.RTOL, site
-    masks = fg.device_relu_masks(c.h, tf, c.w, B, L)
+        assert ug.rel_err(m[:, :spec.DOWN_CH], ref[:, :spec.DOWN_CH]) < ug.RTOL, site
+        assert ug.rel_err(m, ref) < ug.RTOL, site
+    masks = ug.device_relu_masks(c.h, tf, c.w, B, L)
     dm = [buf[..., coff:coff + spec.UNIT_CH].permute(0, 3, 1, 2).cpu() for buf, coff in c.views]
     ref = orc.unit_param_grads_from_dm(tf, c.w, B, L, FLOW, slice_mode, dm, drops, masks)
     assert set(got) == set(ref)
-    bad = dict((k, "%.2e" % bw.rel_err(got[k], ref[k])) for k in ref if not bw.rel_err(got[k], ref[k]) < bw.RTOL or got[k].shape != ref[k].shape)
+    bad = dict((k, "%.2e" % ug.rel_err(got[k], ref[k])) for k in ref if not ug.rel_err(got[k], ref[k]) < ug.RTOL or got[k].shape != ref[k].shape)
     assert not bad, bad
-    for si, g, r in zip(range(spec.NUM_SITES), dx, fg.oracle_dx(c)):
-        assert fg.rel_err(g, r) < fg.RTOL, (spec.SITES[si][0], fg.rel_err(g, r))
+    for si, g, r in zip(range(spec.NUM_SITES), dx, ug.oracle_dx(c)):
+        assert ug.rel_err(g, r) < ug.RTOL, (spec.SITES[si][0], ug.rel_err(g, r))
 
 
 # ---- four-tap -> dense -> four-tap ----------------------------------------------------------------------------------------------------

@@ -31,9 +31,9 @@ from . import head_bwd as hb
 from . import ranges as rg
 from . import test_gpu_conv_s2_dgrad_split as tds
 from . import test_gpu_conv_wgrad_split as tcw
-from . import test_gpu_feat_grad_split as tfs
-from . import test_gpu_units_fwd_split as tuf
-from . import test_gpu_wgrad_split as twg
+from . import units_fwd_split as tuf
+from . import units_grad as ug
+from . import wgrad_split as twg
 from .featmaps import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -162,8 +162,8 @@ def units_case(rt, tag, map_kw, w_kw, b_kw, g_scale, g_kw=None):
         a, x = twg.site_operands(h, B, L, slice_mode, si, maps[si])
         assert float(np.abs(a).max()) > 0
         twg.check_inequality("%s weight gradient site %s" % (tag, name), twg.dw_t(got, si), a, x, twg.KPB[0], max_cols=128)
-        a2, wk = tfs.operands(h, B, L, slice_mode, si, w160[si][:128], w160[si][128:])
-        tfs.check_inequality("%s map gradient site %s" % (tag, name), tfs.rows_of(dx[si]), a2, wk)
+        a2, wk = ug.dx_operands(h, B, L, slice_mode, si, w160[si][:128], w160[si][128:])
+        ug.dx_check_inequality("%s map gradient site %s" % (tag, name), ug.rows_of(dx[si]), a2, wk)
 
 
 def test_wide_draw_units_split_entries(rt):
@@ -469,7 +469,7 @@ def test_nonfinite_units_map_gradient(rt, arith):
     assert h.load_state_dict(w) == []
     maps = [cuda(rg.wide((N, C, H, H), 840 + si, relu=True)) for si, (_n, C, H) in enumerate(spec.SITES)]
     h.off_units(maps)
-    h.off_units_backward(maps, tfs.fg.random_views(P)[1])             # sets the backward-has-run flag; its dG / dD are replaced below
+    h.off_units_backward(maps, ug.random_views(P)[1])             # sets the backward-has-run flag; its dG / dD are replaced below
     fills = [(cuda(rg.scale(rg.wide_t((N * H * H, 128), 860 + si), G_SCALE)), cuda(rg.scale(rg.wide_t((P * H * H, 32), 880 + si), G_SCALE)))
              for si, (_n, _C, H) in enumerate(spec.SITES)]
 
@@ -486,7 +486,7 @@ def test_nonfinite_units_map_gradient(rt, arith):
     fill()
     clean = run()
     assert all(bool(torch.isfinite(t).all()) and bool((t != 0).any()) for t in clean)
-    r_of = tfs.fg.down_rows(B, L, slice_mode)
+    r_of = ug.down_rows(B, L, slice_mode)
     inside = torch.tensor([r >= 0 for r in r_of])
     assert not bool(inside.all())
 
@@ -600,7 +600,7 @@ def test_nonfinite_units_training_forward(rt, arith):
     B, L, slice_mode, w, h, maps = units_plant_setup(rt, 900)
     N, P = B * L, B * (L - 1)
     split = arith == "f32split"
-    r_of = tfs.fg.down_rows(B, L, slice_mode)
+    r_of = ug.down_rows(B, L, slice_mode)
 
     def run(weights, feats):
         if weights is not None:

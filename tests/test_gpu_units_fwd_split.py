@@ -32,23 +32,13 @@ from oracle import off_oracle as orc
 from . import arena as arena_mod
 from . import exact
 from . import featmaps as fm
-from . import split_bound as sb
 from . import test_gpu_exact as gx
-from . import test_gpu_feat_grad as fg
-from . import units_fwd_split as fs
-from .test_gpu_feat16_train import RTOL           # the default path's tolerance against the oracle's autograd (2e-4 of each tensor's max)
-from .test_gpu_wgrad_split import DTS, FORMS, IDS, SHAPES, as_form, exact_case
+from . import units_grad as ug
+from .units_fwd_split import DOWN_B, DOWN_W, GEN_B, GEN_W, check_site
+from .units_grad import DTS, FORMS, IDS, RTOL, SHAPES, as_form, exact_case, rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-GEN_W, DOWN_W, GEN_B, DOWN_B = "motion_conv_gen_%s.weight", "motion_spatial_down_%s.weight", "motion_conv_gen_%s.bias", "motion_spatial_down_%s.bias"
 SPLIT = {"arith": "f32split"}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 # ---- 1. exact integers ----
@@ -94,53 +84,6 @@ def test_equal_bits_with_the_fused_split_kernel(rt, B, L, variant, slice_mode):
 
 # ---- 3. / 4. the inequality ----
 
-def sample(n, max_rows):
-    rows = np.arange(n)
-    if max_rows is not None and n > max_rows:
-        rows = np.unique(np.concatenate((rows[:32], rows[-32:], rows[::max(1, n // (max_rows - 64))])))
-    return rows
-
-
-def check_site(tag, h, B, L, slice_mode, si, x, w160, bias, max_rows=None, default=None):
-    """Asserts the inequality for G_<site> (every row) and D_<site> (every row of the slice) on the operands (w160, x rows).  c_acc: the
-    emulation on all rows, or (max_rows) on a sample of them: the first and last 32 and a stride between; every row is a contraction of
-    its own, so a sampled row's emulation is what the full run gives for it.  Returns (emulated c_acc, measured accumulation constant)."""
-    site, C, H = spec.SITES[si]
-    HW, N = H * H, B * L
-    X = x.float().permute(0, 2, 3, 1).reshape(N * HW, C).cpu().numpy()
-    ref, dropped, mag = fs.terms(w160, X, bias)
-    rows = sample(N * HW, max_rows)
-    c_emu = sb.c_acc(fs.emulate(w160, X[rows], bias), ref[rows], dropped[rows], mag[rows])
-    A = max(1.0, 2.0 * c_emu)
-    G = h.region("G_" + site, 128).cpu().numpy().astype(np.float64)
-    Dg = h.region("D_" + site, 32).view(-1, HW, 32).cpu().numpy().astype(np.float64)
-    dr = fg.down_rows(B, L, slice_mode)
-    frames = [n for n in range(N) if dr[n] >= 0]
-    D = np.stack([Dg[dr[n]] for n in frames]).reshape(-1, 32)
-    drows = np.concatenate([np.arange(n * HW, (n + 1) * HW) for n in frames])
-    assert sorted(dr[n] for n in frames) == list(range(Dg.shape[0]))
-    unit = np.maximum(sb.EPS * mag, 1e-300)
-    g, d = slice(0, fs.GEN), slice(fs.GEN, 160)
-    over_g = sb.excess_map(G, np.maximum(ref[:, g], 0.0), dropped[:, g], mag[:, g], A)
-    over_d = sb.excess_map(D, ref[drows, d], dropped[drows, d], mag[drows, d], A)
-    pos = G > 0
-    c_gpu = max(float((np.abs(G - (ref - dropped)[:, g]) / unit[:, g])[pos].max()) if pos.any() else 0.0,
-                float((np.abs(D - (ref - dropped)[drows, d]) / unit[drows, d]).max()))
-    err = np.concatenate((np.abs(G - np.maximum(ref[:, g], 0.0)).reshape(-1), np.abs(D - ref[drows, d]).reshape(-1)))
-    line = "%s: c_acc emulated %.3f (%d of %d rows) -> A %.3f | gpu accumulation %.3f | dropped (exact) max %.3f | err max %.3e rms %.3e" % (
-        tag, c_emu, len(rows), N * HW, A, c_gpu, float((np.abs(dropped) / unit).max()), float(err.max()), float(np.sqrt((err ** 2).mean())))
-    if default is not None:
-        G0, D0 = default
-        D0 = np.stack([D0.reshape(-1, HW, 32)[dr[n]] for n in frames]).reshape(-1, 32)
-        e0 = np.concatenate((np.abs(G0 - np.maximum(ref[:, g], 0.0)).reshape(-1), np.abs(D0 - ref[drows, d]).reshape(-1)))
-        line += " | default entry: err max %.3e rms %.3e" % (float(e0.max()), float(np.sqrt((e0 ** 2).mean())))
-    print(line)
-    assert not G[mag[:, g] == 0].any() and not D[mag[drows, d] == 0].any(), "%s: elements with sum|w x| = 0 are not exactly 0" % tag
-    for name, ov in (("G", over_g), ("D", over_d)):
-        assert float(ov.max()) <= 0.0, "%s: %s element %d misses the limit by %.3e" % (tag, name, int(ov.argmax()), float(ov.max()))
-    return c_emu, c_gpu
-
-
 ADV = [(p, s) for p in (0x00FFFF, 0x7FFFFF, 0x7F7F7F) for s in ("same", "alternating")]
 WORST = [(1, 2) + ps for ps in ADV] + [(2, 3, 0x00FFFF, "same"), (2, 3, 0x7F7F7F, "alternating")]
 
@@ -173,7 +116,7 @@ def test_worst_case_mantissas(rt, B, L, pattern, signs):
         w160.append(wa)
     h = rt.OffForward(B, L, spec.VARIANT_RGB, slice_mode, training=True)
     assert h.load_state_dict(w) == []
-    maps = [fg.dev(synth.make_adversarial((N, C, H, H), pattern, signs, seed=600 + si, k_axis=1, relu=(pattern == 0x7FFFFF)))
+    maps = [ug.dev(synth.make_adversarial((N, C, H, H), pattern, signs, seed=600 + si, k_axis=1, relu=(pattern == 0x7FFFFF)))
             for si, (_n, C, H) in enumerate(spec.SITES)]
     h.workspace.fill_(0xff)
     h.off_units(maps, **SPLIT)
@@ -192,7 +135,7 @@ def test_random_inputs_within_the_bound(rt, B, L, variant, slice_mode):
     wnp = synth.make_weights(variant)
     h = rt.OffForward(B, L, variant, slice_mode, training=True)
     assert h.load_state_dict(wnp) == []
-    maps = [fg.dev(f) for f in synth.make_features(B, L, 2 if B == 2 else 3)]
+    maps = [ug.dev(f) for f in synth.make_features(B, L, 2 if B == 2 else 3)]
     h.off_units(maps)
     default = [(h.region("G_" + n, 128).cpu().numpy().astype(np.float64), h.region("D_" + n, 32).cpu().numpy().astype(np.float64)) for n, _c, _h in spec.SITES]
     h.workspace.fill_(0xff)
@@ -248,15 +191,7 @@ def test_equal_bits_properties(rt):
     def launch():
         h.off_units_train(xd, fm.DROP_SEED, fm.DROP_P, **SPLIT)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
+    g = ug.captured(launch)
     for _ in range(2):
         h.workspace.fill_(0xff)
         g.replay()
@@ -277,7 +212,7 @@ def test_bound_weights_and_in_place_updates(rt):
         if bind:
             for k, v in wnp.items():
                 if k.startswith(spec.UNIT_PARAM_PREFIXES):
-                    keep[k] = fg.dev(v)
+                    keep[k] = ug.dev(v)
                     h.bind_weight(k, keep[k])
             bound = (h, keep, wnp)
         res.append(run_split(h, x))
@@ -301,7 +236,7 @@ def test_the_backward_consumes_the_workspace_alone(rt):
     P = B * (L - 1)
     h = fm.make_train_handle(rt, B, L)
     x = some_negative(B, L, 13)
-    _bufs, views = fg.random_views(P)
+    _bufs, views = ug.random_views(P)
     regions = [("G_" + n, 128) for n, _c, _h in spec.SITES] + [("D_" + n, 32) for n, _c, _h in spec.SITES]
 
     def backwards():
@@ -328,12 +263,6 @@ def test_the_backward_consumes_the_workspace_alone(rt):
 
 # ---- 7. memory discipline and refusals ----
 
-def region_span(h, name):
-    off, nb = ctypes.c_size_t(), ctypes.c_size_t()
-    _lib.check(h.lib.offk_workspace_region(h._h, name.encode(), ctypes.byref(off), ctypes.byref(nb)), h._h)
-    return off.value, nb.value
-
-
 @pytest.mark.parametrize("layout,dt", [("nchw", "f32"), ("nchw", "bf16"), ("cl", "f32"), ("cl", "f16")])
 @pytest.mark.parametrize("B,L,slice_mode", [(1, 2, spec.SLICE_FLAT), (3, 4, spec.SLICE_PER_CLIP)])
 def test_memory_discipline(rt, B, L, slice_mode, layout, dt):
@@ -345,21 +274,15 @@ def test_memory_discipline(rt, B, L, slice_mode, layout, dt):
     maps = as_form(some_negative(B, L, 14), layout, dt)
     want = run_split(h, maps)
     torch.cuda.synchronize()
-    ar = arena_mod.Arena.for_sizes([h.workspace_bytes] + [m.numel() * m.element_size() for m in maps])
-    ws = ar.carve("workspace", h.workspace_bytes)
-    h.set_workspace(ws)
-    if layout == "nchw":
-        gm = [ar.put("map_%d" % i, m) for i, m in enumerate(maps)]
-    else:
-        gm = [ar.put("map_%d" % i, m.permute(0, 2, 3, 1)).permute(0, 3, 1, 2) for i, m in enumerate(maps)]
-        assert all(m.is_contiguous(memory_format=torch.channels_last) for m in gm)
+    ar, ws = ug.workspace_arena(h, maps)
+    gm = ug.guarded_maps(ar, maps, layout)
     h.off_units_train(gm, fm.DROP_SEED, fm.DROP_P, **SPLIT)
     torch.cuda.synchronize()
     ar.check()
     assert_same(want, fm.written(h), "arena run")
     names = ["G_" + n for n, _c, _h in spec.SITES] + ["D_" + n for n, _c, _h in spec.SITES] + ["fusion_28", "fusion_14", "fusion_7"]
-    spans = sorted(region_span(h, n) for n in names)
-    for (off, nb), (site, _c, H) in zip([region_span(h, "G_" + n) for n, _c, _h in spec.SITES], spec.SITES):
+    spans = sorted(ug.region_span(h, n) for n in names)
+    for (off, nb), (site, _c, H) in zip([ug.region_span(h, "G_" + n) for n, _c, _h in spec.SITES], spec.SITES):
         assert nb == B * L * H * H * 128 * 4, site                     # a region ends with its last row
     cursor = 0
     for off, nb in spans + [(h.workspace_bytes, 0)]:
@@ -454,7 +377,7 @@ def test_module_split_forward(rt, backbone, switches, monkeypatch):
     u.load_state_dict({k: torch.from_numpy(a) for k, a in wnp.items() if k in u.state_dict()}, strict=True)
     u.train()
     w = orc.to_torch_weights(wnp)
-    feats = [fg.dev(f) for f in synth.make_features(B, L, 2)]
+    feats = [ug.dev(f) for f in synth.make_features(B, L, 2)]
     if backbone == "autocast_bf16":
         feats = [f.bfloat16() for f in feats]
     elif backbone == "channels_last":

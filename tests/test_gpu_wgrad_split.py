@@ -20,7 +20,6 @@ Shapes (B, L): (1, 2) flat -- N = 2, the 7x7 sites are one chunk, the 28x28 site
 boundaries inside frames (25 and 7 K-tiles per frame against 4 per block); (3, 4) per-clip; (2, 3) flat, Flow; (8, 7) per-clip -- 13 K-tiles
 per block, chunks that span several frames.  All nine sites always: C % 128 = 64 (320) and 96 (608), 49-pixel rows, 1024 channels."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -33,32 +32,12 @@ from oracle import off_oracle as orc
 from . import arena as arena_mod
 from . import exact
 from . import featmaps as fm
-from . import split_bound as sb
 from . import test_gpu_exact as gx
-from . import test_gpu_feat_grad as fg
-from . import wgrad_split as ws
-from .test_gpu_feat16_train import RTOL           # the default path's tolerance against the oracle's autograd (2e-4 of each tensor's max)
+from . import units_grad as ug
+from .units_grad import DTS, FORMS, IDS, RTOL, SHAPES, as_form, exact_case, rt  # noqa: F401
+from .wgrad_split import KPB, check_inequality, dw_t, site_operands
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(1, 2, spec.VARIANT_RGB, spec.SLICE_FLAT), (2, 3, spec.VARIANT_RGB, spec.SLICE_FLAT), (3, 4, spec.VARIANT_RGB, spec.SLICE_PER_CLIP),
-          (2, 3, spec.VARIANT_FLOW, spec.SLICE_FLAT), (8, 7, spec.VARIANT_RGB, spec.SLICE_PER_CLIP)]
-IDS = ["b1l2_flat", "b2l3_flat", "b3l4_clip", "b2l3_flat_flow", "b8l7_clip"]
-KPB = [4, 4, 4, 4, 13]                                        # K-tiles per block: max(4, ceil(332 N / 1536))
-DTS = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
-FORMS = [(lay, dt) for lay in ("nchw", "cl") for dt in DTS]
-GEN_W, DOWN_W = "motion_conv_gen_%s.weight", "motion_spatial_down_%s.weight"
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def as_form(feats, layout, dt):
-    fmt = torch.contiguous_format if layout == "nchw" else torch.channels_last
-    return [f.to(DTS[dt]).contiguous(memory_format=fmt) for f in feats]
 
 
 def split_bwd(h, feats, views, seed, p, **kw):
@@ -69,64 +48,7 @@ def is_matrix(key):
     return key.endswith(".weight") and (key.startswith("motion_conv_gen_") or key.startswith("motion_spatial_down_"))
 
 
-def dw_t(got, si):
-    """[C, 160]: the two weight gradients of site si, transposed as tests/wgrad_split.py has them"""
-    site, C, _H = spec.SITES[si]
-    return torch.cat((got[GEN_W % site].reshape(128, C), got[DOWN_W % site].reshape(32, C))).t().contiguous()
-
-
-def site_operands(h, B, L, slice_mode, si, x):
-    """The GEMM's own operands of site si in K-tile order on the host: a [K, 160] from the dG_ / dD_ regions (the dD part at row r(f),
-    zeros outside the slice) and X [K, C] from the map (any dtype, any layout), frames padded to whole K-tiles."""
-    site, C, H = spec.SITES[si]
-    HW, N, P = H * H, B * L, B * (L - 1)
-    a = torch.zeros(N, HW, 160, device="cuda")
-    a[..., :128] = h.region("dG_" + site, 128).view(N, HW, 128)
-    dD = h.region("dD_" + site, 32).view(P, HW, 32)
-    for n, r in enumerate(fg.down_rows(B, L, slice_mode)):
-        if r >= 0:
-            a[n, :, 128:] = dD[r]
-    xr = x.float().permute(0, 2, 3, 1).reshape(N, HW, C)
-    return ws.pad_ktiles(a.cpu().numpy()), ws.pad_ktiles(xr.cpu().numpy())
-
-
-def check_inequality(tag, got, a, x, kpb, got32=None, max_cols=None):
-    """Asserts test 2's inequality for got [C, 160] on the operands (a, x), every element.  c_acc: the chunked emulation on the same
-    operands -- on all C channel columns, or (max_cols) on a sample of them: the first and last 32 and a stride between; every column is
-    a contraction of its own, so a sampled column's emulation is what the full run gives for it.  Prints the emulated and the measured
-    accumulation constants (the latter on all elements) and the errors against fp64, beside them the default entry's when given."""
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, dtype=np.float64)
-    ref, dropped, mag = ws.terms(a, x)
-    assert got.shape == ref.shape
-    C = x.shape[1]
-    cols = np.arange(C)
-    if max_cols is not None and C > max_cols:
-        cols = np.unique(np.concatenate((cols[:32], cols[-32:], cols[::max(1, C // (max_cols - 64))])))
-    c_emu = sb.c_acc(ws.emulate_chunked(a, x[:, cols], kpb), ref[cols], dropped[cols], mag[cols])
-    A = max(1.0, 2.0 * c_emu)
-    unit = np.maximum(sb.EPS * mag, 1e-300)
-    err = np.abs(got - ref)
-    c_gpu = float((np.abs(got - (ref - dropped)) / unit).max())
-    line = "%s: c_acc emulated %.3f (%d of %d columns) -> A %.3f | gpu accumulation %.3f | dropped (exact) max %.3f | err max %.3e rms %.3e" % (
-        tag, c_emu, len(cols), C, A, c_gpu, float((np.abs(dropped) / unit).max()), float(err.max()), float(np.sqrt((err ** 2).mean())))
-    if got32 is not None:
-        e32 = np.abs(np.asarray(got32.detach().cpu(), dtype=np.float64) - ref)
-        line += " | default entry: err max %.3e rms %.3e" % (float(e32.max()), float(np.sqrt((e32 ** 2).mean())))
-    print(line)
-    zero = mag == 0
-    assert not got[zero].any(), "%s: %d elements with sum|a x| = 0 are not exactly 0" % (tag, int((got[zero] != 0).sum()))
-    over = err - (np.abs(dropped) + A * sb.EPS * mag + sb.EPS * np.abs(ref))
-    assert float(over.max()) <= 0.0, "%s: element %d misses the limit by %.3e (err %.3e)" % (tag, int(over.argmax()), float(over.max()),
-                                                                                            float(err.reshape(-1)[over.argmax()]))
-    return c_emu, c_gpu
-
-
 # ---- 1. exact integers ----
-
-@functools.lru_cache(maxsize=None)
-def exact_case(B, L, variant, slice_mode):
-    return gx.Case(B, L, variant, slice_mode)           # (its constructor asserts exact.check_caps on every output)
-
 
 @pytest.mark.parametrize("B,L,variant,slice_mode", SHAPES, ids=IDS)
 def test_exact_integers(rt, B, L, variant, slice_mode):
@@ -195,7 +117,7 @@ def test_worst_case_mantissas(rt, B, L, pattern, signs):
         for n in range(N):
             if fs[n % L] < 0:
                 x[n] = -x[n]
-        maps.append(fg.dev(x.reshape(N, C, H, H)))
+        maps.append(ug.dev(x.reshape(N, C, H, H)))
     h.off_units(maps)
     # G decides K2b's ReLU mask only: all on, the middle frame of a three-frame clip off
     for name, _C, H in spec.SITES:
@@ -210,8 +132,8 @@ def test_worst_case_mantissas(rt, B, L, pattern, signs):
             bufs[reg] = torch.full((P, H, H, cs), 7.0, device="cuda")
         dS = synth.make_adversarial((P, H, H, 32), pattern, "same", seed=500 + si)
         dT = synth.make_adversarial((P, H, H, 128), pattern, "same", seed=400 + si, relu=relu)
-        bufs[reg][..., coff:coff + 32] = fg.dev(dS)
-        bufs[reg][..., coff + 32:coff + 160] = fg.dev(dT)
+        bufs[reg][..., coff:coff + 32] = ug.dev(dS)
+        bufs[reg][..., coff + 32:coff + 160] = ug.dev(dT)
         views.append((bufs[reg], coff))
     kpb = gx.k1b_plan(h)[1]
     assert kpb == 4
@@ -238,7 +160,7 @@ def test_worst_case_mantissas(rt, B, L, pattern, signs):
 
 @pytest.mark.parametrize("B,L,variant,slice_mode", SHAPES[:4], ids=IDS[:4])
 def test_random_backward_within_the_bound(rt, B, L, variant, slice_mode):
-    c = fg.case(rt, B, L, variant, slice_mode, 7)
+    c = ug.case(rt, B, L, variant, slice_mode, 7)
     c.forward()
     _flat, got32 = c.backward()
     got32 = dict((k, v.clone()) for k, v in got32.items())
@@ -261,7 +183,7 @@ def test_equal_bits_properties(rt):
     B, L = 2, 3
     P = B * (L - 1)
     h = fm.make_train_handle(rt, B, L)
-    _bufs, views = fg.random_views(P)
+    _bufs, views = ug.random_views(P)
     x32 = fm.relu_maps(B, L, torch.float32, 11)
     x32 = [x - 0.25 * (x > 1.0) for x in x32]                       # some negative values too
     regions = [("dG_" + n, 128) for n, _c, _h in spec.SITES] + [("dD_" + n, 32) for n, _c, _h in spec.SITES]
@@ -304,15 +226,7 @@ def test_equal_bits_properties(rt):
     def launch():
         split_bwd(h, xd, views, fm.DROP_SEED, fm.DROP_P, grads=grads)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        launch()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        launch()
+    g = ug.captured(launch)
     for _ in range(2):
         grads.fill_(float("nan"))
         g.replay()
@@ -324,7 +238,7 @@ def test_any_handle(rt):
     """A split-fp32 handle and bound weights: the same bits as the fp32 handle with set weights; the default backward of the split-fp32
     handle stays the fp32 kernel (the entry is opt-in)."""
     B, L = 1, 2
-    _bufs, views = fg.random_views(B * (L - 1))
+    _bufs, views = ug.random_views(B * (L - 1))
     x = fm.relu_maps(B, L, torch.float32, 12)
     res = []
     for prec, bind in (("fp32", False), ("f32split", True)):
@@ -335,7 +249,7 @@ def test_any_handle(rt):
         if bind:
             for k, v in wnp.items():
                 if k.startswith(spec.UNIT_PARAM_PREFIXES):
-                    keep.append(fg.dev(v))
+                    keep.append(ug.dev(v))
                     h.bind_weight(k, keep[-1])
         h.off_units_train(x, 5, fm.DROP_P)
         d = h.off_units_backward(x, views, 5, fm.DROP_P)[0].clone()
@@ -358,20 +272,14 @@ def test_memory_discipline(rt, B, L, slice_mode, layout, dt):
     h = rt.OffForward(B, L, spec.VARIANT_RGB, slice_mode, training=True)
     assert h.load_state_dict(synth.make_weights(spec.VARIANT_RGB)) == []
     maps = as_form(fm.relu_maps(B, L, torch.float32, 13), layout, dt)
-    bufs, views = fg.random_views(P)
+    bufs, views = ug.random_views(P)
     h.off_units_train(maps, 3, fm.DROP_P)
     want = split_bwd(h, maps, views, 3, fm.DROP_P)[0].clone()
     torch.cuda.synchronize()
     n = want.numel()
-    sizes = [h.workspace_bytes, 4 * n] + [m.numel() * m.element_size() for m in maps] + [4 * b.numel() for b in bufs]
-    ar = arena_mod.Arena.for_sizes(sizes)
-    h.set_workspace(ar.carve("workspace", h.workspace_bytes))
+    ar, _ws = ug.workspace_arena(h, maps, [4 * n] + [4 * b.numel() for b in bufs])
     grads = ar.empty("unit_grads", (n,))
-    if layout == "nchw":
-        gm = [ar.put("map_%d" % i, m) for i, m in enumerate(maps)]
-    else:
-        gm = [ar.put("map_%d" % i, m.permute(0, 2, 3, 1)).permute(0, 3, 1, 2) for i, m in enumerate(maps)]
-        assert all(m.is_contiguous(memory_format=torch.channels_last) for m in gm)
+    gm = ug.guarded_maps(ar, maps, layout)
     gb = [ar.put("dm_%d" % i, b) for i, b in enumerate(bufs)]
     gviews = [(gb[[id(b) for b in bufs].index(id(t))], coff) for t, coff in views]
     h.off_units_train(gm, 3, fm.DROP_P)
@@ -397,7 +305,7 @@ def test_refusals_leave_the_buffers_untouched(rt):
     h = fm.make_train_handle(rt, B, L)
     x = fm.relu_maps(B, L, torch.float32, 14)
     x16 = [t.bfloat16() for t in x]
-    _bufs, views = fg.random_views(P)
+    _bufs, views = ug.random_views(P)
     h.off_units_train(x, 3, fm.DROP_P)
     h.workspace.fill_(0x5a)
     grads = torch.full((h.new_unit_grads().numel(),), 3.25, device="cuda")
@@ -487,7 +395,7 @@ def test_module_split_wgrad(rt, backbone, monkeypatch):
     u.load_state_dict({k: torch.from_numpy(a) for k, a in wnp.items() if k in u.state_dict()}, strict=True)
     u.train()
     w = orc.to_torch_weights(wnp)
-    feats = [fg.dev(f) for f in synth.make_features(B, L, 2)]
+    feats = [ug.dev(f) for f in synth.make_features(B, L, 2)]
     if backbone == "autocast_bf16":
         feats = [f.bfloat16() for f in feats]
     elif backbone == "channels_last":

@@ -9,7 +9,7 @@ import torch
 import offk_amd  # noqa: F401
 from offk_amd import runtime, spec, synth
 from oracle import off_oracle as orc
-from test_gpu_backward import cotangents, grad_views, device_relu_masks, unit_drop
+from featmaps import cotangents, grad_views, device_relu_masks, unit_drop
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 10
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
