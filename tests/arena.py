@@ -137,3 +137,16 @@ def bits(t):
 
 def same_bits(a, b):
     return a.shape == b.shape and torch.equal(bits(a), bits(b))
+
+
+def sentinel_floats(*shape):
+    """An fp32 tensor on the device whose every word is the sentinel."""
+    n = 1
+    for s in shape:
+        n *= s
+    return torch.full((n,), SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32).view(*shape)
+
+
+def untouched(t):
+    """True when every word of a tensor made of sentinel words (sentinel_floats, an int32 fill) still holds it."""
+    return not bool((t.view(torch.int32) != SENTINEL).any())

@@ -259,3 +259,13 @@ def make_slabs(c, device="cuda", pool=None):
 def peak_bytes(c):
     """device bytes of a case's slabs (margins included)"""
     return sum(slab_bytes(c, op) for op in c.operands)
+
+
+def guarded(nbytes):
+    """(int32 words of [2 GiB margin | nbytes], all sentinel; the uint8 view of the payload)"""
+    words = torch.full(((FRONT_MARGIN + nbytes + 3) // 4,), arena.SENTINEL, dtype=torch.int32, device="cuda")
+    return words, words.view(torch.uint8)[FRONT_MARGIN:FRONT_MARGIN + nbytes]
+
+
+def margin_intact(words):
+    return not bool((words[:FRONT_MARGIN // 4] != arena.SENTINEL).any())

@@ -3,10 +3,12 @@ tests/conv_bwd.py (S1 | S2) and the runtime module.  tests/test_gpu_conv_bwd*.py
 tests/test_gpu_conv*_dgrad_split.py and tests/test_gpu_conv*_wgrad_split.py (the split-fp32 entries) keep their test functions, their
 parametrize lists and what only one stride has (the stride-1 kernel's own edges, the stride-2 range tests, the refusal texts, the module
 tests); each shared test there is a call into this module.  Where the two strides' copies once differed in an assertion the body here
-asserts both.  The `rt` fixture and `filled_bytes` live here once; the test files import them.  No tests of its own."""
+asserts both.  `filled_bytes` and the one-layer bound of the module tests (`one_layer`, `within`) live here once; the `rt` fixture is tests/featmaps.py's,
+re-exported here for the conv files.  No tests of its own."""
 import numpy as np
-import pytest
 import torch
+import torch.nn.functional as F
+from torch.nn.grad import conv2d_weight
 
 from offk_amd import synth
 
@@ -15,6 +17,7 @@ from . import conv_bwd
 from . import conv_dgrad_split, conv_s2_dgrad_split, conv_s2_wgrad_split, conv_wgrad_split
 from . import exact
 from . import split_bound as sb
+from .featmaps import rt  # noqa: F401
 
 NAN = float("nan")
 ADV = [(p, s) for p in (0x00FFFF, 0x7FFFFF, 0x7F7F7F) for s in ("same", "alternating")]
@@ -28,13 +31,6 @@ WIDE = {(1, "dgrad"): (0x6D1, [conv_bwd.Case(3, 2, 6, 10, 128, 64), conv_bwd.Cas
         (1, "wgrad"): (0x71D, [conv_bwd.Case(3, 2, 7, 7, 64, 128), conv_bwd.Case(1, 3, 7, 7, 128, 64)]),
         (2, "dgrad"): (0x5D2, [conv_bwd.Case(7, 2, 6, 10, 64, 64), conv_bwd.Case(5, 2, 6, 4, 96, 64)]),
         (2, "wgrad"): (0x72D, [conv_bwd.Case(7, 2, 12, 12, 64, 64), conv_bwd.Case(5, 3, 8, 8, 96, 64)])}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 def filled_bytes(n, value=NAN):
@@ -532,3 +528,44 @@ def wgrad_discipline(rt, form, c, least_chunks):
     assert chunks >= least_chunks
     scratch_never_shows_and_replay_equals_eager({"dw": (c.co, c.ci, c.k, c.k), "db": (c.co,)}, wbytes,
                                                 lambda b: split_wgrad(rt, form, x, g, c, dw=b["dw"], db=b["db"], scratch=b["s"]))
+
+
+# ---- the one-layer bound of the module tests ----
+def one_layer(m, fl, x, gy):
+    """(tests/test_gpu_fusion_conv_s2_module.py, tests/test_gpu_motion_head_module.py)  fp64 values, elementwise error bounds and caps (largest sum of |terms|) of one layer from exact inputs x and gy.
+    m: the fp64 nn.Conv2d.  -> {"y" | "dx" | "weight" | "bias": (value, bound)}, caps, (undecided masks, masks)"""
+    W, b, s, pad = m.weight.detach(), m.bias.detach(), m.stride[0], m.padding[0]
+    co, ci, k, _ = W.shape
+    a = torch.relu(x) if fl.get("relu_in") else x
+    z = F.conv2d(a, W, b, stride=s, padding=pad)
+    S = F.conv2d(a.abs(), W.abs(), b.abs(), stride=s, padding=pad)
+    Ez = conv_bwd.gamma(ci * k * k + 2) * S
+    relu = bool(fl.get("relu"))
+    unstable = (z.abs() <= Ez) & (Ez > 0) if relu else torch.zeros_like(z, dtype=torch.bool)
+    gz = gy * (z > 0).double() if relu else gy
+    Egz = torch.where(unstable, gy.abs(), torch.zeros_like(gy))
+    P = gz.shape[0] * gz.shape[2] * gz.shape[3]
+    op = x.shape[-1] - ((gz.shape[-1] - 1) * s - 2 * pad + k)
+
+    def cw(g, v):
+        return conv2d_weight(v, W.shape, g, stride=s, padding=pad)
+
+    def ct(g, w):
+        return F.conv_transpose2d(g, w, stride=s, padding=pad, output_padding=op)
+
+    Sw, Sb, Sx = cw(gz.abs() + Egz, a.abs()), (gz.abs() + Egz).sum((0, 2, 3)), ct(gz.abs() + Egz, W.abs())
+    mx = co * (-(-k // s)) ** 2
+    dx, Edx = ct(gz, W), ct(Egz, W.abs()) + conv_bwd.gamma(mx + 1) * Sx
+    if fl.get("relu_in"):
+        dx, Edx = dx * (x > 0).double(), Edx * (x > 0).double()
+    out = {"y": (torch.relu(z) if relu else z, Ez), "dx": (dx, Edx),
+           "weight": (cw(gz, a), cw(Egz, a.abs()) + conv_bwd.gamma(P + 1) * Sw), "bias": (gz.sum((0, 2, 3)), Egz.sum((0, 2, 3)) + conv_bwd.gamma(P + 1) * Sb)}
+    caps = {"z": float(S.max()), "dW": float(Sw.max()), "db": float(Sb.max()), "dx": float(Sx.max())}
+    return out, caps, (int(unstable.sum()), z.numel() if relu else 0)
+
+
+def within(got, val, bound, what):
+    err = (got.detach().cpu().double() - val).abs()
+    ratio = float((err / bound.clamp_min(1e-300)).max()) if bool((err > 0).any()) else 0.0
+    print("%s: largest error %.3e, largest error / bound %.3f" % (what, float(err.max()), ratio))
+    assert bool((err <= bound).all()), "%s: error is %.3f of the derived bound" % (what, ratio)

@@ -103,7 +103,7 @@ def stream(seed, kind, site=0):
 
 
 _X, _WG, _BG, _WD, _BD, _TAP, _TB, _DM = range(8)
-_SOBEL = 16          # (8 .. 15: the conv and GEMM inputs of tests/test_gpu_exact.py)
+_SOBEL = 16          # (8 .. 15: the conv and GEMM inputs of tests/exact_units.py)
 
 
 def dense_sobel(seed=1, device="cpu"):

@@ -29,9 +29,9 @@ import torch.nn.functional as F
 from offk_amd import spec
 
 from . import exact
-from .test_gpu_paths import _AT, _BT, _between_reference, _mindex
+from .wino_ref import AT as _AT, BT as _BT, between_reference as _between_reference, mindex as _mindex
 
-# kinds of tensor for exact.stream, clear of exact's own _X .. _DM (0 .. 7) and of tests/test_gpu_exact.py's 8 .. 15
+# kinds of tensor for exact.stream, clear of exact's own _X .. _DM (0 .. 7) and of tests/exact_units.py's 8 .. 15
 (_CX, _CW1, _CB1, _CW2, _CB2, _CW3, _CB3, _CWB, _CBB, _CRES, _BM, _BBIAS, _BW1, _BB1, _FW, _FB) = range(16, 32)
 
 WEIGHT_BITS = 8          # |w| < 2^8: the weight is its own top bf16 plane
@@ -218,7 +218,7 @@ def _classes():
 
 def output_transform(M, phases, absolute=False):
     """A^T M A per class, placed as the 7x7 map [n, 7, 7, c], in the dtype of M -- with the transform matrices and the point numbering of
-    tests/test_gpu_paths.py.  absolute: |A| on |M|, the sum of the absolute terms."""
+    tests/wino_ref.py.  absolute: |A| on |M|, the sum of the absolute terms."""
     dt = M.dtype
     n, cin = M.shape[1], M.shape[2]
     mat = lambda a: (torch.from_numpy(a).abs() if absolute else torch.from_numpy(a)).to(dt)   # noqa: E731
@@ -260,7 +260,7 @@ def input_transform(t, absolute=False):
 
 
 def between_reference(M, bias, phases, w1, b1):
-    """fp64: tests/test_gpu_paths.py's _between_reference for x and V, t restated beside it; and the cap pass with |A|, |w1|, |B|.
+    """fp64: tests/wino_ref.py's between_reference for x and V, t restated beside it; and the cap pass with |A|, |w1|, |B|.
     Returns (out, cap) over x [n, 7, 7, Cin], t [n, 7, 7, Cmid], V [121, n, Cmid]."""
     f64 = lambda t: None if t is None else t.double().numpy()   # noqa: E731
     x, V = _between_reference(f64(M), f64(bias), phases, f64(w1), f64(b1))

@@ -41,9 +41,9 @@ from offk_amd import spec
 
 from . import exact
 from .exact_fusion import FORWARD_SHAPES, assert_weight_bits, check_caps, check_nondegenerate  # noqa: F401
-from .test_gpu_paths import _AT, _BT
+from .wino_ref import AT as _AT, BT as _BT, OFFSETS, mindex  # noqa: F401
 
-# kinds of tensor for exact.stream, clear of exact's 0 .. 7, tests/test_gpu_exact.py's 8 .. 15 and tests/exact_fusion.py's 16 .. 31
+# kinds of tensor for exact.stream, clear of exact's 0 .. 7, tests/exact_units.py's 8 .. 15 and tests/exact_fusion.py's 16 .. 31
 (_WX, _WCH, _WPOS, _WVAL, _WSIGN, _WBIAS, _WRES, _WFW) = range(32, 40)
 
 RELU_PRE, RELU_POST = 2, 4           # the conv flags of the stage entries (offk.h)
@@ -174,23 +174,7 @@ def single_tap_weights(seed, co, ci, k, taps_per_co, cmax, live_ci=None, cover=T
     return w
 
 
-# ---- the point numbering of winograd_common.h --------------------------------------------------------------------------------------
-OFFSETS = {"off1": (0, 36, 66, 96), "offA": (0, 25, 45, 65), "offB": (0, 5, 9, 14), "offC": (0, 5, 10, 14)}
-
-
-def mindex(phases, cy, cx, i, j, offs=OFFSETS):
-    ny, nx, cls = (5 if cy else 6), (5 if cx else 6), 2 * cy + cx
-    if phases == 1:
-        return offs["off1"][cls] + i * nx + j
-    if i < ny - 1 and j < nx - 1:
-        return offs["offA"][cls] + i * (nx - 1) + j
-    if i == ny - 1 and j < nx - 1:
-        return 81 + offs["offB"][cls] + j
-    if j == nx - 1 and i < ny - 1:
-        return 99 + offs["offC"][cls] + i
-    return 117 + cls
-
-
+# ---- the point numbering of winograd_common.h: wino_ref.mindex and OFFSETS ----------------------------------------------------------
 def classes():
     for cy in (0, 1):
         for cx in (0, 1):

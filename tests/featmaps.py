@@ -15,6 +15,8 @@ import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 from oracle import off_oracle as orc
 
+from . import forward
+
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 DTYPES16 = {"bf16": torch.bfloat16, "f16": torch.float16}
 DROP_SEED, DROP_P = 7, 0.8
@@ -28,15 +30,11 @@ def rt():
 
 
 def make_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, consensus=None, precision="f32split", **kw):
-    h = rt.OffForward(B, L, variant, slice_mode, consensus, precision=precision, **kw)
-    assert h.load_state_dict(synth.make_weights(variant)) == []
-    return h
+    return forward.make_handle(rt, B, L, variant, slice_mode, consensus, precision=precision, **kw)[0]
 
 
 def make_train_handle(rt, B, L, variant=spec.VARIANT_RGB, slice_mode=spec.SLICE_FLAT, precision="fp32", **kw):
-    h = rt.OffForward(B, L, variant, slice_mode, precision=precision, training=True, **kw)
-    assert h.load_state_dict(synth.make_weights(variant)) == []
-    return h
+    return forward.make_handle(rt, B, L, variant, slice_mode, precision=precision, training=True, **kw)[0]
 
 
 # ---- inputs ----

@@ -10,6 +10,7 @@ import pytest
 import offk_amd  # noqa: F401
 from offk_amd import _lib
 
+from . import conv_bwd_s2_abi as abi
 from .conv_bwd import S2 as cs
 
 ENTRIES = ("offk_conv2d_s2_backward_data", "offk_conv2d_s2_backward_weight", "offk_conv2d_s2_backward_plan")
@@ -20,10 +21,6 @@ def built():
     import __graft_entry__ as ge
     ge.build()
     return _lib.load()
-
-
-def _fake(addr):
-    return ctypes.c_void_p(addr)
 
 
 def _plan(lib, n, H, W, ci, co, k):
@@ -64,82 +61,9 @@ def test_plan_runs_from_python_wrapper(built):
             assert chunks >= 3 and c.n % (-(-c.n // chunks)) != 0
 
 
-_N, _H, _CI, _CO = 2, 14, 96, 128
-_G_BYTES = _N * (_H // 2) * (_H // 2) * _CO * 4
-_BIG = 1 << 30                     # bytes: no plan of these shapes comes near
-
-
-def _data_args(**over):
-    a = dict(stream=None, g=_fake(0x10000000), g_cstride=_CO, g_coff=0, n_img=_N, H=_H, W=_H, Co=_CO, w=_fake(0x1000), Ci=_CI, KH=5, KW=5,
-             pad=2, dx=_fake(0x20000000), dx_cstride=_CI, dx_coff=0, accumulate=0, scratch=_fake(0x30000000), scratch_bytes=_BIG)
-    assert set(over) <= set(a)
-    a.update(over)
-    return list(a.values())
-
-
-def _weight_args(**over):
-    a = dict(stream=None, x=_fake(0x20000000), x_cstride=_CI, x_coff=0, g=_fake(0x10000000), g_cstride=_CO, g_coff=0, n_img=_N, H=_H, W=_H,
-             Ci=_CI, Co=_CO, KH=5, KW=5, pad=2, relu_in=0, dw=_fake(0x1000), db=_fake(0x2000), accumulate=0, scratch=_fake(0x30000000),
-             scratch_bytes=_BIG)
-    assert set(over) <= set(a)
-    a.update(over)
-    return list(a.values())
-
-
-def _plan_args(n=2, H=14, W=14, ci=96, co=128, kh=5, kw=5):
-    return [n, H, W, ci, co, kh, kw, None, None, None]
-
-
-_D, _W, _P = "offk_conv2d_s2_backward_data", "offk_conv2d_s2_backward_weight", "offk_conv2d_s2_backward_plan"
-_REFUSALS = {
-    "data_null_g": (_D, _data_args, dict(g=None)),
-    "data_null_w": (_D, _data_args, dict(w=None)),
-    "data_null_dx": (_D, _data_args, dict(dx=None)),
-    "data_null_scratch": (_D, _data_args, dict(scratch=None)),
-    "data_k3": (_D, _data_args, dict(KH=3, KW=3, pad=1)),
-    "data_k7_pad2": (_D, _data_args, dict(KH=7, KW=7, pad=2)),
-    "data_k5_pad3": (_D, _data_args, dict(pad=3)),
-    "data_k5x7": (_D, _data_args, dict(KH=5, KW=7)),
-    "data_odd_h": (_D, _data_args, dict(H=13)),
-    "data_odd_w": (_D, _data_args, dict(W=15)),
-    "data_ci_48": (_D, _data_args, dict(Ci=48, dx_cstride=48)),
-    "data_co_96": (_D, _data_args, dict(Co=96, g_cstride=96)),
-    "data_g_stride_short": (_D, _data_args, dict(g_cstride=_CO, g_coff=64)),
-    "data_dx_stride_short": (_D, _data_args, dict(dx_cstride=64)),
-    "data_negative_offset": (_D, _data_args, dict(dx_coff=-4, dx_cstride=256)),
-    "data_odd_offset": (_D, _data_args, dict(g_cstride=_CO + 2, g_coff=2)),
-    "data_short_scratch": (_D, _data_args, dict(scratch_bytes=4 * _CO * _CI * 25 - 4)),
-    "data_dx_is_g": (_D, _data_args, dict(dx=_fake(0x10000000))),
-    "data_dx_overlaps_g_tail": (_D, _data_args, dict(dx=_fake(0x10000000 + _G_BYTES - 1024))),
-    "data_g_inside_dx": (_D, _data_args, dict(g=_fake(0x20000000 + 4096))),
-    "weight_null_x": (_W, _weight_args, dict(x=None)),
-    "weight_null_g": (_W, _weight_args, dict(g=None)),
-    "weight_null_dw": (_W, _weight_args, dict(dw=None)),
-    "weight_null_scratch": (_W, _weight_args, dict(scratch=None)),
-    "weight_k3": (_W, _weight_args, dict(KH=3, KW=3, pad=1)),
-    "weight_k7_pad2": (_W, _weight_args, dict(KH=7, KW=7, pad=2)),
-    "weight_k5_pad3": (_W, _weight_args, dict(pad=3)),
-    "weight_odd_h": (_W, _weight_args, dict(H=13)),
-    "weight_odd_w": (_W, _weight_args, dict(W=15)),
-    "weight_ci_48": (_W, _weight_args, dict(Ci=48, x_cstride=48)),
-    "weight_co_96": (_W, _weight_args, dict(Co=96, g_cstride=96)),
-    "weight_x_stride_short": (_W, _weight_args, dict(x_cstride=128, x_coff=64)),
-    "weight_g_stride_short": (_W, _weight_args, dict(g_cstride=64)),
-    "weight_negative_offset": (_W, _weight_args, dict(x_coff=-4, x_cstride=256)),
-    "weight_odd_offset": (_W, _weight_args, dict(x_cstride=_CI + 2, x_coff=2)),
-    "weight_short_scratch": (_W, _weight_args, dict(scratch_bytes=4 * (_CO * _CI * 25 + _CO) - 4)),
-    "plan_k3": (_P, _plan_args, dict(kh=3, kw=3)),
-    "plan_k5x7": (_P, _plan_args, dict(kw=7)),
-    "plan_odd_h": (_P, _plan_args, dict(H=13)),
-    "plan_odd_w": (_P, _plan_args, dict(W=15)),
-    "plan_ci_48": (_P, _plan_args, dict(ci=48)),
-    "plan_co_96": (_P, _plan_args, dict(co=96)),
-}
-
-
-@pytest.mark.parametrize("rule", sorted(_REFUSALS))
+@pytest.mark.parametrize("rule", sorted(abi.REFUSALS))
 def test_refusals_name_the_entry(built, rule):
-    entry, make, over = _REFUSALS[rule]
+    entry, make, over = abi.REFUSALS[rule]
     rc = getattr(built, entry)(*make(**over))
     assert rc == -1, (rule, rc, built.offk_last_error(None))
     assert entry.encode() in built.offk_last_error(None), built.offk_last_error(None)
@@ -147,12 +71,12 @@ def test_refusals_name_the_entry(built, rule):
 
 def test_the_unmodified_arguments_are_not_refused_for_their_shape(built):
     """the refusal table's base arguments are valid: the same call with only a short scratch is refused for the scratch, nothing else"""
-    rc = built.offk_conv2d_s2_backward_data(*_data_args(scratch_bytes=0))
+    rc = built.offk_conv2d_s2_backward_data(*abi.data_args(scratch_bytes=0))
     assert rc == -1 and b"scratch too small" in built.offk_last_error(None)
-    rc = built.offk_conv2d_s2_backward_weight(*_weight_args(scratch_bytes=0, db=None))
+    rc = built.offk_conv2d_s2_backward_weight(*abi.weight_args(scratch_bytes=0, db=None))
     assert rc == -1 and b"scratch too small" in built.offk_last_error(None)
     for k, pad in cs.FORMS.items():
-        assert built.offk_conv2d_s2_backward_plan(*_plan_args(kh=k, kw=k)) == 0
+        assert built.offk_conv2d_s2_backward_plan(*abi.plan_args(kh=k, kw=k)) == 0
 
 
 def test_stride1_entries_keep_refusing_the_large_kernels(built):

@@ -20,7 +20,7 @@ from offk_amd import _lib
 from .conv_bwd import S1 as cb
 from . import conv_dgrad_split as dg
 from . import split_bound as sb
-from . import test_conv_bwd_abi as fp32_abi
+from . import conv_bwd_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA, PLAN, FORM = "offk_conv2d_backward_data_split", "offk_conv2d_backward_data_plan_split", "offk_conv2d_backward_data_form_split"
@@ -44,10 +44,6 @@ def _form(lib, n, H, W, ci, co, k):
     a, b = ctypes.c_int(0), ctypes.c_int(0)
     rc = lib.offk_conv2d_backward_data_form_split(n, H, W, ci, co, k, k, ctypes.byref(a), ctypes.byref(b))
     return rc, a.value, b.value
-
-
-def round256(b):
-    return -(-b // 256) * 256
 
 
 def test_symbols_are_exported_bound_and_declared(built):
@@ -80,7 +76,7 @@ def test_plan_is_a_pure_function_with_pinned_bytes(built, shape):
     for n_img in (1, 6, 384):
         first = _plan(built, n_img, H, H, ci, co, k)
         assert first[0] == 0, built.offk_last_error(None)
-        assert first[1] == round256(co * ci * k * k * 6) + round256(n_img * H * H * co * 6), (shape, n_img, first[1])
+        assert first[1] == fp32_abi.round256(co * ci * k * k * 6) + fp32_abi.round256(n_img * H * H * co * 6), (shape, n_img, first[1])
         for _ in range(3):
             assert _plan(built, n_img, H, H, ci, co, k) == first
     assert built.offk_conv2d_backward_data_plan_split(6, H, H, ci, co, k, k, None) == 0, "the output pointer may be NULL"
@@ -120,36 +116,27 @@ def test_the_block_form_is_pinned(built, shape, at384):
     assert FORM.encode() + b":" in built.offk_last_error(None)
 
 
-# every refusal tests/test_conv_bwd_abi.py asks of the fp32 data entry, asked of the split entry; the scratch one byte short of the split plan's
-_SPLIT_SCRATCH = round256(9 * fp32_abi._CO * fp32_abi._CI * 6) + round256(fp32_abi._ROWS * fp32_abi._CO * 6)
-_REFUSALS = dict((rule, over) for rule, (entry, _make, over) in fp32_abi._REFUSALS.items() if entry == "offk_conv2d_backward_data")
-_REFUSALS["data_short_scratch"] = dict(scratch_bytes=_SPLIT_SCRATCH - 1)
-_REFUSALS.update(data_kh_7=dict(KH=7, KW=7, pad=3), data_kh_not_kw=dict(KW=1), data_co_96=dict(Co=96, g_cstride=96), data_n_img_0=dict(n_img=0),
-                 data_h_0=dict(H=0), data_g_negative_offset=dict(g_coff=-4, g_cstride=256), data_odd_offset=dict(dx_cstride=130, dx_coff=2),
-                 data_scratch_not_aligned=dict(scratch=ctypes.c_void_p(0x30000008)))
-
-
 def test_the_refusal_table_covers_the_fp32_entrys(built):
-    assert len([1 for e, _m, _o in fp32_abi._REFUSALS.values() if e == "offk_conv2d_backward_data"]) == 14
-    assert _plan(built, fp32_abi._N, fp32_abi._H, fp32_abi._H, fp32_abi._CI, fp32_abi._CO, 3) == (0, _SPLIT_SCRATCH)
+    assert len([1 for e, _m, _o in fp32_abi.REFUSALS.values() if e == "offk_conv2d_backward_data"]) == 14
+    assert _plan(built, fp32_abi.N, fp32_abi.H, fp32_abi.H, fp32_abi.CI, fp32_abi.CO, 3) == (0, fp32_abi.DGRAD_SPLIT_SCRATCH)
 
 
-@pytest.mark.parametrize("rule", sorted(_REFUSALS))
+@pytest.mark.parametrize("rule", sorted(fp32_abi.DGRAD_SPLIT_REFUSALS))
 def test_refusals_name_the_split_entry(built, rule):
-    over = _REFUSALS[rule]
-    rc = getattr(built, DATA)(*fp32_abi._data_args(**over))
+    over = fp32_abi.DGRAD_SPLIT_REFUSALS[rule]
+    rc = getattr(built, DATA)(*fp32_abi.data_args(**over))
     assert rc == -1, (rule, rc, built.offk_last_error(None))
     assert DATA.encode() + b":" in built.offk_last_error(None), built.offk_last_error(None)
 
 
 def test_the_scratch_message_and_both_stride_1_entries_on_k5_and_k7(built):
-    rc = getattr(built, DATA)(*fp32_abi._data_args(scratch_bytes=0))
+    rc = getattr(built, DATA)(*fp32_abi.data_args(scratch_bytes=0))
     assert rc == -1 and b"scratch too small (offk_conv2d_backward_data_plan_split)" in built.offk_last_error(None)
-    rc = getattr(built, DATA)(*fp32_abi._data_args(scratch=ctypes.c_void_p(0x30000004)))
+    rc = getattr(built, DATA)(*fp32_abi.data_args(scratch=ctypes.c_void_p(0x30000004)))
     assert rc == -1 and b"scratch must be 16-byte aligned" in built.offk_last_error(None)
     for k in (5, 7):
         for entry in (DATA, "offk_conv2d_backward_data"):
-            rc = getattr(built, entry)(*fp32_abi._data_args(KH=k, KW=k, pad=(k - 1) // 2))
+            rc = getattr(built, entry)(*fp32_abi.data_args(KH=k, KW=k, pad=(k - 1) // 2))
             assert rc == -1 and entry.encode() + b": the kernel must be 1x1 or 3x3" in built.offk_last_error(None), (k, entry)
     for bad in ((2, 14, 14, 64, 64, 5, 5), (2, 14, 14, 64, 64, 3, 1), (2, 14, 14, 96, 64, 3, 3), (2, 14, 14, 64, 96, 1, 1), (0, 14, 14, 64, 64, 3, 3)):
         assert built.offk_conv2d_backward_data_plan_split(*bad, None) == -1

@@ -19,7 +19,7 @@ from offk_amd import _lib
 from .conv_bwd import S2 as cs
 from . import conv_s2_dgrad_split as ds
 from . import split_bound as sb
-from . import test_conv_bwd_s2_abi as fp32_abi
+from . import conv_bwd_s2_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA, PLAN = "offk_conv2d_s2_backward_data_split", "offk_conv2d_s2_backward_plan_split"
@@ -84,31 +84,24 @@ def test_plan_rounds_each_region_and_runs_from_the_python_wrapper(built):
     assert runtime.DGRAD_ARITHS == ("fp32", "f32split")
 
 
-# every refusal tests/test_conv_bwd_s2_abi.py asks of the fp32 data entry, asked of the split entry; the scratch one byte short of the split plan's
-_SPLIT_SCRATCH = 25 * fp32_abi._CO * fp32_abi._CI * 6 + fp32_abi._N * (fp32_abi._H // 2) ** 2 * fp32_abi._CO * 6
-_REFUSALS = dict((rule, over) for rule, (entry, _make, over) in fp32_abi._REFUSALS.items() if entry == "offk_conv2d_s2_backward_data")
-_REFUSALS["data_short_scratch"] = dict(scratch_bytes=_SPLIT_SCRATCH - 1)
-_REFUSALS.update(data_n_img_0=dict(n_img=0), data_h_0=dict(H=0), data_g_negative_offset=dict(g_coff=-4, g_cstride=256))
-
-
 def test_the_refusal_table_covers_the_fp32_entrys(built):
-    assert len([1 for e, _m, _o in fp32_abi._REFUSALS.values() if e == "offk_conv2d_s2_backward_data"]) == 20
-    assert _plan(built, fp32_abi._N, fp32_abi._H, fp32_abi._H, fp32_abi._CI, fp32_abi._CO, 5) == (0, _SPLIT_SCRATCH)
+    assert len([1 for e, _m, _o in fp32_abi.REFUSALS.values() if e == "offk_conv2d_s2_backward_data"]) == 20
+    assert _plan(built, fp32_abi.N, fp32_abi.H, fp32_abi.H, fp32_abi.CI, fp32_abi.CO, 5) == (0, fp32_abi.DGRAD_SPLIT_SCRATCH)
 
 
-@pytest.mark.parametrize("rule", sorted(_REFUSALS))
+@pytest.mark.parametrize("rule", sorted(fp32_abi.DGRAD_SPLIT_REFUSALS))
 def test_refusals_name_the_split_entry(built, rule):
-    over = _REFUSALS[rule]
-    rc = getattr(built, DATA)(*fp32_abi._data_args(**over))
+    over = fp32_abi.DGRAD_SPLIT_REFUSALS[rule]
+    rc = getattr(built, DATA)(*fp32_abi.data_args(**over))
     assert rc == -1, (rule, rc, built.offk_last_error(None))
     assert DATA.encode() + b":" in built.offk_last_error(None), built.offk_last_error(None)
 
 
 def test_the_unmodified_arguments_are_refused_for_the_scratch_only_and_plan_refusals(built):
-    rc = getattr(built, DATA)(*fp32_abi._data_args(scratch_bytes=0))
+    rc = getattr(built, DATA)(*fp32_abi.data_args(scratch_bytes=0))
     assert rc == -1 and b"scratch too small (offk_conv2d_s2_backward_plan_split)" in built.offk_last_error(None)
     for over in (dict(kh=3, kw=3), dict(kw=7), dict(H=13), dict(W=15), dict(ci=48), dict(co=96), dict(n=0)):
-        assert built.offk_conv2d_s2_backward_plan_split(*fp32_abi._plan_args(**over)[:8]) == -1
+        assert built.offk_conv2d_s2_backward_plan_split(*fp32_abi.plan_args(**over)[:8]) == -1
         assert PLAN.encode() + b":" in built.offk_last_error(None)
 
 

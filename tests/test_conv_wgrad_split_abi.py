@@ -17,7 +17,7 @@ from offk_amd import _lib, synth
 from .conv_bwd import S1 as cb
 from . import conv_wgrad_split as cs
 from . import split_bound as sb
-from . import test_conv_bwd_abi as fp32_abi
+from . import conv_bwd_abi as fp32_abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WEIGHT, PLAN = "offk_conv2d_backward_weight_split", "offk_conv2d_backward_plan_split"
@@ -87,32 +87,23 @@ def test_plan_runs_from_the_python_wrapper_and_chunks_short(built):
         assert chunks >= 3 and n % (-(-n // chunks)) != 0
 
 
-# every refusal of the fp32 entry (tests/test_conv_bwd_abi.py), asked of the split entry; the scratch one byte short of the split plan's
-_SPLIT_SCRATCH = 4 * (fp32_abi._CO * fp32_abi._CI * 9 + fp32_abi._CO)        # (2, 14, 14, 64, 128, 3): one chunk
-_REFUSALS = dict((rule, over) for rule, (entry, _make, over) in fp32_abi._REFUSALS.items() if entry == "offk_conv2d_backward_weight")
-_REFUSALS["weight_short_scratch"] = dict(scratch_bytes=_SPLIT_SCRATCH - 1)
-_REFUSALS.update(weight_kh_2=dict(KH=2, KW=2, pad=0), weight_kh_not_kw=dict(KH=3, KW=1), weight_co_96=dict(Co=96, g_cstride=96),
-                 weight_negative_offset=dict(x_coff=-4, x_cstride=256), weight_g_negative_offset=dict(g_coff=-4, g_cstride=256),
-                 weight_g_odd_stride=dict(g_cstride=130), weight_n_img_0=dict(n_img=0))
-
-
 def test_the_refusal_table_covers_the_fp32_entrys(built):
-    assert len([1 for e, _m, _o in fp32_abi._REFUSALS.values() if e == "offk_conv2d_backward_weight"]) == 11
-    assert _plan(built, fp32_abi._N, fp32_abi._H, fp32_abi._H, fp32_abi._CI, fp32_abi._CO, 3)[1:] == (_SPLIT_SCRATCH, 1)
+    assert len([1 for e, _m, _o in fp32_abi.REFUSALS.values() if e == "offk_conv2d_backward_weight"]) == 11
+    assert _plan(built, fp32_abi.N, fp32_abi.H, fp32_abi.H, fp32_abi.CI, fp32_abi.CO, 3)[1:] == (fp32_abi.WGRAD_SPLIT_SCRATCH, 1)
 
 
-@pytest.mark.parametrize("rule", sorted(_REFUSALS))
+@pytest.mark.parametrize("rule", sorted(fp32_abi.WGRAD_SPLIT_REFUSALS))
 def test_refusals_name_the_split_entry(built, rule):
-    over = _REFUSALS[rule]
+    over = fp32_abi.WGRAD_SPLIT_REFUSALS[rule]
     for entry in (WEIGHT, "offk_conv2d_backward_weight"):
-        rc = getattr(built, entry)(*fp32_abi._weight_args(**over))
+        rc = getattr(built, entry)(*fp32_abi.weight_args(**over))
         assert rc == -1, (rule, entry, rc, built.offk_last_error(None))
         assert entry.encode() + b":" in built.offk_last_error(None), built.offk_last_error(None)
 
 
 def test_db_may_be_null_and_plan_refusals(built):
     # db = NULL is no refusal: the same call with a short scratch is refused for the scratch, not for the pointer
-    rc = getattr(built, WEIGHT)(*fp32_abi._weight_args(db=None, scratch_bytes=_SPLIT_SCRATCH - 1))
+    rc = getattr(built, WEIGHT)(*fp32_abi.weight_args(db=None, scratch_bytes=fp32_abi.WGRAD_SPLIT_SCRATCH - 1))
     assert rc == -1 and b"scratch too small" in built.offk_last_error(None)
     for a in ([2, 14, 14, 96, 64, 3, 3, None, None], [2, 14, 14, 64, 64, 5, 5, None, None], [0, 14, 14, 64, 64, 3, 3, None, None]):
         assert built.offk_conv2d_backward_plan_split(*a) == -1

@@ -3,7 +3,7 @@
 For every case the GPU file uses (the stage-entry cases of the three convs, the forward shapes):
 
 1. The transforms: each (B^T, G, A^T) is a Winograd algorithm in exact fractions; tap_scales are the least integers; the point
-   numbering is tests/test_gpu_paths.py's.
+   numbering is tests/wino_ref.py's (held to its two earlier spellings by tests/test_forward_checks.py).
 2. The direct fp64 reference equals the Winograd restatement value for value; every cap of every exact stage is below 2^24 (printed
    per case); the ReLU zeroes 5 % .. 95 %; at least 8 distinct values.
 3. U in fp32 the way the device computes it -- constant times value, both pass orders, plain and fused with a zero addend -- equals
@@ -26,7 +26,7 @@ from offk_amd import spec
 
 from . import exact
 from . import exact_wino as ew
-from .test_gpu_paths import _mindex
+from .wino_ref import mindex as _mindex
 
 _CACHE = {}
 CASES = [(k,) + c for k in (3, 5, 7) for c in ew.conv_cases(k)]

@@ -24,7 +24,7 @@ clip" are the same one at this N.
 Which K1T kernel ran cannot be read from the per-launch trace: "units:pw_tdiff (K1T)" is marked once, before pw_tdiff_launch picks among
 pw_tdiff16_kernel, pw_tdiff_split_kernel and pw_tdiff_kernel<0, 0> (offk_api.hip:583, pw_tdiff.hip:727-735); the trace shows K1T against
 K1 + K2 only.  The bits show the rest: with the whole 3b map both handle kinds must write the SAME bits into fusion_28 (one fp32 kernel),
-with the maps as parts the split handle's bits must differ from the fp32 handle's (its own split-fp32 kernel ran).  Tolerance: RTOL of tests/test_gpu_parity.py, max-normalised as test_pw_reduce_vs_oracle and the stage-tensor tests have it.
+with the maps as parts the split handle's bits must differ from the fp32 handle's (its own split-fp32 kernel ran).  Tolerance: RTOL of tests/forward.py, max-normalised as test_pw_reduce_vs_oracle and the stage-tensor tests have it.
 
 The 3b map and the workspace each sit behind a 2 GiB margin of arena.SENTINEL inside their own allocation (tests/big.py has the
 reasoning: a byte offset wrapped as int32 lands there, changes a sentinel or reads a NaN, and faults nothing); both margins must be
@@ -56,7 +56,8 @@ from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
 from . import arena, big, featmaps
-from .test_gpu_parity import RTOL, RTOL_NORTH_STAR, rel_err, signal_err
+from .big import guarded, margin_intact
+from .forward import RTOL, RTOL_NORTH_STAR, STAGES, check_whole_forward, rel_err, signal_err
 
 pytestmark = pytest.mark.gpu
 B, L = 306, 7
@@ -64,16 +65,6 @@ N, P = B * L, B * (L - 1)
 MARGIN = big.FRONT_MARGIN
 SITE_3B = 1
 PRECS = ["fp32", "f32split"]
-
-
-def guarded(nbytes):
-    """(int32 words of [2 GiB margin | nbytes], all sentinel; the uint8 view of the payload)"""
-    words = torch.full(((MARGIN + nbytes + 3) // 4,), arena.SENTINEL, dtype=torch.int32, device="cuda")
-    return words, words.view(torch.uint8)[MARGIN:MARGIN + nbytes]
-
-
-def margin_intact(words):
-    return not bool((words[:MARGIN // 4] != arena.SENTINEL).any())
 
 
 class World:
@@ -208,9 +199,6 @@ def test_units_at_all_nine_sites(world, prec, fused):
     check_margins(wd)
 
 
-STAGES = (("fusion_28", 320, 28), ("fusion_14", 1056, 14), ("fusion_7", 832, 7), ("sum_7", 1024, 7))      # as tests/test_gpu_paths.py reads them
-
-
 def oracle_forward(wd, c):
     if c not in wd.fwd:
         with torch.no_grad():
@@ -230,20 +218,11 @@ def test_forward_at_n_2142(world, prec):
     torch.cuda.synchronize()
     for o in outs:
         assert tuple(o.shape) == (P, spec.NUM_CLASSES) and not bool(o.isnan().any())
-    rows = torch.cat([torch.arange(c * (L - 1), (c + 1) * (L - 1)) for c in wd.clips])
+    rows = torch.cat([torch.arange(c * (L - 1), (c + 1) * (L - 1)) for c in wd.clips]).cuda()
     refs = [oracle_forward(wd, c) for c in wd.clips]
-    for k, name in enumerate(("fc7", "fc14", "fc28")):
-        want = torch.cat([r[0][k] for r in refs])
-        got = outs[k][rows.cuda()]
-        e, sg = rel_err(got, want), signal_err(got, want)
-        print("forward %s %s at N = %d: error %.2e, row-to-row signal error %.2e" % (prec, name, N, e, sg))
-        assert e < RTOL and sg < RTOL_NORTH_STAR, (name, e, sg)
-    for name, ch, H in STAGES:
-        got = h.region(name, ch).view(P, H, H, ch)[rows.cuda()].permute(0, 3, 1, 2)
-        want = torch.cat([r[1][name] for r in refs])
-        e = rel_err(got, want)
-        print("forward %s %s at N = %d: error %.2e" % (prec, name, N, e))
-        assert e < RTOL, (name, e)
+    want = [torch.cat([r[0][k] for r in refs]) for k in range(3)]
+    stages = dict((name, torch.cat([r[1][name] for r in refs])) for name, _ch, _H in STAGES)
+    check_whole_forward(h, [o[rows] for o in outs], None, wd.w, "forward %s at N = %d" % (prec, N), rows=rows, oracle_run=(want, stages))
     check_margins(wd)
 
 
@@ -313,17 +292,6 @@ def test_forward_parts_at_n_2142(world, prec):
 
 # ---- the training side of the units on fp32 maps at N = 2142 ----------------------------------------------------------------------
 DROP_SEED, DROP_P = 7, 0.8
-
-
-def sentinel_floats(*shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return torch.full((n,), arena.SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32).view(*shape)
-
-
-def untouched(t):
-    return not bool((t.view(torch.int32) != arena.SENTINEL).any())
 
 
 def keep_rows(seed, site_index, first_pair, npairs, H, p):

@@ -21,7 +21,7 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
 from . import arena, featmaps
-from .test_gpu_big_batch import sentinel_floats, untouched
+from .arena import sentinel_floats, untouched
 
 pytestmark = pytest.mark.gpu
 L = 7
@@ -82,8 +82,8 @@ def test_forward_typed_on_16_bit_maps_of_2_gib(dtype):
     upcast maps, with the bounds of the B = 64 tests; the 3b map and the workspace behind 2 GiB sentinel margins."""
     from offk_amd import runtime as rt
     from oracle import off_oracle as orc
-    from .test_gpu_big_batch import MARGIN, guarded, margin_intact
-    from .test_gpu_parity import RTOL, RTOL_NORTH_STAR, rel_err, signal_err
+    from .big import FRONT_MARGIN as MARGIN, guarded, margin_intact
+    from .forward import RTOL, RTOL_NORTH_STAR, rel_err, signal_err
     Nb, Pb = B16 * L, B16 * (L - 1)
     weights = synth.make_weights(spec.VARIANT_RGB)
     h = rt.OffForward(B16, L, spec.VARIANT_RGB, spec.SLICE_PER_CLIP, False, precision="f32split")

@@ -74,8 +74,9 @@ from .conv_bwd import S2 as cs2
 from . import exact_fusion as ef
 from . import exact_wino as ew
 from . import head_bwd as hb
-from .test_gpu_exact import conv_inputs, conv_ref
-from .test_gpu_parity import RTOL, make_handle, rel_err
+from .exact_units import conv_inputs, conv_ref
+from .featmaps import rt  # noqa: F401
+from .forward import RTOL, make_handle, rel_err
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -84,13 +85,6 @@ NAN = float("nan")
 # accumulate (None: the entry has none), call(bufs, accumulate) -> {name: dense device output} with bufs {operand: (buffer [n, H, W, cs],
 # coff)}, check_a(outs, accumulate) asserting run A against fp64, refusal(case) -> None or the regular expression of the error
 Spec = collections.namedtuple("Spec", "shapes inputs bases call check_a refusal")
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 @pytest.fixture(scope="module")

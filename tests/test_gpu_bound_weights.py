@@ -25,8 +25,9 @@ from offk_amd import spec, synth
 from . import weight_updates as wu
 from .arena import same_bits
 from .units_grad import random_views
-from .test_gpu_parity import HANDLE_PRECISIONS, dev, rt  # noqa: F401
-from .test_gpu_weight_updates import CONFIGS, differing, feats, run
+from .featmaps import rt  # noqa: F401
+from .forward import HANDLE_PRECISIONS, dev
+from .weight_updates import CONFIGS, differing, feats, run
 
 pytestmark = pytest.mark.gpu
 

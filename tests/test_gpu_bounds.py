@@ -54,179 +54,27 @@ import torch
 import offk_amd  # noqa: F401
 from offk_amd import _lib, spec, synth
 
-from .arena import SENTINEL, Arena, bits, same_bits
-from .featmaps import DTYPES
-from .test_gpu_parity import HANDLE_PRECISIONS, rt  # noqa: F401
-from .test_gpu_paths import forced_handle
-from .test_gpu_split import _chain_inputs
-from .test_gpu_switches import switched_handle
+from .arena import same_bits
+from .featmaps import DTYPES, rt  # noqa: F401
+from .forward import BOUNDS_PATHS as PATHS
+from .forward import HANDLE_PRECISIONS, chain_inputs, make_handle
+from .guarded import FUSION, Guarded, forward_body, g_regions_stay, np_feats, put_feats, two_runs
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 2), (3, 3)]      # one pair, 49-row 7x7 sites; P = 6: 294 rows at 7x7 -- partial against 16-, 32-, 96- and 128-row tiles
 VARIANTS = [spec.VARIANT_RGB, spec.VARIANT_FLOW]
-# unit channels (9 x [S 32 | T 128]) of the three fusion buffers: (region, channels per pixel, unit channels)
-FUSION = (("fusion_28", 320, 320), ("fusion_14", 1056, 800), ("fusion_7", 832, 320))
-PATHS = {"default": {}, "unfused_units": {"OFFK_FUSED_UNITS": "0"}, "direct_convs": {"OFFK_WINOGRAD": "0", "OFFK_CHAIN": "0"},
-         "separate_pools": {"OFFK_FOLD_POOL": "0"}, "gates_open": None}      # None: every pair-count gate forced open (forced_handle)
-
-
-# ---- the two runs -----------------------------------------------------------------------------------------------------------------
-class Plain:
-    """Run A: ordinary allocations.  Records the byte size of every buffer so that run B's arena can be sized."""
-    arena = None
-
-    def __init__(self):
-        self.sizes = []
-
-    def put(self, name, t, offset=0):
-        self.sizes.append(t.numel() * t.element_size())
-        return t.to("cuda").contiguous()
-
-    def out(self, name, shape, dtype=torch.float32, offset=0):
-        t = torch.empty(*shape, dtype=dtype, device="cuda")
-        self.sizes.append(t.numel() * t.element_size())
-        return t
-
-    def workspace(self, h):
-        self.sizes.append(h.workspace_bytes)
-        h._ws = None                                   # the handle's own cached torch.empty, as ever
-        return h.workspace
-
-    def must_stay(self, view, what):
-        pass
-
-
-class Guarded:
-    """Run B: every buffer a carve of one arena, inputs copied in, everything else left full of the sentinel."""
-
-    def __init__(self, sizes):
-        self.arena = Arena.for_sizes(sizes)
-        self.stay = []
-
-    def put(self, name, t, offset=0):
-        return self.arena.put(name, t, offset=offset)
-
-    def out(self, name, shape, dtype=torch.float32, offset=0):
-        return self.arena.empty(name, shape, dtype, offset=offset)
-
-    def workspace(self, h):
-        ws = self.arena.carve("workspace", h.workspace_bytes)
-        h.set_workspace(ws)
-        return ws
-
-    def must_stay(self, view, what):
-        self.stay.append((view, what))
-
-
-def two_runs(body):
-    """body(run) -> {name: tensor the call must have filled}.  Runs it plain, then guarded; checks the guards, that everything is
-    finite and bit-equal to the plain run, and that what must stay untouched did.  Returns (plain results, guarded results)."""
-    plain = Plain()
-    a = body(plain)
-    torch.cuda.synchronize()
-    a = dict((k, v.clone()) for k, v in a.items())
-    g = Guarded(plain.sizes)
-    b = body(g)
-    torch.cuda.synchronize()
-    g.arena.check()
-    assert a.keys() == b.keys()
-    for k in b:
-        if b[k].is_floating_point():
-            assert bool(torch.isfinite(b[k]).all()), "%s: %d non-finite value(s) -- the call left them unwritten, or read memory it did not write" \
-                % (k, int((~torch.isfinite(b[k])).sum()))
-        assert same_bits(a[k], b[k]), "%s differs from the run in ordinary allocations in %d element(s)" % (k, int((bits(a[k]) != bits(b[k])).sum()))
-    for view, what in g.stay:
-        words = view.contiguous().view(torch.int32) if view.element_size() == 4 else view.contiguous().view(torch.uint8).view(torch.int32)
-        n = int((words != SENTINEL).sum())
-        assert n == 0, "%s: %d word(s) written that the path documents as untouched" % (what, n)
-    return a, b
-
-
 _HANDLES = {}
 
 
-def handle(rt, monkeypatch, B, L, variant=spec.VARIANT_RGB, prec="fp32", path="default", consensus=False):
+def handle(rt, B, L, variant=spec.VARIANT_RGB, prec="fp32", path="default", consensus=False):
     """One handle per configuration for the module (the switches are read once, at offk_create)."""
     key = (B, L, variant, prec, path, consensus)
     if key not in _HANDLES:
-        if PATHS[path] is None:
-            _HANDLES[key] = forced_handle(rt, monkeypatch, B, L, variant, consensus=consensus, precision=prec)[0]
-        else:
-            _HANDLES[key] = switched_handle(rt, monkeypatch, PATHS[path], B, L, variant, consensus=consensus, precision=prec)[0]
+        _HANDLES[key] = make_handle(rt, B, L, variant, consensus=consensus, precision=prec, env=PATHS[path])[0]
     h = _HANDLES[key]
     h.training = False
     return h
-
-
-def np_feats(B, L, cfg=5):
-    return [torch.from_numpy(f) for f in synth.make_features(B, L, cfg)]
-
-
-def part_channels(i, C):
-    """Two to four channel groups of site i, multiples of 32, unequal."""
-    units, k = C // 32, 2 + i % 3
-    sizes = [units // k] * k
-    sizes[0] += units - sum(sizes)
-    return [32 * s for s in sizes]
-
-
-def put_feats(r, feats, form="f32", offset=0, parts=False):
-    """The nine maps in run r: form = dtype + optional "cl" (channels_last); parts: every site as its channel groups."""
-    dtype, cl = DTYPES[form.replace("cl", "")], form.endswith("cl")
-    out = []
-    for i, f in enumerate(feats):
-        groups = torch.split(f, part_channels(i, f.shape[1]), dim=1) if parts else [f]
-        ts = []
-        for q, t in enumerate(groups):
-            name = "feat_%s%s" % (spec.SITES[i][0], "_part%d" % q if parts else "")
-            t = t.to(dtype)
-            if cl:
-                ts.append(r.put(name, t.permute(0, 2, 3, 1).contiguous(), offset).permute(0, 3, 1, 2))
-            else:
-                ts.append(r.put(name, t.contiguous(), offset))
-        out.append(ts if parts else ts[0])
-    return out
-
-
-def forward_regions(h, fused):
-    """What offk.h names as filled after a forward: D_<site>, the fusion buffers, sum_7 -- and G_<site> in the two-kernel form."""
-    out = {}
-    for name, _c, _h in spec.SITES:
-        out["D_" + name] = h.region("D_" + name, 32)
-        if not fused:
-            out["G_" + name] = h.region("G_" + name, 128)
-    for name, ch, _u in FUSION:
-        out[name] = h.region(name, ch)
-    out["sum_7"] = h.region("sum_7", 1024)
-    return out
-
-
-def g_regions_stay(r, h):
-    for name, _c, _h in spec.SITES:
-        r.must_stay(h.region("G_" + name, 128), "G_%s (the fused units fill D_<site> but not G_<site>)" % name)
-
-
-def forward_body(h, feats, form="f32", parts=False, offset=0, want28=True, fused=True, superset=False):
-    """fused: True -- the fused units (G_<site> must stay untouched); False -- the two-kernel form (G_<site> filled); None -- neither is
-    promised (bound weights)."""
-    def body(r):
-        fs = put_feats(r, feats, form, offset, parts)
-        ws = r.workspace(h)
-        shape = (h.out_rows(), h.num_classes)
-        outs = (r.out("out7", shape), r.out("out14", shape), r.out("out28", shape) if want28 else None)
-        got = h.forward(fs, want28=want28, out=outs)
-        res = dict(("out%d" % s, o) for s, o in zip((7, 14, 28), got) if o is not None)
-        assert all(o.data_ptr() == g_.data_ptr() for o, g_ in zip(outs, got) if o is not None)
-        res.update(forward_regions(h, fused is not False))
-        if fused:
-            g_regions_stay(r, h)
-        if superset:
-            fwd = int(h.lib.offk_workspace_bytes(h._h))
-            assert fwd % 4 == 0 and ws.numel() == int(h.lib.offk_train_workspace_bytes(h._h)) > fwd
-            r.must_stay(ws[fwd:], "workspace from offk_workspace_bytes to offk_train_workspace_bytes after a forward")
-        return res
-    return body
 
 
 def test_arena_checker_on_the_device():
@@ -247,34 +95,34 @@ def test_arena_checker_on_the_device():
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_forward_paths(rt, monkeypatch, B, L, variant, prec, path):
+def test_forward_paths(rt, B, L, variant, prec, path):
     """offk_forward through every path switch: about 32 launches over about 40 workspace regions, split-K slabs, pool partials and
     Winograd V / M, on a workspace, logits buffers and maps that sit between guard bands and start out as NaN."""
-    h = handle(rt, monkeypatch, B, L, variant, prec, path)
+    h = handle(rt, B, L, variant, prec, path)
     two_runs(forward_body(h, np_feats(B, L), fused=path != "unfused_units"))
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
-def test_forward_consensus_avg(rt, monkeypatch, prec):
+def test_forward_consensus_avg(rt, prec):
     """Consensus AVG at (3, 3): the caller's logits buffers hold B = 3 rows while the heads compute P = 6 -- a head that writes its
     per-pair rows into the caller's buffer breaches the guard behind it."""
-    h = handle(rt, monkeypatch, 3, 3, spec.VARIANT_FLOW, prec, consensus=True)
+    h = handle(rt, 3, 3, spec.VARIANT_FLOW, prec, consensus=True)
     assert h.out_rows() == 3 and h.P == 6
     two_runs(forward_body(h, np_feats(3, 3)))
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
-def test_forward_without_out28(rt, monkeypatch, prec):
-    h = handle(rt, monkeypatch, 3, 3, spec.VARIANT_RGB, prec)
+def test_forward_without_out28(rt, prec):
+    h = handle(rt, 3, 3, spec.VARIANT_RGB, prec)
     a, _b = two_runs(forward_body(h, np_feats(3, 3), want28=False))
     assert "out28" not in a
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_forward_training_superset_stays_untouched(rt, monkeypatch, B, L, prec):
+def test_forward_training_superset_stays_untouched(rt, B, L, prec):
     """A training handle's workspace is the superset offk_train_workspace_bytes; a forward may write only the forward layout."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, prec)
+    h = handle(rt, B, L, spec.VARIANT_RGB, prec)
     h.training = True
     two_runs(forward_body(h, np_feats(B, L), superset=True))
 
@@ -285,11 +133,11 @@ FORMS = [("f32", True), ("bf16", False), ("bf16", True), ("f16", False), ("f16",
 
 @pytest.mark.parametrize("form,parts", FORMS, ids=["%s%s" % (f, "-parts" if p else "") for f, p in FORMS])
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_forward_entry_forms(rt, monkeypatch, B, L, form, parts):
+def test_forward_entry_forms(rt, B, L, form, parts):
     """Split-fp32 handles: the forward from channel groups (two to four per site), from bf16 / fp16 maps and from channels_last maps
     of all three dtypes.  Beside the two runs: equal to the same handle on x.float() / the contiguous copy, as the entries' own
     modules hold them."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, "f32split")
+    h = handle(rt, B, L, spec.VARIANT_RGB, "f32split")
     feats = [f.to(DTYPES[form.replace("cl", "")]) for f in np_feats(B, L)]
     a, _b = two_runs(forward_body(h, feats, form, parts))
     h._ws = None
@@ -346,10 +194,10 @@ UNIT_CASES = [(p, e, f) for p in HANDLE_PRECISIONS for e, f in (("units", "f32")
 
 @pytest.mark.parametrize("prec,entry,form", UNIT_CASES, ids=["%s-%s-%s" % c for c in UNIT_CASES])
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_off_units(rt, monkeypatch, B, L, prec, entry, form):
+def test_off_units(rt, B, L, prec, entry, form):
     """offk_off_units (K1 + K2: G, D and the unit channels) and offk_off_units_fused (D and the unit channels; G_<site> untouched), their
     16-bit and channels-last forms included; neither may write another channel of the fusion buffers."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, prec)
+    h = handle(rt, B, L, spec.VARIANT_RGB, prec)
     h.training = True
     feats = [f.to(DTYPES[form.replace("cl", "")]) for f in np_feats(B, L)]
 
@@ -404,11 +252,11 @@ def train_body(h, feats, form, drop_p, accumulate, offset=0):
 @pytest.mark.parametrize("drop_p", [0.0, 0.8])
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_units_train_and_backward(rt, monkeypatch, B, L, prec, drop_p, accumulate):
+def test_units_train_and_backward(rt, B, L, prec, drop_p, accumulate):
     """offk_off_units_train then offk_off_units_backward: accumulate = 0 into a sentinel-filled gradient carve of exactly
     offk_unit_grad_floats (every slot must be overwritten), accumulate = 1 onto a finite fill; gradient views with a wider cstride
     and a non-zero coff; the workspace is the training superset, between guards."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, prec)
+    h = handle(rt, B, L, spec.VARIANT_RGB, prec)
     h.training = True
     two_runs(train_body(h, np_feats(B, L), "f32", drop_p, accumulate))
 
@@ -420,10 +268,10 @@ PW_FORMS = ["f32", "bf16", "f16cl", "f32cl"]
 @pytest.mark.parametrize("site", [0, 3, 8], ids=["3a", "4a", "5b"])
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_pw_reduce_writes_all_of_g_and_d(rt, monkeypatch, B, L, prec, site, form):
+def test_pw_reduce_writes_all_of_g_and_d(rt, B, L, prec, site, form):
     """offk_pw_reduce alone with G and D both full of the sentinel: K1 writes every row of both (runtime.pw_reduce allocates D
     with torch.empty on the strength of this test)."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, prec)
+    h = handle(rt, B, L, spec.VARIANT_RGB, prec)
     _name, C, H = spec.SITES[site]
     x = np_feats(B, L)[site].to(DTYPES[form.replace("cl", "")])
 
@@ -440,10 +288,10 @@ def test_pw_reduce_writes_all_of_g_and_d(rt, monkeypatch, B, L, prec, site, form
 @pytest.mark.parametrize("algo", [0, 1, 4])
 @pytest.mark.parametrize("site", [0, 3, 8], ids=["3a", "4a", "5b"])
 @pytest.mark.parametrize("variant", VARIANTS)
-def test_sobel_tdiff(rt, monkeypatch, variant, site, algo):
+def test_sobel_tdiff(rt, variant, site, algo):
     """offk_sobel_tdiff into a 160-channel slice of a 352-channel carve: channels AND rows guarded."""
     B, L = 3, 3
-    h = handle(rt, monkeypatch, B, L, variant)
+    h = handle(rt, B, L, variant)
     H = spec.SITES[site][2]
     g = torch.Generator().manual_seed(site + 10 * variant)
     Gin = torch.relu(torch.randn(h.N * H * H, 128, generator=g))
@@ -461,9 +309,9 @@ def test_sobel_tdiff(rt, monkeypatch, variant, site, algo):
 
 @pytest.mark.parametrize("algo", [0, 1, 4])
 @pytest.mark.parametrize("B,L", SHAPES)
-def test_sobel_tdiff_all_after_units(rt, monkeypatch, B, L, algo):
+def test_sobel_tdiff_all_after_units(rt, B, L, algo):
     """offk_sobel_tdiff_all reads the G / D regions of the matching offk_off_units: that one runs in the arena first."""
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_FLOW)
+    h = handle(rt, B, L, spec.VARIANT_FLOW)
     feats = np_feats(B, L)
 
     def body(r):
@@ -486,11 +334,11 @@ def test_sobel_tdiff_all_after_units(rt, monkeypatch, B, L, algo):
 @pytest.mark.parametrize("entry,offset", [("forward_typed", 4), ("train_typed", 8), ("forward_cl", 16), ("train_cl", 16)],
                          ids=["forward_typed-4", "train_typed-8", "forward_cl-16", "train_cl-16"])
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-def test_minimal_alignment(rt, monkeypatch, entry, offset, dt):
+def test_minimal_alignment(rt, entry, offset, dt):
     """All nine maps at the least alignment the header accepts (4 bytes: offk_forward_typed; 8: the _typed training entries; 16: the
     _cl entries) and no more: bit-equal to the run on 256-byte-aligned maps, guards clean."""
     B, L = 3, 3
-    h = handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, "f32split")
+    h = handle(rt, B, L, spec.VARIANT_RGB, "f32split")
     feats = [f.to(DTYPES[dt]) for f in np_feats(B, L)]
     form = dt + ("cl" if entry.endswith("_cl") else "")
     if entry.startswith("forward"):
@@ -505,11 +353,11 @@ def test_minimal_alignment(rt, monkeypatch, entry, offset, dt):
 
 
 # ---- distinct handles are independent -------------------------------------------------------------------------------------------------
-def test_two_handles_on_two_streams(rt, monkeypatch):
+def test_two_handles_on_two_streams(rt):
     """offk.h: "distinct handles are independent".  Two handles on one device, each with its own carves, their forwards enqueued
     alternately, three times, on two streams with no synchronisation in between: each one's logits equal its own serial run."""
     cfgs = [(1, 2, spec.VARIANT_RGB, "fp32"), (3, 3, spec.VARIANT_FLOW, "f32split")]
-    hs = [handle(rt, monkeypatch, *c) for c in cfgs]
+    hs = [handle(rt, *c) for c in cfgs]
     feats = [np_feats(c[0], c[1], 6 + i) for i, c in enumerate(cfgs)]
     serial = []
     for h, f in zip(hs, feats):
@@ -604,7 +452,7 @@ CHAIN_CASES = ["28a", "28b_residual", "28c_into_slice"]
 def test_bottleneck_chain14(rt, case, n):
     """offk_bottleneck_chain14 (half-image blocks of 98 rows): the merged 28a form, the residual form, output into a channel slice."""
     merged = case == "28a"
-    x, w1, b1, w2, b2, w3, b3, wb, bb = _chain_inputs("28a_branch" if merged else case, n, "normal", 100 + n)
+    x, w1, b1, w2, b2, w3, b3, wb, bb = chain_inputs("28a_branch" if merged else case, n, "normal", 100 + n)
     if merged:
         w3, b3 = torch.cat([w3, wb], 1).contiguous(), b3 + bb          # c3 over [t2 | x0], K3 = 128
 
@@ -630,7 +478,7 @@ def test_bottleneck_chain14_split(rt, case, n):
     """offk_bottleneck_chain14_split (stores y and loads res through raw pointers): the branch form of 28a, the residual form, output
     into a channel slice; scratch at exactly the header's 6 * (64 * Cin + 64 * 576 + 2 * 256 * 64) bytes."""
     branch = case == "28a"
-    x, w1, b1, w2, b2, w3, b3, wb, bb = _chain_inputs("28a_branch" if branch else case, n, "normal", 300 + n)
+    x, w1, b1, w2, b2, w3, b3, wb, bb = chain_inputs("28a_branch" if branch else case, n, "normal", 300 + n)
     Cin = 64 if branch else 256
 
     def body(r):

@@ -63,10 +63,6 @@ def test_wide_integers_equal_fp64(rt, c, side):
 
 # ---- 3. / 4. the inequality ----
 
-def check_inequality(rt, what, k, g, w, dx_gpu, base=None):
-    return chk.dgrad_inequality(rt, cs, what, k, g, w, dx_gpu, base=base)
-
-
 @pytest.mark.parametrize("pattern,signs", chk.ADV, ids=chk.ADV_IDS)
 @pytest.mark.parametrize("shape", cs.WORST, ids=["k7_2x6x10_64to64", "k5_2x6x4_96to64"])
 def test_worst_case_mantissas(rt, shape, pattern, signs):
@@ -167,7 +163,7 @@ def test_module_routes_only_the_data_gradient(rt, spec, kind, monkeypatch):
         assert torch.equal(xs.grad, xf.grad), "integers are exact in both arithmetics"
         assert bool((xs.grad != 0).any())
     else:
-        check_inequality(rt, "module %s" % name, k, gr.cpu().numpy(), fp32.weight.detach().cpu().numpy(), got)
+        chk.dgrad_inequality(rt, cs, "module %s" % name, k, gr.cpu().numpy(), fp32.weight.detach().cpu().numpy(), got)
         assert not arena.same_bits(xs.grad, xf.grad), "the switch reached the kernel"
     # an input that needs no gradient: no data-gradient launch
     calls = []

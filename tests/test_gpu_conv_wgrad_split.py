@@ -70,10 +70,6 @@ def test_wide_integers_equal_fp64(rt, c, side):
 
 # ---- 4. / 5. the inequality ----
 
-def check_inequality(rt, what, c, g, x, dw_gpu, relu_in=False):
-    return chk.wgrad_inequality(rt, cb, what, c, g, x, dw_gpu, relu_in=relu_in)
-
-
 WORST_SHAPES = [cb.Case(3, 2, 5, 3, 128, 128), cb.Case(3, 2, 7, 7, 128, 128), cb.Case(3, 1, 14, 14, 64, 64), cb.Case(1, 2, 7, 7, 64, 256)]
 
 
@@ -184,7 +180,7 @@ def test_module_routes_only_the_weight_gradient(rt):
         g = y.grad * (y.detach() > 0) if relu else y.grad
         gr, hr = g.permute(0, 2, 3, 1).contiguous(), h.detach().permute(0, 2, 3, 1).contiguous()
         c = cb.Case(k, MOD_N, MOD_HW, MOD_HW, ci, co)
-        check_inequality(rt, "module %s" % name, c, gr.cpu().numpy(), hr.cpu().numpy(), split[name].weight.grad)
+        chk.wgrad_inequality(rt, cb, "module %s" % name, c, gr.cpu().numpy(), hr.cpu().numpy(), split[name].weight.grad)
         # the fp64 nn.Conv2d layer on the same operands gives the reference the inequality was asserted against
         conv = nn.Conv2d(ci, co, k, padding=(k - 1) // 2).double()
         conv(h.detach().cpu().double()).backward(g.cpu().double())

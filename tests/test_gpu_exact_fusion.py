@@ -28,19 +28,13 @@ from offk_amd import spec
 
 from . import exact
 from . import exact_fusion as ef
+from .featmaps import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN, SENTINEL = float("nan"), -3.0
 CHAIN_CASES = ef.chain_cases()
 CHAIN_IDS = [c[0] for c in CHAIN_CASES]
 _REF = {}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 def chain_case(n, kind, hand):

@@ -29,17 +29,11 @@ from offk_amd import spec
 from . import exact
 from . import exact_wino as ew
 from .arena import Arena
+from .featmaps import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 _REF = {}
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 def dev(t):

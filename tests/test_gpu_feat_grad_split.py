@@ -27,7 +27,7 @@ from offk_amd import _lib, spec, synth
 
 from . import arena as arena_mod
 from . import exact
-from . import test_gpu_exact as gx
+from . import exact_units as gx
 from . import units_dx_checks as checks
 from . import units_grad as ug
 from .units_grad import DX_SPLIT as FORM

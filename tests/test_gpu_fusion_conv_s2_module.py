@@ -17,13 +17,11 @@ that element's gradient may be off by |gy|.  Nothing in the bound comes from the
 import pytest
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
-from torch.nn.grad import conv2d_weight
 
 import offk_amd  # noqa: F401
 
-from .conv_bwd import S2 as cs
 from . import exact
+from .conv_grad_checks import one_layer, within
 
 pytestmark = pytest.mark.gpu
 N = 2
@@ -114,46 +112,6 @@ def run_stack(stack, x, r):
 
 def on_device(*ts):
     return [t.cuda().contiguous(memory_format=torch.channels_last) for t in ts]
-
-
-def one_layer(m, fl, x, gy):
-    """fp64 values, elementwise error bounds and caps (largest sum of |terms|) of one layer from exact inputs x and gy.
-    m: the fp64 nn.Conv2d.  -> {"y" | "dx" | "weight" | "bias": (value, bound)}, caps, (undecided masks, masks)"""
-    W, b, s, pad = m.weight.detach(), m.bias.detach(), m.stride[0], m.padding[0]
-    co, ci, k, _ = W.shape
-    a = torch.relu(x) if fl.get("relu_in") else x
-    z = F.conv2d(a, W, b, stride=s, padding=pad)
-    S = F.conv2d(a.abs(), W.abs(), b.abs(), stride=s, padding=pad)
-    Ez = cs.gamma(ci * k * k + 2) * S
-    relu = bool(fl.get("relu"))
-    unstable = (z.abs() <= Ez) & (Ez > 0) if relu else torch.zeros_like(z, dtype=torch.bool)
-    gz = gy * (z > 0).double() if relu else gy
-    Egz = torch.where(unstable, gy.abs(), torch.zeros_like(gy))
-    P = gz.shape[0] * gz.shape[2] * gz.shape[3]
-    op = x.shape[-1] - ((gz.shape[-1] - 1) * s - 2 * pad + k)
-
-    def cw(g, v):
-        return conv2d_weight(v, W.shape, g, stride=s, padding=pad)
-
-    def ct(g, w):
-        return F.conv_transpose2d(g, w, stride=s, padding=pad, output_padding=op)
-
-    Sw, Sb, Sx = cw(gz.abs() + Egz, a.abs()), (gz.abs() + Egz).sum((0, 2, 3)), ct(gz.abs() + Egz, W.abs())
-    mx = co * (-(-k // s)) ** 2
-    dx, Edx = ct(gz, W), ct(Egz, W.abs()) + cs.gamma(mx + 1) * Sx
-    if fl.get("relu_in"):
-        dx, Edx = dx * (x > 0).double(), Edx * (x > 0).double()
-    out = {"y": (torch.relu(z) if relu else z, Ez), "dx": (dx, Edx),
-           "weight": (cw(gz, a), cw(Egz, a.abs()) + cs.gamma(P + 1) * Sw), "bias": (gz.sum((0, 2, 3)), Egz.sum((0, 2, 3)) + cs.gamma(P + 1) * Sb)}
-    caps = {"z": float(S.max()), "dW": float(Sw.max()), "db": float(Sb.max()), "dx": float(Sx.max())}
-    return out, caps, (int(unstable.sum()), z.numel() if relu else 0)
-
-
-def within(got, val, bound, what):
-    err = (got.detach().cpu().double() - val).abs()
-    ratio = float((err / bound.clamp_min(1e-300)).max()) if bool((err > 0).any()) else 0.0
-    print("%s: largest error %.3e, largest error / bound %.3f" % (what, float(err.max()), ratio))
-    assert bool((err <= bound).all()), "%s: error is %.3f of the derived bound" % (what, ratio)
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -22,18 +22,12 @@ import offk_amd  # noqa: F401
 
 from . import arena
 from . import head_bwd as hb
+from .featmaps import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 FORMS = {"head28": (14, 14, 1, 256, 0), "head14": (7, 7, 0, 512, 1), "head7": (7, 7, 0, 1024, 2)}
 CASES = [hb.Case(H, W, mp, C, 101, n, 0.8, head, 100 + 7 * head + n) for (H, W, mp, C, head) in FORMS.values() for n in (3, 5)]
 IDS = [hb.case_id(c) for c in CASES]
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 _CACHE = {}

@@ -17,18 +17,12 @@ import offk_amd  # noqa: F401
 from . import arena
 from . import exact
 from . import head_bwd as hb
+from .featmaps import rt  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 CASES = hb.EXACT_CASES
 IDS = [hb.case_id(c) for c in CASES]
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
 
 
 def nan_bytes(n):

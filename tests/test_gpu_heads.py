@@ -28,7 +28,6 @@ ratios of 1.1e6 (7-head) and 2.0e6 (14-head, OFFK_WINOGRAD=0) and fails every sl
 The pooled partial sums (`poolpart_28`; `pooled_7 / 14 / 28` under OFFK_FOLD_POOL=0) are held to 16 2^-24 sum |v| of their own cells (the
 max of the 28-head is exact); measured: poolpart_28 <= 2.6, pooled_* <= 4.1.
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -36,58 +35,20 @@ import torch.nn.functional as F
 import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
-from .test_gpu_parity import HANDLE_PRECISIONS, dev, make_handle, rel_err, rt  # noqa: F401
-from .test_gpu_switches import traced_forward, check_trace
+from .featmaps import rt  # noqa: F401
+from .forward import HEAD_CH, HEAD_KEY, HANDLE_PRECISIONS, check_trace, dev, head_handle, rel_err, traced_forward
+from .forward import HEAD_PATHS as PATHS
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -24
-HEAD_CH = {"7": 1024, "14": 512, "28": 256}
-HEAD_KEY = {"7": "fc_action_motion", "14": "fc_action_motion_14", "28": "fc_action_motion_28"}
 CEILING = dict((k, c + 64) for k, c in HEAD_CH.items())
 MEASURED = {"7": 0.67, "14": 1.12, "28": 1.42}       # worst |err| / (2^-24 mag) seen on an MI355X, all cases of this module
 HEAD_C = dict((k, 4.0 * v) for k, v in MEASURED.items())
 PART_C = 16.0
 
-PATHS = {
-    # switches, launches that must be there, launches that must not
-    "default": ({}, ("head_28 (max pool rows)", "heads (fc on folded pools, one launch)", "motion_conv3_trans_14b [winograd: output transform]"),
-                ("(pool + fc)",)),
-    "winograd0": ({"OFFK_WINOGRAD": "0"}, ("head_28 (max pool rows)", "heads (fc on folded pools, one launch)"), ("(pool + fc)", "[winograd")),
-    "fold_pool0": ({"OFFK_FOLD_POOL": "0"}, ("head_7 (pool + fc)", "head_14 (pool + fc)", "head_28 (pool + fc)"), ("heads (fc on folded", "(max pool rows)")),
-}
 # P = 1: one image, one 16-image block, two slabs; P = 18: two blocks, a last partial slab; P = 33: a third block holding ONE image, 1617 rows = 50.5 slabs
 SHAPES = {"p1": (1, 2), "p18": (3, 7), "p33": (3, 12)}
-
-_WEIGHTS = {}
-
-
-def head_weights(ncls):
-    """synth's weights with the three FCs replaced: N(0, 1) / sqrt(C), biases N(0, 0.1) -- and `ncls` classes."""
-    if ncls not in _WEIGHTS:
-        w = dict(synth.make_weights(spec.VARIANT_RGB))
-        g = np.random.default_rng(4100 + ncls)
-        for k, C in HEAD_CH.items():
-            w[HEAD_KEY[k] + ".weight"] = (g.standard_normal((ncls, C)) / C ** 0.5).astype(np.float32)
-            w[HEAD_KEY[k] + ".bias"] = (g.standard_normal(ncls) * 0.1).astype(np.float32)
-        _WEIGHTS[ncls] = w
-    return _WEIGHTS[ncls]
-
-
-def head_handle(rt, monkeypatch, env, B, L, prec, ncls=spec.NUM_CLASSES, consensus=False):
-    w = head_weights(ncls)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    try:
-        if ncls == spec.NUM_CLASSES:
-            h, _ = make_handle(rt, B, L, spec.VARIANT_RGB, consensus=consensus, weights=w, precision=prec)
-        else:
-            h = rt.OffForward(B, L, spec.VARIANT_RGB, consensus=consensus, num_classes=ncls, precision=prec)
-            assert h.load_state_dict(w) == [] and h.missing_weights()[0] == 0
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-    return h, w
 
 
 def head_inputs(h, P):
@@ -131,11 +92,11 @@ def check_partial(got, ref, mag, name):
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("shape", list(SHAPES))
 @pytest.mark.parametrize("path", list(PATHS))
-def test_forward_heads_vs_fp64_from_device_input(rt, monkeypatch, path, shape, prec):
+def test_forward_heads_vs_fp64_from_device_input(rt, path, shape, prec):
     env, must, must_not = PATHS[path]
     B, L = SHAPES[shape]
     P = B * (L - 1)
-    h, w = head_handle(rt, monkeypatch, env, B, L, prec)
+    h, w = head_handle(rt, env, B, L, prec)
     names, (o7, o14, o28) = traced_forward(h, [dev(f) for f in synth.make_features(B, L, 5)])
     check_trace(names, must, must_not)
     xs = head_inputs(h, P)
@@ -153,10 +114,10 @@ def test_forward_heads_vs_fp64_from_device_input(rt, monkeypatch, path, shape, p
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("path", list(PATHS))
-def test_heads_without_the_28_head(rt, monkeypatch, path, prec):
+def test_heads_without_the_28_head(rt, path, prec):
     """forward(want28=False): the 7- and 14-heads alone (two jobs in the one FC launch)."""
     B, L = 3, 7
-    h, w = head_handle(rt, monkeypatch, PATHS[path][0], B, L, prec)
+    h, w = head_handle(rt, PATHS[path][0], B, L, prec)
     feats = [dev(f) for f in synth.make_features(B, L, 5)]
     o7, o14, o28 = h.forward(feats, want28=False)
     torch.cuda.synchronize()
@@ -166,11 +127,11 @@ def test_heads_without_the_28_head(rt, monkeypatch, path, prec):
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("path", list(PATHS))
-def test_heads_under_consensus(rt, monkeypatch, path, prec):
+def test_heads_under_consensus(rt, path, prec):
     """Consensus on: the per-pair logits sit in the logit_* regions and obey the same bound; the outputs are their mean over T."""
     B, L = 3, 7
     P, T = B * (L - 1), L - 1
-    h, w = head_handle(rt, monkeypatch, PATHS[path][0], B, L, prec, consensus=True)
+    h, w = head_handle(rt, PATHS[path][0], B, L, prec, consensus=True)
     outs = h.forward([dev(f) for f in synth.make_features(B, L, 5)])
     torch.cuda.synchronize()
     logits = dict((k, h.region("logit_" + k, spec.NUM_CLASSES)) for k in ("7", "14", "28"))
@@ -183,12 +144,12 @@ def test_heads_under_consensus(rt, monkeypatch, path, prec):
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("shape", ["p18", "p33"])
 @pytest.mark.parametrize("path", list(PATHS))
-def test_heads_with_51_classes(rt, monkeypatch, path, shape, prec):
+def test_heads_with_51_classes(rt, path, shape, prec):
     """51 classes: no multiple of 4, 8 or 32 -- the class tails of fc_pooled_body (a second class block with 19 live rows, a lane's
     last class quad cut at 3) and of fc_kernel (a last block of 3), and the min(cls, ncls - 1) clamps of their weight-row loads."""
     B, L = SHAPES[shape]
     ncls = 51
-    h, w = head_handle(rt, monkeypatch, PATHS[path][0], B, L, prec, ncls=ncls)
+    h, w = head_handle(rt, PATHS[path][0], B, L, prec, ncls=ncls)
     o7, o14, o28 = h.forward([dev(f) for f in synth.make_features(B, L, 5)])
     torch.cuda.synchronize()
     assert o7.shape == (B * (L - 1), ncls)

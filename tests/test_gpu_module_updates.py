@@ -20,7 +20,8 @@ from offk_amd import off_module, spec, synth
 
 from . import weight_updates as wu
 from .arena import same_bits
-from .test_gpu_parity import dev, rt  # noqa: F401
+from .featmaps import rt  # noqa: F401
+from .forward import dev
 
 pytestmark = pytest.mark.gpu
 

@@ -27,7 +27,7 @@ import offk_amd  # noqa: F401
 
 from . import exact
 from . import head_bwd as hb
-from .test_gpu_fusion_conv_s2_module import one_layer, within
+from .conv_grad_checks import one_layer, within
 
 pytestmark = pytest.mark.gpu
 N, C, CLS, SEED = 2, 64, 101, 31

@@ -18,46 +18,11 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
+from .featmaps import rt  # noqa: F401
+from .forward import (CONV_CASES, GOLDEN, HANDLE_PRECISIONS, PATCH_CASES, PRECISIONS, RET_GOLDEN, RTOL, RTOL_NORTH_STAR, StubBackbone,
+                      check_sobel_tdiff, check_whole_forward, dev, features, make_handle, nhwc, rel_err, shape_of, signal_err)
+
 pytestmark = pytest.mark.gpu
-RTOL_NORTH_STAR = 1e-3
-RTOL = 2e-4
-PRECISIONS = ["fp32"]   # (until round 4 also "bf16x3", the two-plane split mode: retired in ABI v9 in favour of the exact three-plane mode)
-# handle-level arithmetic modes: f32split = fp32 operands as three bf16 planes on the bf16 pipe (round 5; its own error tests:
-# tests/test_gpu_split.py); kernels without a split form run as in fp32
-HANDLE_PRECISIONS = PRECISIONS + ["f32split"]
-
-
-def rel_err(a, b):
-    a = a.detach().double().cpu() if torch.is_tensor(a) else torch.as_tensor(a).double()
-    b = b.detach().double().cpu() if torch.is_tensor(b) else torch.as_tensor(b).double()
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
-
-
-def signal_err(a, b):
-    """Error of the ROW-TO-ROW signal: the logits are bias-dominated under default init (the part that
-    differs between rows is ~2.6 % of their magnitude), so rel_err admits ~1 % of the actual signal.  This removes the
-    per-class mean over rows from both sides and normalises by the signal's own maximum."""
-    a = a.detach().double().cpu() if torch.is_tensor(a) else torch.as_tensor(a).double()
-    b = b.detach().double().cpu() if torch.is_tensor(b) else torch.as_tensor(b).double()
-    assert a.shape == b.shape and a.shape[0] >= 2, (a.shape, b.shape)
-    da, db = a - a.mean(0, keepdim=True), b - b.mean(0, keepdim=True)
-    return ((da - db).abs().max() / (db.abs().max() + 1e-30)).item()
-
-
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def dev(x):
-    return torch.as_tensor(x).to("cuda").contiguous()
-
-
-def nhwc(x):  # logical NCHW cpu tensor -> channels-last physical, on device
-    return x.permute(0, 2, 3, 1).contiguous().to("cuda")
 
 
 def test_layout_helpers(rt):
@@ -67,13 +32,6 @@ def test_layout_helpers(rt):
     assert torch.equal(y.cpu(), x.permute(0, 2, 3, 1).contiguous())
     z = rt.nhwc_to_nchw(y, coff=5, c=20)
     assert torch.equal(z.cpu(), x[:, 5:25].contiguous())
-
-
-CONV_CASES = [  # (Ci, Co, k, stride, pad, H, n_img)  -- the distinct shapes of spec.FUSION_CONVS at small size
-    (320, 64, 7, 2, 3, 28, 2), (64, 64, 1, 1, 0, 14, 3), (64, 64, 3, 1, 1, 14, 2), (64, 256, 1, 1, 0, 14, 2),
-    (256, 64, 1, 1, 0, 14, 2), (1056, 128, 5, 2, 2, 14, 2), (128, 128, 3, 1, 1, 7, 5), (128, 512, 1, 1, 0, 7, 3),
-    (512, 128, 1, 1, 0, 7, 3), (128, 512, 3, 1, 1, 7, 3), (832, 256, 3, 1, 1, 7, 2), (256, 1024, 1, 1, 0, 7, 3),
-]
 
 
 @pytest.mark.parametrize("prec", [0])
@@ -154,13 +112,6 @@ def test_conv2d_tile_plans_and_splitk(rt, cfg, splitk, prec):
     assert torch.equal(y, y2)      # split-K sums slabs in a fixed order: bit-reproducible
 
 
-PATCH_CASES = [  # (k, stride, H, Ci, Co, n_img, cfg, splitk): the four shapes of the LDS-patch kernel, partial last groups
-    (7, 2, 28, 320, 64, 3, 7, 1), (7, 2, 28, 64, 128, 2, 6, 2), (5, 2, 14, 1056, 128, 6, 6, 3), (5, 2, 14, 96, 64, 9, 7, 1),
-    (3, 1, 14, 64, 64, 3, 7, 2), (3, 1, 14, 128, 256, 2, 6, 1), (3, 1, 7, 832, 256, 7, 6, 4), (3, 1, 7, 128, 128, 5, 7, 1),
-    (3, 1, 7, 256, 256, 8, 6, 3),
-]
-
-
 @pytest.mark.parametrize("prec", [0])
 @pytest.mark.parametrize("k,stride,H,Ci,Co,n,cfg,splitk", PATCH_CASES)
 def test_conv2d_patch_kernel_vs_torch(rt, k, stride, H, Ci, Co, n, cfg, splitk, prec):
@@ -214,14 +165,6 @@ def test_head_and_consensus(rt):
     assert rel_err(rt.segment_consensus(dev(x), 4), orc.segment_consensus(x, 4)) < 1e-6
 
 
-def make_handle(rt, B, L, variant, slice_mode=spec.SLICE_FLAT, consensus=None, weights=None, precision="fp32"):
-    h = rt.OffForward(B, L, variant, slice_mode, consensus, precision=precision)
-    w = synth.make_weights(variant) if weights is None else weights
-    assert h.load_state_dict(w) == []
-    assert h.missing_weights()[0] == 0
-    return h, orc.to_torch_weights(w)
-
-
 @pytest.mark.parametrize("prec", PRECISIONS)
 @pytest.mark.parametrize("slice_mode", [spec.SLICE_FLAT, spec.SLICE_PER_CLIP])
 @pytest.mark.parametrize("site", range(spec.NUM_SITES))
@@ -238,32 +181,13 @@ def test_pw_reduce_vs_oracle(rt, site, slice_mode, prec):
     assert rel_err(D.view(B * (L - 1), H, H, 32).permute(0, 3, 1, 2), d_ref) < RTOL
 
 
-def _check_sobel_tdiff(h, w, B, L, site, variant, algo):
-    name, _C, H = spec.SITES[site]
-    g = torch.Generator().manual_seed(site + 10 * variant)
-    G = torch.relu(torch.randn(B * L, 128, H, H, generator=g))
-    D = torch.randn(B * (L - 1), 32, H, H, generator=g)
-    t_ref = orc.temporal_diff(G, B)
-    if variant == spec.VARIANT_RGB:
-        s_ref = F.conv2d(D, w["motion_spatial_grad_%s.weight" % name], w["motion_spatial_grad_%s.bias" % name],
-                         padding=1, groups=32)
-    else:
-        s_ref = F.conv2d(D, w[spec.SOBEL_KEY], None, padding=1, groups=32)
-    M = torch.full((B * (L - 1) * H * H, 352), -3.0, device="cuda")
-    h.sobel_tdiff(site, nhwc(G).view(-1, 128), nhwc(D).view(-1, 32), M, 160, algo)
-    Mv = M.view(B * (L - 1), H, H, 352).permute(0, 3, 1, 2)
-    assert rel_err(Mv[:, 160:192], s_ref) < RTOL, name
-    assert rel_err(Mv[:, 192:320], t_ref) < 1e-6, name          # a single fp32 subtraction: exact
-    assert torch.all(Mv[:, :160] == -3.0) and torch.all(Mv[:, 320:] == -3.0), name
-
-
 @pytest.mark.parametrize("algo", [0, 1, 4])      # temporal difference by register rotation / wavefront shuffle / flat shifted stream
 @pytest.mark.parametrize("variant", [spec.VARIANT_RGB, spec.VARIANT_FLOW])
 @pytest.mark.parametrize("site", range(spec.NUM_SITES))      # every site's own depthwise taps and map size, not only through whole-forward buffers
 def test_sobel_tdiff_vs_oracle(rt, site, variant, algo):
     B, L = 2, 4
     h, w = make_handle(rt, B, L, variant)
-    _check_sobel_tdiff(h, w, B, L, site, variant, algo)
+    check_sobel_tdiff(h, w, B, L, site, variant, algo)
 
 
 @pytest.mark.parametrize("algo", [0, 1, 4])
@@ -273,47 +197,20 @@ def test_sobel_tdiff_vs_oracle_clip_shapes(rt, B, L, variant, algo):
     """A single pair (B = 1, L = 2: no neighbour pair on either side) and an odd batch of longer clips, all nine sites."""
     h, w = make_handle(rt, B, L, variant)
     for site in range(spec.NUM_SITES):
-        _check_sobel_tdiff(h, w, B, L, site, variant, algo)
-
-
-GOLDEN = ["rgb_b1_l7", "rgb_b2_l3", "rgb_b3_l7", "flow_b1_l7", "flow_b2_l3", "flow_b3_l7", "rgbv2_b2_l3"]
+        check_sobel_tdiff(h, w, B, L, site, variant, algo)
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("tag", GOLDEN)
-def test_forward_vs_golden_and_oracle(rt, tag, golden_dir, prec):
-    g = np.load(os.path.join(golden_dir, tag + ".npz"))
-    variant, B, L, cfg = (int(v) for v in g["meta"])
+def test_forward_vs_golden_and_oracle(rt, tag, prec):
+    """The reference's own outputs (captured by oracle/gen_golden.py) and the oracle, every fusion-stage intermediate included; the
+    logits are bias-dominated under default init, so the row-to-row signal is pinned too, at the north_star tolerance
+    (the signal is ~2.6 % of the logit magnitude: ~40x stricter than the logit check)."""
+    variant, B, L, cfg, _g = shape_of(tag)
     h, w = make_handle(rt, B, L, variant, consensus=False, precision=prec)
-    feats_np = synth.make_features(B, L, cfg)
-    out7, out14, out28 = h.forward([dev(f) for f in feats_np])
+    out = h.forward([dev(f) for f in features(B, L, cfg)])
     torch.cuda.synchronize()
-    # (1) the reference's own outputs (captured by oracle/gen_golden.py)
-    for out, key in ((out7, "fc7"), (out14, "fc14"), (out28, "fc28")):
-        assert rel_err(out, g[key]) < RTOL, key
-    # (2) the oracle, including every fusion-stage intermediate
-    with torch.no_grad():
-        (r7, r14, r28), st = orc.off_forward([torch.from_numpy(f) for f in feats_np], w, B, L, variant,
-                                             orc.SLICE_FLAT, consensus=False, return_stages=True)
-    assert rel_err(out7, r7) < RTOL and rel_err(out14, r14) < RTOL and rel_err(out28, r28) < RTOL
-    P = B * (L - 1)
-    for name, ch, H in (("fusion_28", 320, 28), ("fusion_14", 1056, 14), ("fusion_7", 832, 7), ("sum_7", 1024, 7)):
-        got = h.region(name, ch).view(P, H, H, ch).permute(0, 3, 1, 2)
-        assert rel_err(got, st[name]) < RTOL, name
-    if "full_motion_5a" in g.files:
-        got = h.region("fusion_7", 832).view(P, 7, 7, 832).permute(0, 3, 1, 2)[:, :160]
-        assert rel_err(got, g["full_motion_5a"]) < RTOL
-    # logits are bias-dominated under default init (SURVEY 7.3 item 6): also pin the row-to-row signal, at the
-    # north_star tolerance (the signal is ~2.6 % of the logit magnitude, so this is ~40x stricter than the check above)
-    for out, key in ((out7, "fc7"), (out14, "fc14"), (out28, "fc28")):
-        if B * (L - 1) < 2:
-            continue
-        d = (out - out.mean(0, keepdim=True)).cpu().double()
-        dr = torch.from_numpy(g[key]).double()
-        dr = dr - dr.mean(0, keepdim=True)
-        sig_err = ((d - dr).abs().max() / dr.abs().max()).item()
-        print("%s %s %s: row-to-row signal error %.2e" % (tag, prec, key, sig_err))
-        assert sig_err < RTOL_NORTH_STAR, (key, sig_err)
+    check_whole_forward(h, out, tag, w, "%s %s" % (tag, prec))
 
 
 @pytest.mark.parametrize("tag", ["flow_b2_l3", "flow_b3_l7"])
@@ -611,22 +508,6 @@ def test_pw_reduce_cancellation_case(rt, prec):
 
 # ---- round 2: the drop-in class itself on the GPU (VERDICT r01 missing #1) -------------------
 
-class _StubBackbone(torch.nn.Module):
-    """Stands for the TSN backbone (out of scope, RGB_OFF.py:362-594): hands back the nine tap maps, the per-frame
-    Feature_Generation_Score the golden captured from the reference's own backbone and, for RGB_OFF_v2, conv2."""
-
-    def __init__(self, feats, fgs, conv2=None):
-        super().__init__()
-        self.feats, self.fgs, self.conv2 = feats, fgs, conv2
-
-    def forward(self, frames):
-        assert frames.shape[0] == self.fgs.shape[0]
-        return (self.feats, self.fgs) if self.conv2 is None else (self.feats, self.fgs, self.conv2)
-
-
-RET_GOLDEN = ["ret_rgb_b2_l3", "ret_rgb_b1_l2", "ret_flow_b2_l3", "ret_flow_b1_l2", "ret_rgbv2_b2_l3"]
-
-
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("tag", RET_GOLDEN)
 def test_bninception_off_mirror_returns_what_the_reference_returns(rt, tag, prec, golden_dir):
@@ -642,7 +523,7 @@ def test_bninception_off_mirror_returns_what_the_reference_returns(rt, tag, prec
     fgs = dev(g["fgs_raw"])
     in_ch = 10 if ref_file == "flow" else 3
     conv2 = torch.full((B * L, 192, 2, 2), 3.0, device="cuda") if ref_file == "rgb_v2" else None
-    m = off_module.bninception_off(101, B, L, variant=ref_file, backbone=_StubBackbone(feats, fgs, conv2), precision=prec)
+    m = off_module.bninception_off(101, B, L, variant=ref_file, backbone=StubBackbone(feats, fgs, conv2), precision=prec)
     sd = {"module." + k: torch.from_numpy(v) for k, v in synth.make_weights(variant).items()}
     m.load_state_dict(sd, strict=False)
     assert (m.batch, m.length, m.modality_fuse) == (B, L, False)

@@ -24,108 +24,49 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
-from .test_gpu_parity import GOLDEN, HANDLE_PRECISIONS, RTOL, RTOL_NORTH_STAR, dev, make_handle, rel_err, rt, signal_err  # noqa: F401
+from .featmaps import rt  # noqa: F401
+from .forward import (FORCE, GOLDEN, HANDLE_PRECISIONS, RTOL, RTOL_NORTH_STAR, STAGES, StubBackbone, check_whole_forward, dev, features,
+                      make_handle, oracle_b64, rel_err, shape_of, signal_err, stage_errs, traced_forward)
+from .wino_ref import between_reference
 
 pytestmark = pytest.mark.gpu
-
-STAGES = (("fusion_28", 320, 28), ("fusion_14", 1056, 14), ("fusion_7", 832, 7), ("sum_7", 1024, 7))
-FORCE = {"OFFK_CHAIN": "2", "OFFK_WINOGRAD_5X5": "2", "OFFK_WINOGRAD_7X7": "2"}
-
-
-def forced_handle(rt, monkeypatch, *args, **kw):
-    for k, v in FORCE.items():
-        monkeypatch.setenv(k, v)
-    try:
-        return make_handle(rt, *args, **kw)
-    finally:
-        for k in FORCE:
-            monkeypatch.delenv(k)
-
-
-def stage_errs(h, st, P):
-    return dict((name, rel_err(h.region(name, ch).view(P, H, H, ch).permute(0, 3, 1, 2), st[name])) for name, ch, H in STAGES)
-
-
-def launches_of(h, feats):
-    """Names of the launch groups one forward enqueues (per-launch trace of the library)."""
-    h.set_profiling(2)
-    h.forward(feats)
-    torch.cuda.synchronize()
-    names = list(h.launch_times().keys())
-    h.set_profiling(0)
-    return names
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("tag", GOLDEN)
-def test_goldens_through_the_gated_kernels(rt, tag, golden_dir, monkeypatch, prec):
+def test_goldens_through_the_gated_kernels(rt, tag, prec):
     """All seven reference goldens with every pair-count gate forced open: the reference's own outputs (fc7 / fc14 / fc28) and the
     oracle's stage tensors after chain14_kernel, the polyphase 5x5 and the 7x7 Winograd kernels -- in both arithmetic modes (split-fp32:
     the GEMMs of both polyphase convs and the chains' contractions on the bf16 pipe see reference-held outputs here)."""
-    g = np.load(os.path.join(golden_dir, tag + ".npz"))
-    variant, B, L, cfg = (int(v) for v in g["meta"])
-    h, w = forced_handle(rt, monkeypatch, B, L, variant, consensus=False, precision=prec)
-    feats_np = synth.make_features(B, L, cfg)
-    feats = [dev(f) for f in feats_np]
-    names = launches_of(h, feats)
-    assert any(n.startswith("chain_28a") for n in names), names
-    assert any(n.startswith("motion_conv_trans_14 [winograd") for n in names), names
-    assert any(n.startswith("motion_conv_trans_28 [winograd") for n in names), names
-    out7, out14, out28 = h.forward(feats)
+    variant, B, L, cfg, _g = shape_of(tag)
+    h, w = make_handle(rt, B, L, variant, consensus=False, precision=prec, env=FORCE)
+    feats = [dev(f) for f in features(B, L, cfg)]
+    names, _traced = traced_forward(h, feats)
+    for sub in ("chain_28a", "motion_conv_trans_14 [winograd", "motion_conv_trans_28 [winograd"):
+        assert any(n.startswith(sub) for n in names), (sub, names)
+    out = h.forward(feats)                                  # (checked: a forward with the trace off)
     torch.cuda.synchronize()
-    for out, key in ((out7, "fc7"), (out14, "fc14"), (out28, "fc28")):
-        assert rel_err(out, g[key]) < RTOL, key
-    with torch.no_grad():
-        _ref, st = orc.off_forward([torch.from_numpy(f) for f in feats_np], w, B, L, variant, orc.SLICE_FLAT, consensus=False,
-                                   return_stages=True)
-    P = B * (L - 1)
-    errs = stage_errs(h, st, P)
-    print("%s %s gates open: stage errors %s" % (tag, prec, " ".join("%s %.1e" % kv for kv in errs.items())))
-    assert max(errs.values()) < RTOL, errs
-    if P >= 2:
-        for out, key in ((out7, "fc7"), (out14, "fc14"), (out28, "fc28")):
-            se = signal_err(out, g[key])
-            assert se < RTOL_NORTH_STAR, (key, se)
+    check_whole_forward(h, out, tag, w, "%s %s gates open" % (tag, prec))
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("kind", ["full_mantissa", "heavy_tail"])
 @pytest.mark.parametrize("mode", ["gates_open_p18", "default_gates_p72"])
-def test_stress_inputs_through_the_gated_kernels(rt, kind, mode, monkeypatch, prec):
+def test_stress_inputs_through_the_gated_kernels(rt, kind, mode, prec):
     """Full-mantissa / heavy-tailed maps (synth.make_features_kind) through the chain and polyphase-Winograd kernels: at B = 3
     with the gates forced open, and at B = 12 (P = 72) where the default gates select them."""
     B, L = (3, 7) if mode == "gates_open_p18" else (12, 7)
     feats_np = synth.make_features_kind(B, L, 3, kind)
-    if mode == "gates_open_p18":
-        h, w = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, precision=prec)
-    else:
-        h, w = make_handle(rt, B, L, spec.VARIANT_RGB, precision=prec)
+    h, w = make_handle(rt, B, L, spec.VARIANT_RGB, precision=prec, env=FORCE if mode == "gates_open_p18" else None)
     feats = [dev(f) for f in feats_np]
-    names = launches_of(h, feats)
-    assert any(n.startswith("chain_28a") for n in names) and any(n.startswith("motion_conv_trans_14 [winograd") for n in names), names
+    names, _traced = traced_forward(h, feats)
+    for sub in ("chain_28a", "motion_conv_trans_14 [winograd"):
+        assert any(n.startswith(sub) for n in names), (sub, names)
     got = h.forward(feats)
     torch.cuda.synchronize()
     with torch.no_grad():
-        want, st = orc.off_forward([torch.from_numpy(f) for f in feats_np], w, B, L, spec.VARIANT_RGB, orc.SLICE_FLAT, return_stages=True)
-    P = B * (L - 1)
-    errs = stage_errs(h, st, P)
-    lerr = [rel_err(a, b) for a, b in zip(got, want)]
-    sig = signal_err(got[0], want[0])
-    print("forward %s on %s maps, %s: logits %.2e %.2e %.2e, stages %s, fc7 row-to-row signal %.2e"
-          % ((prec, kind, mode) + tuple(lerr) + (" ".join("%.1e" % v for v in errs.values()), sig)))
-    assert max(lerr) < RTOL and max(errs.values()) < RTOL and sig < RTOL_NORTH_STAR
-
-
-_ORACLE_B64 = {}
-
-
-def oracle_b64(variant, feats_np, w):
-    """The oracle's B = 64 forward with stage tensors (~25 s of host time): once per variant, shared by both arithmetic modes."""
-    if variant not in _ORACLE_B64:
-        with torch.no_grad():
-            _ORACLE_B64[variant] = orc.off_forward([torch.from_numpy(f) for f in feats_np], w, 64, 7, variant, orc.SLICE_FLAT, consensus=False,
-                                                   return_stages=True)
-    return _ORACLE_B64[variant]
+        ref = orc.off_forward([torch.from_numpy(f) for f in feats_np], w, B, L, spec.VARIANT_RGB, orc.SLICE_FLAT, return_stages=True)
+    check_whole_forward(h, got, None, w, "forward %s on %s maps, %s" % (prec, kind, mode), oracle_run=ref)
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
@@ -265,14 +206,14 @@ def test_chain_winograd_weights_follow_a_weight_update(rt, monkeypatch):
     weight finaliser) before the next forward: gates open (B = 3), against a fresh handle holding the updated weights."""
     B, L = 3, 7
     feats = [dev(f) for f in synth.make_features(B, L, 2)]
-    h, _w = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB)
+    h, _w = make_handle(rt, B, L, spec.VARIANT_RGB, env=FORCE)
     a = [t.clone() for t in h.forward(feats)]
     w1 = dict(synth.make_weights(spec.VARIANT_RGB))
     for i, k in enumerate(("motion_conv2_trans_28a", "motion_conv2_trans_28b", "motion_conv2_trans_28c")):
         w1[k + ".weight"] = w1[k + ".weight"] * np.float32(1.5 + 0.25 * i)
         h.set_weight(k + ".weight", torch.from_numpy(w1[k + ".weight"]))
     b = h.forward(feats)
-    h2, _w2 = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB, weights=w1)
+    h2, _w2 = make_handle(rt, B, L, spec.VARIANT_RGB, weights=w1, env=FORCE)
     c = h2.forward(feats)
     torch.cuda.synchronize()
     for x, y in zip(b, c):
@@ -285,11 +226,10 @@ def test_modality_fuse_keeps_the_backbone_score_differentiable(rt):
     backbone's score requires grad (fine-tuning the TSN stream through the fused score) the sum must stay on the autograd graph:
     d fused / d fgs = 1 / L per frame (SegmentConsensus avg, basic_ops.py:19-21, 29-33)."""
     from offk_amd import off_module
-    from .test_gpu_parity import _StubBackbone
     B, L = 2, 3
     feats = [dev(f) for f in synth.make_features(B, L, 2)]
     fgs = torch.randn(B * L, 101, device="cuda", requires_grad=True)
-    m = off_module.bninception_off(101, B, L, variant="flow", backbone=_StubBackbone(feats, fgs))
+    m = off_module.bninception_off(101, B, L, variant="flow", backbone=StubBackbone(feats, fgs))
     m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_weights(spec.VARIANT_FLOW).items()}, strict=False)
     m.modality_fuse = True
     frames = torch.zeros(B * L, 10, 8, 8, device="cuda")
@@ -321,58 +261,6 @@ def test_single_rank_rccl_smoke():
 
 # ---- round 4: what sits between two Winograd convs (wino_mid.hip) through its C-ABI entry point ----------------------------------
 
-# the 1-D transforms of winograd.hip as matrices: F(4, 3) (points 0, +-1, +-2, inf) and F(3, 3) (points 0, 1, -1, 2, inf)
-_AT = {4: np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], dtype=np.float64),
-       3: np.array([[1, 1, 1, 1, 0], [0, 1, -1, 2, 0], [0, 1, 1, 4, 1]], dtype=np.float64)}
-_BT = {6: np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
-                    [0, 4, 0, -5, 0, 1]], dtype=np.float64),
-       5: np.array([[2, -1, -2, 1, 0], [0, -2, -1, 1, 0], [0, 2, -3, 1, 0], [0, -1, 0, 1, 0], [0, 2, -1, -2, 1]], dtype=np.float64)}
-
-
-def _mindex(phases, cy, cx, i, j):
-    """Point numbering of winograd.hip (wino_mindex): class (cy, cx) has NY x NX points."""
-    ny, nx, cls = (5 if cy else 6), (5 if cx else 6), 2 * cy + cx
-    if phases == 1:
-        return (0, 36, 66, 96)[cls] + i * nx + j
-    offa, offb, offc = (0, 25, 45, 65), (0, 5, 9, 14), (0, 5, 10, 14)
-    if i < ny - 1 and j < nx - 1:
-        return offa[cls] + i * (nx - 1) + j
-    if i == ny - 1 and j < nx - 1:
-        return 81 + offb[cls] + j
-    if j == nx - 1 and i < ny - 1:
-        return 99 + offc[cls] + i
-    return 117 + cls
-
-
-def _between_reference(M, bias, phases, w1, b1):
-    """fp64 restatement: x = relu(A^T M A + bias) per class -> [n, 7, 7, Cin]; t = relu(x W1^T + b1); V = B^T t B per class."""
-    _pts, n, cin = M.shape
-    x = np.zeros((n, 7, 7, cin))
-    for cy in (0, 1):
-        for cx in (0, 1):
-            ny, nx = (5 if cy else 6), (5 if cx else 6)
-            m = np.stack([np.stack([M[_mindex(phases, cy, cx, i, j)] for j in range(nx)], 0) for i in range(ny)], 0)   # [ny, nx, n, c]
-            y = np.einsum("oi,ijnc,pj->opnc", _AT[3 if cy else 4], m, _AT[3 if cx else 4])
-            oy, ox = (4 if cy else 0), (4 if cx else 0)
-            x[:, oy:oy + y.shape[0], ox:ox + y.shape[1]] = np.transpose(y, (2, 0, 1, 3))
-    x = np.maximum(x + bias, 0.0)
-    t = np.maximum(x @ w1.T + b1, 0.0) if w1 is not None else x
-    cm = t.shape[-1]
-    tp = np.zeros((n, 9, 9, cm))
-    tp[:, 1:8, 1:8] = t                                     # zero padding 1
-    V = np.zeros((121, n, cm))
-    for cy in (0, 1):
-        for cx in (0, 1):
-            ny, nx = (5 if cy else 6), (5 if cx else 6)
-            oy, ox = (4 if cy else 0), (4 if cx else 0)
-            d = tp[:, oy:oy + ny, ox:ox + nx]                # window rows oy - 1 .. (padded index = image index + 1)
-            v = np.einsum("pi,nijc,qj->pqnc", _BT[ny], d, _BT[nx])
-            for i in range(ny):
-                for j in range(nx):
-                    V[_mindex(1, cy, cx, i, j)] = v[i, j]
-    return x, V
-
-
 # (the forms with a 1x1 conv in both arithmetic modes -- stage B is what runs in split arithmetic; the forms without one have no such mode)
 @pytest.mark.parametrize("cin,phases,gemm,prec", [(128, 4, True, "fp32"), (128, 1, True, "fp32"), (256, 1, True, "fp32"), (128, 1, False, "fp32"),
                                                   (256, 1, False, "fp32"), (128, 4, True, "f32split"), (128, 1, True, "f32split"), (256, 1, True, "f32split")])
@@ -389,7 +277,7 @@ def test_winograd_between_vs_fp64(rt, cin, phases, gemm, n, prec):
     xbuf = torch.full((n, 7, 7, cin + 64), -3.0, device="cuda")
     V = rt.winograd_between(dev(M), dev(bias), phases, dev(w1) if gemm else None, dev(b1) if gemm else None, x=xbuf, x_coff=32, precision=prec)
     torch.cuda.synchronize()
-    x_ref, v_ref = _between_reference(M.astype(np.float64), bias.astype(np.float64), phases,
+    x_ref, v_ref = between_reference(M.astype(np.float64), bias.astype(np.float64), phases,
                                       w1.astype(np.float64) if gemm else None, b1.astype(np.float64) if gemm else None)
     ex = rel_err(xbuf[..., 32:32 + cin], x_ref)
     ev = rel_err(V, v_ref)
@@ -407,12 +295,12 @@ def test_winograd_between_off_matches_on(rt, monkeypatch):
     feats_np = synth.make_features(B, L, 2)
     feats = [dev(f) for f in feats_np]
     h1, w = make_handle(rt, B, L, spec.VARIANT_RGB)
-    names = launches_of(h1, feats)
+    names = traced_forward(h1, feats)[0]
     assert sum("[winograd: between]" in n for n in names) == 3, names
     monkeypatch.setenv("OFFK_WINO_MID", "0")
     h0, _ = make_handle(rt, B, L, spec.VARIANT_RGB)
     monkeypatch.delenv("OFFK_WINO_MID")
-    assert not any("[winograd: between]" in n for n in launches_of(h0, feats))
+    assert not any("[winograd: between]" in n for n in traced_forward(h0, feats)[0])
     a, b = h1.forward(feats), h0.forward(feats)
     torch.cuda.synchronize()
     for x, y in zip(a, b):
@@ -431,9 +319,9 @@ def test_chain_winograd_3x3_vs_direct_and_oracle(rt, monkeypatch, B, kind):
     L = 7
     feats_np = synth.make_features(B, L, 2) if kind is None else synth.make_features_kind(B, L, 3, kind)
     feats = [dev(f) for f in feats_np]
-    h1, w = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB)
+    h1, w = make_handle(rt, B, L, spec.VARIANT_RGB, env=FORCE)
     monkeypatch.setenv("OFFK_CHAIN_WINO", "0")
-    h0, _ = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB)
+    h0, _ = make_handle(rt, B, L, spec.VARIANT_RGB, env=FORCE)
     monkeypatch.delenv("OFFK_CHAIN_WINO")
     a, b = h1.forward(feats), h0.forward(feats)
     torch.cuda.synchronize()
@@ -460,9 +348,9 @@ def test_wino_gemm_persistent_matches_generic(rt, monkeypatch, B):
     a few per block; 64: the benchmark shape, grouped launches with three K lengths."""
     L = 7
     feats = [dev(f) for f in synth.make_features(B, L, 2)]
-    h1, _ = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB)
+    h1, _ = make_handle(rt, B, L, spec.VARIANT_RGB, env=FORCE)
     monkeypatch.setenv("OFFK_WINO_GEMM", "0")
-    h0, _ = forced_handle(rt, monkeypatch, B, L, spec.VARIANT_RGB)
+    h0, _ = make_handle(rt, B, L, spec.VARIANT_RGB, env=FORCE)
     monkeypatch.delenv("OFFK_WINO_GEMM")
     a, b = h1.forward(feats), h0.forward(feats)
     torch.cuda.synchronize()

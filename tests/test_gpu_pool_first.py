@@ -25,10 +25,9 @@ import torch
 import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
-from .test_gpu_bounds import forward_body, np_feats, two_runs
-from .test_gpu_heads import head_handle, head_weights
-from .test_gpu_parity import HANDLE_PRECISIONS, dev, rel_err, rt  # noqa: F401
-from .test_gpu_switches import check_trace, switched_handle, traced_forward
+from .featmaps import rt  # noqa: F401
+from .forward import HANDLE_PRECISIONS, check_trace, dev, head_handle, head_weights, make_handle, rel_err, traced_forward
+from .guarded import forward_body, np_feats, two_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -59,9 +58,9 @@ def random_feats(B, L):
 # ---- trace ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("shape", list(SHAPES))
-def test_forced_gate_drops_merged_7(rt, monkeypatch, shape, prec):
+def test_forced_gate_drops_merged_7(rt, shape, prec):
     B, L = SHAPES[shape]
-    h, _ = head_handle(rt, monkeypatch, GATE, B, L, prec)
+    h, _ = head_handle(rt, GATE, B, L, prec)
     names, _out = traced_forward(h, feats_of(shape))
     check_trace(names, (FC_LAUNCH, "motion_conv2_trans [winograd: output transform]", "merged_14a"), ("merged_7", "head_7"))
 
@@ -82,9 +81,9 @@ OFF = {"pool_first0": {"OFFK_POOL_FIRST_7": "0"}, "fold_pool0": dict(GATE, OFFK_
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("switch", list(OFF))
-def test_each_switch_restores_merged_7(rt, monkeypatch, switch, prec):
+def test_each_switch_restores_merged_7(rt, switch, prec):
     B, L = SHAPES["p18"]
-    h, _ = head_handle(rt, monkeypatch, OFF[switch], B, L, prec)
+    h, _ = head_handle(rt, OFF[switch], B, L, prec)
     names, _out = traced_forward(h, feats_of("p18"))
     check_trace(names, ("merged_7",), ())
 
@@ -110,11 +109,11 @@ CONFIGS = {"ncls101": (101, False, True), "ncls51": (51, False, True), "consensu
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("shape", list(SHAPES))
 @pytest.mark.parametrize("config", list(CONFIGS))
-def test_head7_vs_fp64_from_device_xv(rt, monkeypatch, config, shape, prec):
+def test_head7_vs_fp64_from_device_xv(rt, config, shape, prec):
     ncls, consensus, want28 = CONFIGS[config]
     B, L = SHAPES[shape]
     P = B * (L - 1)
-    h, w = head_handle(rt, monkeypatch, GATE, B, L, prec, ncls=ncls, consensus=consensus)
+    h, w = head_handle(rt, GATE, B, L, prec, ncls=ncls, consensus=consensus)
     h.region("poolpart_7t", 512)                      # (the region exists on handles that take the path only)
     o7, _o14, o28 = h.forward(feats_of(shape), want28=want28)
     torch.cuda.synchronize()
@@ -137,17 +136,17 @@ def raw_region(h, name, channels):
     return h.workspace[off.value:off.value + nb.value].view(torch.float32).view(-1, channels)
 
 
-def pair_of_handles(rt, monkeypatch, shape, prec):
+def pair_of_handles(rt, shape, prec):
     B, L = SHAPES[shape]
-    h1, _ = head_handle(rt, monkeypatch, GATE, B, L, prec)
-    h0, _ = head_handle(rt, monkeypatch, {"OFFK_POOL_FIRST_7": "0"}, B, L, prec)
+    h1, _ = head_handle(rt, GATE, B, L, prec)
+    h0, _ = head_handle(rt, {"OFFK_POOL_FIRST_7": "0"}, B, L, prec)
     return h1, h0
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("shape", list(SHAPES))
-def test_against_the_old_path(rt, monkeypatch, shape, prec):
-    h1, h0 = pair_of_handles(rt, monkeypatch, shape, prec)
+def test_against_the_old_path(rt, shape, prec):
+    h1, h0 = pair_of_handles(rt, shape, prec)
     a, b = h1.forward(feats_of(shape)), h0.forward(feats_of(shape))
     torch.cuda.synchronize()
     assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
@@ -163,8 +162,8 @@ def test_against_the_old_path(rt, monkeypatch, shape, prec):
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
-def test_sum_7_on_demand(rt, monkeypatch, prec):
-    h1, h0 = pair_of_handles(rt, monkeypatch, "p18", prec)
+def test_sum_7_on_demand(rt, prec):
+    h1, h0 = pair_of_handles(rt, "p18", prec)
     fa = feats_of("p18")
     fb = [f.flip(0).contiguous() for f in fa]
     h1.workspace.zero_()
@@ -195,21 +194,16 @@ def test_sum_7_on_demand(rt, monkeypatch, prec):
 # ---- weight updates ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("key", SOURCES)
-def test_set_weight_remakes_the_composed_head(rt, monkeypatch, key, prec):
+def test_set_weight_remakes_the_composed_head(rt, key, prec):
     B, L = SHAPES["p18"]
     w = head_weights(spec.NUM_CLASSES)
-    h, _ = head_handle(rt, monkeypatch, GATE, B, L, prec)
+    h, _ = head_handle(rt, GATE, B, L, prec)
     before = h.forward(feats_of("p18"))[0].clone()
     g = np.random.default_rng(SOURCES.index(key))
     new = (w[key] * 0.5 + 0.05 * g.standard_normal(w[key].shape) * (np.abs(w[key]).max() + 0.1)).astype(np.float32)
     h.set_weight(key, new)
     got = h.forward(feats_of("p18"))
-    for k, v in GATE.items():
-        monkeypatch.setenv(k, v)
-    fresh = rt.OffForward(B, L, spec.VARIANT_RGB, precision=prec)
-    for k in GATE:
-        monkeypatch.delenv(k)
-    assert fresh.load_state_dict(dict(w, **{key: new})) == []
+    fresh, _ = make_handle(rt, B, L, spec.VARIANT_RGB, weights=dict(w, **{key: new}), precision=prec, env=GATE)
     want = fresh.forward(feats_of("p18"))
     torch.cuda.synchronize()
     assert not torch.equal(got[0], before), key
@@ -220,10 +214,10 @@ def test_set_weight_remakes_the_composed_head(rt, monkeypatch, key, prec):
 
 # ---- the other forward entries -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["bf16", "f32cl", "f16cl", "parts"])
-def test_typed_and_channels_last_entries(rt, monkeypatch, form):
+def test_typed_and_channels_last_entries(rt, form):
     """offk_forward_typed / _cl / _parts share the forward behind the units: same logits as the plain entry on the widened, contiguous maps."""
     B, L = SHAPES["p18"]
-    h, _ = head_handle(rt, monkeypatch, GATE, B, L, "f32split")
+    h, _ = head_handle(rt, GATE, B, L, "f32split")
     dt = {"bf16": torch.bfloat16, "f16cl": torch.float16}.get(form, torch.float32)
     base = [f.to(dt) for f in feats_of("p18")]
     if form.endswith("cl"):
@@ -245,11 +239,11 @@ def test_typed_and_channels_last_entries(rt, monkeypatch, form):
 # ---- bounds ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
 @pytest.mark.parametrize("B,L", [(1, 3), (3, 3)])
-def test_forced_gate_forward_in_the_arena(rt, monkeypatch, B, L, prec):
-    """One forward on the new path with every buffer between guard bands and full of NaN beforehand (tests/test_gpu_bounds.two_runs):
+def test_forced_gate_forward_in_the_arena(rt, B, L, prec):
+    """One forward on the new path with every buffer between guard bands and full of NaN beforehand (tests/guarded.two_runs):
     the per-tile sums poolpart_7t and, after offk_stage_tensors, sum_7 stay inside their regions, are written completely and do not
     depend on what the workspace held."""
-    h = switched_handle(rt, monkeypatch, GATE, B, L, spec.VARIANT_RGB, precision=prec)[0]
+    h = make_handle(rt, B, L, spec.VARIANT_RGB, precision=prec, env=GATE)[0]
     inner = forward_body(h, np_feats(B, L))
 
     def body(r):

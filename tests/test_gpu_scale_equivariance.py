@@ -22,7 +22,7 @@ from . import featmaps as fx
 from . import head_bwd as hb
 from . import ranges as rg
 from .featmaps import rt  # noqa: F401
-from .test_gpu_heads import PATHS
+from .forward import HEAD_PATHS as PATHS
 
 pytestmark = pytest.mark.gpu
 SWEEP = rg.SWEEP

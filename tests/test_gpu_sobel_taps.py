@@ -21,12 +21,12 @@ from offk_amd import spec, synth
 from oracle import off_oracle as orc
 
 from . import exact
-from . import test_gpu_exact as ge
+from . import exact_units as ge
 from . import units_grad as ug
 from . import weight_updates as wu
 from .arena import same_bits
-from .test_gpu_parity import HANDLE_PRECISIONS, _check_sobel_tdiff, dev, make_handle, rt  # noqa: F401
-from .test_gpu_switches import traced_forward
+from .featmaps import rt  # noqa: F401
+from .forward import HANDLE_PRECISIONS, check_sobel_tdiff, dev, make_handle, traced_forward
 
 pytestmark = pytest.mark.gpu
 FLOW = spec.VARIANT_FLOW
@@ -78,7 +78,7 @@ def test_one_hot_taps_shift_d(rt, prec):
 
 # ---- integer taps -----------------------------------------------------------------------------------------------------------------
 class DenseSobelCase(ge.Case):
-    """tests/test_gpu_exact.py's Case with exact.dense_sobel at all nine sites."""
+    """tests/exact_units.py's Case with exact.dense_sobel at all nine sites."""
 
     def __init__(self, B, L, variant, slice_mode):
         sob = exact.dense_sobel()
@@ -101,12 +101,12 @@ def sobel_case(request):
 
 
 @pytest.mark.parametrize("prec", HANDLE_PRECISIONS)
-def test_units_forward_exact_with_integer_taps(rt, sobel_case, prec, monkeypatch):
-    ge.test_units_forward_exact(rt, sobel_case, prec, monkeypatch)
+def test_units_forward_exact_with_integer_taps(rt, sobel_case, prec):
+    ge.units_forward_exact(rt, sobel_case, prec)
 
 
 def test_units_backward_exact_with_integer_taps(rt, sobel_case):
-    ge.test_units_backward_exact(rt, sobel_case)
+    ge.units_backward_exact(rt, sobel_case)
 
 
 # ---- a dense weight against the oracle ----------------------------------------------------------------------------------------------
@@ -116,7 +116,7 @@ def test_sobel_tdiff_vs_oracle_with_a_dense_weight(rt, algo):
     h, w = make_handle(rt, B, L, FLOW, weights=dense_weights())
     assert bool((w[spec.SOBEL_KEY] != 0).all())
     for site in range(spec.NUM_SITES):
-        _check_sobel_tdiff(h, w, B, L, site, FLOW, algo)
+        check_sobel_tdiff(h, w, B, L, site, FLOW, algo)
 
 
 class DenseCase(ug.Case):

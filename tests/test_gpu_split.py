@@ -17,28 +17,21 @@ import torch.nn.functional as F
 import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
+from . import forward
+from .featmaps import rt  # noqa: F401
+from .forward import chain_inputs, dev, rel_err
+from .wino_ref import between_reference
+
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -24
 KINDS = ["synth", "full_mantissa", "heavy_tail"]
 
 
-@pytest.fixture(scope="module")
-def rt():
-    assert torch.cuda.is_available(), "gpu tests need a HIP device"
-    from offk_amd import runtime
-    return runtime
-
-
-def dev(x):
-    return torch.as_tensor(x).to("cuda").contiguous()
-
-
-def make_handle(rt, B, L, precision, weights=None, variant=spec.VARIANT_RGB):
-    h = rt.OffForward(B, L, variant, spec.SLICE_FLAT, None, precision=precision)
+def make_handle(rt, B, L, precision, weights=None, variant=spec.VARIANT_RGB, env=None):
+    """-> (handle, its weights as numpy arrays)"""
     w = synth.make_weights(variant) if weights is None else weights
-    assert h.load_state_dict(w) == []
-    return h, w
+    return forward.make_handle(rt, B, L, variant, weights=w, precision=precision, env=env)[0], w
 
 
 def units_reference_fp64(feats, w, B, L):
@@ -203,16 +196,14 @@ def test_batched_gemm_split_error_is_no_larger_than_the_fp32_pipes(rt, kind):
 
 
 @pytest.mark.parametrize("B", [2, 12])
-def test_forward_split_gemms_against_fp32_pipe_gemms(rt, monkeypatch, B):
+def test_forward_split_gemms_against_fp32_pipe_gemms(rt, B):
     """A split-fp32 handle with its GEMMs / 1x1 convs on the bf16 pipe (default) against the same handle with OFFK_SPLIT_GEMM=0 (only the
     units kernel split): same logits and stage tensors to summation-order noise (the convs' own Winograd error is 1e-5 of max |ref|), and
     the 7-head's folded pool of the split kernel's epilogue gives the same logits."""
     L = 7
     feats = [dev(f) for f in synth.make_features(B, L, 3)]
     h1, _ = make_handle(rt, B, L, "f32split")
-    monkeypatch.setenv("OFFK_SPLIT_GEMM", "0")
-    h0, _ = make_handle(rt, B, L, "f32split")
-    monkeypatch.delenv("OFFK_SPLIT_GEMM")
+    h0, _ = make_handle(rt, B, L, "f32split", env={"OFFK_SPLIT_GEMM": "0"})
     a, b = h1.forward(feats), h0.forward(feats)
     torch.cuda.synchronize()
     for x, y in zip(a, b):
@@ -288,27 +279,6 @@ def test_split_nonfinite_and_tiny_inputs(rt):
 
 # ---- the bottleneck chains of fusion@28 in split-fp32 arithmetic (chain_split.hip) through their C-ABI entry point (ABI v10) ----
 
-def _chain_inputs(case, n, kind, seed):
-    g = torch.Generator().manual_seed(seed)
-    branch = case == "28a_branch"
-    Cin = 64 if branch else 256
-    x = torch.randn(n, 14, 14, Cin + (64 if branch else 0), generator=g) * (1.0 if branch else 0.5)
-    if kind == "heavy_tail":
-        x = x * torch.exp(1.5 * torch.randn(n, 14, 14, 1, generator=g))
-    if not branch:
-        x = x.clamp_min(0)                               # sa / sb are post-ReLU
-    k1 = 1.0 / Cin ** 0.5
-    w1 = (torch.rand(64, Cin, generator=g) * 2 - 1) * k1
-    b1 = (torch.rand(64, generator=g) * 2 - 1) * k1
-    w2 = (torch.rand(64, 64, 3, 3, generator=g) * 2 - 1) / 24.0
-    b2 = (torch.rand(64, generator=g) * 2 - 1) / 24.0
-    w3 = (torch.rand(256, 64, generator=g) * 2 - 1) / 8.0
-    b3 = (torch.rand(256, generator=g) * 2 - 1) / 8.0
-    wb = (torch.rand(256, 64, generator=g) * 2 - 1) / 8.0
-    bb = (torch.rand(256, generator=g) * 2 - 1) / 8.0
-    return x.float().contiguous(), w1, b1, w2, b2, w3, b3, wb, bb
-
-
 @pytest.mark.parametrize("kind", ["normal", "heavy_tail"])
 @pytest.mark.parametrize("case", ["28a_branch", "28b_residual", "28c_into_slice"])
 @pytest.mark.parametrize("n", [1, 5, 11])
@@ -317,7 +287,7 @@ def test_bottleneck_chain14_split_vs_fp64(rt, case, n, kind):
     branch conv on the pre-ReLU x0, inside the kernel), the residual form, output into a channel slice; odd image counts exercise the grid
     rounding.  Beside it the fp32-pipe kernel (offk_bottleneck_chain14, direct 3x3): the split chain may not be further from fp64."""
     branch = case == "28a_branch"
-    x, w1, b1, w2, b2, w3, b3, wb, bb = _chain_inputs(case, n, kind, 300 + n)
+    x, w1, b1, w2, b2, w3, b3, wb, bb = chain_inputs(case, n, kind, 300 + n)
     Cin, x_coff = (64, 64) if branch else (256, 0)
     xin = x[..., x_coff:x_coff + Cin].permute(0, 3, 1, 2).double()
     t1 = F.relu(F.conv2d(F.relu(xin) if branch else xin, w1.double()[:, :, None, None], b1.double()))
@@ -520,7 +490,7 @@ def test_bottleneck_chain14_split_worst_case_mantissas(rt, case, signs, pattern)
     through the whole chain against fp64 exactly as test_bottleneck_chain14_split_vs_fp64 measures it (max error / max |want| < 2e-6).  The
     fp32-pipe kernel is printed beside it and is not a limit here."""
     n, branch = 5, case == "28a_branch"
-    _x, _w1, b1, w2, b2, w3, b3, wb, bb = _chain_inputs(case, n, "normal", 900)
+    _x, _w1, b1, w2, b2, w3, b3, wb, bb = chain_inputs(case, n, "normal", 900)
     Cin, x_coff = (64, 64) if branch else (256, 0)
     x = torch.from_numpy(synth.make_adversarial((n, 14, 14, Cin + x_coff), pattern, "same", seed=40))
     w1 = torch.from_numpy(synth.make_adversarial((64, Cin), pattern, signs, seed=41) * _pow2_scale(Cin))
@@ -553,13 +523,12 @@ def test_winograd_between_split_worst_case_mantissas(rt, signs, pattern):
     """winograd_between with its 1x1 conv in split arithmetic (Cin = Cmid = 128, n = 5): w1 adversarial, the Winograd-domain input too (the
     activations the 1x1 contracts are its output transform); limits and normalisation of tests/test_gpu_paths.py::
     test_winograd_between_vs_fp64, the fp32-pipe kernel printed beside it."""
-    from tests.test_gpu_paths import _between_reference, rel_err
     n, cin = 5, 128
     M = synth.make_adversarial((121, n, cin), pattern, "same", seed=60) * np.float32(0.125)
     bias = synth.uniform_values(61, cin, 0.5)
     w1 = synth.make_adversarial((cin, cin), pattern, signs, seed=62) * _pow2_scale(cin)
     b1 = synth.uniform_values(63, cin, 0.1)
-    x_ref, v_ref = _between_reference(M.astype(np.float64), bias.astype(np.float64), 1, w1.astype(np.float64), b1.astype(np.float64))
+    x_ref, v_ref = between_reference(M.astype(np.float64), bias.astype(np.float64), 1, w1.astype(np.float64), b1.astype(np.float64))
     errs = {}
     for prec in ("f32split", "fp32"):
         xbuf = torch.full((n, 7, 7, cin + 64), -3.0, device="cuda")

@@ -24,13 +24,12 @@ import offk_amd  # noqa: F401
 from offk_amd import spec, synth
 
 from . import arena
+from . import conv_grad_checks as chk
 from .conv_bwd import S1 as cb
 from .conv_bwd import S2 as cs2
 from . import featmaps as fx
 from . import head_bwd as hb
 from . import ranges as rg
-from . import test_gpu_conv_s2_dgrad_split as tds
-from . import test_gpu_conv_wgrad_split as tcw
 from . import units_fwd_split as tuf
 from . import units_grad as ug
 from . import wgrad_split as twg
@@ -102,7 +101,7 @@ def test_wide_draw_conv_weight_gradient_split(rt, c):
     g = rg.scale(inp["g"], G_SCALE)
     dw, _db = rt.conv2d_backward_weight(cuda(inp["x"]), cuda(g), c.k, (c.k - 1) // 2, arith="f32split")
     torch.cuda.synchronize()
-    ce, cg, cf = tcw.check_inequality(rt, "wide draw %s" % cb.case_id(c), c, g.numpy(), inp["x"].numpy(), dw)
+    ce, cg, cf = chk.wgrad_inequality(rt, cb, "wide draw %s" % cb.case_id(c), c, g.numpy(), inp["x"].numpy(), dw)
     print("RATIO conv2d_backward_weight_split %s: gpu accumulation / A = %.3f" % (cb.case_id(c), cg / max(1.0, 2 * ce)))
 
 
@@ -112,7 +111,7 @@ def test_wide_draw_s2_data_gradient_split(rt, c):
     g = rg.scale(inp["g"], G_SCALE)
     dx = rt.conv2d_s2_backward_data(cuda(g), cuda(inp["w"]), (c.k - 1) // 2, arith="f32split")
     torch.cuda.synchronize()
-    ce, cg, cf = tds.check_inequality(rt, "wide draw %s" % cs2.case_id(c), c.k, g.numpy(), inp["w"].numpy(), dx)
+    ce, cg, cf = chk.dgrad_inequality(rt, cs2, "wide draw %s" % cs2.case_id(c), c.k, g.numpy(), inp["w"].numpy(), dx)
     print("RATIO conv2d_s2_backward_data_split %s: gpu accumulation / A = %.3f" % (cs2.case_id(c), cg / max(1.0, 2 * ce)))
 
 
@@ -209,7 +208,7 @@ def test_tiny_conv_weight_gradient_split(rt, c, side):
     dw, _db = rt.conv2d_backward_weight(cuda(inp["x"]), cuda(inp["g"]), c.k, (c.k - 1) // 2, arith="f32split")
     torch.cuda.synchronize()
     assert bool((dw != 0).any())
-    tcw.check_inequality(rt, "tiny %s %s" % (side, cb.case_id(c)), c, inp["g"].numpy(), inp["x"].numpy(), dw)
+    chk.wgrad_inequality(rt, cb, "tiny %s %s" % (side, cb.case_id(c)), c, inp["g"].numpy(), inp["x"].numpy(), dw)
 
 
 @pytest.mark.parametrize("side", ["g", "w"])
@@ -221,7 +220,7 @@ def test_tiny_s2_data_gradient_split(rt, c, side):
     dx = rt.conv2d_s2_backward_data(cuda(inp["g"]), cuda(inp["w"]), (c.k - 1) // 2, arith="f32split")
     torch.cuda.synchronize()
     assert bool((dx != 0).any())
-    tds.check_inequality(rt, "tiny %s %s" % (side, cs2.case_id(c)), c.k, inp["g"].numpy(), inp["w"].numpy(), dx)
+    chk.dgrad_inequality(rt, cs2, "tiny %s %s" % (side, cs2.case_id(c)), c.k, inp["g"].numpy(), inp["w"].numpy(), dx)
 
 
 @pytest.mark.parametrize("tiny", ["maps", "gradient"])

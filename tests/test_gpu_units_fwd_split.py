@@ -32,7 +32,7 @@ from oracle import off_oracle as orc
 from . import arena as arena_mod
 from . import exact
 from . import featmaps as fm
-from . import test_gpu_exact as gx
+from . import exact_units as gx
 from . import units_grad as ug
 from .units_fwd_split import DOWN_B, DOWN_W, GEN_B, GEN_W, check_site
 from .units_grad import DTS, FORMS, IDS, RTOL, SHAPES, as_form, exact_case, rt  # noqa: F401

@@ -46,8 +46,6 @@ must give reload's bits.  No assertion here is a tolerance.
 Wall time of this module on an MI355X: 25.8 s on the first run (281 items then), 45.4 s for today's 285 on another machine of the pool; the
 slowest item 0.5 s (the first, which loads the library).
 """
-import functools
-
 import pytest
 import torch
 
@@ -56,56 +54,21 @@ from offk_amd import spec, synth
 
 from . import weight_updates as wu
 from .arena import same_bits
-from .test_gpu_parity import HANDLE_PRECISIONS, dev, rt  # noqa: F401
-from .test_gpu_switches import BETWEEN, CHAINS, FC_FOLDED, W5, W7, WINO, check_trace, switched_handle, traced_forward
+from .featmaps import rt  # noqa: F401
+from .forward import BETWEEN, CHAINS, FC_FOLDED, HANDLE_PRECISIONS, W5, W7, WINO, check_trace, dev, make_handle, traced_forward
+from .weight_updates import CONFIGS, SPLIT, differing, feats, run
 
 pytestmark = pytest.mark.gpu
 
-FEATURE_CONFIG = 2
-GATES_OPEN = {"OFFK_CHAIN": "2", "OFFK_WINOGRAD_5X5": "2", "OFFK_WINOGRAD_7X7": "2", "OFFK_POOL_FIRST_7": "2"}
-SPLIT = "f32split"
-CONFIGS = {
-    "default": ({}, HANDLE_PRECISIONS),
-    "gates_open": (GATES_OPEN, HANDLE_PRECISIONS),
-    "unfused_units": ({"OFFK_FUSED_UNITS": "0"}, HANDLE_PRECISIONS),
-    "direct_convs": ({"OFFK_WINOGRAD": "0", "OFFK_CHAIN": "0"}, HANDLE_PRECISIONS),
-    "split_on_fp32_pipe": (dict(GATES_OPEN, OFFK_SPLIT_GEMM="0", OFFK_SPLIT_CHAIN="0", OFFK_SPLIT_MID="0"), [SPLIT]),
-}
 SETUPS = [(c, p, v) for c, (_env, precs) in CONFIGS.items() for p in precs for v in wu.VARIANTS]
-REGIONS = [("fusion_28", 320), ("fusion_14", 1056), ("fusion_7", 832)] + [("D_" + s, spec.DOWN_CH) for s in spec.SITE_NAMES] + [("sum_7", 1024)]
 
 
 def setup_id(c, p, v):
     return "%s-%s-%s" % (c, p, wu.VARIANT_TAGS[v])
 
 
-@functools.lru_cache(maxsize=None)
-def _feats():
-    return tuple(dev(f) for f in synth.make_features(wu.B, wu.L, FEATURE_CONFIG))
-
-
-def feats():
-    return list(_feats())
-
-
 def new_handle(rt, config, prec, variant, weights):
-    with pytest.MonkeyPatch.context() as mp:
-        h, _w = switched_handle(rt, mp, CONFIGS[config][0], wu.B, wu.L, variant, consensus=False, weights=weights, precision=prec)
-    return h
-
-
-def run(h):
-    """One forward: name -> a copy of the three heads and of every stage region."""
-    out = h.forward(feats())
-    snap = dict((name, o.clone()) for name, o in zip(wu.HEAD_ORDER, out))
-    for name, ch in REGIONS:
-        snap[name] = h.region(name, ch).clone()
-    torch.cuda.synchronize()
-    return snap
-
-
-def differing(a, b):
-    return sorted(name for name in a if not same_bits(a[name], b[name]))
+    return make_handle(rt, wu.B, wu.L, variant, consensus=False, weights=weights, precision=prec, env=CONFIGS[config][0])[0]
 
 
 class Setup:

@@ -181,7 +181,7 @@ def oracle_dx(c):
 
 @functools.lru_cache(maxsize=None)
 def exact_case(B, L, variant, slice_mode):
-    from . import test_gpu_exact as gx
+    from . import exact_units as gx
     return gx.Case(B, L, variant, slice_mode)           # (its constructor asserts exact.check_caps on every output, dX among them)
 
 

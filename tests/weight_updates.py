@@ -11,9 +11,15 @@ of the stage before it (spec.FUSION[..]["carry"]), so the 28x28 units and the fu
 ones the 14- and the 7-head, the 7x7 ones the 7-head alone, and each FC its own head.  tests/test_weight_update_cases.py proves
 the table against the fp64 oracle, key by key.
 """
-import numpy as np
+import functools
 
-from offk_amd import spec
+import numpy as np
+import torch
+
+from offk_amd import spec, synth
+
+from .arena import same_bits
+from .forward import HANDLE_PRECISIONS, dev
 
 VARIANTS = (spec.VARIANT_RGB, spec.VARIANT_FLOW)
 VARIANT_TAGS = {spec.VARIANT_RGB: "rgb", spec.VARIANT_FLOW: "flow"}
@@ -158,3 +164,40 @@ def site_of(key):
         if base.startswith(prefix):
             return spec.SITE_NAMES.index(base[len(prefix):])
     raise KeyError(key)
+
+
+# ---- the GPU side: the configurations, one forward and what it left (tests/test_gpu_weight_updates.py, test_gpu_bound_weights.py) ----
+FEATURE_CONFIG = 2
+GATES_OPEN = {"OFFK_CHAIN": "2", "OFFK_WINOGRAD_5X5": "2", "OFFK_WINOGRAD_7X7": "2", "OFFK_POOL_FIRST_7": "2"}
+SPLIT = "f32split"
+CONFIGS = {
+    "default": ({}, HANDLE_PRECISIONS),
+    "gates_open": (GATES_OPEN, HANDLE_PRECISIONS),
+    "unfused_units": ({"OFFK_FUSED_UNITS": "0"}, HANDLE_PRECISIONS),
+    "direct_convs": ({"OFFK_WINOGRAD": "0", "OFFK_CHAIN": "0"}, HANDLE_PRECISIONS),
+    "split_on_fp32_pipe": (dict(GATES_OPEN, OFFK_SPLIT_GEMM="0", OFFK_SPLIT_CHAIN="0", OFFK_SPLIT_MID="0"), [SPLIT]),
+}
+REGIONS = [("fusion_28", 320), ("fusion_14", 1056), ("fusion_7", 832)] + [("D_" + s, spec.DOWN_CH) for s in spec.SITE_NAMES] + [("sum_7", 1024)]
+
+
+@functools.lru_cache(maxsize=None)
+def _feats():
+    return tuple(dev(f) for f in synth.make_features(B, L, FEATURE_CONFIG))
+
+
+def feats():
+    return list(_feats())
+
+
+def run(h):
+    """One forward: name -> a copy of the three heads and of every stage region."""
+    out = h.forward(feats())
+    snap = dict((name, o.clone()) for name, o in zip(HEAD_ORDER, out))
+    for name, ch in REGIONS:
+        snap[name] = h.region(name, ch).clone()
+    torch.cuda.synchronize()
+    return snap
+
+
+def differing(a, b):
+    return sorted(name for name in a if not same_bits(a[name], b[name]))

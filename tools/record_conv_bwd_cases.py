@@ -1,6 +1,6 @@
 """Records tests/golden/conv_bwd_cases.json: one sha256 per generated input of the conv backward tests (integer and normal inputs of every
 case of both strides, the data gradient's worst-case operands, the wide-integer operands), from the case modules in the tree.  The job list
-is tests/test_conv_bwd_cases.py's, which holds later trees to the file.  Needs no library and no GPU; from the repository root:
+is tests/conv_bwd_cases.py's; tests/test_conv_bwd_cases.py holds later trees to the file.  Needs no library and no GPU; from the repository root:
 
     python tools/record_conv_bwd_cases.py
 """
@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tests import test_conv_bwd_cases as t  # noqa: E402
+from tests import conv_bwd_cases as t  # noqa: E402
 
 
 def main():

@@ -1,7 +1,7 @@
 """Records tests/golden/conv_bwd_entries.json: what every conv backward entry of include/offk.h refuses (return code and the full
-offk_last_error text, fp32 entry and split twin, for every rule of the refusal tables of tests/test_conv_*_abi.py) and what its six plan
-entries return over a sweep of n_img, from the library in the tree (or OFFK_LIB).  The case lists are tests/test_conv_bwd_entries.py's,
-which holds later builds to the file.  Needs no GPU (every refusal fires before the first HIP call, the plans are host code); from the
+offk_last_error text, fp32 entry and split twin, for every rule of the refusal tables of tests/conv_bwd_abi.py and tests/conv_bwd_s2_abi.py) and what its six plan
+entries return over a sweep of n_img, from the library in the tree (or OFFK_LIB).  The case lists are tests/conv_bwd_entries.py's;
+tests/test_conv_bwd_entries.py holds later builds to the file.  Needs no GPU (every refusal fires before the first HIP call, the plans are host code); from the
 repository root:
 
     [OFFK_LIB=<an earlier build's liboffk.so>] python tools/record_conv_bwd_entries.py
@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 
 import offk_amd  # noqa: E402,F401
 from offk_amd import _lib  # noqa: E402
-from tests import test_conv_bwd_entries as t  # noqa: E402
+from tests import conv_bwd_entries as t  # noqa: E402
 
 
 def main():

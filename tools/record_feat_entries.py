@@ -1,6 +1,6 @@
 """Records tests/golden/feat_entry_refusals.json: what every feature-map entry of include/offk.h refuses (return code and
 offk_last_error text) and the launch names of its good calls, from the library in the tree (or OFFK_LIB).  The case lists are
-tests/test_gpu_feat_entries.py's, which holds later builds to the file.  Run on an MI355X, from the repository root:
+tests/feat_entries.py's; tests/test_gpu_feat_entries.py holds later builds to the file.  Run on an MI355X, from the repository root:
 
     python tools/record_feat_entries.py
 """
@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 
 import offk_amd  # noqa: E402,F401
 from offk_amd import runtime  # noqa: E402
-from tests import test_gpu_feat_entries as t  # noqa: E402
+from tests import feat_entries as t  # noqa: E402
 
 
 def main():

@@ -1,11 +1,11 @@
 """Records tests/golden/forward_plans.json: the ordered launch-group names of one forward for every case of
-tests/test_gpu_forward_plan.py, from the library in the tree (or OFFK_LIB).  Run on an MI355X, from the repository root:
+tests/forward_plan.py (the list tests/test_gpu_forward_plan.py holds later builds to), from the library in the tree (or OFFK_LIB).  Run on an MI355X, from the repository root:
 
     python tools/record_forward_plans.py
 
     python tools/record_forward_plans.py --digests OUT.txt
         writes no golden; OUT.txt gets the bytes of device memory offk_create takes for three handles and one line per case: SHA-256
-        (first 16 hex digits each) of the launch names, the three logit tensors and the stage regions (test_gpu_forward_plan.REGIONS).
+        (first 16 hex digits each) of the launch names, the three logit tensors and the stage regions (tests/forward_plan.py REGIONS).
         For a one-off A/B of two builds on one box (OFFK_LIB=<the other liboffk.so>): the files of two builds that compute the same
         are identical.  Digests are not committed as goldens: split-K depths follow the device's grid (tests/test_gpu_switches.py).
 """
@@ -20,7 +20,8 @@ import torch  # noqa: E402
 
 import offk_amd  # noqa: E402,F401
 from offk_amd import runtime, spec  # noqa: E402
-from tests import test_gpu_forward_plan as t  # noqa: E402
+from tests import forward_plan as t  # noqa: E402
+from tests.forward import switches  # noqa: E402
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
@@ -36,7 +37,7 @@ def create_bytes():
     for name, prec, env in (("fp32", "fp32", {}), ("f32split", "f32split", {}), ("f32split-winograd0", "f32split", {"OFFK_WINOGRAD": "0"})):
         torch.cuda.synchronize()
         before = torch.cuda.mem_get_info()[0]
-        with t.switches(env):
+        with switches(env):
             h = runtime.OffForward(3, 7, spec.VARIANT_RGB, consensus=False, precision=prec)
         out[name] = before - torch.cuda.mem_get_info()[0]
         del h

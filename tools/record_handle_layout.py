@@ -1,7 +1,7 @@
-"""Records tests/golden/handle_layout.json: per handle of tests/test_gpu_handle_layout.py's list the workspace sizes, every workspace
+"""Records tests/golden/handle_layout.json: per handle of tests/handle_layout.py's list the workspace sizes, every workspace
 region and unit-gradient slot by name (or the code and text with which the handle says it has none), and on the smallest handles what the
 unit entries answer while one weight is missing and what binding a parameter returns -- from the library in the tree (or OFFK_LIB).  The
-case lists are the test's, which holds later builds to the file.  Run on an MI355X, from the repository root:
+case lists are those tests/test_gpu_handle_layout.py holds later builds to.  Run on an MI355X, from the repository root:
 
     [OFFK_LIB=<an earlier build's liboffk.so>] python tools/record_handle_layout.py [output path]
 """
@@ -14,7 +14,7 @@ sys.path.insert(0, ROOT)
 
 import offk_amd  # noqa: E402,F401
 from offk_amd import _lib  # noqa: E402
-from tests import test_gpu_handle_layout as t  # noqa: E402
+from tests import handle_layout as t  # noqa: E402
 
 
 def main():
